@@ -32,6 +32,9 @@ Prints ONE JSON line on rank 0 (contract in the task description) including
   cpu_baseline   -- the C oracle (oracle/fhesi_oracle.c) on a bounded sample of the same workload: one thread (at any N, on rank 0), and at
                     N = 1 also all cores and the reference's own Bluestein-over-FFT-primes structure (like for like)
   matches_oracle -- the first cpu-sample outputs of the timed buffer compared bit for bit with the oracle's (exit code 1 otherwise)
+
+--dump-outputs DIR writes, after the timed steps, what the last of them left in the output buffer (dump_outputs below): the inputs and keys
+are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes
@@ -130,6 +133,43 @@ def rand_coeffs(rng, shape, nlimbs):
     hi = rng.integers(0, 1 << 63, size=tuple(shape) + (nlimbs,), dtype=np.uint64)
     lo = rng.integers(0, 2, size=tuple(shape) + (nlimbs,), dtype=np.uint64)
     return hi * np.uint64(2) + lo
+
+
+# ---- --dump-outputs: what the timed path computed in its last step, as float32 arrays two builds can be compared on -------------------------------
+DUMP_WORDS = 1 << 21          # 64-bit words one run writes, over all its ranks: four float32 each = 32 MiB
+
+
+def dump_pick(words, count, world):
+    """the word positions kept of every one of the `count` output items ([count][words] u64) of a rank: all of them while the run's outputs
+    fit DUMP_WORDS, otherwise a fixed seeded sample -- the same positions in every item, on every rank, in every run"""
+    k = max(1, DUMP_WORDS // (count * world))
+    return np.arange(words) if k >= words else np.sort(np.random.default_rng(64).choice(words, size=k, replace=False))
+
+
+def dump_outputs(args, rank, world, name, sample):
+    """DIR/<name>.npy (<name>_rank<r>.npy at N > 1): `sample` [count][k] u64 as float32 [count][k][4], every word in four 16-bit pieces from
+    the least significant one -- integers float32 holds exactly, and small enough that a comparison with a tolerance still sees one bit"""
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    pieces = (sample[..., None] >> np.arange(0, 64, 16, dtype=np.uint64)) & np.uint64(0xFFFF)
+    np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), pieces.astype(np.float32))
+
+
+def download_at(ctx, buf, offset, out):
+    """fills the contiguous array `out` from a device buffer, starting `offset` bytes into it"""
+    from fhe_si_amd import binding as Bd
+    assert out.flags.c_contiguous and offset + out.nbytes <= buf.nbytes
+    Bd._ck(Bd._load().fhesi_dev_download(ctx.h, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(buf.ptr.value + offset), out.nbytes))
+
+
+def download_picked(ctx, buf, count, words, pick):
+    """the words `pick` of each of the `count` items of a device buffer [count][words] u64, fetched in pieces of at most 256 MiB"""
+    per = max(1, (1 << 28) // (8 * words))
+    piece, out = np.empty((per, words), dtype=np.uint64), np.empty((count, len(pick)), dtype=np.uint64)
+    for first in range(0, count, per):
+        c = min(per, count - first)
+        download_at(ctx, buf, first * words * 8, piece[:c])
+        out[first:first + c] = piece[:c, pick]
+    return out
 
 
 def host_cpu_info():
@@ -292,11 +332,13 @@ def run_regression(args, ctx, ksk, primes, n, nd, nl, rank, world, local_rank, d
     first = be.upload(rand_coeffs(np.random.default_rng(7), (nin, 2, n), nl))      # same inputs on every rank
     assert first == 0
     mark = pool.used
-    stats = {}
+    stats, result = {}, []
 
     def step():
         pool.used = mark
-        stats.update(G.regress_waves(be, X, y)[2])
+        theta, det, counts = G.regress_waves(be, X, y)
+        stats.update(counts)
+        result[:] = theta + [det]
 
     for _ in range(max(1, args.warmup)):
         step()
@@ -325,6 +367,9 @@ def run_regression(args, ctx, ksk, primes, n, nd, nl, rank, world, local_rank, d
     row_elems = max(n if M_RING & (M_RING - 1) == 0 else 1 << (2 * n - 2).bit_length(), 1 << 14) if kname.startswith("ntt32_") else n      # (padded rows of 2^14 / 2^15 on the linear-convolution rings)
     achieved = rows * 2 * row_elems * (4 if kname.startswith("ntt32_") else 8) / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
     ks_form, ks_rows, ks_limb_bits = ksk.form()
+    if args.dump_outputs:           # theta[0..d) and det, the ciphertexts Regress returns
+        got = pool.t[result].cpu().numpy().view(np.uint64)
+        dump_outputs(args, rank, world, "regress_theta_det", got[:, dump_pick(got.shape[1], len(result), world)])
     if rank == 0:
         ksw = stats["key_switches"] + stats["automorph_key_switches"]
         line = {
@@ -394,6 +439,8 @@ def run_ntt_round_trips(args, rank, world, local_rank, dist, torch, F):
     il, irows, ims = ctx.prof_read("ntt_inv")
     fname, iname = ctx.prof_kernel_name("ntt_fwd"), ctx.prof_kernel_name("ntt_inv")
     ctx.prof_enable(False)
+    if args.dump_outputs:
+        dump_outputs(args, rank, world, "ntt_round_trip", download_picked(ctx, buf, B, L * n, dump_pick(L * n, B, world)))
     identity = bool(np.array_equal(buf.download(host.shape), host))
     cpu = None
     oracle_ok = None
@@ -451,7 +498,7 @@ def self_launch(args):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps: every timed block (--gpu-seconds) runs exactly this many")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="ciphertext mults per GPU per step (default 1024 = 16 chunks of the library, so that 20 steps time more than "
                     "a second; stress: 64; ntt workload: DoubleCRTs per step, default 8192)")
@@ -486,6 +533,8 @@ def parse_args():
                     "line), 50 = the NTL 5.x / 6.x of the reference's era (22 primes instead of 18 at the metric ring)")
     ap.add_argument("--gpu-seconds", type=float, default=5.0, help="metric / stress workloads: the block of exactly --steps timed steps is repeated until the GPU phase has "
                     "lasted about this long (every block bracketed like the first; `value` is the MEDIAN block, all blocks are listed); 0 = one block")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed (the output buffer a caller of the timed path reads) "
+                    "to DIR/<name>.npy: float32, every 64-bit word in four 16-bit pieces; all of it up to 32 MiB, a fixed seeded sample of every output item beyond")
     return ap.parse_args()
 
 
@@ -927,6 +976,8 @@ def run_mult(args, r, torch, F, options):
     prof = {k: ctx.prof_read(k) for k in F.binding.PROF_CLASSES}
     names = {k: ctx.prof_kernel_name(k) for k in F.binding.PROF_CLASSES}
     ctx.prof_enable(False)
+    if args.dump_outputs:           # (before anything below writes the buffer again)
+        dump_outputs(args, rank, world, "ct_mul_relin", download_picked(ctx, dout, B, 2 * n * nl, dump_pick(2 * n * nl, B, world)))
 
     # ---- roofline of the fused ByteDecomp + forward transform of the digit polynomials ------------------------------------------------------------
     launches, rows, ms = prof["ntt_fwd_digits_main"]
@@ -1123,10 +1174,8 @@ def main():
 
 def ctx_download_tail(ctx, buf, B, ct_bytes):
     """bytes of the last ciphertext of a device batch"""
-    import ctypes as C
     out = np.empty(ct_bytes, dtype=np.uint8)
-    from fhe_si_amd import binding as Bd
-    Bd._ck(Bd._load().fhesi_dev_download(ctx.h, out.ctypes.data_as(C.c_void_p), C.c_void_p(buf.ptr.value + (B - 1) * ct_bytes), ct_bytes))
+    download_at(ctx, buf, (B - 1) * ct_bytes, out)
     return out.tobytes()
 
 

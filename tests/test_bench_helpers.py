@@ -1,9 +1,14 @@
 """CPU: the helpers behind bench.py's roofline record -- what the line says about the binding roof must follow from the committed counter files
 by arithmetic a reader can redo (issue ceiling, K2' bytes, min / median over blocks), and must degrade to nulls, not guesses, when the committed
-pass is not the run's kernel or batch."""
+pass is not the run's kernel or batch.  And --dump-outputs: its sample and file format on the CPU, one run against the oracle on the GPU."""
 import json
 import os
+import subprocess
 import sys
+import types
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -56,3 +61,62 @@ def test_kernel_clock_block_statistics():
     assert clk.stats("dot") == (4.8, 5.0)
     clk2 = B.KernelClock(ctx, ("dot",))
     assert clk2.stats("dot") == (None, None)
+
+
+def _words(path):
+    """a --dump-outputs file back as the 64-bit words it holds"""
+    f = np.load(path)
+    assert f.dtype == np.float32 and f.shape[-1] == 4 and np.array_equal(f, np.floor(f)) and f.min() >= 0 and f.max() < 65536
+    return (f.astype(np.uint64) << np.arange(0, 64, 16, dtype=np.uint64)).sum(axis=-1, dtype=np.uint64)
+
+
+def test_dump_outputs_keeps_every_bit_of_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the kept word positions are the same in every run and on every rank and bound the run's files to 32 MiB; the float32
+    pieces give the words back exactly; a device buffer larger than one 256 MiB piece is fetched piece by piece."""
+    assert np.array_equal(B.dump_pick(1000, 8, 1), np.arange(1000))                                      # all of a small output
+    pick = B.dump_pick(1 << 18, 1024, 1)
+    assert len(pick) == 2048 == len(set(pick)) and np.array_equal(pick, np.sort(pick)) and np.array_equal(pick, B.dump_pick(1 << 18, 1024, 1))
+    assert len(B.dump_pick(1 << 18, 1024, 8)) == 256 and 1024 * 8 * 256 * 16 == 1 << 25                  # 8 ranks share the 32 MiB
+    rng = np.random.default_rng(3)
+    dev = rng.integers(0, 1 << 64, size=(3, 1 << 24), dtype=np.uint64)                                   # 3 items of 128 MiB: pieces of 2 and 1
+    dev[0, :3] = (0, 1, (1 << 64) - 1)
+    calls = []
+
+    def fake_download_at(ctx, buf, offset, out):
+        calls.append((offset, out.shape[0]))
+        out[...] = dev.reshape(-1)[offset // 8:offset // 8 + out.size].reshape(out.shape)
+    monkeypatch.setattr(B, "download_at", fake_download_at)
+    pick = np.concatenate([np.arange(3), B.dump_pick(1 << 24, 3, 1)[:1000]])
+    got = B.download_picked(None, None, 3, 1 << 24, pick)
+    assert calls == [(0, 2), (1 << 28, 1)] and np.array_equal(got, dev[:, pick])
+    args = types.SimpleNamespace(dump_outputs=str(tmp_path / "made" / "here"))
+    B.dump_outputs(args, 0, 1, "x", got)
+    B.dump_outputs(args, 1, 2, "x", got)
+    assert sorted(os.listdir(args.dump_outputs)) == ["x.npy", "x_rank1.npy"]
+    assert np.array_equal(_words(os.path.join(args.dump_outputs, "x.npy")), got)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_timed_buffer_and_repeats(tmp_path):
+    """Two runs of bench.py with the same workload arguments write the same file (the inputs are seeded; the number of timed steps does not
+    enter), and the file holds the product of the run's inputs: ciphertexts of the batch against the oracle at the kept word positions."""
+    n, nl, nd, batch = B.M_RING // 2, (B.LOGQ + 63) // 64, (B.LOGQ + 8 * B.DECOMP - 1) // (8 * B.DECOMP), 16
+    got = []
+    for tag, steps in (("a", "2"), ("b", "3")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", "1", "--batch", str(batch), "--keys", "uniform",
+                            "--cpu-sample", "0", "--no-surface", "--gpu-seconds", "0", "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["steps"] == int(steps)
+        assert os.listdir(tmp_path / tag) == ["ct_mul_relin.npy"] and os.path.getsize(tmp_path / tag / "ct_mul_relin.npy") <= 64 << 20
+        got.append(_words(tmp_path / tag / "ct_mul_relin.npy"))
+    pick = B.dump_pick(2 * n * nl, batch, 1)
+    assert got[0].shape == (batch, len(pick)) and len(pick) < 2 * n * nl and np.array_equal(got[0], got[1])
+    primes = B.prime_chain(B.M_RING, B.LOGQ, B.P_PLAIN, n)
+    roots = [B.root_2m(q, B.M_RING) for q in primes]
+    rng = np.random.default_rng(7)
+    a = B.rand_coeffs(rng, (batch, 2, n), nl)
+    b = B.rand_coeffs(rng, (batch, 2, n), nl)
+    ksm = B.rand_residue_rows(np.random.default_rng(8), primes, (2, 3 * nd), n)
+    for i in (0, batch - 1):
+        want = B.oracle_outputs(primes, roots, ksm, a[i:i + 1], b[i:i + 1], 1)
+        assert np.array_equal(got[0][i], want.reshape(-1)[pick]), i
