@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "fhesi_ksk_form", "fhesi_ct_add_const_dev", "fhesi_ct_mul_poly_dev",
     "fhesi_encrypt_batch_seeded", "fhesi_keyswitch_init_batch_seeded", "fhesi_dcrt_sample",
     "fhesi_abi_version", "fhesi_host_stage_release",
+    "fhesi_slots_plan", "fhesi_slots_create", "fhesi_slots_free", "fhesi_slots_info", "fhesi_slots_exponents", "fhesi_slots_embed", "fhesi_slots_decode",
+    "fhesi_slots_embed_dev", "fhesi_slots_decode_dev", "fhesi_encrypt_slots_batch_seeded", "fhesi_decrypt_slots_batch", "fhesi_encrypt_noise_batch_seeded",
 ]
 ABI_VERSION = 7          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8}
@@ -178,6 +180,18 @@ def _load():
         "fhesi_dcrt_sample": [_vp, _i32, _i64, _u64, _u64],
         "fhesi_ct_add_const_dev": [_vp, _i32, _u64, _vp, _i32, _i32, _i64, _vp, _i32],
         "fhesi_ct_mul_poly_dev": [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _i32],
+        "fhesi_slots_plan": [_i64, _u64, _i64, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_slots_create": [_vp, _u64, _i64, _vp],
+        "fhesi_slots_free": [_vp],
+        "fhesi_slots_info": [_vp, _vp, _vp, _vp, _vp],
+        "fhesi_slots_exponents": [_vp, _vp],
+        "fhesi_slots_embed": [_vp, _vp, _i64, _i32, _i64, _vp],
+        "fhesi_slots_decode": [_vp, _vp, _i64, _i64, _i32, _vp],
+        "fhesi_slots_embed_dev": [_vp, _vp, _i64, _i32, _i64, _vp],
+        "fhesi_slots_decode_dev": [_vp, _vp, _i64, _i64, _i32, _vp],
+        "fhesi_encrypt_slots_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _vp, _i64, _i32, _i64, _vp, _i32],
+        "fhesi_decrypt_slots_batch": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i32, _vp],
+        "fhesi_encrypt_noise_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _i64, _vp, _i32],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -453,6 +467,82 @@ class Context:
     def release_host_staging(self):
         """hand back the pinned + device staging ring the host-buffer calls keep between uses"""
         _ck(_load().fhesi_host_stage_release(self.h))
+
+
+def slots_plan(m: int, p: int, generator: int) -> dict:
+    """The host half of PlaintextSpace::Init (no device, no context): checks (m, p, g) and returns total / usable slots, rho0, the number of
+    auxiliary primes and the exponents e_j; raises FhesiError naming the failed condition on a refused ring."""
+    total, usable, rho0, naux = _i64(0), _i64(0), _u64(0), _i32(0)
+    _ck(_load().fhesi_slots_plan(m, p, generator, C.byref(total), C.byref(usable), C.byref(rho0), C.byref(naux), None))
+    e = np.zeros(total.value, dtype=np.int32)
+    _ck(_load().fhesi_slots_plan(m, p, generator, None, None, None, None, _p(e)))
+    return {"total": total.value, "usable": usable.value, "rho0": rho0.value, "aux_primes": naux.value, "exps": e}
+
+
+class SlotSpace:
+    """One PlaintextSpace on a context's GPU (fhesi_slots_create): batched EmbedInSlots / DecodeSlots and the slot-valued Encrypt / Decrypt."""
+
+    def __init__(self, ctx: "Context", p: int, generator: int):
+        self.ctx, self.p, self.generator = ctx, p, generator
+        self.h = _vp()
+        _ck(_load().fhesi_slots_create(ctx.h, p, generator, C.byref(self.h)))
+        total, usable, rho0, naux = _i64(0), _i64(0), _u64(0), _i32(0)
+        _ck(_load().fhesi_slots_info(self.h, C.byref(total), C.byref(usable), C.byref(rho0), C.byref(naux)))
+        self.total, self.usable, self.rho0, self.aux_primes = total.value, usable.value, rho0.value, naux.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            _load().fhesi_slots_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def exponents(self) -> np.ndarray:
+        e = np.zeros(self.total, dtype=np.int32)
+        _ck(_load().fhesi_slots_exponents(self.h, _p(e)))
+        return e
+
+    def embed(self, vals: np.ndarray, only_usable: bool = True) -> np.ndarray:
+        """vals [count][nvals] -> message polynomials [count][phi(m)] (EmbedInSlots)."""
+        vals = np.ascontiguousarray(np.atleast_2d(vals), dtype=np.int64)
+        msg = np.zeros((vals.shape[0], self.ctx.phim), dtype=np.int64)
+        _ck(_load().fhesi_slots_embed(self.h, _p(vals), vals.shape[1], int(only_usable), vals.shape[0], _p(msg)))
+        return msg
+
+    def decode(self, msg: np.ndarray, nvals: int = None, only_usable: bool = True) -> np.ndarray:
+        """message polynomials [count][phi(m)] -> slot values [count][nvals] (DecodeSlots)."""
+        msg = np.ascontiguousarray(np.atleast_2d(msg), dtype=np.int64)
+        nvals = self.total if nvals is None else nvals
+        vals = np.zeros((msg.shape[0], nvals), dtype=np.int64)
+        _ck(_load().fhesi_slots_decode(self.h, _p(msg), msg.shape[0], nvals, int(only_usable), _p(vals)))
+        return vals
+
+    def embed_dev(self, vals: DevBuf, nvals: int, count: int, msg: DevBuf, only_usable: bool = True):
+        _ck(_load().fhesi_slots_embed_dev(self.h, vals.ptr, nvals, int(only_usable), count, msg.ptr))
+
+    def decode_dev(self, msg: DevBuf, count: int, nvals: int, vals: DevBuf, only_usable: bool = True):
+        _ck(_load().fhesi_slots_decode_dev(self.h, msg.ptr, count, nvals, int(only_usable), vals.ptr))
+
+    def encrypt_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, vals: np.ndarray, out: DevBuf, nlimbs: int,
+                             only_usable: bool = True):
+        """Plaintext(context, vals[i]) + Encrypt under (seed, first_index + i); the message polynomials stay in HBM."""
+        vals = np.ascontiguousarray(np.atleast_2d(vals), dtype=np.int64)
+        _ck(_load().fhesi_encrypt_slots_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, _p(vals), vals.shape[1], int(only_usable),
+                                                     vals.shape[0], out.ptr, nlimbs))
+
+    def decrypt_batch(self, sk1: "DoubleCRT", logQ: int, ct: DevBuf, nlimbs: int, count: int, nvals: int = None, only_usable: bool = True) -> np.ndarray:
+        nvals = self.total if nvals is None else nvals
+        vals = np.zeros((count, nvals), dtype=np.int64)
+        _ck(_load().fhesi_decrypt_slots_batch(self.ctx.h, self.h, sk1.h, logQ, ct.ptr, nlimbs, count, nvals, int(only_usable), _p(vals)))
+        return vals
+
+    def encrypt_noise_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, count: int, out: DevBuf, nlimbs: int):
+        """Regression::GenerateNoise for `count` masks (slot 0 zero, the others uniform from (seed, index))."""
+        _ck(_load().fhesi_encrypt_noise_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, count, out.ptr, nlimbs))
 
 
 class DoubleCRT:

@@ -91,9 +91,19 @@ extern "C" int fhesi_ct_gather_dev(fhesi_ctx* c, const uint64_t* pool, const int
 // --------------------------------------------------------------------------------------------- Encrypt / Decrypt batches
 // FHESIPubKey::Encrypt (FHE-SI.cpp:10-36) for `count` plaintexts; the randomness is the caller's (the reference draws it from NTL's
 // PRNG): rand_host = [count][3][phi(m)] int64 = (r binary, e0, e1 Gaussian samples before the multiplication by p)
+// Where the message polynomials of a batch come from: the caller's coefficient arrays, or slot values embedded on the device
+// (kernels_slots.hip) straight into the message staging buffer -- given by the caller, or drawn there as noise masks.
+struct MsgSource {
+  const int64_t* msg_host = nullptr;   // [count][phi(m)] coefficient form (slots == nullptr)
+  fhesi_slots* slots = nullptr;
+  const int64_t* vals_host = nullptr;  // [count][nvals] slot values; nullptr with slots set: Regression::GenerateNoise masks from (seed, index)
+  i64 nvals = 0;
+  bool only_usable = true;
+};
 static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, const int64_t* rand_host, bool seeded, u64 seed, u64 first,
-                              const int64_t* msg_host, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+                              const MsgSource& src, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
   CHECK_CTX(c);
+  if (src.slots && src.slots->ctx != c) FHESI_FAIL("Encrypt: the plaintext space belongs to another context");
   if (!pk0 || !pk1 || pk0->ctx != c || pk1->ctx != c) FHESI_FAIL("Encrypt: public key belongs to another context");
   if ((int)pk0->idx.size() != c->L || (int)pk1->idx.size() != c->L) FHESI_FAIL("Encrypt: public key must be defined over all primes");
   if (logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("Encrypt: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
@@ -115,7 +125,19 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
     if (logQ == 64 * nlimbs) { /* 2^logQ needs limb nlimbs: redo with the extra limb */ rem = 1; for (int i = nlimbs - 1; i >= 0; --i) { const u128 cur = rem << 64; delta[i] = (u64)(cur / p); rem = cur % p; } } }
   if (seeded) FHESI_TRY(launch_sample_encrypt(c, (i64*)d_small, count, seed, first));      // r, e0, e1 drawn in HBM (kernels_sample.hip)
   else HIP_TRY(hipMemcpyAsync(d_small, rand_host, (size_t)count * 3 * n * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_msg, msg_host, (size_t)count * n * 8, hipMemcpyHostToDevice, c->stream));
+  if (!src.slots) HIP_TRY(hipMemcpyAsync(d_msg, src.msg_host, (size_t)count * n * 8, hipMemcpyHostToDevice, c->stream));
+  else {
+    void* d_vals;
+    if (src.vals_host) {
+      FHESI_TRY(ws_reserve(c, 9, (size_t)count * src.nvals * 8, &d_vals));
+      HIP_TRY(hipMemcpyAsync(d_vals, src.vals_host, (size_t)count * src.nvals * 8, hipMemcpyHostToDevice, c->stream));
+      FHESI_TRY(slots_embed_rows(src.slots, (const i64*)d_vals, src.nvals, src.only_usable, count, (i64*)d_msg));
+    } else {      // slot 0 zero, the others uniform (Regression.h:181-185); all phi(m) slots embedded (:188)
+      FHESI_TRY(ws_reserve(c, 9, (size_t)count * n * 8, &d_vals));
+      FHESI_TRY(slots_noise_rows(src.slots, seed, first, count, (i64*)d_vals));
+      FHESI_TRY(slots_embed_rows(src.slots, (const i64*)d_vals, n, false, count, (i64*)d_msg));
+    }
+  }
   HIP_TRY(hipMemcpyAsync(d_delta, delta.data(), (size_t)nlimbs * 8, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_pk, pk0->d_rows, (size_t)L * n * 8, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync((u64*)d_pk + (size_t)L * n, pk1->d_rows, (size_t)L * n * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -136,18 +158,43 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
 extern "C" int fhesi_encrypt_batch(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, const int64_t* rand_host,
                                    const int64_t* msg_host, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
   if (!rand_host) FHESI_FAIL("Encrypt: null randomness (fhesi_encrypt_batch_seeded draws it on the device)");
-  return encrypt_batch_impl(c, pk0, pk1, logQ, p, rand_host, false, 0, 0, msg_host, count, out_dev, nlimbs);
+  MsgSource src;
+  src.msg_host = msg_host;
+  return encrypt_batch_impl(c, pk0, pk1, logQ, p, rand_host, false, 0, 0, src, count, out_dev, nlimbs);
 }
 // ... with the randomness drawn on the device: plaintext i takes the streams of object index first_index + i (philox.h)
 extern "C" int fhesi_encrypt_batch_seeded(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, uint64_t seed, uint64_t first_index,
                                           const int64_t* msg_host, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
-  return encrypt_batch_impl(c, pk0, pk1, logQ, p, nullptr, true, seed, first_index, msg_host, count, out_dev, nlimbs);
+  MsgSource src;
+  src.msg_host = msg_host;
+  return encrypt_batch_impl(c, pk0, pk1, logQ, p, nullptr, true, seed, first_index, src, count, out_dev, nlimbs);
+}
+// ... of plaintexts given as slot values (Plaintext(context, vector) + Encrypt): the message polynomials are embedded on the device and never
+// leave HBM.  Bit for bit fhesi_encrypt_batch_seeded(fhesi_slots_embed(vals)) under the same (seed, index).
+extern "C" int fhesi_encrypt_slots_batch_seeded(fhesi_ctx* c, fhesi_slots* s, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                                const int64_t* vals_host, int64_t nvals, int32_t only_usable, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+  if (!s) FHESI_FAIL("Encrypt: null plaintext space");
+  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
+  if (nvals < 1 || nvals > s->S.phim) FHESI_FAIL("Encrypt: %lld values per plaintext, the ring has %lld slots", (long long)nvals, (long long)s->S.phim);
+  MsgSource src;
+  src.slots = s; src.vals_host = vals_host; src.nvals = nvals; src.only_usable = only_usable != 0;
+  return encrypt_batch_impl(c, pk0, pk1, logQ, s->S.p, nullptr, true, seed, first_index, src, count, out_dev, nlimbs);
+}
+// Regression::GenerateNoise (Regression.h:180-191) for `count` masks: slot 0 is 0, slots 1 .. phi(m)-1 are uniform on [0, p), drawn on the device
+// from (seed, first_index + i, slot, purpose 7) (philox.h); all phi(m) slots embedded, then an ordinary encryption under the same (seed, index)
+extern "C" int fhesi_encrypt_noise_batch_seeded(fhesi_ctx* c, fhesi_slots* s, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                                int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+  if (!s) FHESI_FAIL("GenerateNoise: null plaintext space");
+  MsgSource src;
+  src.slots = s;
+  return encrypt_batch_impl(c, pk0, pk1, logQ, s->S.p, nullptr, true, seed, first_index, src, count, out_dev, nlimbs);
 }
 
 // FHESISecKey::Decrypt (FHE-SI.cpp:93-119) of `count` unscaled 2-part ciphertexts [count][2][phi(m)][nlimbs] in HBM
-extern "C" int fhesi_decrypt_batch(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
-                                   int64_t* msg_host) {
+static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                              int64_t* msg_host, fhesi_slots* slots, i64 nvals, bool only_usable, int64_t* vals_host) {
   CHECK_CTX(c);
+  if (slots && slots->ctx != c) FHESI_FAIL("Decrypt: the plaintext space belongs to another context");
   if (!sk1 || sk1->ctx != c) FHESI_FAIL("Decrypt: secret key belongs to another context");
   if ((int)sk1->idx.size() != c->L) FHESI_FAIL("Decrypt: secret key must be defined over all primes");
   if (logQ < 1 || nlimbs < 1) FHESI_FAIL("Decrypt: bad shape");
@@ -169,9 +216,26 @@ extern "C" int fhesi_decrypt_batch(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t 
   FHESI_TRY(get_crt_tables(c, all, &t));
   FHESI_TRY(launch_crt(c, t, (const u64*)d_z, L, nullptr, count, 0, 0, 0, (u64*)d_big, nw));                         // toPoly, low logQ+1 bits kept
   FHESI_TRY(launch_decrypt_round(c, (const u64*)d_big, count * n, nw, logQ, p, (i64*)d_msg));                        // round(p z / q) mod p (:110-116)
-  HIP_TRY(hipMemcpyAsync(msg_host, d_msg, (size_t)count * n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (!slots) HIP_TRY(hipMemcpyAsync(msg_host, d_msg, (size_t)count * n * 8, hipMemcpyDeviceToHost, c->stream));
+  else {          // DecodeSlots on the message polynomials where they are
+    void* d_vals;
+    FHESI_TRY(ws_reserve(c, 9, (size_t)count * nvals * 8, &d_vals));
+    FHESI_TRY(slots_decode_rows(slots, (const i64*)d_msg, count, nvals, only_usable, (i64*)d_vals));
+    HIP_TRY(hipMemcpyAsync(vals_host, d_vals, (size_t)count * nvals * 8, hipMemcpyDeviceToHost, c->stream));
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+extern "C" int fhesi_decrypt_batch(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                                   int64_t* msg_host) {
+  return decrypt_batch_impl(c, sk1, logQ, p, ct_dev, nlimbs, count, msg_host, nullptr, 0, true, nullptr);
+}
+// ... followed by Plaintext::DecodeSlots (Test_Regression.cpp:47-58: Decrypt, DecodeSlots, msgs[0]): vals_host [count][nvals]
+extern "C" int fhesi_decrypt_slots_batch(fhesi_ctx* c, fhesi_slots* s, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                                         int64_t nvals, int32_t only_usable, int64_t* vals_host) {
+  if (!s) FHESI_FAIL("Decrypt: null plaintext space");
+  if (nvals < 1 || nvals > s->S.phim) FHESI_FAIL("Decrypt: %lld values per plaintext, the ring has %lld slots", (long long)nvals, (long long)s->S.phim);
+  return decrypt_batch_impl(c, sk1, logQ, s->S.p, ct_dev, nlimbs, count, nullptr, s, nvals, only_usable != 0, vals_host);
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

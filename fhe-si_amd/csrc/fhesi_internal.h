@@ -156,6 +156,8 @@ struct fhesi_ctx {
   //   6 row transforms above 2^14 (two-pass, bit reversal)   7 Bluestein slot map / wave operands
   //   8 Bluestein convolution buffer, index lists        9 Bluestein inverse output, scalar lists (no Bluestein call in between)
   //   10 auxiliary-prime dot product output (kernels_ksaux.hip)      11 staging of host batches (fhesi_ct_mul_relin_batch)
+  //   (kernels_slots.hip borrows 8 for its convolution buffer, 9 for slot values and 5 for message polynomials: before the transforms of an
+  //   encryption start, after those of a decryption are done)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -265,7 +267,38 @@ std::vector<i64> cyclotomic_cofactor(i64 m);     // (X^m - 1) / Phi_m
 bool is_primitive_2m_root(u64 root, i64 m, u64 q);
 u64 bn_mod(const u64* limbs, int nlimbs, u64 q);          // signed two's complement -> [0,q)  (role of NTL rem(ZZ,long))
 std::vector<u64> bn_mul_small(const std::vector<u64>& a, u64 b);   // non-negative
+// plaintext slots for p prime, p = 1 mod m, (Z/m)^* cyclic (PlaintextSpace::Init): slot j <-> root rho0^(exps[j]), exps[j] = g^j mod m
+struct SlotSpace {
+  i64 m = 0, phim = 0, usable = 0;     // usable = 2^floor(log2 phi(m))  (PlaintextSpace.cpp:37-42)
+  u64 p = 0, g = 0, rho0 = 0;          // rho0 = least primitive m-th root of unity in [1, p)
+  int kind = 0;                        // 0: m = q^k (q prime; 2 and 4 included), 1: m = 2 q^k (q odd)
+  i64 q = 0, s = 0;                    // Phi_m(X) = Phi_q(+-X^s)
+  int naux = 1;                        // auxiliary primes the exact chirp convolution needs (m p^2 against 2^59)
+  std::vector<int> exps, slot_of_exp;  // [phim], [m] (-1 off Z_m^*)
+};
+const char* slot_space(i64 m, u64 p, i64 g, SlotSpace* out);     // nullptr, or the condition that refuses the ring
 }  // namespace hm
+
+// --------------------------------------------------------------------------------- plaintext slots (kernels_slots.hip)
+// One PlaintextSpace (PlaintextSpace.h): the tables of the length-m DFT modulo the plaintext prime that embeds / decodes slot values.
+struct fhesi_slots {
+  fhesi_ctx* ctx = nullptr;
+  hm::SlotSpace S;
+  fhesi_ctx* aux = nullptr;            // internal power-of-two context of N points over the one or two auxiliary primes
+  i64 N = 0;
+  u64 P[2] = {0, 0};
+  Shoup2* d_pre = nullptr;             // [2][m]  rho0^T'(i) (decode), rho0^-T'(i) (embed) modulo p, T'(i) = i (i + 1) / 2
+  Shoup2* d_post = nullptr;            // [2][m]  rho0^T(k), rho0^-T(k) / m modulo p, T(k) = k (k - 1) / 2
+  u64* d_bhat = nullptr;               // [2][naux][N] transforms of the chirps rho0^-+T(d), d = -(m-1) .. m-1
+  int* d_exps = nullptr;               // [phim] e_j = g^j mod m
+  int* d_slot_of_exp = nullptr;        // [m] inverse table, -1 off Z_m^*
+  bool orderfree = false;
+};
+// d_vals [count][nvals] int64 (any sign; reduced modulo p) <-> d_msg [count][phi(m)] int64 in [0, p).  Slots at or above min(nvals, cap), cap =
+// usable or phi(m), are zero on embed and written as zero on decode.  Everything is enqueued on the context's stream.
+int slots_embed_rows(fhesi_slots* s, const i64* d_vals, i64 nvals, bool only_usable, i64 count, i64* d_msg);
+int slots_decode_rows(fhesi_slots* s, const i64* d_msg, i64 count, i64 nvals, bool only_usable, i64* d_vals);
+int slots_noise_rows(fhesi_slots* s, u64 seed, u64 first, i64 count, i64* d_vals /* [count][phi(m)] */);      // Regression::GenerateNoise's randVec
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

@@ -157,6 +157,83 @@ bool is_primitive_2m_root(u64 root, i64 m, u64 q) {
   return true;
 }
 
+// ---- plaintext slots (PlaintextSpace::Init / FindSlots / ReorderSlots, PlaintextSpace.cpp:20-110) for p prime, p = 1 mod m: Phi_m splits
+// into linear factors X - r over Z_p, slot j sits on the root rho0^(g^j mod m).  Everything here is O(m) and runs once per slot space.
+static std::vector<u64> prime_factors(u64 n) {
+  std::vector<u64> f;
+  for (u64 d = 2; d * d <= n; ++d)
+    if (n % d == 0) { f.push_back(d); while (n % d == 0) n /= d; }
+  if (n > 1) f.push_back(n);
+  return f;
+}
+// 0, or why the ring is refused (each message names the failed condition)
+const char* slot_space(i64 m, u64 p, i64 g, SlotSpace* out) {
+  if (m < 2 || m > (1 << 20)) return "m outside [2, 2^20]";
+  if (p >= (1ull << 32)) return "plaintext modulus p >= 2^32 (slot arithmetic is 32-bit)";
+  if (!is_prime(p)) return "plaintext modulus p is not prime (p^r and composite moduli are not supported)";
+  if ((p - 1) % (u64)m != 0) return "p != 1 mod m: ord_m(p) > 1, the slots would live in an extension field GF(p^d)";
+  // (Z/m)^* cyclic  <=>  m = 2, 4, q^k or 2 q^k with q an odd prime
+  SlotSpace S;
+  S.m = m; S.p = p;
+  {
+    i64 odd = m;
+    int twos = 0;
+    while (odd % 2 == 0) { odd /= 2; ++twos; }
+    const std::vector<u64> f = prime_factors((u64)odd);
+    if (odd == 1) {
+      if (twos > 2) return "(Z/m)^* is not cyclic (m = 2^k, k >= 3): no single generator walks all slots";
+      S.kind = 0; S.q = 2;
+    } else {
+      if (f.size() != 1 || twos > 1) return "(Z/m)^* is not cyclic (m is not 2, 4, q^k or 2 q^k): no single generator walks all slots";
+      S.kind = twos; S.q = (i64)f[0];
+    }
+    S.s = (S.kind ? m / 2 : m) / S.q;
+    S.phim = (S.q - 1) * S.s;
+  }
+  const i64 n = S.phim;
+  S.usable = 1;
+  while (S.usable * 2 <= n) S.usable *= 2;
+  // g generates (Z/m)^*: coprime to m and of order phi(m)  (PlaintextSpace.cpp:103 asserts that the walk visits every slot)
+  {
+    const u64 gm = (u64)(((g % m) + m) % m);
+    bool ok = gcd(gm, (u64)m) == 1;
+    if (ok && n > 1)
+      for (u64 f : prime_factors((u64)n)) ok = ok && powmod(gm, (u64)n / f, (u64)m) != 1;
+    if (!ok) return "the generator does not generate (Z/m)^*: its powers do not reach every slot";
+    S.g = gm;
+  }
+  // rho0 = the least integer in [1, p) of multiplicative order m: the primitive m-th roots are z^j, gcd(j, m) = 1, for any z of order m
+  {
+    const std::vector<u64> fm = prime_factors((u64)m);
+    u64 z = 0;
+    for (u64 h = 2; h < p; ++h) {
+      const u64 c = powmod(h, (p - 1) / (u64)m, p);
+      bool ok = true;
+      for (u64 f : fm) ok = ok && powmod(c, (u64)m / f, p) != 1;
+      if (ok) { z = c; break; }
+    }
+    if (!z) return "no element of order m modulo p";
+    u64 best = p, x = 1;
+    for (i64 j = 1; j < m; ++j) {
+      x = mulmod(x, z, p);
+      if (gcd((u64)j, (u64)m) == 1 && x < best) best = x;
+    }
+    S.rho0 = best;
+  }
+  S.exps.resize(n);
+  S.slot_of_exp.assign(m, -1);
+  u64 e = 1 % (u64)m;
+  for (i64 j = 0; j < n; ++j) {
+    S.exps[j] = (int)e;
+    S.slot_of_exp[e] = (int)j;
+    e = mulmod(e, S.g, (u64)m);
+  }
+  // the chirp convolution has at most m terms below p^2: one auxiliary prime near 2^60 holds it exactly when m p^2 < 2^59, else two
+  S.naux = ((u128)m * p * p < ((u128)1 << 59)) ? 1 : 2;
+  *out = S;
+  return nullptr;
+}
+
 u64 bn_mod(const u64* limbs, int nlimbs, u64 q) {
   bool neg = limbs[nlimbs - 1] >> 63;
   u64 r = 0;

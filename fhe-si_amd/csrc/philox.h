@@ -7,6 +7,7 @@
 //               counter = (coefficient index j, object index low word, object index high word, purpose << 16 | block)
 //   purposes    0 binary polynomial r of Encrypt (FHE-SI.cpp:14-18)    1, 2 noise of ciphertext part 0, 1 (:24-25)
 //               3 random polynomial of a key-switch column (:176-179)   4 its error (:190)   5 sampleHWt draws   6 DoubleCRT::sampleGaussian
+//               7 slot values of a noise mask (Regression::GenerateNoise, Regression.h:180-191); the coefficient index is the slot index
 //   binary      word 0, bit 0
 //   Gaussian    the distribution of round(N(0, 3.2^2)) -- what sampleGaussian's Box-Muller + floor(x + 0.5) produces (NumbTh.cpp:377-404 with
 //               FHEContext.h:106's stdev) -- by inversion in INTEGER arithmetic: u = word0 | word1 << 32, magnitude = number of table
@@ -14,6 +15,8 @@
 //               anywhere, so host and device agree bit for bit.
 //   uniform     SampleRandom(poly, 2^logQ, n) (Util.cpp:49-55: RandomBnd(q) - q / 2): logQ random bits taken limb by limb from blocks
 //               0, 1, ... (limb i = words 2 (i mod 2), 2 (i mod 2) + 1 of block i / 2), minus 2^(logQ-1)
+//   slot mask   slot 0 is 0; slot j >= 1 is floor(u p / 2^64) with u = word0 | word1 << 32 of block 0: uniform on [0, p) up to a bias below
+//               p / 2^64 (p < 2^32: below 2^-32 per value)
 //   sampleHWt   draw t = 0, 1, ...: position (word0 | word1 << 32) mod n, value +1 if word 2 bit 0 else -1, kept when the position is
 //               still zero, until Hwt positions are set (NumbTh.cpp:340-360)
 //
@@ -41,7 +44,7 @@ PHILOX_HD Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t 
   }
   return Philox4{{c0, c1, c2, c3}};
 }
-enum { PHX_BINARY = 0, PHX_NOISE0 = 1, PHX_NOISE1 = 2, PHX_KEY_POLY = 3, PHX_KEY_ERR = 4, PHX_HWT = 5, PHX_GAUSS = 6 };
+enum { PHX_BINARY = 0, PHX_NOISE0 = 1, PHX_NOISE1 = 2, PHX_KEY_POLY = 3, PHX_KEY_ERR = 4, PHX_HWT = 5, PHX_GAUSS = 6, PHX_SLOT_NOISE = 7 };
 PHILOX_HD Philox4 phx_draw(uint64_t seed, uint64_t object, uint32_t j, uint32_t purpose, uint32_t block) {
   return philox4x32_10(j, (uint32_t)object, (uint32_t)(object >> 32), purpose << 16 | block, (uint32_t)seed, (uint32_t)(seed >> 32));
 }

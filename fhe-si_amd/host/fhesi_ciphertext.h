@@ -1,5 +1,5 @@
 // fhesi_ciphertext.h -- part of the C++ mirror of the reference's class surface (see fhesi_host.h, which includes the parts in order; not a
-// standalone header): CiphertextPart / CtParts / Ciphertext (Ciphertext.h, Ciphertext.cpp) -- recording its operations on device-resident values (fhesi_engine.h) -- and Plaintext (coefficient form).
+// standalone header): CiphertextPart / CtParts / Ciphertext (Ciphertext.h, Ciphertext.cpp) -- recording its operations on device-resident values (fhesi_engine.h) -- and Plaintext (Plaintext.h).
 #pragma once
 
 namespace fhesi {
@@ -255,7 +255,39 @@ class Ciphertext {
   }
 };
 
-// ---------------------------------------------------------------- Plaintext (coefficient form only; slot packing is out of scope)
-struct Plaintext { std::vector<long> message; };
+// ---------------------------------------------------------------- Plaintext (Plaintext.h:10-125)
+// `message` is the coefficient form (the reference's ZZ_pX), as machine words in [0, p).  A default-constructed Plaintext is a bare message
+// (`Plaintext P; P.message = ...`); the slot methods need the context (constructor argument, or activeContext as in Plaintext.h:12) and go
+// through its PlaintextSpace, i.e. through the device (fhesi_slots_embed / fhesi_slots_decode).
+struct Plaintext {
+  std::vector<long> message;
+  const FHEcontext* context = nullptr;
+  Plaintext() {}
+  explicit Plaintext(const FHEcontext& c) : context(&c) {}
+  Plaintext(const FHEcontext& c, const std::vector<long>& msgs) : context(&c) { EmbedInSlots(msgs); }                // Plaintext.h:30-31 -> Init(vector) :40-47
+  Plaintext(const FHEcontext& c, const std::vector<ZZ>& msgs) : context(&c) { std::vector<long> v; for (auto& z : msgs) v.push_back(rem(z, c.ModulusP().to_long())); EmbedInSlots(v); }
+  const FHEcontext& ctx() const { const FHEcontext* c = context ? context : activeContext; if (!c) Error("Plaintext: no context"); return *c; }
+  void EmbedInSlots(const std::vector<long>& msgs, bool onlyUsable = true) { ctx().GetPlaintextSpace().EmbedInSlots(message, msgs, onlyUsable); }
+  void DecodeSlots(std::vector<long>& msgBatch, bool onlyUsable = true) const { ctx().GetPlaintextSpace().DecodeSlots(msgBatch, message, onlyUsable); }
+  void DecodeSlot(long& val, unsigned slot) const { ctx().GetPlaintextSpace().DecodeSlot(val, message, slot); }
+  bool operator==(const Plaintext& o) const { return padded(message) == padded(o.message); }
+  Plaintext& operator+=(const Plaintext& o) { return combine(o, +1); }                                                  // Plaintext.h:68-78
+  Plaintext& operator-=(const Plaintext& o) { return combine(o, -1); }
+  Plaintext& operator>>=(long k) {          // Plaintext.h:87-96: decode all slots, rotated[(i + n - k) % n] = plain[i], embed all slots
+    std::vector<long> plain; DecodeSlots(plain, false);
+    const long n = (long)plain.size(); std::vector<long> rotated(n);
+    for (long i = 0; i < n; ++i) rotated[(((i - k) % n) + n) % n] = plain[i];
+    EmbedInSlots(rotated, false);
+    return *this;
+  }
+ private:
+  std::vector<long> padded(const std::vector<long>& v) const { std::vector<long> r = v; r.resize(ctx().zMstar.phiM(), 0); return r; }
+  Plaintext& combine(const Plaintext& o, long sign) {
+    const long p = ctx().ModulusP().to_long(); const size_t n = ctx().zMstar.phiM();
+    message.resize(n, 0);
+    for (size_t i = 0; i < n && i < o.message.size(); ++i) message[i] = (((message[i] + sign * o.message[i]) % p) + p) % p;
+    return *this;
+  }
+};
 
 }  // namespace fhesi

@@ -1,5 +1,5 @@
 // fhesi_context.h -- part of the C++ mirror of the reference's class surface (see fhesi_host.h, which includes the parts in order; not a
-// standalone header): IndexSet (IndexSet.h:26-127), PAlgebra (PAlgebra.h:53-88), Cmodulus (CModulus.h:42-170) and FHEcontext (FHEContext.h:40-205, FHEContext.cpp): the prime chain and the handle of the HIP context.
+// standalone header): IndexSet (IndexSet.h:26-127), PAlgebra (PAlgebra.h:53-88), Cmodulus (CModulus.h:42-170), PlaintextSpace (PlaintextSpace.h) and FHEcontext (FHEContext.h:40-205, FHEContext.cpp): the prime chain and the handle of the HIP context.
 #pragma once
 
 namespace fhesi {
@@ -72,10 +72,67 @@ class Cmodulus {
   void iFFT(ZZX& x, const vec_long& y) const;   // x = FFT^{-1}(y)  (CModulus.cpp:110-132)
 };
 
+// ---------------------------------------------------------------- PlaintextSpace (PlaintextSpace.h:10-44, PlaintextSpace.cpp) on a fhesi_slots handle
+// Slot values are elements of Z_p held as machine words (the reference's vector<ZZ_pX> of constants).  Rings the device layer refuses
+// (include/fhesi_hip.h, "plaintext slots": p not prime, p >= 2^32, p != 1 mod m, no generator of (Z/m)^*) raise the library's message.
+class PlaintextSpace {
+  fhesi_slots* h = nullptr;
+  long total = 0, usable = 0, phim = 0;
+  unsigned long rho0 = 0;
+  // bound where the handle is made: the destructor (reached from ~FHEcontext in every program) then names no slot entry point, so a program
+  // that never creates a slot space links against an ABI without them (the host-memory stand-in of the CPU-only harness)
+  int (*release)(fhesi_slots*) = nullptr;
+ public:
+  PlaintextSpace(fhesi_ctx* ctx, unsigned long p, unsigned generator) {        // Init(PhiX, p, generator) :53-56
+    ck(fhesi_slots_create(ctx, (uint64_t)p, (int64_t)generator, &h));
+    release = &fhesi_slots_free;
+    int64_t t = 0, u = 0; uint64_t r = 0; int32_t na = 0;
+    ck(fhesi_slots_info(h, &t, &u, &r, &na));
+    total = (long)t; usable = (long)u; rho0 = (unsigned long)r; phim = (long)t;
+  }
+  ~PlaintextSpace() { if (h) release(h); }
+  PlaintextSpace(const PlaintextSpace&) = delete;
+  PlaintextSpace& operator=(const PlaintextSpace&) = delete;
+  unsigned GetUsableSlots() const { return (unsigned)usable; }
+  unsigned GetTotalSlots() const { return (unsigned)total; }
+  unsigned long Rho0() const { return rho0; }                                   // slot j sits on the root rho0^(g^j mod m)
+  fhesi_slots* handle() const { return h; }
+  // many plaintexts in one device call: msgs[i] holds at most usable (onlyUsable) / total values, missing slots are 0
+  void EmbedInSlots(std::vector<std::vector<long>>& embedded, const std::vector<std::vector<long>>& msgs, bool onlyUsable = true) const {
+    const long count = (long)msgs.size(), cap = onlyUsable ? usable : total;
+    long nvals = 1;
+    for (auto& v : msgs) nvals = std::max(nvals, std::min((long)v.size(), cap));
+    std::vector<int64_t> vals((size_t)count * nvals, 0), out((size_t)count * phim);
+    for (long c = 0; c < count; ++c) for (long j = 0; j < nvals && j < (long)msgs[c].size(); ++j) vals[c * nvals + j] = msgs[c][j];
+    ck(fhesi_slots_embed(h, vals.data(), nvals, onlyUsable ? 1 : 0, count, out.data()));
+    embedded.assign(count, std::vector<long>());
+    for (long c = 0; c < count; ++c) embedded[c].assign(out.begin() + c * phim, out.begin() + (c + 1) * phim);
+  }
+  void DecodeSlots(std::vector<std::vector<long>>& msgBatch, const std::vector<std::vector<long>>& msgs, bool onlyUsable = true) const {
+    const long count = (long)msgs.size();
+    std::vector<int64_t> in((size_t)count * phim, 0), out((size_t)count * total);
+    for (long c = 0; c < count; ++c) for (long j = 0; j < phim && j < (long)msgs[c].size(); ++j) in[c * phim + j] = msgs[c][j];
+    ck(fhesi_slots_decode(h, in.data(), count, total, onlyUsable ? 1 : 0, out.data()));
+    msgBatch.assign(count, std::vector<long>());
+    for (long c = 0; c < count; ++c) msgBatch[c].assign(out.begin() + c * total, out.begin() + (c + 1) * total);      // totalSlots entries, the first usable filled (:123-129)
+  }
+  void EmbedInSlots(std::vector<long>& embedded, const std::vector<long>& msgs, bool onlyUsable = true) const {       // :112-121
+    std::vector<std::vector<long>> e; EmbedInSlots(e, std::vector<std::vector<long>>(1, msgs), onlyUsable); embedded = e[0];
+  }
+  void DecodeSlots(std::vector<long>& msgBatch, const std::vector<long>& msg, bool onlyUsable = true) const {         // :123-129
+    std::vector<std::vector<long>> d; DecodeSlots(d, std::vector<std::vector<long>>(1, msg), onlyUsable); msgBatch = d[0];
+  }
+  void DecodeSlot(long& val, const std::vector<long>& msg, unsigned ind) const {                                        // :131-133
+    if ((long)ind >= total) Error("PlaintextSpace::DecodeSlot: no such slot");
+    std::vector<long> d; DecodeSlots(d, msg, false); val = d[ind];
+  }
+};
+
 // ---------------------------------------------------------------- FHEcontext (FHEContext.h:40-205, FHEContext.cpp)
 class FHEcontext {
   std::vector<Cmodulus> moduli;
   mutable fhesi_ctx* dev = nullptr;
+  mutable std::unique_ptr<PlaintextSpace> ptxtSpace;     // created on first use (GetPlaintextSpace): contexts that never ask behave as before
   ZZ ptxtP;
   unsigned generator = 0;
   int device;
@@ -88,7 +145,7 @@ class FHEcontext {
   unsigned logQ = 0, decompSize = 3, ndigits = 0;
 
   FHEcontext(unsigned m, unsigned logQ_, unsigned p, unsigned gen, unsigned decomp = 3, int device_ = 0) : device(device_) { Init(m, logQ_, ZZ((long)p), gen, decomp); }
-  ~FHEcontext() { drop_ct_engine(this); if (dev) fhesi_ctx_destroy(dev); }
+  ~FHEcontext() { drop_ct_engine(this); ptxtSpace.reset(); if (dev) fhesi_ctx_destroy(dev); }
   FHEcontext(const FHEcontext&) = delete;
   void Init(unsigned m, unsigned logQ_, const ZZ& p, unsigned gen, unsigned decomp = 3) {   // FHEContext.h:105-118
     m_ = m; logQ = logQ_; modulusQ = ZZ(1L) << (long)logQ_; decompSize = decomp;
@@ -100,6 +157,11 @@ class FHEcontext {
     zMstar.init(m, gen, idx, std::vector<int64_t>());
   }
   unsigned Generator() const { return generator; }
+  // FHEContext.h:127: the slot structure of ModulusP() and Generator(); the rings outside the device layer's scope raise its message here
+  const PlaintextSpace& GetPlaintextSpace() const {
+    if (!ptxtSpace) ptxtSpace.reset(new PlaintextSpace(handle(), (unsigned long)ptxtP.to_long(), generator));
+    return *ptxtSpace;
+  }
   const ZZ& ModulusP() const { return ptxtP; }
   long ithPrime(unsigned i) const { return i < moduli.size() ? moduli[i].getQ() : 0; }
   const Cmodulus& ithModulus(unsigned i) const { return moduli[i]; }

@@ -40,6 +40,34 @@ class FHESISecKey {
     ptxts.assign(count, Plaintext());
     for (long c = 0; c < count; ++c) ptxts[c].message.assign(msg.begin() + c * n, msg.begin() + (c + 1) * n);
   }
+  // Decrypt + Plaintext::DecodeSlots (Test_Regression.cpp:47-58) for many ciphertexts in one device call (fhesi_decrypt_slots_batch): the
+  // message polynomials never leave HBM.  vals[i] has nvals entries (0 = all phi(m) slots), the first min(nvals, usable or total) filled.
+  void DecryptSlotsBatch(std::vector<std::vector<long>>& vals, const std::vector<Ciphertext>& ctxts, long nvals = 0, bool onlyUsable = true) const {
+    const PlaintextSpace& ps = context.GetPlaintextSpace();
+    const long n = context.zMstar.phiM(), count = (long)ctxts.size(); const int nl = (int)((context.logQ + 63) / 64);
+    if (nvals <= 0) nvals = ps.GetTotalSlots();
+    std::vector<int64_t> out((size_t)count * nvals);
+    if (LazyCiphertexts() && count) {
+      CtEngine& e = ct_engine(context);
+      std::vector<CtRef> v; for (auto& c : ctxts) v.push_back(c.device_value());
+      e.flush();
+      std::vector<int32_t> idx; for (auto& x : v) { e.force(x); idx.push_back((int32_t)x->slot); }
+      const long run = e.alloc_run(count);
+      ck(fhesi_ct_gather_dev(e.h, e.pool(), idx.data(), count, e.words, e.ptr(run)));
+      int rc = fhesi_decrypt_slots_batch(e.h, ps.handle(), sKeys[1].handle(), (int32_t)context.logQ, e.ptr(run), nl, count, nvals, onlyUsable ? 1 : 0, out.data());
+      e.free_run(run, count);
+      ck(rc);
+    } else if (count) {
+      std::vector<uint64_t> host((size_t)count * 2 * n * nl);
+      for (long c = 0; c < count; ++c) for (int part = 0; part < 2; ++part) for (long j = 0; j < n; ++j) coeff(ctxts[c].GetPart((unsigned)part).poly, j).to_limbs(&host[((c * 2 + part) * n + j) * nl], nl);
+      void* dev; ck(fhesi_dev_alloc(context.handle(), host.size() * 8, &dev)); ck(fhesi_dev_upload(context.handle(), dev, host.data(), host.size() * 8));
+      int rc = fhesi_decrypt_slots_batch(context.handle(), ps.handle(), sKeys[1].handle(), (int32_t)context.logQ, (const uint64_t*)dev, nl, count, nvals, onlyUsable ? 1 : 0, out.data());
+      fhesi_dev_free(context.handle(), dev);
+      ck(rc);
+    }
+    vals.assign(count, std::vector<long>());
+    for (long c = 0; c < count; ++c) vals[c].assign(out.begin() + c * nvals, out.begin() + (c + 1) * nvals);
+  }
   void Decrypt(Plaintext& ptxt, const Ciphertext& ctxt) const {   // FHE-SI.cpp:93-119
     if (LazyCiphertexts() && !ctxt.isScaledUp() && ctxt.parts.resident() && sKeys.size() == 2) {
       // the ciphertext lives in HBM: the same dot product with (1, t), rounding and reduction as ONE device call on it (fhesi_decrypt_batch)
@@ -140,6 +168,55 @@ class FHESIPubKey {
     ctxts.assign(count, Ciphertext(context));
     for (long c = 0; c < count; ++c) { ctxts[c].Initialize(2, context); for (int part = 0; part < 2; ++part) limbs_to_poly(ctxts[c][part].poly, &host[((size_t)(c * 2 + part) * n) * nl], n, nl); }
   }
+  // Plaintext(context, vals[i]) + Encrypt for a whole batch, the message polynomials embedded on the device and kept in HBM
+  // (fhesi_encrypt_slots_batch_seeded); the same ciphertexts as EncryptBatchSeeded on the embedded plaintexts under the same (seed, index).
+  // vals[i] holds at most usable (onlyUsable) / total slot values, missing slots are 0.
+  void EncryptSlotsBatchSeeded(std::vector<Ciphertext>& ctxts, const std::vector<std::vector<long>>& vals, SeedSequence& seq, bool onlyUsable = true) const {
+    EncryptSlotsBatchSeeded(ctxts, vals, seq.seed, seq.take(vals.size()), onlyUsable);
+  }
+  void EncryptSlotsBatchSeeded(std::vector<Ciphertext>& ctxts, const std::vector<std::vector<long>>& vals, uint64_t seed, uint64_t first_obj, bool onlyUsable = true) const {
+    const PlaintextSpace& ps = context.GetPlaintextSpace();
+    const long count = (long)vals.size(), cap = onlyUsable ? ps.GetUsableSlots() : ps.GetTotalSlots();
+    long nvals = 1;
+    for (auto& v : vals) nvals = std::max(nvals, std::min((long)v.size(), cap));
+    std::vector<int64_t> flat((size_t)count * nvals, 0);
+    for (long c = 0; c < count; ++c) for (long j = 0; j < nvals && j < (long)vals[c].size(); ++j) flat[c * nvals + j] = vals[c][j];
+    encrypt_on_device(ctxts, count, [&](fhesi_ctx* h, uint64_t* out, int nl) {
+      return fhesi_encrypt_slots_batch_seeded(h, ps.handle(), publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, seed, first_obj, flat.data(), nvals, onlyUsable ? 1 : 0, count, out, nl);
+    });
+  }
+  // Regression::GenerateNoise (Regression.h:180-191) for `count` masks in one device call: slot 0 is 0, the others uniform on [0, p) from
+  // (seed, index, slot) -- philox.h purpose 7 --, all slots embedded, encrypted under the same (seed, index)
+  void EncryptNoiseBatchSeeded(std::vector<Ciphertext>& ctxts, long count, SeedSequence& seq) const {
+    const PlaintextSpace& ps = context.GetPlaintextSpace();
+    const uint64_t first_obj = seq.take((uint64_t)count);
+    encrypt_on_device(ctxts, count, [&](fhesi_ctx* h, uint64_t* out, int nl) {
+      return fhesi_encrypt_noise_batch_seeded(h, ps.handle(), publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, seq.seed, first_obj, count, out, nl);
+    });
+  }
+ private:
+  // `count` fresh ciphertexts written by one device call: into the arena when recording is on, else through a temporary buffer to host objects
+  template <class F> void encrypt_on_device(std::vector<Ciphertext>& ctxts, long count, F call) const {
+    const long n = context.zMstar.phiM(); const int nl = (int)((context.logQ + 63) / 64);
+    ctxts.assign(count, Ciphertext(context));
+    if (!count) return;
+    if (LazyCiphertexts()) {
+      CtEngine& e = ct_engine(context); const long first = e.alloc_run(count);
+      int rc = call(e.h, e.ptr(first), nl);
+      if (rc) { e.free_run(first, count); ck(rc); }
+      e.publish(first, count);
+      for (long c = 0; c < count; ++c) ctxts[c].set_device_value(e.wrap(first + c));
+      return;
+    }
+    void* dev; ck(fhesi_dev_alloc(context.handle(), (size_t)count * 2 * n * nl * 8, &dev));
+    int rc = call(context.handle(), (uint64_t*)dev, nl);
+    std::vector<uint64_t> host((size_t)count * 2 * n * nl);
+    if (!rc) rc = fhesi_dev_download(context.handle(), host.data(), dev, host.size() * 8);
+    fhesi_dev_free(context.handle(), dev);
+    ck(rc);
+    for (long c = 0; c < count; ++c) { ctxts[c].Initialize(2, context); for (int part = 0; part < 2; ++part) limbs_to_poly(ctxts[c][part].poly, &host[((size_t)(c * 2 + part) * n) * nl], n, nl); }
+  }
+ public:
   // Encrypt (FHE-SI.cpp:10-36).  With recording on, the randomness is drawn here exactly as below and the arithmetic is the device call of
   // EncryptBatch on one plaintext; the ciphertext stays in HBM (the same bits: tests/host/test_wire.cpp compares EncryptBatch with EncryptObjects)
   void Encrypt(Ciphertext& ctxt, const Plaintext& ptxt) const {

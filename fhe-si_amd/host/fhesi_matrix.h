@@ -13,11 +13,17 @@
 //                          level (inner products -> SumBatchedData -> minors of growing size -> determinant -> adj * last) in waves.  Every ciphertext operation is deterministic, so equal minors
 //                          the Laplace recursion of Matrix.cpp:227-263 recomputes are evaluated once; results are bit-identical to the
 //                          literal object-at-a-time control flow (tests/host/matrix_literal.h: RegressLiteral).
-// Slot packing (PlaintextSpace.cpp) is outside the hot-path scope: plaintexts are coefficient vectors and only the slot COUNT
-// (Regression.h:72-79) is mirrored.  GenerateNoise (Regression.h:180-191) needs EmbedInSlots and is therefore not applied;
-// both evaluators return the unmasked theta / det.
+// Slot packing (PlaintextSpace.cpp) runs on the device (fhesi_context.h: PlaintextSpace; csrc/kernels_slots.hip): LoadData / BatchData /
+// AddDataSlots feed Regress from a data file, DecryptSlotsBatch reads the coefficients back.  GenerateNoise (Regression.h:180-191) is the
+// OPT-IN masked evaluation RegressBatched(theta, det, SeedSequence&): the signatures without a SeedSequence keep returning the unmasked
+// theta / det, which the tests compare bit for bit with the literal evaluator -- and whose slots 1 .. still hold partial sums, so a
+// deployment that hands results to whoever decrypts uses the masked form.
 #pragma once
+#include <cstdio>
+#include <ctime>
 #include <functional>
+#include <iostream>
+#include <string>
 #include <map>
 #include <memory>
 #include <thread>
@@ -60,6 +66,51 @@ class Matrix {
 // ---------------------------------------------------------------- slot counts (PlaintextSpace.cpp:29-43): factors of Phi_m mod p
 inline unsigned TotalSlots(unsigned m, unsigned long p, unsigned phim) { unsigned d = 1; unsigned long x = p % m; while (x != 1) { x = (x * (p % m)) % m; ++d; } return phim / d; }
 inline unsigned UsableSlots(unsigned m, unsigned long p, unsigned phim) { unsigned u = 1, t = TotalSlots(m, p, phim); while (t > 1) { u <<= 1; t >>= 1; } return u; }
+
+// ---------------------------------------------------------------- LoadData / BatchData (Regression.h:16-66)
+// data file: "dim n", then n rows of dim integers and a label
+inline bool LoadData(Matrix<ZZ>& rawData, std::vector<ZZ>& labels, unsigned& dim, const std::string& filename) {
+  FILE* f = fopen(filename.c_str(), "r");
+  if (!f) { std::cout << "Unable to read data file." << std::endl; return false; }
+  rawData.Clear(); labels.clear();
+  int n = 0; long v = 0;
+  bool ok = fscanf(f, "%u %d", &dim, &n) == 2;
+  for (int i = 0; ok && i < n; ++i) {
+    std::vector<ZZ> row(dim);
+    for (unsigned j = 0; ok && j < dim; ++j) { ok = fscanf(f, "%ld", &v) == 1; row[j] = ZZ(v); }
+    ok = ok && fscanf(f, "%ld", &v) == 1;
+    if (ok) { rawData.AddRow(row); labels.push_back(ZZ(v)); }
+  }
+  fclose(f);
+  return ok;
+}
+// the slot values BatchData packs: block b = rows [b usable, (b + 1) usable), one vector per column and one for the labels, reduced modulo p
+inline void BatchValues(std::vector<std::vector<long>>& vals /* [blocks][dim + 1] flattened, label last */, const Matrix<ZZ>& rawData, const std::vector<ZZ>& labels, const FHEcontext& context) {
+  const long p = context.ModulusP().to_long(); const unsigned batchSize = context.GetPlaintextSpace().GetUsableSlots(), d = rawData.NumCols();
+  vals.clear();
+  for (unsigned i = 0; i < rawData.NumRows(); i += batchSize)
+    for (unsigned j = 0; j <= d; ++j) {
+      std::vector<long> col;
+      for (unsigned k = i; k < i + batchSize && k < rawData.NumRows(); ++k) col.push_back(rem(j < d ? rawData(k, j) : labels[k], p));
+      vals.push_back(col);
+    }
+}
+// ONE device embed for the whole data set (the reference embeds plaintext by plaintext and reports it as "Batch time")
+inline double BatchData(std::vector<std::vector<Plaintext>>& ptxtData, std::vector<Plaintext>& ptxtLabels, const Matrix<ZZ>& rawData, const std::vector<ZZ>& labels, const FHEcontext& context) {
+  const double start = (double)clock();
+  std::vector<std::vector<long>> vals, msgs;
+  BatchValues(vals, rawData, labels, context);
+  context.GetPlaintextSpace().EmbedInSlots(msgs, vals, true);
+  const unsigned d = rawData.NumCols();
+  ptxtData.clear(); ptxtLabels.clear();
+  for (size_t b = 0; b * (d + 1) < msgs.size(); ++b) {
+    std::vector<Plaintext> row(d, Plaintext(context));
+    for (unsigned j = 0; j < d; ++j) row[j].message = msgs[b * (d + 1) + j];
+    Plaintext lab(context); lab.message = msgs[b * (d + 1) + d];
+    ptxtData.push_back(row); ptxtLabels.push_back(lab);
+  }
+  return ((double)clock() - start) / CLOCKS_PER_SEC;
+}
 
 // ---------------------------------------------------------------- wave executors
 // A wave = a set of independent groups  out[g] = KeySwitch(sum_t pool[a_t] * pool[b_t])  over pool indices (ProductWave).  The pool
@@ -349,7 +400,32 @@ class Regression {
       labels.push_back(lab);
     }
   }
+  // BatchData + AddData in one device call: the raw values go to the device, are embedded and encrypted there (fhesi_encrypt_slots_batch_seeded);
+  // the same ciphertexts as EncryptBatchSeeded on BatchData's plaintexts under the same indices (block-major, the label after its block's columns)
+  void AddDataSlots(const Matrix<ZZ>& rawData, const std::vector<ZZ>& rawLabels, SeedSequence& seq) {
+    std::vector<std::vector<long>> vals;
+    BatchValues(vals, rawData, rawLabels, context);
+    std::vector<Ciphertext> cts;
+    publicKey.EncryptSlotsBatchSeeded(cts, vals, seq, true);
+    const unsigned d = rawData.NumCols();
+    for (size_t b = 0; b * (d + 1) < cts.size(); ++b) {
+      std::vector<Ciphertext> row(cts.begin() + b * (d + 1), cts.begin() + b * (d + 1) + d);
+      data.AddRow(row);
+      labels.push_back(cts[b * (d + 1) + d]);
+    }
+  }
   void Clear() { data.Clear(); labels.clear(); }
+  // Regression.h:180-191 for `count` masks at once: encryptions of (0, uniform, uniform, ...) in slot order
+  void GenerateNoise(std::vector<Ciphertext>& noise, long count, SeedSequence& seq) const { publicKey.EncryptNoiseBatchSeeded(noise, count, seq); }
+  // Regression.h:139-148: theta[i] += noise, det += noise -- slot 0 keeps the result, every other slot becomes uniform.  As in the reference the
+  // dimension-1 shortcut (:120-126) returns before the masks.
+  void AddNoise(std::vector<Ciphertext>& theta, Ciphertext& det, SeedSequence& seq) const {
+    if (data.NumCols() == 1) return;
+    std::vector<Ciphertext> noise;
+    GenerateNoise(noise, (long)theta.size() + 1, seq);
+    for (size_t i = 0; i < theta.size(); ++i) theta[i] += noise[i];
+    det += noise[theta.size()];
+  }
 
   // access for the object-at-a-time checker (tests/host/matrix_literal.h)
   const Matrix<Ciphertext>& Data() const { return data; }
@@ -362,6 +438,12 @@ class Regression {
     if (!single) single.reset(new SingleGpuExecutor(context, keySwitch, autoKeySwitch, autoK));
     single->reset();
     RegressWaves(*single, theta, det);
+  }
+  // ... masked as Regression::Regress masks its results (opt-in: the form above is what the bit-for-bit comparisons use)
+  void RegressBatched(std::vector<Ciphertext>& theta, Ciphertext& det, SeedSequence& noise) { RegressBatched(theta, det); AddNoise(theta, det, noise); }
+  void RegressBatchedMultiGpu(const std::vector<int>& devices, std::vector<Ciphertext>& theta, Ciphertext& det, int overlap_chunks, SeedSequence* noise) {
+    RegressBatchedMultiGpu(devices, theta, det, overlap_chunks);
+    if (noise) AddNoise(theta, det, *noise);
   }
   // ... sharded over the GPUs `devices` of this node (devices[0] = the context's GPU); keys are broadcast on the first call
   // overlap_chunks > 1: every wave in that many chunks, the exchange of a chunk overlapped with the next chunk's compute (GroupExecutor)

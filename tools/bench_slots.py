@@ -1,0 +1,93 @@
+#!/usr/bin/env python3
+"""Slot packing on the device, measured: embeds/s and decodes/s on HBM buffers, the fused encrypt-from-slots against encrypt-from-coefficients
+on the same batch, and parity of a sample against the model (tests/slots_model.py).  One JSON line per ring.
+
+    python3 tools/bench_slots.py [--p 32603 65543] [--count 256] [--logQ 128] [--warmup 2] [--reps 7]
+
+Times are host clocks around work that ends in a stream synchronise; every figure is the median of --reps calls after --warmup calls.
+`bytes` are algorithmic (slot values in, message polynomials out, 8 bytes each -- the basis of bench.py's roofline lines), `bound` is
+"unknown": no counter pass exists for these kernels."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for d in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, d)
+
+import numpy as np  # noqa: E402
+
+import fhe_si_amd as F  # noqa: E402
+import params as P  # noqa: E402
+import slots_model as M  # noqa: E402
+
+
+def median_time(fn, sync, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    sync()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--p", type=int, nargs="+", default=[32603, 65543])
+    ap.add_argument("--count", type=int, default=256)
+    ap.add_argument("--logQ", type=int, default=128)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=7)
+    a = ap.parse_args()
+    for p in a.p:
+        m, logQ, count = p - 1, a.logQ, a.count
+        g = M.least_generator(m)
+        primes, roots = P.chain_for(m, logQ, p)
+        ctx = F.Context(m, primes, roots)
+        S = F.SlotSpace(ctx, p, g)
+        n, nl = S.total, (logQ + 63) // 64
+        rng = np.random.default_rng(p)
+        vals = rng.integers(0, p, size=(count, S.usable)).astype(np.int64)
+        d_vals, d_msg, d_back = ctx.upload(vals), ctx.alloc(count * n * 8), ctx.alloc(count * S.usable * 8)
+        t_emb = median_time(lambda: S.embed_dev(d_vals, S.usable, count, d_msg), ctx.sync, a.warmup, a.reps)
+        t_dec = median_time(lambda: S.decode_dev(d_msg, count, S.usable, d_back), ctx.sync, a.warmup, a.reps)
+        msg = d_msg.download((count, n), np.int64)
+        back = d_back.download((count, S.usable), np.int64)
+        mod = M.slot_space(m, p, g)
+        sample = [0, 1, S.usable - 1]
+        parity = bool(np.array_equal(back, vals)) and all(M.decode_slot(mod, [int(x) for x in msg[c]], j) == vals[c, j] for c in (0, count - 1) for j in sample)
+        pk = []
+        rows = P.rand_rows(rng, primes, n, 2)
+        for r in range(2):
+            d = F.DoubleCRT(ctx)
+            for i in range(len(primes)):
+                d.set_row(i, np.ascontiguousarray(rows[r, i]))
+            pk.append(d)
+        out_a, out_b = ctx.alloc(count * 2 * n * nl * 8), ctx.alloc(count * 2 * n * nl * 8)
+        t_es = median_time(lambda: S.encrypt_batch_seeded(pk[0], pk[1], logQ, 11, 0, vals, out_a, nl), ctx.sync, a.warmup, a.reps)
+        t_ec = median_time(lambda: ctx.encrypt_batch_seeded(pk[0], pk[1], logQ, p, 11, 0, msg, out_b, nl), ctx.sync, a.warmup, a.reps)
+        same = bool(np.array_equal(out_a.download((count, 2, n, nl)), out_b.download((count, 2, n, nl))))
+        emb_bytes = count * (S.usable + n) * 8
+        print(json.dumps({
+            "workload": "slots", "p": p, "m": m, "generator": g, "slots": n, "usable": S.usable, "aux_primes": S.aux_primes, "logQ": logQ, "chain_primes": len(primes),
+            "count": count, "warmup": a.warmup, "reps": a.reps,
+            "embeds_per_s": round(count / t_emb[0], 1), "embed_ms": [round(x * 1e3, 3) for x in t_emb],
+            "decodes_per_s": round(count / t_dec[0], 1), "decode_ms": [round(x * 1e3, 3) for x in t_dec],
+            "encrypt_slots_per_s": round(count / t_es[0], 1), "encrypt_slots_ms": [round(x * 1e3, 3) for x in t_es],
+            "encrypt_coeffs_per_s": round(count / t_ec[0], 1), "encrypt_coeffs_ms": [round(x * 1e3, 3) for x in t_ec],
+            "encrypt_slots_over_coeffs_time": round(t_es[0] / t_ec[0], 3), "fused_equals_embed_then_encrypt": same, "parity": parity,
+            "roofline": {"embed_algorithmic_bytes": emb_bytes, "embed_GBps": round(emb_bytes / t_emb[0] / 1e9, 2), "bound": "unknown"},
+            "loadavg": [round(x, 2) for x in os.getloadavg()],
+        }), flush=True)
+        S.close()
+
+
+if __name__ == "__main__":
+    main()
