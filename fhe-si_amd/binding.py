@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "fhesi_abi_version", "fhesi_host_stage_release",
     "fhesi_slots_plan", "fhesi_slots_create", "fhesi_slots_free", "fhesi_slots_info", "fhesi_slots_exponents", "fhesi_slots_embed", "fhesi_slots_decode",
     "fhesi_slots_embed_dev", "fhesi_slots_decode_dev", "fhesi_encrypt_slots_batch_seeded", "fhesi_decrypt_slots_batch", "fhesi_encrypt_noise_batch_seeded",
+    "fhesi_slots_plan_pow2", "fhesi_slots_create_pow2", "fhesi_slots_shape", "fhesi_slots_set_path",
 ]
 ABI_VERSION = 7          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8}
@@ -192,6 +193,10 @@ def _load():
         "fhesi_encrypt_slots_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _vp, _i64, _i32, _i64, _vp, _i32],
         "fhesi_decrypt_slots_batch": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _i32, _vp],
         "fhesi_encrypt_noise_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _i64, _vp, _i32],
+        "fhesi_slots_plan_pow2": [_i64, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_slots_create_pow2": [_vp, _u64, _i64, _vp],
+        "fhesi_slots_shape": [_vp, _vp, _vp, _vp],
+        "fhesi_slots_set_path": [_vp, _i32],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -479,16 +484,43 @@ def slots_plan(m: int, p: int, generator: int) -> dict:
     return {"total": total.value, "usable": usable.value, "rho0": rho0.value, "aux_primes": naux.value, "exps": e}
 
 
-class SlotSpace:
-    """One PlaintextSpace on a context's GPU (fhesi_slots_create): batched EmbedInSlots / DecodeSlots and the slot-valued Encrypt / Decrypt."""
+def slots_plan_pow2(m: int, p: int, generator: int) -> dict:
+    """The host half of the two-row space of a power-of-two ring (m = 2^k, k >= 3, p = 1 mod m, g = 3 or 5 mod 8): total slots, rows, cols, rho0,
+    the path (0 direct transform, 1 / 2 chirp with one / two auxiliary primes) and the exponents e_s; raises FhesiError on a refused ring."""
+    total, rows, cols, rho0, path = _i64(0), _i64(0), _i64(0), _u64(0), _i32(0)
+    _ck(_load().fhesi_slots_plan_pow2(m, p, generator, C.byref(total), C.byref(rows), C.byref(cols), C.byref(rho0), C.byref(path), None))
+    e = np.zeros(total.value, dtype=np.int32)
+    _ck(_load().fhesi_slots_plan_pow2(m, p, generator, None, None, None, None, None, _p(e)))
+    return {"total": total.value, "rows": rows.value, "cols": cols.value, "rho0": rho0.value, "path": path.value, "exps": e}
 
-    def __init__(self, ctx: "Context", p: int, generator: int):
+
+class SlotSpace:
+    """One PlaintextSpace on a context's GPU (fhesi_slots_create): batched EmbedInSlots / DecodeSlots and the slot-valued Encrypt / Decrypt.
+    SlotSpace.pow2(ctx, p, g) makes the two-row space of a power-of-two ring (fhesi_slots_create_pow2) with the same methods."""
+
+    def __init__(self, ctx: "Context", p: int, generator: int, _two_rows: bool = False):
         self.ctx, self.p, self.generator = ctx, p, generator
         self.h = _vp()
-        _ck(_load().fhesi_slots_create(ctx.h, p, generator, C.byref(self.h)))
+        _ck((_load().fhesi_slots_create_pow2 if _two_rows else _load().fhesi_slots_create)(ctx.h, p, generator, C.byref(self.h)))
         total, usable, rho0, naux = _i64(0), _i64(0), _u64(0), _i32(0)
         _ck(_load().fhesi_slots_info(self.h, C.byref(total), C.byref(usable), C.byref(rho0), C.byref(naux)))
         self.total, self.usable, self.rho0, self.aux_primes = total.value, usable.value, rho0.value, naux.value
+        self._shape()
+
+    @classmethod
+    def pow2(cls, ctx: "Context", p: int, generator: int) -> "SlotSpace":
+        """The two-row space: slot r * cols + j sits on rho0^((-1)^r g^j mod m)."""
+        return cls(ctx, p, generator, _two_rows=True)
+
+    def _shape(self):
+        rows, cols, path = _i64(0), _i64(0), _i32(0)
+        _ck(_load().fhesi_slots_shape(self.h, C.byref(rows), C.byref(cols), C.byref(path)))
+        self.rows, self.cols, self.path = rows.value, cols.value, path.value
+
+    def set_path(self, path: int):
+        """Two-row spaces: 0 = the direct transform, otherwise the chirp (the results do not change)."""
+        _ck(_load().fhesi_slots_set_path(self.h, path))
+        self._shape()
 
     def close(self):
         if getattr(self, "h", None):

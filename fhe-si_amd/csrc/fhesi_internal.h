@@ -275,8 +275,13 @@ struct SlotSpace {
   i64 q = 0, s = 0;                    // Phi_m(X) = Phi_q(+-X^s)
   int naux = 1;                        // auxiliary primes the exact chirp convolution needs (m p^2 against 2^59)
   std::vector<int> exps, slot_of_exp;  // [phim], [m] (-1 off Z_m^*)
+  int rows = 1;                        // 2: the two-row space of a power-of-two ring (slot_space_pow2); the columns are phim / rows
+  bool direct = false;                 // two-row spaces only: one negacyclic transform modulo p in LDS (kernels_slots_pow2.hip) instead of the chirp
 };
 const char* slot_space(i64 m, u64 p, i64 g, SlotSpace* out);     // nullptr, or the condition that refuses the ring
+// m = 2^k, k >= 3, p = 1 mod m, g = 3 or 5 mod 8: (Z/m)^* = <-1> x <g>, n = m/2 slots as 2 rows of h = n/2 columns; slot r h + j sits on
+// rho0^((-1)^r g^j mod m).  Same record (kind 0, q = 2, s = n: the fold out[i] = f[i] - f[i + n] of X^n + 1), usable = total = n.
+const char* slot_space_pow2(i64 m, u64 p, i64 g, SlotSpace* out);
 }  // namespace hm
 
 // --------------------------------------------------------------------------------- plaintext slots (kernels_slots.hip)
@@ -293,7 +298,16 @@ struct fhesi_slots {
   int* d_exps = nullptr;               // [phim] e_j = g^j mod m
   int* d_slot_of_exp = nullptr;        // [m] inverse table, -1 off Z_m^*
   bool orderfree = false;
+  // the direct path of a two-row space (S.direct): tables of the length-n negacyclic transform modulo p with psi = rho0
+  struct Tw { u32 w, wp; };            // constant and floor(w 2^32 / p)
+  Tw* d_p2tw = nullptr;                // [2][n]  psi^brv(i), psi^-brv(i)  (i = groups of the stage + group)
+  u32* d_p2pos = nullptr;              // [n] slot -> position of rho0^(e_slot) in the transform's (bit-reversed) output
+  Tw p2ninv = {0, 0}, p2ninv_w1 = {0, 0};    // n^-1 and n^-1 psi^-brv(1): the scaling of the inverse, folded into its last stage
 };
+int slots_build(fhesi_slots* s);       // the chirp tables and the internal context (kernels_slots.hip)
+void slots_release(fhesi_slots* s);
+int slots_pow2_build(fhesi_slots* s);  // the direct tables (kernels_slots_pow2.hip)
+int slots_pow2_run(fhesi_slots* s, bool embed, const i64* d_in, i64* d_out, i64 nvals, i64 take, i64 count);
 // d_vals [count][nvals] int64 (any sign; reduced modulo p) <-> d_msg [count][phi(m)] int64 in [0, p).  Slots at or above min(nvals, cap), cap =
 // usable or phi(m), are zero on embed and written as zero on decode.  Everything is enqueued on the context's stream.
 int slots_embed_rows(fhesi_slots* s, const i64* d_vals, i64 nvals, bool only_usable, i64 count, i64* d_msg);

@@ -234,6 +234,56 @@ const char* slot_space(i64 m, u64 p, i64 g, SlotSpace* out) {
   return nullptr;
 }
 
+// ---- two-row slot spaces of the power-of-two rings.  (Z/2^k)^* = <-1> x <g> for g = 3 or 5 mod 8 (g then has order h = m/4 and -1 is no
+// power of it), so the n = m/2 roots of X^n + 1 modulo p = 1 mod m are rho0^(+-g^j): row 0 on g^j, row 1 on -g^j, j = 0 .. h-1.
+const char* slot_space_pow2(i64 m, u64 p, i64 g, SlotSpace* out) {
+  if (m < 1 || (m & (m - 1)) != 0) return "m is not a power of two (the two-row space is the one of X^(m/2) + 1)";
+  if (m < 8) return "m = 2^k with k < 3: (Z/m)^* is cyclic there, the single-generator space covers it";
+  if (m > (1 << 20)) return "m outside [8, 2^20]";
+  if (p >= (1ull << 32)) return "plaintext modulus p >= 2^32 (slot arithmetic is 32-bit)";
+  if (!is_prime(p)) return "plaintext modulus p is not prime (p^r and composite moduli are not supported)";
+  if ((p - 1) % (u64)m != 0) return "p != 1 mod m: ord_m(p) > 1, the slots would live in an extension field GF(p^d)";
+  const u64 gm = (u64)(((g % m) + m) % m);
+  if (gm % 8 != 3 && gm % 8 != 5) return "the generator is not 3 or 5 mod 8: its powers and their negatives do not reach every slot";
+  SlotSpace S;
+  S.m = m; S.p = p; S.g = gm;
+  S.kind = 0; S.q = 2; S.s = m / 2;
+  S.phim = S.usable = m / 2;
+  S.rows = 2;
+  const i64 n = S.phim, h = n / 2;
+  // rho0 = the least integer in [1, p) of order m: z^j, j odd, for any z of order m (z^(m/2) = -1)
+  {
+    u64 z = 0;
+    for (u64 c = 2; c < p && !z; ++c) {
+      const u64 x = powmod(c, (p - 1) / (u64)m, p);
+      if (powmod(x, (u64)m / 2, p) != 1) z = x;
+    }
+    if (!z) return "no element of order m modulo p";
+    const u64 z2 = mulmod(z, z, p);
+    u64 best = p, x = z;
+    for (i64 j = 1; j < m; j += 2) {
+      if (x < best) best = x;
+      x = mulmod(x, z2, p);
+    }
+    S.rho0 = best;
+  }
+  S.exps.resize(n);
+  S.slot_of_exp.assign(m, -1);
+  u64 e = 1;
+  for (i64 j = 0; j < h; ++j) {
+    S.exps[j] = (int)e;
+    S.exps[h + j] = (int)((u64)m - e);
+    S.slot_of_exp[e] = (int)j;
+    S.slot_of_exp[(u64)m - e] = (int)(h + j);
+    e = mulmod(e, gm, (u64)m);
+  }
+  S.naux = ((u128)m * p * p < ((u128)1 << 59)) ? 1 : 2;
+  // the whole row of n 32-bit words sits in one workgroup's LDS up to n = 2^15, and lazy values below 2p fit a word up to p < 2^31
+  S.direct = n <= (1 << 15) && p < (1ull << 31);
+  *out = S;
+  return nullptr;
+}
+
 u64 bn_mod(const u64* limbs, int nlimbs, u64 q) {
   bool neg = limbs[nlimbs - 1] >> 63;
   u64 r = 0;

@@ -275,9 +275,18 @@ struct Plaintext {
   Plaintext& operator-=(const Plaintext& o) { return combine(o, -1); }
   Plaintext& operator>>=(long k) {          // Plaintext.h:87-96: decode all slots, rotated[(i + n - k) % n] = plain[i], embed all slots
     std::vector<long> plain; DecodeSlots(plain, false);
-    const long n = (long)plain.size(); std::vector<long> rotated(n);
-    for (long i = 0; i < n; ++i) rotated[(((i - k) % n) + n) % n] = plain[i];
+    const long rows = (long)ctx().GetPlaintextSpace().Rows();                  // a two-row space rotates each row by k columns
+    const long n = (long)plain.size() / rows; std::vector<long> rotated(plain.size());
+    for (long r = 0; r < rows; ++r) for (long i = 0; i < n; ++i) rotated[r * n + (((i - k) % n) + n) % n] = plain[r * n + i];
     EmbedInSlots(rotated, false);
+    return *this;
+  }
+  Plaintext& SwapRows() {                   // two-row spaces: what X -> X^(m-1) does to the slots (Ciphertext >>= m - 1 plus its key switch)
+    const PlaintextSpace& ps = ctx().GetPlaintextSpace();
+    if (ps.Rows() != 2) Error("Plaintext::SwapRows: the plaintext space has one row");
+    std::vector<long> plain; DecodeSlots(plain, false);
+    std::rotate(plain.begin(), plain.begin() + ps.Cols(), plain.end());
+    EmbedInSlots(plain, false);
     return *this;
   }
  private:

@@ -77,7 +77,7 @@ class Cmodulus {
 // (include/fhesi_hip.h, "plaintext slots": p not prime, p >= 2^32, p != 1 mod m, no generator of (Z/m)^*) raise the library's message.
 class PlaintextSpace {
   fhesi_slots* h = nullptr;
-  long total = 0, usable = 0, phim = 0;
+  long total = 0, usable = 0, phim = 0, rows = 1;
   unsigned long rho0 = 0;
   // bound where the handle is made: the destructor (reached from ~FHEcontext in every program) then names no slot entry point, so a program
   // that never creates a slot space links against an ABI without them (the host-memory stand-in of the CPU-only harness)
@@ -90,11 +90,26 @@ class PlaintextSpace {
     ck(fhesi_slots_info(h, &t, &u, &r, &na));
     total = (long)t; usable = (long)u; rho0 = (unsigned long)r; phim = (long)t;
   }
+  // the two-row space of a power-of-two ring (m = 2^k, k >= 3, p = 1 mod m, generator 3 or 5 mod 8; include/fhesi_hip.h): slot r Cols() + j
+  // sits on rho0^((-1)^r g^j mod m).  Not in the reference, whose single-generator walk asserts on these rings.
+  struct TwoRows {};
+  PlaintextSpace(fhesi_ctx* ctx, unsigned long p, unsigned generator, TwoRows) {
+    ck(fhesi_slots_create_pow2(ctx, (uint64_t)p, (int64_t)generator, &h));
+    release = &fhesi_slots_free;
+    int64_t t = 0, u = 0, rw = 0, cl = 0; uint64_t r = 0; int32_t na = 0, path = 0;
+    ck(fhesi_slots_info(h, &t, &u, &r, &na));
+    ck(fhesi_slots_shape(h, &rw, &cl, &path));
+    total = (long)t; usable = (long)u; rho0 = (unsigned long)r; phim = (long)t; rows = (long)rw;
+  }
+  // m = 2^k with k >= 3 and p = 1 mod m: the rings whose slots form two rows
+  static bool IsTwoRowRing(unsigned long m, unsigned long p) { return m >= 8 && (m & (m - 1)) == 0 && p % m == 1; }
   ~PlaintextSpace() { if (h) release(h); }
   PlaintextSpace(const PlaintextSpace&) = delete;
   PlaintextSpace& operator=(const PlaintextSpace&) = delete;
   unsigned GetUsableSlots() const { return (unsigned)usable; }
   unsigned GetTotalSlots() const { return (unsigned)total; }
+  unsigned Rows() const { return (unsigned)rows; }                              // 1, or 2 on a power-of-two ring
+  unsigned Cols() const { return (unsigned)(total / rows); }
   unsigned long Rho0() const { return rho0; }                                   // slot j sits on the root rho0^(g^j mod m)
   fhesi_slots* handle() const { return h; }
   // many plaintexts in one device call: msgs[i] holds at most usable (onlyUsable) / total values, missing slots are 0
@@ -157,9 +172,14 @@ class FHEcontext {
     zMstar.init(m, gen, idx, std::vector<int64_t>());
   }
   unsigned Generator() const { return generator; }
-  // FHEContext.h:127: the slot structure of ModulusP() and Generator(); the rings outside the device layer's scope raise its message here
+  // FHEContext.h:127: the slot structure of ModulusP() and Generator(); the rings outside the device layer's scope raise its message here.
+  // On m = 2^k (k >= 3) with p = 1 mod m, where the reference's single-generator walk fails, it is the two-row space.
   const PlaintextSpace& GetPlaintextSpace() const {
-    if (!ptxtSpace) ptxtSpace.reset(new PlaintextSpace(handle(), (unsigned long)ptxtP.to_long(), generator));
+    if (!ptxtSpace) {
+      const unsigned long p = (unsigned long)ptxtP.to_long();
+      if (PlaintextSpace::IsTwoRowRing(m_, p)) ptxtSpace.reset(new PlaintextSpace(handle(), p, generator, PlaintextSpace::TwoRows()));
+      else ptxtSpace.reset(new PlaintextSpace(handle(), p, generator));
+    }
     return *ptxtSpace;
   }
   const ZZ& ModulusP() const { return ptxtP; }

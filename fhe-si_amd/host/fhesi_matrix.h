@@ -358,7 +358,7 @@ class Regression {
   FHESIPubKey publicKey;
   KeySwitchSI keySwitch;
   std::vector<KeySwitchSI> autoKeySwitch;
-  std::vector<unsigned> autoK;                                   // k = g, g^2, g^4, ... mod m (Regression.h:71-80)
+  std::vector<unsigned> autoK;                                   // k = g, g^2, g^4, ... mod m (Regression.h:71-80); on a two-row ring ..., g^(n/4), m - 1
   Matrix<Ciphertext> data;
   std::unique_ptr<SingleGpuExecutor> single;                     // device copies of the keys, created on the first batched call
   std::unique_ptr<GroupExecutor> group;
@@ -379,7 +379,11 @@ class Regression {
   Regression(const FHEcontext& c) : context(c), secretKey(c), publicKey(secretKey), keySwitch(secretKey), data(Ciphertext(c)) {
     unsigned k = c.Generator();
     unsigned nSlots = UsableSlots(c.zMstar.M(), (unsigned long)c.ModulusP().to_long(), c.zMstar.phiM());
+    // two-row rings (m = 2^k, k >= 3, p = 1 mod m): g has order n/2, so the last step of the walk g, g^2, g^4, ... would be the identity;
+    // it is the row swap m - 1 instead, and the log2 n steps leave the sum of all n slots in every slot
+    const bool twoRows = PlaintextSpace::IsTwoRowRing(c.zMstar.M(), (unsigned long)c.ModulusP().to_long());
     while (nSlots > 1) {
+      if (twoRows && nSlots == 2) k = c.zMstar.M() - 1;
       autoKeySwitch.push_back(KeySwitchSI(secretKey, k));
       autoK.push_back(k);
       nSlots >>= 1;

@@ -330,6 +330,32 @@ int fhesi_decrypt_slots_batch(fhesi_ctx* ctx, fhesi_slots* s, const fhesi_dcrt* 
 int fhesi_encrypt_noise_batch_seeded(fhesi_ctx* ctx, fhesi_slots* s, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
                                      int64_t count, uint64_t* out_dev, int32_t nlimbs);
 
+/* ---- plaintext slots on the power-of-two rings: the TWO-ROW space (fhe-si_amd/csrc/kernels_slots_pow2.hip).  An extension of the mirror: the
+ * reference's single-generator walk (PlaintextSpace.cpp:88-103) asserts on these rings, and fhesi_slots_create / fhesi_slots_plan keep refusing them.
+ *
+ * SCOPE.  m = 2^k with k >= 3, n = m / 2, h = n / 2; p PRIME, p < 2^32, p = 1 mod m (X^n + 1 splits into n linear factors); generator g = 3 or 5
+ * mod 8 (g then has order h modulo m and -1 is not among its powers: (Z/m)^* = <-1> x <g>).  Everything else -- k < 3 (cyclic: the constructor
+ * above), m not a power of two, p not prime, p >= 2^32, p != 1 mod m, another g -- is REFUSED on the host before anything is launched, the
+ * message names the condition.
+ *
+ * SLOT ORDER.  rho0 = the least primitive m-th root of unity in [1, p), as above.  Slot s = r h + j (row r = 0, 1; column j = 0 .. h-1) sits on
+ * rho0^(e_s), e_s = (-1)^r g^j mod m.  total = usable = n.  X -> X^(g^t) rotates BOTH rows left by t columns (the direction of
+ * Plaintext::operator>>=), X -> X^(m-1) swaps the rows (fhesi_ct_automorph_key_switch_dev takes any k in Z_m^*).  The automorphisms g, g^2, g^4,
+ * ..., g^(h/2), m - 1, each followed by an addition (log2 n steps), leave the sum of all n slots in EVERY slot.
+ *
+ * PATH.  0: n <= 2^15 and p < 2^31 -- one negacyclic transform of length n modulo p per plaintext (psi = rho0, no chirp, no auxiliary prime),
+ * one workgroup per plaintext with the row in LDS.  1 / 2: otherwise the chirp of the single-generator spaces on the two-row exponent table,
+ * with one / two auxiliary primes (m p^2 against 2^59).  Both compute the same words.
+ *
+ * The handle is a fhesi_slots: fhesi_slots_free / info / exponents / embed / decode / embed_dev / decode_dev, fhesi_encrypt_slots_batch_seeded,
+ * fhesi_decrypt_slots_batch and fhesi_encrypt_noise_batch_seeded take it unchanged (only_usable makes no difference: usable = total). */
+int fhesi_slots_plan_pow2(int64_t m, uint64_t p, int64_t generator, int64_t* total, int64_t* rows, int64_t* cols, uint64_t* rho0,
+                          int32_t* path /* 0 direct, 1 chirp with one prime, 2 chirp with two */, int32_t* e_out /* [n] or null */);
+int fhesi_slots_create_pow2(fhesi_ctx* ctx, uint64_t p, int64_t generator, fhesi_slots** out);
+int fhesi_slots_shape(const fhesi_slots* s, int64_t* rows, int64_t* cols, int32_t* path);   /* (1, phi(m), aux primes) for the single-generator spaces */
+int fhesi_slots_set_path(fhesi_slots* s, int32_t path);      /* two-row spaces: 0 = the direct transform (refused where the plan does not admit it), otherwise the chirp.
+                                                                Result-neutral; for measurements and for comparing the two.  Synchronises the context's stream. */
+
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
  * fhesi_comm_init_all: one process, one host thread per GPU -- ncclCommInitAll over `devices`, comms_out[r] is rank r's handle.
