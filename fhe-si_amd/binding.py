@@ -42,6 +42,9 @@ ABI_SYMBOLS = [
     "fhesi_slots_plan", "fhesi_slots_create", "fhesi_slots_free", "fhesi_slots_info", "fhesi_slots_exponents", "fhesi_slots_embed", "fhesi_slots_decode",
     "fhesi_slots_embed_dev", "fhesi_slots_decode_dev", "fhesi_encrypt_slots_batch_seeded", "fhesi_decrypt_slots_batch", "fhesi_encrypt_noise_batch_seeded",
     "fhesi_slots_plan_pow2", "fhesi_slots_create_pow2", "fhesi_slots_shape", "fhesi_slots_set_path",
+    "fhesi_slots_basis_plan", "fhesi_slots_basis_check", "fhesi_slots_basis_create", "fhesi_slots_basis_free", "fhesi_slots_basis_info", "fhesi_slots_basis_channel",
+    "fhesi_slots_basis_embed", "fhesi_slots_basis_decode", "fhesi_slots_basis_embed_dev", "fhesi_slots_basis_decode_dev",
+    "fhesi_encrypt_int_slots_batch_seeded", "fhesi_decrypt_int_slots_batch", "fhesi_encrypt_noise_int_batch_seeded",
 ]
 ABI_VERSION = 7          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8}
@@ -197,6 +200,19 @@ def _load():
         "fhesi_slots_create_pow2": [_vp, _u64, _i64, _vp],
         "fhesi_slots_shape": [_vp, _vp, _vp, _vp],
         "fhesi_slots_set_path": [_vp, _i32],
+        "fhesi_slots_basis_plan": [_i64, _i32, _i32, _i64, _vp, _vp, _vp],
+        "fhesi_slots_basis_check": [_i64, _vp, _i32, _i64, _vp, _vp],
+        "fhesi_slots_basis_create": [_vp, _vp, _i32, _i64, _vp],
+        "fhesi_slots_basis_free": [_vp],
+        "fhesi_slots_basis_info": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_slots_basis_channel": [_vp, _i32, _vp],
+        "fhesi_slots_basis_embed": [_vp, _vp, _i32, _i64, _i64, _vp],
+        "fhesi_slots_basis_decode": [_vp, _vp, _i64, _i64, _vp],
+        "fhesi_slots_basis_embed_dev": [_vp, _vp, _i32, _i64, _i64, _vp],
+        "fhesi_slots_basis_decode_dev": [_vp, _vp, _i64, _i64, _vp],
+        "fhesi_encrypt_int_slots_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _vp, _i32, _i64, _i64, _vp, _i32],
+        "fhesi_decrypt_int_slots_batch": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _vp],
+        "fhesi_encrypt_noise_int_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _i64, _vp, _i32],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -575,6 +591,163 @@ class SlotSpace:
     def encrypt_noise_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, count: int, out: DevBuf, nlimbs: int):
         """Regression::GenerateNoise for `count` masks (slot 0 zero, the others uniform from (seed, index))."""
         _ck(_load().fhesi_encrypt_noise_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, count, out.ptr, nlimbs))
+
+
+def slots_basis_plan(m: int, bits: int, prime_bits: int, generator: int) -> dict:
+    """A slot basis for results of up to `bits` bits (host only): the largest primes = 1 mod m below 2^prime_bits, descending, until their
+    product exceeds 2^(bits + 1); raises FhesiError naming the condition when there are too few or more than 32 would be needed."""
+    k, limbs = _i32(0), _i32(0)
+    primes = np.zeros(32, dtype=np.uint64)
+    _ck(_load().fhesi_slots_basis_plan(m, bits, prime_bits, generator, C.byref(k), _p(primes), C.byref(limbs)))
+    return {"primes": [int(x) for x in primes[:k.value]], "limbs": limbs.value}
+
+
+def slots_basis_check(m: int, primes, generator: int) -> dict:
+    """The host half of SlotBasis (no device, no context): the checks of the constructor; returns the limbs of a result and the modulus P."""
+    pr = np.ascontiguousarray(list(primes), dtype=np.uint64)
+    limbs, mod = _i32(0), np.zeros(16, dtype=np.uint64)
+    _ck(_load().fhesi_slots_basis_check(m, _p(pr) if len(pr) else None, len(pr), generator, C.byref(limbs), _p(mod)))
+    return {"limbs": limbs.value, "modulus": sum(int(x) << (64 * i) for i, x in enumerate(mod))}
+
+
+def pack_limbs(vals, limbs: int = None) -> np.ndarray:
+    """Integers (Python ints of any size, nested lists or an integer array) -> [...][L] int64 little-endian two's complement limbs.
+    L = `limbs`, or the least that holds every value."""
+    a = np.asarray(vals)
+    if a.dtype != object:
+        a64 = np.ascontiguousarray(a, dtype=np.int64)
+        if limbs in (None, 1):
+            return a64.reshape(a64.shape + (1,))
+        out = np.empty(a64.shape + (limbs,), dtype=np.int64)
+        out[..., 0] = a64
+        out[..., 1:] = (a64 >> 63)[..., None]
+        return out
+    flat = [int(v) for v in a.reshape(-1)]
+    need = max([1] + [((v if v >= 0 else ~v).bit_length() + 1 + 63) // 64 for v in flat])
+    L = need if limbs is None else limbs
+    if L < need:
+        raise ValueError(f"pack_limbs: {need} limbs needed, {L} given")
+    mask = (1 << (64 * L)) - 1
+    raw = b"".join((v & mask).to_bytes(8 * L, "little") for v in flat)
+    return np.frombuffer(raw, dtype=np.int64).reshape(a.shape + (L,)).copy()
+
+
+def _value_limbs(vals, limbs):
+    """[count][nvals][L] limbs of what a SlotBasis call was given: a 3-d int64 array is limbs already, anything else is integers to pack"""
+    if isinstance(vals, np.ndarray) and vals.ndim == 3 and vals.dtype == np.int64:
+        return np.ascontiguousarray(vals)
+    return pack_limbs(np.atleast_2d(vals if isinstance(vals, np.ndarray) else np.asarray(vals)), limbs)
+
+
+def unpack_limbs(limbs: np.ndarray) -> np.ndarray:
+    """[...][L] two's complement limbs -> object array [...] of Python ints."""
+    limbs = np.ascontiguousarray(limbs, dtype=np.int64)
+    L = limbs.shape[-1]
+    raw = limbs.tobytes()
+    out = np.empty(limbs.shape[:-1], dtype=object)
+    flat = out.reshape(-1)
+    for i in range(flat.shape[0]):
+        flat[i] = int.from_bytes(raw[8 * L * i: 8 * L * (i + 1)], "little", signed=True)
+    return out
+
+
+class SlotBasis:
+    """Integer slots over k plaintext primes on a two-row ring (fhesi_slots_basis_create): a slot holds a signed integer of (-P/2, P/2),
+    P the product of the primes; a logical plaintext / ciphertext is k channel plaintexts / ciphertexts on ONE context and key set, channel c
+    an ordinary two-row space modulo primes[c].  The caller owes |result| < P/2."""
+
+    def __init__(self, ctx: "Context", primes, generator: int):
+        self.ctx, self.generator = ctx, generator
+        self.h = _vp()
+        pr = np.ascontiguousarray(list(primes), dtype=np.uint64)
+        _ck(_load().fhesi_slots_basis_create(ctx.h, _p(pr) if len(pr) else None, len(pr), generator, C.byref(self.h)))
+        k, limbs, total, rows, cols = _i32(0), _i32(0), _i64(0), _i64(0), _i64(0)
+        _ck(_load().fhesi_slots_basis_info(self.h, C.byref(k), _p(pr), C.byref(limbs), C.byref(total), C.byref(rows), C.byref(cols)))
+        self.k, self.limbs, self.total, self.rows, self.cols = k.value, limbs.value, total.value, rows.value, cols.value
+        self.primes = [int(x) for x in pr]
+        self.modulus = 1
+        for x in self.primes:
+            self.modulus *= x
+        self._channels = {}
+
+    @classmethod
+    def pow2(cls, ctx: "Context", primes, generator: int) -> "SlotBasis":
+        return cls(ctx, primes, generator)
+
+    @classmethod
+    def plan(cls, ctx: "Context", bits: int, prime_bits: int, generator: int) -> "SlotBasis":
+        """The basis slots_basis_plan picks for results of up to `bits` bits."""
+        return cls(ctx, slots_basis_plan(ctx.m, bits, prime_bits, generator)["primes"], generator)
+
+    def close(self):
+        if getattr(self, "h", None):
+            for s in self._channels.values():
+                s.h = None                       # the basis owns the channels' spaces
+            _load().fhesi_slots_basis_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def channel(self, c: int) -> "SlotSpace":
+        """Channel c as a SlotSpace (p = primes[c]) for every existing call; it lives as long as the basis."""
+        if c not in self._channels:
+            h = _vp()
+            _ck(_load().fhesi_slots_basis_channel(self.h, c, C.byref(h)))
+            s = SlotSpace.__new__(SlotSpace)
+            s.ctx, s.p, s.generator, s.h = self.ctx, self.primes[c], self.generator, h
+            total, usable, rho0, naux = _i64(0), _i64(0), _u64(0), _i32(0)
+            _ck(_load().fhesi_slots_info(h, C.byref(total), C.byref(usable), C.byref(rho0), C.byref(naux)))
+            s.total, s.usable, s.rho0, s.aux_primes = total.value, usable.value, rho0.value, naux.value
+            s._shape()
+            s.close = lambda: None
+            s._basis = self
+            self._channels[c] = s
+        return self._channels[c]
+
+    def embed(self, vals, limbs: int = None) -> np.ndarray:
+        """vals [count][nvals] (Python ints or an int64 array; a 3-d int64 array is taken as limbs [count][nvals][L]) -> message polynomials
+        [k][count][phi(m)]."""
+        v = _value_limbs(vals, limbs)
+        count, nvals, L = v.shape
+        msg = np.zeros((self.k, count, self.total), dtype=np.int64)
+        _ck(_load().fhesi_slots_basis_embed(self.h, _p(v), L, nvals, count, _p(msg)))
+        return msg
+
+    def decode(self, msg: np.ndarray, nvals: int = None, raw: bool = False) -> np.ndarray:
+        """message polynomials [k][count][phi(m)] -> [count][nvals] Python ints in (-P/2, P/2) (raw: the limbs [count][nvals][L])."""
+        msg = np.ascontiguousarray(msg, dtype=np.int64)
+        if msg.ndim == 2:
+            msg = msg[:, None, :]
+        nvals = self.total if nvals is None else nvals
+        out = np.zeros((msg.shape[1], nvals, self.limbs), dtype=np.int64)
+        _ck(_load().fhesi_slots_basis_decode(self.h, _p(msg), msg.shape[1], nvals, _p(out)))
+        return out if raw else unpack_limbs(out)
+
+    def embed_dev(self, vals: DevBuf, limbs: int, nvals: int, count: int, msg: DevBuf):
+        _ck(_load().fhesi_slots_basis_embed_dev(self.h, vals.ptr, limbs, nvals, count, msg.ptr))
+
+    def decode_dev(self, msg: DevBuf, count: int, nvals: int, vals: DevBuf):
+        _ck(_load().fhesi_slots_basis_decode_dev(self.h, msg.ptr, count, nvals, vals.ptr))
+
+    def encrypt_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, vals, out: DevBuf, nlimbs: int, limbs: int = None):
+        """`count` logical plaintexts -> out [k][count] ciphertexts; channel c, plaintext i under (seed, first_index + c * count + i)."""
+        v = _value_limbs(vals, limbs)
+        count, nvals, L = v.shape
+        _ck(_load().fhesi_encrypt_int_slots_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, _p(v), L, nvals, count, out.ptr, nlimbs))
+
+    def decrypt_batch(self, sk1: "DoubleCRT", logQ: int, ct: DevBuf, nlimbs: int, count: int, nvals: int = None, raw: bool = False) -> np.ndarray:
+        nvals = self.total if nvals is None else nvals
+        out = np.zeros((count, nvals, self.limbs), dtype=np.int64)
+        _ck(_load().fhesi_decrypt_int_slots_batch(self.ctx.h, self.h, sk1.h, logQ, ct.ptr, nlimbs, count, nvals, _p(out)))
+        return out if raw else unpack_limbs(out)
+
+    def encrypt_noise_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, count: int, out: DevBuf, nlimbs: int):
+        """k masks per logical mask (slot 0 = 0 modulo P, the others uniform), object indices first_index .. first_index + k * count - 1."""
+        _ck(_load().fhesi_encrypt_noise_int_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, count, out.ptr, nlimbs))
 
 
 class DoubleCRT:

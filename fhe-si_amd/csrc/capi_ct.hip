@@ -99,6 +99,7 @@ struct MsgSource {
   const int64_t* vals_host = nullptr;  // [count][nvals] slot values; nullptr with slots set: Regression::GenerateNoise masks from (seed, index)
   i64 nvals = 0;
   bool only_usable = true;
+  const int64_t* msg_dev = nullptr;    // [count][phi(m)] already in HBM (one channel of a slot basis, embedded by the caller): used where it is
 };
 static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, const int64_t* rand_host, bool seeded, u64 seed, u64 first,
                               const MsgSource& src, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
@@ -117,7 +118,8 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
   FHESI_TRY(ws_reserve(c, 0, (size_t)count * 3 * L * n * 8, &d_rows));
   FHESI_TRY(ws_reserve(c, 1, (size_t)count * 2 * L * n * 8, &d_ct));
   FHESI_TRY(ws_reserve(c, 3, (size_t)2 * L * n * 8, &d_pk));
-  FHESI_TRY(ws_reserve(c, 5, (size_t)count * n * 8, &d_msg));
+  if (src.msg_dev) d_msg = (void*)src.msg_dev;
+  else FHESI_TRY(ws_reserve(c, 5, (size_t)count * n * 8, &d_msg));
   FHESI_TRY(ws_reserve(c, 4, (size_t)(nlimbs + 1) * 8, &d_delta));
   // delta = floor(2^logQ / p) (FHE-SI.cpp:31), nlimbs limbs
   std::vector<u64> delta(nlimbs, 0);
@@ -125,7 +127,8 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
     if (logQ == 64 * nlimbs) { /* 2^logQ needs limb nlimbs: redo with the extra limb */ rem = 1; for (int i = nlimbs - 1; i >= 0; --i) { const u128 cur = rem << 64; delta[i] = (u64)(cur / p); rem = cur % p; } } }
   if (seeded) FHESI_TRY(launch_sample_encrypt(c, (i64*)d_small, count, seed, first));      // r, e0, e1 drawn in HBM (kernels_sample.hip)
   else HIP_TRY(hipMemcpyAsync(d_small, rand_host, (size_t)count * 3 * n * 8, hipMemcpyHostToDevice, c->stream));
-  if (!src.slots) HIP_TRY(hipMemcpyAsync(d_msg, src.msg_host, (size_t)count * n * 8, hipMemcpyHostToDevice, c->stream));
+  if (src.msg_dev) {}
+  else if (!src.slots) HIP_TRY(hipMemcpyAsync(d_msg, src.msg_host, (size_t)count * n * 8, hipMemcpyHostToDevice, c->stream));
   else {
     void* d_vals;
     if (src.vals_host) {
@@ -192,7 +195,7 @@ extern "C" int fhesi_encrypt_noise_batch_seeded(fhesi_ctx* c, fhesi_slots* s, co
 
 // FHESISecKey::Decrypt (FHE-SI.cpp:93-119) of `count` unscaled 2-part ciphertexts [count][2][phi(m)][nlimbs] in HBM
 static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
-                              int64_t* msg_host, fhesi_slots* slots, i64 nvals, bool only_usable, int64_t* vals_host) {
+                              int64_t* msg_host, fhesi_slots* slots, i64 nvals, bool only_usable, int64_t* vals_host, int64_t* msg_dev = nullptr) {
   CHECK_CTX(c);
   if (slots && slots->ctx != c) FHESI_FAIL("Decrypt: the plaintext space belongs to another context");
   if (!sk1 || sk1->ctx != c) FHESI_FAIL("Decrypt: secret key belongs to another context");
@@ -207,7 +210,8 @@ static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ,
   FHESI_TRY(ws_reserve(c, 0, (size_t)count * 2 * L * n * 8, &d_rows));
   FHESI_TRY(ws_reserve(c, 1, (size_t)count * L * n * 8, &d_z));
   FHESI_TRY(ws_reserve(c, 2, (size_t)count * n * nw * 8, &d_big));
-  FHESI_TRY(ws_reserve(c, 5, (size_t)count * n * 8, &d_msg));
+  if (msg_dev) d_msg = msg_dev;         // one channel of a slot basis: the message polynomials stay in HBM for the caller, nothing is copied or synchronised
+  else FHESI_TRY(ws_reserve(c, 5, (size_t)count * n * 8, &d_msg));
   FHESI_TRY(launch_rns_reduce(c, (const u64*)ct_dev, nlimbs, n, count, 2, nullptr, (u64*)d_rows, L, nullptr));     // DoubleCRT(parts[i]) (:98-101)
   FHESI_TRY(row_fwd(c, (u64*)d_rows, count * 2, L, nullptr, all.data()));
   FHESI_TRY(launch_decrypt_dot(c, (const u64*)d_rows, sk1->d_rows, count, (u64*)d_z));                              // DotProduct with (1, t) (:105-107)
@@ -216,6 +220,7 @@ static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ,
   FHESI_TRY(get_crt_tables(c, all, &t));
   FHESI_TRY(launch_crt(c, t, (const u64*)d_z, L, nullptr, count, 0, 0, 0, (u64*)d_big, nw));                         // toPoly, low logQ+1 bits kept
   FHESI_TRY(launch_decrypt_round(c, (const u64*)d_big, count * n, nw, logQ, p, (i64*)d_msg));                        // round(p z / q) mod p (:110-116)
+  if (msg_dev) return 0;
   if (!slots) HIP_TRY(hipMemcpyAsync(msg_host, d_msg, (size_t)count * n * 8, hipMemcpyDeviceToHost, c->stream));
   else {          // DecodeSlots on the message polynomials where they are
     void* d_vals;
@@ -236,6 +241,70 @@ extern "C" int fhesi_decrypt_slots_batch(fhesi_ctx* c, fhesi_slots* s, const fhe
   if (!s) FHESI_FAIL("Decrypt: null plaintext space");
   if (nvals < 1 || nvals > s->S.phim) FHESI_FAIL("Decrypt: %lld values per plaintext, the ring has %lld slots", (long long)nvals, (long long)s->S.phim);
   return decrypt_batch_impl(c, sk1, logQ, s->S.p, ct_dev, nlimbs, count, nullptr, s, nvals, only_usable != 0, vals_host);
+}
+
+// ---- the same over a slot basis (kernels_slots_basis.hip): k channels on one key set, channel c with p = p_c.  One embedding launch for all
+// channels into the message staging [k][count][phi(m)], then k ordinary encryptions reading their part of it; object index of channel c,
+// plaintext i: first_index + c count + i.
+static int basis_check(fhesi_ctx* c, const fhesi_slots_basis* b, const char* what, i64 nvals) {
+  CHECK_CTX(c);
+  if (!b) FHESI_FAIL("%s: null slot basis", what);
+  if (b->ctx != c) FHESI_FAIL("%s: the slot basis belongs to another context", what);
+  if (nvals < 1 || nvals > c->phim) FHESI_FAIL("%s: %lld values per plaintext, the ring has %lld slots", what, (long long)nvals, (long long)c->phim);
+  return 0;
+}
+extern "C" int fhesi_encrypt_int_slots_batch_seeded(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                                    const int64_t* vals_host, int32_t L_in, int64_t nvals, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+  FHESI_TRY(basis_check(c, b, "Encrypt", nvals));
+  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
+  if (L_in < 1 || L_in > hm::SlotBasis::MAXL) FHESI_FAIL("Encrypt: %d limbs per value, 1 .. %d are taken", L_in, hm::SlotBasis::MAXL);
+  if (count < 0) FHESI_FAIL("negative count");
+  if (!count) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  const i64 n = c->phim;
+  const int k = b->B.k;
+  void *d_vals, *d_msg;
+  FHESI_TRY(ws_reserve(c, 9, (size_t)count * nvals * L_in * 8, &d_vals));
+  FHESI_TRY(ws_reserve(c, 5, (size_t)k * count * n * 8, &d_msg));
+  HIP_TRY(hipMemcpyAsync(d_vals, vals_host, (size_t)count * nvals * L_in * 8, hipMemcpyHostToDevice, c->stream));
+  FHESI_TRY(slots_basis_embed_rows(b, (const i64*)d_vals, L_in, nvals, count, (i64*)d_msg));
+  for (int ch = 0; ch < k; ++ch) {
+    MsgSource src;
+    src.msg_dev = (const int64_t*)d_msg + (size_t)ch * count * n;
+    FHESI_TRY(encrypt_batch_impl(c, pk0, pk1, logQ, b->B.primes[ch], nullptr, true, seed, first_index + (u64)ch * (u64)count, src, count,
+                                 out_dev + (size_t)ch * count * 2 * n * nlimbs, nlimbs));
+  }
+  return 0;
+}
+extern "C" int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                                    int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+  FHESI_TRY(basis_check(c, b, "GenerateNoise", 1));
+  if (count < 0) FHESI_FAIL("negative count");
+  for (int ch = 0; ch < b->B.k; ++ch)
+    FHESI_TRY(fhesi_encrypt_noise_batch_seeded(c, b->ch[ch], pk0, pk1, logQ, seed, first_index + (u64)ch * (u64)count, count, out_dev + (size_t)ch * count * 2 * c->phim * nlimbs, nlimbs));
+  return 0;
+}
+// k decryptions leave their message polynomials in the staging [k][count][phi(m)]; one decoding launch and one recombination follow
+extern "C" int fhesi_decrypt_int_slots_batch(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                                             int64_t nvals, int64_t* vals_host) {
+  FHESI_TRY(basis_check(c, b, "Decrypt", nvals));
+  if (!vals_host) FHESI_FAIL("Decrypt: null output");
+  if (count < 0) FHESI_FAIL("negative count");
+  if (!count) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  const i64 n = c->phim;
+  const int k = b->B.k;
+  void *d_vals, *d_msg;
+  FHESI_TRY(ws_reserve(c, 5, (size_t)k * count * n * 8, &d_msg));
+  for (int ch = 0; ch < k; ++ch)
+    FHESI_TRY(decrypt_batch_impl(c, sk1, logQ, b->B.primes[ch], ct_dev + (size_t)ch * count * 2 * n * nlimbs, nlimbs, count, nullptr, nullptr, 0, true, nullptr,
+                                 (int64_t*)d_msg + (size_t)ch * count * n));
+  const size_t bv = (size_t)count * nvals * b->B.limbs * 8;
+  FHESI_TRY(ws_reserve(c, 9, bv, &d_vals));
+  FHESI_TRY(slots_basis_decode_rows(b, (const i64*)d_msg, count, nvals, (i64*)d_vals));
+  HIP_TRY(hipMemcpyAsync(vals_host, d_vals, bv, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

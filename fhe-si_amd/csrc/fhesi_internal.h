@@ -282,6 +282,21 @@ const char* slot_space(i64 m, u64 p, i64 g, SlotSpace* out);     // nullptr, or 
 // m = 2^k, k >= 3, p = 1 mod m, g = 3 or 5 mod 8: (Z/m)^* = <-1> x <g>, n = m/2 slots as 2 rows of h = n/2 columns; slot r h + j sits on
 // rho0^((-1)^r g^j mod m).  Same record (kind 0, q = 2, s = n: the fold out[i] = f[i] - f[i + n] of X^n + 1), usable = total = n.
 const char* slot_space_pow2(i64 m, u64 p, i64 g, SlotSpace* out);
+// a slot basis: k distinct primes p_c = 1 mod m on one two-row ring (m = 2^3 .. 2^16, every p_c < 2^31: the direct transform of each channel),
+// P = prod p_c.  A slot holds an integer modulo P as a signed value in (-P/2, P/2); channel c is the two-row space of (m, p_c, g).
+struct SlotBasis {
+  static constexpr int MAXK = 32, MAXL = 16;
+  i64 m = 0;
+  u64 g = 0;
+  int k = 0, limbs = 0;                // limbs = ceil((bitlen(P) + 1) / 64): two's complement limbs of a value in (-P/2, P/2)
+  std::vector<u64> primes;             // [k]
+  std::vector<SlotSpace> ch;           // [k]
+  std::vector<u64> garner;             // [k][k]: entry [c][j], j < c, is p_j^-1 mod p_c (mixed-radix digits, Garner)
+  std::vector<u64> P, halfP;           // [limbs] each: P and floor(P / 2)
+};
+const char* slot_basis(i64 m, const u64* primes, int k, i64 g, SlotBasis* out);
+// the largest primes 1 mod m below 2^prime_bits, descending, until P > 2^(bits + 1)
+const char* slot_basis_plan(i64 m, int bits, int prime_bits, i64 g, std::vector<u64>* primes, int* limbs);
 }  // namespace hm
 
 // --------------------------------------------------------------------------------- plaintext slots (kernels_slots.hip)
@@ -313,6 +328,21 @@ int slots_pow2_run(fhesi_slots* s, bool embed, const i64* d_in, i64* d_out, i64 
 int slots_embed_rows(fhesi_slots* s, const i64* d_vals, i64 nvals, bool only_usable, i64 count, i64* d_msg);
 int slots_decode_rows(fhesi_slots* s, const i64* d_msg, i64 count, i64 nvals, bool only_usable, i64* d_vals);
 int slots_noise_rows(fhesi_slots* s, u64 seed, u64 first, i64 count, i64* d_vals /* [count][phi(m)] */);      // Regression::GenerateNoise's randVec
+
+// --------------------------------------------------------------------------------- slot bases (kernels_slots_basis.hip)
+// k channels on one context: the two-row spaces of (m, p_c, g), owned by the basis, and the tables of the recombination
+struct fhesi_slots_basis {
+  fhesi_ctx* ctx = nullptr;
+  hm::SlotBasis B;
+  std::vector<fhesi_slots*> ch;        // [k] channel c's space (direct path)
+  void* d_chan = nullptr;              // [k] per-channel records of the kernels: transform tables and the constants of the limb reduction
+  Shoup2* d_garner = nullptr;          // [k][k] p_j^-1 mod p_c, j < c
+  u32* d_words = nullptr;              // [2][2 limbs] P and floor(P / 2) as 32-bit words, then [k] the primes
+};
+// d_vals [count][nvals][L] two's complement limbs <-> d_msg [k][count][phi(m)] int64 in [0, p_c).  embed takes any L_in <= 16 and reduces;
+// decode writes L = B.limbs limbs per value, centred in (-P/2, P/2), and borrows workspace slot 8 for the residues.  Enqueued on the context's stream.
+int slots_basis_embed_rows(fhesi_slots_basis* b, const i64* d_vals, int L_in, i64 nvals, i64 count, i64* d_msg);
+int slots_basis_decode_rows(fhesi_slots_basis* b, const i64* d_msg, i64 count, i64 nvals, i64* d_vals);
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

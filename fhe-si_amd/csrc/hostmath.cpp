@@ -312,4 +312,75 @@ std::vector<u64> bn_mul_small(const std::vector<u64>& a, u64 b) {
   return r;
 }
 
+// ---- slot bases: k distinct primes p_c = 1 mod m on one two-row ring, P = prod p_c; a slot holds an integer modulo P, channel c its residue
+// modulo p_c in the two-row space of (m, p_c, g).  Scope = the direct transform of every channel: m = 2^3 .. 2^16, p_c < 2^31.
+static int bn_bitlen(const std::vector<u64>& a) {
+  for (int i = (int)a.size() - 1; i >= 0; --i)
+    if (a[i]) return 64 * i + 64 - __builtin_clzll(a[i]);
+  return 0;
+}
+static const char* basis_ring(i64 m, i64 g, u64* gm) {
+  if (m < 1 || (m & (m - 1)) != 0) return "m is not a power of two (a slot basis lives on a two-row ring)";
+  if (m < 8) return "m = 2^k with k < 3: no two-row space there";
+  if (m > (1 << 16)) return "m above 2^16: the channels of a slot basis run the direct transform, which needs n <= 2^15";
+  *gm = (u64)(((g % m) + m) % m);
+  if (*gm % 8 != 3 && *gm % 8 != 5) return "the generator is not 3 or 5 mod 8: its powers and their negatives do not reach every slot";
+  return nullptr;
+}
+const char* slot_basis(i64 m, const u64* primes, int k, i64 g, SlotBasis* out) {
+  static thread_local char why[256];
+  u64 gm = 0;
+  if (const char* w = basis_ring(m, g, &gm)) return w;
+  if (k < 1) return "no primes: a slot basis needs at least one";
+  if (k > SlotBasis::MAXK) return "more than 32 primes";
+  if (!primes) return "null prime list";
+  SlotBasis B;
+  B.m = m; B.g = gm; B.k = k;
+  B.primes.assign(primes, primes + k);
+  B.ch.resize(k);
+  for (int c = 0; c < k; ++c) {
+    const u64 p = primes[c];
+    const char* w = nullptr;
+    if (p >= (1ull << 31)) w = "p >= 2^31 (the direct transform keeps lazy values below 2p in a 32-bit word)";
+    else if (!is_prime(p)) w = "not prime (p^r and composite moduli are not supported)";
+    else if ((p - 1) % (u64)m != 0) w = "p != 1 mod m: ord_m(p) > 1, the slots would live in an extension field GF(p^d)";
+    for (int j = 0; j < c && !w; ++j)
+      if (primes[j] == p) w = "given twice (the residues modulo equal primes carry nothing new)";
+    if (!w) w = slot_space_pow2(m, p, (i64)gm, &B.ch[c]);
+    if (!w && !B.ch[c].direct) w = "outside the direct transform";
+    if (w) { snprintf(why, sizeof(why), "prime %d (%llu): %s", c, (unsigned long long)p, w); return why; }
+  }
+  std::vector<u64> P(1, 1);
+  for (int c = 0; c < k; ++c) P = bn_mul_small(P, primes[c]);
+  B.limbs = (bn_bitlen(P) + 1 + 63) / 64;
+  P.resize(B.limbs, 0);
+  B.P = P;
+  B.halfP.assign(B.limbs, 0);                                // floor(P / 2)
+  for (int i = 0; i < B.limbs; ++i) B.halfP[i] = (P[i] >> 1) | (i + 1 < B.limbs ? P[i + 1] << 63 : 0);
+  B.garner.assign((size_t)k * k, 0);                         // [c][j], j < c: p_j^-1 mod p_c
+  for (int c = 0; c < k; ++c)
+    for (int j = 0; j < c; ++j) B.garner[(size_t)c * k + j] = invmod(primes[j] % primes[c], primes[c]);
+  *out = B;
+  return nullptr;
+}
+const char* slot_basis_plan(i64 m, int bits, int prime_bits, i64 g, std::vector<u64>* primes, int* limbs) {
+  u64 gm = 0;
+  if (const char* w = basis_ring(m, g, &gm)) return w;
+  if (bits < 1 || bits > 31 * SlotBasis::MAXK) return "bits outside [1, 992]: 32 primes below 2^31 hold no more";
+  if (prime_bits < 4 || prime_bits > 31) return "prime_bits outside [4, 31]";
+  std::vector<u64> P(1, 1);
+  primes->clear();
+  u64 cand = (((1ull << prime_bits) - 2) / (u64)m) * (u64)m + 1;      // the largest 1 mod m below 2^prime_bits
+  while (bn_bitlen(P) < bits + 2) {                          // P > 2^(bits + 1)  <=>  P >= 2^(bits + 1) + 1 (P is odd)  <=>  bitlen(P) >= bits + 2
+    while (cand > (u64)m && !is_prime(cand)) cand -= (u64)m;
+    if (cand <= (u64)m) return "not enough primes 1 mod m below 2^prime_bits for that many bits";
+    if ((int)primes->size() == SlotBasis::MAXK) return "more than 32 primes would be needed: raise prime_bits";
+    primes->push_back(cand);
+    P = bn_mul_small(P, cand);
+    cand -= (u64)m;
+  }
+  *limbs = (bn_bitlen(P) + 1 + 63) / 64;                    // at most 16: P < 2^(31 * 32)
+  return nullptr;
+}
+
 }  // namespace hm

@@ -356,6 +356,58 @@ int fhesi_slots_shape(const fhesi_slots* s, int64_t* rows, int64_t* cols, int32_
 int fhesi_slots_set_path(fhesi_slots* s, int32_t path);      /* two-row spaces: 0 = the direct transform (refused where the plan does not admit it), otherwise the chirp.
                                                                 Result-neutral; for measurements and for comparing the two.  Synchronises the context's stream. */
 
+/* ---- integer slots over a BASIS of plaintext primes on a two-row ring (fhe-si_amd/csrc/kernels_slots_basis.hip).  A residue modulo one
+ * prime p < 2^32 is what a two-row space gives back; results of real data (det(X^T X) of thousands of rows) need hundreds of bits.  A slot
+ * basis is k distinct primes p_c = 1 mod m on ONE ring, P = prod p_c: the computation runs once per prime ("channel") and the results are
+ * recombined by the Chinese remainder theorem on the device.
+ *
+ * CONVENTION.  A slot holds an integer modulo P, given and returned as a SIGNED integer in (-P/2, P/2) (P is odd: no tie).  A logical
+ * plaintext / ciphertext is k channel plaintexts / ciphertexts; channel c is the two-row space of (m, p_c, g) exactly as fhesi_slots_create_pow2
+ * makes it (same rho0 rule per prime, same generator, same slot order s = r h + j), so every existing operation applies channel by channel with
+ * that channel's p: products, sums, row rotations, the row swap, the total-sum walk, the noise masks.  Nothing on the device knows p until a
+ * call passes it: ONE context and ONE key set (secret key, public key, key-switch matrices) serve every channel.  The chain of the context must
+ * be sized for the LARGEST prime of the basis (every multiplication pays log2 p_c bits of logQ).
+ *
+ * VALUES travel as L little-endian 64-bit limbs in two's complement.  On output L = limbs = ceil((bitlen(P) + 1) / 64) <= 16.  On input any
+ * L_in in 1 .. 16 is taken and reduced modulo each p_c (plain int64 data is L_in = 1).
+ * CAPACITY.  The caller owes |result| < P / 2 for everything the computation produces; a result that wraps modulo P comes back as another
+ * integer of (-P/2, P/2) and nothing on the device can detect it.  fhesi_slots_basis_plan sizes a basis for a bound of `bits` bits.
+ *
+ * SCOPE.  m = 2^k with 3 <= k <= 16 and every p_c < 2^31 (the direct transform, PATH 0 above), 1 <= k <= 32 primes, each prime, = 1 mod m, no
+ * prime twice, g = 3 or 5 mod 8.  Everything else is REFUSED on the host before anything is launched, fhesi_last_error names the condition and
+ * the context stays usable.
+ *
+ * INDEX RULE of the seeded forms.  A batch of `count` logical plaintexts uses the object indices first_index .. first_index + k count - 1:
+ * channel c, plaintext i takes first_index + c count + i, so channel c of fhesi_encrypt_int_slots_batch_seeded equals
+ * fhesi_encrypt_slots_batch_seeded(channel c's space, first_index + c count, vals mod p_c) BIT FOR BIT, and the caller advances by k count.
+ * fhesi_encrypt_noise_int_batch_seeded draws k independent masks per logical mask under the same rule: slot 0 of every channel is 0, hence
+ * slot 0 modulo P is untouched; the other slots are uniform modulo every p_c, hence modulo P.
+ *
+ * LAYOUTS.  vals [count][nvals][L] limbs; msg [k][count][n] int64 in [0, p_c) (what the encryption's message staging takes);
+ * ciphertexts [k][count] of [2][n][nlimbs] words.  The _dev forms take HBM buffers, enqueue on the context's stream and do not synchronise. */
+typedef struct fhesi_slots_basis fhesi_slots_basis;
+int fhesi_slots_basis_plan(int64_t m, int32_t bits, int32_t prime_bits, int64_t generator, int32_t* k, uint64_t* primes_out /* [32] */, int32_t* limbs);
+                                   /* host only, no device, no context: the largest primes = 1 mod m below 2^prime_bits (prime_bits <= 31), descending,
+                                      until P > 2^(bits + 1); refused when there are not enough of them or more than 32 would be needed */
+int fhesi_slots_basis_check(int64_t m, const uint64_t* primes, int32_t k, int64_t generator, int32_t* limbs, uint64_t* modulus_out /* [16] or null: P, little-endian */);
+                                   /* host only: the checks of fhesi_slots_basis_create on a ring given by m */
+int fhesi_slots_basis_create(fhesi_ctx* ctx, const uint64_t* primes, int32_t k, int64_t generator, fhesi_slots_basis** out);
+int fhesi_slots_basis_free(fhesi_slots_basis* b);                                  /* frees the channels' spaces with it */
+int fhesi_slots_basis_info(const fhesi_slots_basis* b, int32_t* k, uint64_t* primes /* [k] or null */, int32_t* limbs, int64_t* total, int64_t* rows, int64_t* cols);
+int fhesi_slots_basis_channel(fhesi_slots_basis* b, int32_t c, fhesi_slots** slots); /* channel c's fhesi_slots for every existing call; OWNED by the basis: never fhesi_slots_free it */
+int fhesi_slots_basis_embed(fhesi_slots_basis* b, const int64_t* vals_host /* [count][nvals][L_in] */, int32_t L_in, int64_t nvals, int64_t count,
+                            int64_t* msg_host /* [k][count][n] */);                /* slots nvals .. n-1 are zero */
+int fhesi_slots_basis_decode(fhesi_slots_basis* b, const int64_t* msg_host /* [k][count][n] */, int64_t count, int64_t nvals,
+                             int64_t* vals_host /* [count][nvals][limbs] */);
+int fhesi_slots_basis_embed_dev(fhesi_slots_basis* b, const int64_t* vals_dev, int32_t L_in, int64_t nvals, int64_t count, int64_t* msg_dev);
+int fhesi_slots_basis_decode_dev(fhesi_slots_basis* b, const int64_t* msg_dev, int64_t count, int64_t nvals, int64_t* vals_dev);
+int fhesi_encrypt_int_slots_batch_seeded(fhesi_ctx* ctx, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                         const int64_t* vals_host /* [count][nvals][L_in] */, int32_t L_in, int64_t nvals, int64_t count, uint64_t* out_dev /* [k][count] */, int32_t nlimbs);
+int fhesi_decrypt_int_slots_batch(fhesi_ctx* ctx, fhesi_slots_basis* b, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev /* [k][count] */, int32_t nlimbs, int64_t count,
+                                  int64_t nvals, int64_t* vals_host /* [count][nvals][limbs] */);
+int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* ctx, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                         int64_t count, uint64_t* out_dev /* [k][count] */, int32_t nlimbs);
+
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
  * fhesi_comm_init_all: one process, one host thread per GPU -- ncclCommInitAll over `devices`, comms_out[r] is rank r's handle.
