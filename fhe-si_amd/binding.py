@@ -514,10 +514,16 @@ class SlotSpace:
     """One PlaintextSpace on a context's GPU (fhesi_slots_create): batched EmbedInSlots / DecodeSlots and the slot-valued Encrypt / Decrypt.
     SlotSpace.pow2(ctx, p, g) makes the two-row space of a power-of-two ring (fhesi_slots_create_pow2) with the same methods."""
 
-    def __init__(self, ctx: "Context", p: int, generator: int, _two_rows: bool = False):
-        self.ctx, self.p, self.generator = ctx, p, generator
-        self.h = _vp()
-        _ck((_load().fhesi_slots_create_pow2 if _two_rows else _load().fhesi_slots_create)(ctx.h, p, generator, C.byref(self.h)))
+    def __init__(self, ctx: "Context", p: int, generator: int, _two_rows: bool = False, _borrowed=None):
+        h = _borrowed
+        if h is None:
+            h = _vp()
+            _ck((_load().fhesi_slots_create_pow2 if _two_rows else _load().fhesi_slots_create)(ctx.h, p, generator, C.byref(h)))
+        self._from_handle(ctx, p, generator, h, owned=_borrowed is None)
+
+    def _from_handle(self, ctx: "Context", p: int, generator: int, h, owned: bool = True):
+        """The record of the space behind handle h.  A borrowed space (owned=False: a channel of a SlotBasis) does not free its handle."""
+        self.ctx, self.p, self.generator, self.h, self.owned = ctx, p, generator, h, owned
         total, usable, rho0, naux = _i64(0), _i64(0), _u64(0), _i32(0)
         _ck(_load().fhesi_slots_info(self.h, C.byref(total), C.byref(usable), C.byref(rho0), C.byref(naux)))
         self.total, self.usable, self.rho0, self.aux_primes = total.value, usable.value, rho0.value, naux.value
@@ -539,7 +545,7 @@ class SlotSpace:
         self._shape()
 
     def close(self):
-        if getattr(self, "h", None):
+        if getattr(self, "h", None) and self.owned:
             _load().fhesi_slots_free(self.h)
             self.h = None
 
@@ -697,13 +703,7 @@ class SlotBasis:
         if c not in self._channels:
             h = _vp()
             _ck(_load().fhesi_slots_basis_channel(self.h, c, C.byref(h)))
-            s = SlotSpace.__new__(SlotSpace)
-            s.ctx, s.p, s.generator, s.h = self.ctx, self.primes[c], self.generator, h
-            total, usable, rho0, naux = _i64(0), _i64(0), _u64(0), _i32(0)
-            _ck(_load().fhesi_slots_info(h, C.byref(total), C.byref(usable), C.byref(rho0), C.byref(naux)))
-            s.total, s.usable, s.rho0, s.aux_primes = total.value, usable.value, rho0.value, naux.value
-            s._shape()
-            s.close = lambda: None
+            s = SlotSpace(self.ctx, self.primes[c], self.generator, _borrowed=h)
             s._basis = self
             self._channels[c] = s
         return self._channels[c]

@@ -89,22 +89,14 @@ extern "C" int fhesi_ct_gather_dev(fhesi_ctx* c, const uint64_t* pool, const int
 }
 
 // --------------------------------------------------------------------------------------------- Encrypt / Decrypt batches
-// FHESIPubKey::Encrypt (FHE-SI.cpp:10-36) for `count` plaintexts; the randomness is the caller's (the reference draws it from NTL's
-// PRNG): rand_host = [count][3][phi(m)] int64 = (r binary, e0, e1 Gaussian samples before the multiplication by p)
-// Where the message polynomials of a batch come from: the caller's coefficient arrays, or slot values embedded on the device
-// (kernels_slots.hip) straight into the message staging buffer -- given by the caller, or drawn there as noise masks.
-struct MsgSource {
-  const int64_t* msg_host = nullptr;   // [count][phi(m)] coefficient form (slots == nullptr)
-  fhesi_slots* slots = nullptr;
-  const int64_t* vals_host = nullptr;  // [count][nvals] slot values; nullptr with slots set: Regression::GenerateNoise masks from (seed, index)
-  i64 nvals = 0;
-  bool only_usable = true;
-  const int64_t* msg_dev = nullptr;    // [count][phi(m)] already in HBM (one channel of a slot basis, embedded by the caller): used where it is
-};
-static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, const int64_t* rand_host, bool seeded, u64 seed, u64 first,
-                              const MsgSource& src, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+// FHESIPubKey::Encrypt (FHE-SI.cpp:10-36) for `count` plaintexts whose message polynomials d_msg [count][phi(m)] are already in HBM: the one
+// core behind every Encrypt entry point.  The randomness is the caller's (the reference draws it from NTL's PRNG): rand_host =
+// [count][3][phi(m)] int64 = (r binary, e0, e1 Gaussian samples before the multiplication by p); or, seeded, drawn in HBM from (seed, first).
+// Ends in a synchronise: delta lives on this frame, and rand_host and the array the stage in front uploaded from are the caller's, free to go
+// when the entry point returns.  (A slot basis therefore synchronises once per channel.)
+static int encrypt_rows_dev(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, const int64_t* rand_host, bool seeded, u64 seed, u64 first,
+                            const i64* d_msg, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
   CHECK_CTX(c);
-  if (src.slots && src.slots->ctx != c) FHESI_FAIL("Encrypt: the plaintext space belongs to another context");
   if (!pk0 || !pk1 || pk0->ctx != c || pk1->ctx != c) FHESI_FAIL("Encrypt: public key belongs to another context");
   if ((int)pk0->idx.size() != c->L || (int)pk1->idx.size() != c->L) FHESI_FAIL("Encrypt: public key must be defined over all primes");
   if (logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("Encrypt: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
@@ -113,13 +105,11 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
   const i64 n = c->phim;
   const int L = c->L;
   const std::vector<int> all = full_set(c);
-  void *d_small, *d_rows, *d_ct, *d_pk, *d_msg, *d_delta;
+  void *d_small, *d_rows, *d_ct, *d_pk, *d_delta;
   FHESI_TRY(ws_reserve(c, 2, (size_t)count * 3 * n * 8, &d_small));
   FHESI_TRY(ws_reserve(c, 0, (size_t)count * 3 * L * n * 8, &d_rows));
   FHESI_TRY(ws_reserve(c, 1, (size_t)count * 2 * L * n * 8, &d_ct));
   FHESI_TRY(ws_reserve(c, 3, (size_t)2 * L * n * 8, &d_pk));
-  if (src.msg_dev) d_msg = (void*)src.msg_dev;
-  else FHESI_TRY(ws_reserve(c, 5, (size_t)count * n * 8, &d_msg));
   FHESI_TRY(ws_reserve(c, 4, (size_t)(nlimbs + 1) * 8, &d_delta));
   // delta = floor(2^logQ / p) (FHE-SI.cpp:31), nlimbs limbs
   std::vector<u64> delta(nlimbs, 0);
@@ -127,20 +117,6 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
     if (logQ == 64 * nlimbs) { /* 2^logQ needs limb nlimbs: redo with the extra limb */ rem = 1; for (int i = nlimbs - 1; i >= 0; --i) { const u128 cur = rem << 64; delta[i] = (u64)(cur / p); rem = cur % p; } } }
   if (seeded) FHESI_TRY(launch_sample_encrypt(c, (i64*)d_small, count, seed, first));      // r, e0, e1 drawn in HBM (kernels_sample.hip)
   else HIP_TRY(hipMemcpyAsync(d_small, rand_host, (size_t)count * 3 * n * 8, hipMemcpyHostToDevice, c->stream));
-  if (src.msg_dev) {}
-  else if (!src.slots) HIP_TRY(hipMemcpyAsync(d_msg, src.msg_host, (size_t)count * n * 8, hipMemcpyHostToDevice, c->stream));
-  else {
-    void* d_vals;
-    if (src.vals_host) {
-      FHESI_TRY(ws_reserve(c, 9, (size_t)count * src.nvals * 8, &d_vals));
-      HIP_TRY(hipMemcpyAsync(d_vals, src.vals_host, (size_t)count * src.nvals * 8, hipMemcpyHostToDevice, c->stream));
-      FHESI_TRY(slots_embed_rows(src.slots, (const i64*)d_vals, src.nvals, src.only_usable, count, (i64*)d_msg));
-    } else {      // slot 0 zero, the others uniform (Regression.h:181-185); all phi(m) slots embedded (:188)
-      FHESI_TRY(ws_reserve(c, 9, (size_t)count * n * 8, &d_vals));
-      FHESI_TRY(slots_noise_rows(src.slots, seed, first, count, (i64*)d_vals));
-      FHESI_TRY(slots_embed_rows(src.slots, (const i64*)d_vals, n, false, count, (i64*)d_msg));
-    }
-  }
   HIP_TRY(hipMemcpyAsync(d_delta, delta.data(), (size_t)nlimbs * 8, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(d_pk, pk0->d_rows, (size_t)L * n * 8, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync((u64*)d_pk + (size_t)L * n, pk1->d_rows, (size_t)L * n * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -153,51 +129,125 @@ static int encrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_d
   CrtTables* t;
   FHESI_TRY(get_crt_tables(c, all, &t));
   FHESI_TRY(launch_crt(c, t, (const u64*)d_ct, L, nullptr, count * 2, 2, 0, logQ, (u64*)out_dev, nlimbs));
-  FHESI_TRY(launch_add_scaled_msg(c, (u64*)out_dev, (const i64*)d_msg, (const u64*)d_delta, count, nlimbs, logQ));   // += delta*msg, Reduce (:31-35)
-  HIP_TRY(hipStreamSynchronize(c->stream));      // the host arrays may be released on return
+  FHESI_TRY(launch_add_scaled_msg(c, (u64*)out_dev, d_msg, (const u64*)d_delta, count, nlimbs, logQ));     // += delta*msg, Reduce (:31-35)
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// ---- the stages in front of the core.  Each checks its own arguments and leaves the message polynomials [rows][phi(m)] in workspace slot 5
+// (slot values pass through slot 9: dead before the transforms of the encryption start); nothing here synchronises -- the core does.
+static int ws_i64(fhesi_ctx* c, int slot, size_t bytes, i64** out) { void* d; FHESI_TRY(ws_reserve(c, slot, bytes, &d)); *out = (i64*)d; return 0; }
+static int msg_staging(fhesi_ctx* c, i64 rows, i64** d_msg) { return ws_i64(c, 5, (size_t)rows * c->phim * 8, d_msg); }
+static int upload_vals(fhesi_ctx* c, const int64_t* vals_host, size_t bytes, i64** d_vals) {
+  FHESI_TRY(ws_i64(c, 9, bytes, d_vals));
+  HIP_TRY(hipMemcpyAsync(*d_vals, vals_host, bytes, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+static int stage_msg_host(fhesi_ctx* c, const int64_t* msg_host, i64 count, i64** d_msg) {      // [count][phi(m)] coefficient form
+  if (count <= 0) return 0;
+  FHESI_TRY(msg_staging(c, count, d_msg));
+  HIP_TRY(hipMemcpyAsync(*d_msg, msg_host, (size_t)count * c->phim * 8, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+static int stage_msg_slots(fhesi_ctx* c, fhesi_slots* s, const int64_t* vals_host, i64 nvals, bool only_usable, i64 count, i64** d_msg) {      // [count][nvals] slot values
+  if (!s) FHESI_FAIL("Encrypt: null plaintext space");
+  if (s->ctx != c) FHESI_FAIL("Encrypt: the plaintext space belongs to another context");
+  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
+  FHESI_TRY(slots_check_shape("Encrypt", nvals, count, s->S.phim));
+  if (!count) return 0;
+  i64* d_vals;
+  FHESI_TRY(msg_staging(c, count, d_msg));
+  FHESI_TRY(upload_vals(c, vals_host, (size_t)count * nvals * 8, &d_vals));
+  return slots_embed_rows(s, d_vals, nvals, only_usable, count, *d_msg);
+}
+// Regression::GenerateNoise masks: slot 0 zero, the others uniform from (seed, first + i) (Regression.h:181-185); all phi(m) slots embedded (:188)
+static int stage_msg_noise(fhesi_ctx* c, fhesi_slots* s, u64 seed, u64 first, i64 count, i64** d_msg) {
+  if (!s) FHESI_FAIL("GenerateNoise: null plaintext space");
+  if (s->ctx != c) FHESI_FAIL("Encrypt: the plaintext space belongs to another context");
+  if (count <= 0) return 0;
+  i64* d_vals;
+  FHESI_TRY(msg_staging(c, count, d_msg));
+  FHESI_TRY(ws_i64(c, 9, (size_t)count * c->phim * 8, &d_vals));
+  FHESI_TRY(slots_noise_rows(s, seed, first, count, d_vals));
+  return slots_embed_rows(s, d_vals, c->phim, false, count, *d_msg);
+}
+// a slot basis (kernels_slots_basis.hip): one embedding launch for all k channels, [k][count][phi(m)]
+static int basis_check(fhesi_ctx* c, const fhesi_slots_basis* b, const char* what, i64 nvals, i64 count) {
+  if (!b) FHESI_FAIL("%s: null slot basis", what);
+  if (b->ctx != c) FHESI_FAIL("%s: the slot basis belongs to another context", what);
+  return slots_check_shape(what, nvals, count, c->phim);
+}
+static int stage_msg_basis(fhesi_ctx* c, fhesi_slots_basis* b, const int64_t* vals_host, int L_in, i64 nvals, i64 count, i64** d_msg) {      // [count][nvals][L_in] limbs
+  FHESI_TRY(basis_check(c, b, "Encrypt", nvals, count));
+  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
+  if (L_in < 1 || L_in > hm::SlotBasis::MAXL) FHESI_FAIL("Encrypt: %d limbs per value, 1 .. %d are taken", L_in, hm::SlotBasis::MAXL);
+  if (!count) return 0;
+  i64* d_vals;
+  FHESI_TRY(msg_staging(c, b->B.k * count, d_msg));
+  FHESI_TRY(upload_vals(c, vals_host, (size_t)count * nvals * L_in * 8, &d_vals));
+  return slots_basis_embed_rows(b, d_vals, L_in, nvals, count, *d_msg);
 }
 
 extern "C" int fhesi_encrypt_batch(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, const int64_t* rand_host,
                                    const int64_t* msg_host, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
   if (!rand_host) FHESI_FAIL("Encrypt: null randomness (fhesi_encrypt_batch_seeded draws it on the device)");
-  MsgSource src;
-  src.msg_host = msg_host;
-  return encrypt_batch_impl(c, pk0, pk1, logQ, p, rand_host, false, 0, 0, src, count, out_dev, nlimbs);
+  CHECK_CTX(c);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_host(c, msg_host, count, &d_msg));
+  return encrypt_rows_dev(c, pk0, pk1, logQ, p, rand_host, false, 0, 0, d_msg, count, out_dev, nlimbs);
 }
 // ... with the randomness drawn on the device: plaintext i takes the streams of object index first_index + i (philox.h)
 extern "C" int fhesi_encrypt_batch_seeded(fhesi_ctx* c, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t p, uint64_t seed, uint64_t first_index,
                                           const int64_t* msg_host, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
-  MsgSource src;
-  src.msg_host = msg_host;
-  return encrypt_batch_impl(c, pk0, pk1, logQ, p, nullptr, true, seed, first_index, src, count, out_dev, nlimbs);
+  CHECK_CTX(c);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_host(c, msg_host, count, &d_msg));
+  return encrypt_rows_dev(c, pk0, pk1, logQ, p, nullptr, true, seed, first_index, d_msg, count, out_dev, nlimbs);
 }
 // ... of plaintexts given as slot values (Plaintext(context, vector) + Encrypt): the message polynomials are embedded on the device and never
 // leave HBM.  Bit for bit fhesi_encrypt_batch_seeded(fhesi_slots_embed(vals)) under the same (seed, index).
 extern "C" int fhesi_encrypt_slots_batch_seeded(fhesi_ctx* c, fhesi_slots* s, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
                                                 const int64_t* vals_host, int64_t nvals, int32_t only_usable, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
-  if (!s) FHESI_FAIL("Encrypt: null plaintext space");
-  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
-  if (nvals < 1 || nvals > s->S.phim) FHESI_FAIL("Encrypt: %lld values per plaintext, the ring has %lld slots", (long long)nvals, (long long)s->S.phim);
-  MsgSource src;
-  src.slots = s; src.vals_host = vals_host; src.nvals = nvals; src.only_usable = only_usable != 0;
-  return encrypt_batch_impl(c, pk0, pk1, logQ, s->S.p, nullptr, true, seed, first_index, src, count, out_dev, nlimbs);
+  CHECK_CTX(c);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_slots(c, s, vals_host, nvals, only_usable != 0, count, &d_msg));
+  return encrypt_rows_dev(c, pk0, pk1, logQ, s->S.p, nullptr, true, seed, first_index, d_msg, count, out_dev, nlimbs);
 }
 // Regression::GenerateNoise (Regression.h:180-191) for `count` masks: slot 0 is 0, slots 1 .. phi(m)-1 are uniform on [0, p), drawn on the device
 // from (seed, first_index + i, slot, purpose 7) (philox.h); all phi(m) slots embedded, then an ordinary encryption under the same (seed, index)
 extern "C" int fhesi_encrypt_noise_batch_seeded(fhesi_ctx* c, fhesi_slots* s, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
                                                 int64_t count, uint64_t* out_dev, int32_t nlimbs) {
-  if (!s) FHESI_FAIL("GenerateNoise: null plaintext space");
-  MsgSource src;
-  src.slots = s;
-  return encrypt_batch_impl(c, pk0, pk1, logQ, s->S.p, nullptr, true, seed, first_index, src, count, out_dev, nlimbs);
+  CHECK_CTX(c);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_noise(c, s, seed, first_index, count, &d_msg));
+  return encrypt_rows_dev(c, pk0, pk1, logQ, s->S.p, nullptr, true, seed, first_index, d_msg, count, out_dev, nlimbs);
+}
+// ... over a slot basis: k channels on one key set, channel ch with p = p_ch reading its part of the staging; object index of channel ch,
+// plaintext i: first_index + ch count + i
+extern "C" int fhesi_encrypt_int_slots_batch_seeded(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                                    const int64_t* vals_host, int32_t L_in, int64_t nvals, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+  CHECK_CTX(c);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_basis(c, b, vals_host, L_in, nvals, count, &d_msg));
+  const size_t n = (size_t)c->phim;
+  for (int ch = 0; ch < b->B.k; ++ch)
+    FHESI_TRY(encrypt_rows_dev(c, pk0, pk1, logQ, b->B.primes[ch], nullptr, true, seed, first_index + (u64)ch * (u64)count, d_msg + ch * count * n, count,
+                               out_dev + ch * count * 2 * n * nlimbs, nlimbs));
+  return 0;
+}
+extern "C" int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
+                                                    int64_t count, uint64_t* out_dev, int32_t nlimbs) {
+  CHECK_CTX(c);
+  FHESI_TRY(basis_check(c, b, "GenerateNoise", 1, count));
+  for (int ch = 0; ch < b->B.k; ++ch)
+    FHESI_TRY(fhesi_encrypt_noise_batch_seeded(c, b->ch[ch], pk0, pk1, logQ, seed, first_index + (u64)ch * (u64)count, count, out_dev + (size_t)ch * count * 2 * c->phim * nlimbs, nlimbs));
+  return 0;
 }
 
-// FHESISecKey::Decrypt (FHE-SI.cpp:93-119) of `count` unscaled 2-part ciphertexts [count][2][phi(m)][nlimbs] in HBM
-static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
-                              int64_t* msg_host, fhesi_slots* slots, i64 nvals, bool only_usable, int64_t* vals_host, int64_t* msg_dev = nullptr) {
+// FHESISecKey::Decrypt (FHE-SI.cpp:93-119) of `count` unscaled 2-part ciphertexts [count][2][phi(m)][nlimbs] in HBM: the one core behind every
+// Decrypt entry point.  Leaves round(p z / q) mod p in d_msg [count][phi(m)] (HBM) and returns; only enqueues, and reads no host array.
+static int decrypt_rows_dev(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count, i64* d_msg) {
   CHECK_CTX(c);
-  if (slots && slots->ctx != c) FHESI_FAIL("Decrypt: the plaintext space belongs to another context");
   if (!sk1 || sk1->ctx != c) FHESI_FAIL("Decrypt: secret key belongs to another context");
   if ((int)sk1->idx.size() != c->L) FHESI_FAIL("Decrypt: secret key must be defined over all primes");
   if (logQ < 1 || nlimbs < 1) FHESI_FAIL("Decrypt: bad shape");
@@ -206,12 +256,10 @@ static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ,
   const i64 n = c->phim;
   const int L = c->L, nw = (logQ + 1 + 63) / 64;
   const std::vector<int> all = full_set(c);
-  void *d_rows, *d_z, *d_big, *d_msg;
+  void *d_rows, *d_z, *d_big;
   FHESI_TRY(ws_reserve(c, 0, (size_t)count * 2 * L * n * 8, &d_rows));
   FHESI_TRY(ws_reserve(c, 1, (size_t)count * L * n * 8, &d_z));
   FHESI_TRY(ws_reserve(c, 2, (size_t)count * n * nw * 8, &d_big));
-  if (msg_dev) d_msg = msg_dev;         // one channel of a slot basis: the message polynomials stay in HBM for the caller, nothing is copied or synchronised
-  else FHESI_TRY(ws_reserve(c, 5, (size_t)count * n * 8, &d_msg));
   FHESI_TRY(launch_rns_reduce(c, (const u64*)ct_dev, nlimbs, n, count, 2, nullptr, (u64*)d_rows, L, nullptr));     // DoubleCRT(parts[i]) (:98-101)
   FHESI_TRY(row_fwd(c, (u64*)d_rows, count * 2, L, nullptr, all.data()));
   FHESI_TRY(launch_decrypt_dot(c, (const u64*)d_rows, sk1->d_rows, count, (u64*)d_z));                              // DotProduct with (1, t) (:105-107)
@@ -219,92 +267,54 @@ static int decrypt_batch_impl(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ,
   CrtTables* t;
   FHESI_TRY(get_crt_tables(c, all, &t));
   FHESI_TRY(launch_crt(c, t, (const u64*)d_z, L, nullptr, count, 0, 0, 0, (u64*)d_big, nw));                         // toPoly, low logQ+1 bits kept
-  FHESI_TRY(launch_decrypt_round(c, (const u64*)d_big, count * n, nw, logQ, p, (i64*)d_msg));                        // round(p z / q) mod p (:110-116)
-  if (msg_dev) return 0;
-  if (!slots) HIP_TRY(hipMemcpyAsync(msg_host, d_msg, (size_t)count * n * 8, hipMemcpyDeviceToHost, c->stream));
-  else {          // DecodeSlots on the message polynomials where they are
-    void* d_vals;
-    FHESI_TRY(ws_reserve(c, 9, (size_t)count * nvals * 8, &d_vals));
-    FHESI_TRY(slots_decode_rows(slots, (const i64*)d_msg, count, nvals, only_usable, (i64*)d_vals));
-    HIP_TRY(hipMemcpyAsync(vals_host, d_vals, (size_t)count * nvals * 8, hipMemcpyDeviceToHost, c->stream));
-  }
+  return launch_decrypt_round(c, (const u64*)d_big, count * n, nw, logQ, p, d_msg);                                  // round(p z / q) mod p (:110-116)
+}
+// ---- behind the core: the message staging in slot 5 for the core to fill; slot values, once the transforms of the decryption are enqueued,
+// in slot 9; the host copy and the synchronise every Decrypt entry point ends in
+static int copy_out(fhesi_ctx* c, int64_t* out_host, const i64* d, size_t bytes) {
+  if (bytes) HIP_TRY(hipMemcpyAsync(out_host, d, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 extern "C" int fhesi_decrypt_batch(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
                                    int64_t* msg_host) {
-  return decrypt_batch_impl(c, sk1, logQ, p, ct_dev, nlimbs, count, msg_host, nullptr, 0, true, nullptr);
+  CHECK_CTX(c);
+  i64* d_msg;
+  FHESI_TRY(msg_staging(c, count, &d_msg));
+  FHESI_TRY(decrypt_rows_dev(c, sk1, logQ, p, ct_dev, nlimbs, count, d_msg));
+  return copy_out(c, msg_host, d_msg, (size_t)count * c->phim * 8);
 }
-// ... followed by Plaintext::DecodeSlots (Test_Regression.cpp:47-58: Decrypt, DecodeSlots, msgs[0]): vals_host [count][nvals]
+// ... followed by Plaintext::DecodeSlots (Test_Regression.cpp:47-58: Decrypt, DecodeSlots, msgs[0]) on the message polynomials where they
+// are: vals_host [count][nvals]
 extern "C" int fhesi_decrypt_slots_batch(fhesi_ctx* c, fhesi_slots* s, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
                                          int64_t nvals, int32_t only_usable, int64_t* vals_host) {
-  if (!s) FHESI_FAIL("Decrypt: null plaintext space");
-  if (nvals < 1 || nvals > s->S.phim) FHESI_FAIL("Decrypt: %lld values per plaintext, the ring has %lld slots", (long long)nvals, (long long)s->S.phim);
-  return decrypt_batch_impl(c, sk1, logQ, s->S.p, ct_dev, nlimbs, count, nullptr, s, nvals, only_usable != 0, vals_host);
-}
-
-// ---- the same over a slot basis (kernels_slots_basis.hip): k channels on one key set, channel c with p = p_c.  One embedding launch for all
-// channels into the message staging [k][count][phi(m)], then k ordinary encryptions reading their part of it; object index of channel c,
-// plaintext i: first_index + c count + i.
-static int basis_check(fhesi_ctx* c, const fhesi_slots_basis* b, const char* what, i64 nvals) {
   CHECK_CTX(c);
-  if (!b) FHESI_FAIL("%s: null slot basis", what);
-  if (b->ctx != c) FHESI_FAIL("%s: the slot basis belongs to another context", what);
-  if (nvals < 1 || nvals > c->phim) FHESI_FAIL("%s: %lld values per plaintext, the ring has %lld slots", what, (long long)nvals, (long long)c->phim);
-  return 0;
+  if (!s) FHESI_FAIL("Decrypt: null plaintext space");
+  if (s->ctx != c) FHESI_FAIL("Decrypt: the plaintext space belongs to another context");
+  FHESI_TRY(slots_check_shape("Decrypt", nvals, count, s->S.phim));
+  const size_t bv = (size_t)count * nvals * 8;
+  i64 *d_msg, *d_vals;
+  FHESI_TRY(msg_staging(c, count, &d_msg));
+  FHESI_TRY(decrypt_rows_dev(c, sk1, logQ, s->S.p, ct_dev, nlimbs, count, d_msg));
+  FHESI_TRY(ws_i64(c, 9, bv, &d_vals));
+  FHESI_TRY(slots_decode_rows(s, d_msg, count, nvals, only_usable != 0, d_vals));
+  return copy_out(c, vals_host, d_vals, bv);
 }
-extern "C" int fhesi_encrypt_int_slots_batch_seeded(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
-                                                    const int64_t* vals_host, int32_t L_in, int64_t nvals, int64_t count, uint64_t* out_dev, int32_t nlimbs) {
-  FHESI_TRY(basis_check(c, b, "Encrypt", nvals));
-  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
-  if (L_in < 1 || L_in > hm::SlotBasis::MAXL) FHESI_FAIL("Encrypt: %d limbs per value, 1 .. %d are taken", L_in, hm::SlotBasis::MAXL);
-  if (count < 0) FHESI_FAIL("negative count");
-  if (!count) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  const i64 n = c->phim;
-  const int k = b->B.k;
-  void *d_vals, *d_msg;
-  FHESI_TRY(ws_reserve(c, 9, (size_t)count * nvals * L_in * 8, &d_vals));
-  FHESI_TRY(ws_reserve(c, 5, (size_t)k * count * n * 8, &d_msg));
-  HIP_TRY(hipMemcpyAsync(d_vals, vals_host, (size_t)count * nvals * L_in * 8, hipMemcpyHostToDevice, c->stream));
-  FHESI_TRY(slots_basis_embed_rows(b, (const i64*)d_vals, L_in, nvals, count, (i64*)d_msg));
-  for (int ch = 0; ch < k; ++ch) {
-    MsgSource src;
-    src.msg_dev = (const int64_t*)d_msg + (size_t)ch * count * n;
-    FHESI_TRY(encrypt_batch_impl(c, pk0, pk1, logQ, b->B.primes[ch], nullptr, true, seed, first_index + (u64)ch * (u64)count, src, count,
-                                 out_dev + (size_t)ch * count * 2 * n * nlimbs, nlimbs));
-  }
-  return 0;
-}
-extern "C" int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
-                                                    int64_t count, uint64_t* out_dev, int32_t nlimbs) {
-  FHESI_TRY(basis_check(c, b, "GenerateNoise", 1));
-  if (count < 0) FHESI_FAIL("negative count");
-  for (int ch = 0; ch < b->B.k; ++ch)
-    FHESI_TRY(fhesi_encrypt_noise_batch_seeded(c, b->ch[ch], pk0, pk1, logQ, seed, first_index + (u64)ch * (u64)count, count, out_dev + (size_t)ch * count * 2 * c->phim * nlimbs, nlimbs));
-  return 0;
-}
-// k decryptions leave their message polynomials in the staging [k][count][phi(m)]; one decoding launch and one recombination follow
+// ... over a slot basis: k decryptions leave their message polynomials in the staging [k][count][phi(m)]; one decoding launch and one
+// recombination follow
 extern "C" int fhesi_decrypt_int_slots_batch(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
                                              int64_t nvals, int64_t* vals_host) {
-  FHESI_TRY(basis_check(c, b, "Decrypt", nvals));
+  CHECK_CTX(c);
+  FHESI_TRY(basis_check(c, b, "Decrypt", nvals, count));
   if (!vals_host) FHESI_FAIL("Decrypt: null output");
-  if (count < 0) FHESI_FAIL("negative count");
-  if (!count) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  const i64 n = c->phim;
-  const int k = b->B.k;
-  void *d_vals, *d_msg;
-  FHESI_TRY(ws_reserve(c, 5, (size_t)k * count * n * 8, &d_msg));
-  for (int ch = 0; ch < k; ++ch)
-    FHESI_TRY(decrypt_batch_impl(c, sk1, logQ, b->B.primes[ch], ct_dev + (size_t)ch * count * 2 * n * nlimbs, nlimbs, count, nullptr, nullptr, 0, true, nullptr,
-                                 (int64_t*)d_msg + (size_t)ch * count * n));
-  const size_t bv = (size_t)count * nvals * b->B.limbs * 8;
-  FHESI_TRY(ws_reserve(c, 9, bv, &d_vals));
-  FHESI_TRY(slots_basis_decode_rows(b, (const i64*)d_msg, count, nvals, (i64*)d_vals));
-  HIP_TRY(hipMemcpyAsync(vals_host, d_vals, bv, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  const size_t n = (size_t)c->phim, bv = (size_t)count * nvals * b->B.limbs * 8;
+  i64 *d_msg, *d_vals;
+  FHESI_TRY(msg_staging(c, b->B.k * count, &d_msg));
+  for (int ch = 0; ch < b->B.k; ++ch)
+    FHESI_TRY(decrypt_rows_dev(c, sk1, logQ, b->B.primes[ch], ct_dev + ch * count * 2 * n * nlimbs, nlimbs, count, d_msg + ch * count * n));
+  FHESI_TRY(ws_i64(c, 9, bv, &d_vals));
+  FHESI_TRY(slots_basis_decode_rows(b, d_msg, count, nvals, d_vals));
+  return copy_out(c, vals_host, d_vals, bv);
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

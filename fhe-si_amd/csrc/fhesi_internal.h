@@ -156,8 +156,9 @@ struct fhesi_ctx {
   //   6 row transforms above 2^14 (two-pass, bit reversal)   7 Bluestein slot map / wave operands
   //   8 Bluestein convolution buffer, index lists        9 Bluestein inverse output, scalar lists (no Bluestein call in between)
   //   10 auxiliary-prime dot product output (kernels_ksaux.hip)      11 staging of host batches (fhesi_ct_mul_relin_batch)
-  //   (kernels_slots.hip borrows 8 for its convolution buffer, 9 for slot values and 5 for message polynomials: before the transforms of an
-  //   encryption start, after those of a decryption are done)
+  //   (the slot layer borrows 8 for its convolution buffer / basis residues, 9 for slot values and 5 for message polynomials -- slots_stage_host,
+  //   the stage_msg_* functions in front of encrypt_rows_dev: before the transforms of an encryption start; what follows decrypt_rows_dev:
+  //   after those of a decryption are enqueued)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -319,9 +320,15 @@ struct fhesi_slots {
   u32* d_p2pos = nullptr;              // [n] slot -> position of rho0^(e_slot) in the transform's (bit-reversed) output
   Tw p2ninv = {0, 0}, p2ninv_w1 = {0, 0};    // n^-1 and n^-1 psi^-brv(1): the scaling of the inverse, folded into its last stage
 };
+// make: checks phi(m), allocates, builds the direct or the chirp tables by S.direct, counts the live handle; releases on failure.  unmake: the
+// counterpart (the stream is the caller's to synchronise).  The one pair that touches live_handles for slot spaces, basis channels included.
+int slots_make(fhesi_ctx* c, const hm::SlotSpace& S, fhesi_slots** out);
+void slots_unmake(fhesi_slots* s);
 int slots_build(fhesi_slots* s);       // the chirp tables and the internal context (kernels_slots.hip)
-void slots_release(fhesi_slots* s);
 int slots_pow2_build(fhesi_slots* s);  // the direct tables (kernels_slots_pow2.hip)
+// what the plan / info / shape entry points report (any pointer may be null); path: 0 direct, else the chirp's auxiliary primes
+void slots_describe(const hm::SlotSpace& S, int64_t* total, int64_t* usable, int64_t* rows, int64_t* cols, uint64_t* rho0, int32_t* aux_primes, int32_t* path, int32_t* e_out);
+int slots_check_shape(const char* what, i64 nvals, i64 count, i64 total);      // 1 <= nvals <= total, count >= 0
 int slots_pow2_run(fhesi_slots* s, bool embed, const i64* d_in, i64* d_out, i64 nvals, i64 take, i64 count);
 // d_vals [count][nvals] int64 (any sign; reduced modulo p) <-> d_msg [count][phi(m)] int64 in [0, p).  Slots at or above min(nvals, cap), cap =
 // usable or phi(m), are zero on embed and written as zero on decode.  Everything is enqueued on the context's stream.
@@ -343,6 +350,20 @@ struct fhesi_slots_basis {
 // decode writes L = B.limbs limbs per value, centred in (-P/2, P/2), and borrows workspace slot 8 for the residues.  Enqueued on the context's stream.
 int slots_basis_embed_rows(fhesi_slots_basis* b, const i64* d_vals, int L_in, i64 nvals, i64 count, i64* d_msg);
 int slots_basis_decode_rows(fhesi_slots_basis* b, const i64* d_msg, i64 count, i64 nvals, i64* d_vals);
+// A host batch through the device, for a space or a basis: slot values in workspace slot 9 (bv bytes), message polynomials in slot 5 (bm bytes).
+// Uploads the input side, run(d_vals, d_msg) enqueues the transform, downloads the other side, synchronises.
+template <class F> int slots_stage_host(fhesi_ctx* c, bool embed, const int64_t* in_host, int64_t* out_host, size_t bv, size_t bm, F run) {
+  if (!bm) return 0;                   // an empty batch
+  HIP_TRY(hipSetDevice(c->device));
+  void *d_vals, *d_msg;
+  FHESI_TRY(ws_reserve(c, 9, bv, &d_vals));
+  FHESI_TRY(ws_reserve(c, 5, bm, &d_msg));
+  HIP_TRY(hipMemcpyAsync(embed ? d_vals : d_msg, in_host, embed ? bv : bm, hipMemcpyHostToDevice, c->stream));
+  FHESI_TRY(run((i64*)d_vals, (i64*)d_msg));
+  HIP_TRY(hipMemcpyAsync(out_host, embed ? d_msg : d_vals, embed ? bm : bv, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

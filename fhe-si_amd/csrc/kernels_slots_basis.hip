@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(SB_GT) slots_basis_garner(const u32* __restric
 // ------------------------------------------------------------------------------------------------ setup and launch
 static void basis_release(fhesi_slots_basis* b) {
   for (fhesi_slots* s : b->ch)
-    if (s) { b->ctx->live_handles--; slots_release(s); }
+    if (s) slots_unmake(s);
   hipFree(b->d_chan); hipFree(b->d_garner); hipFree(b->d_words);
   delete b;
 }
@@ -135,15 +135,10 @@ static int basis_build(fhesi_slots_basis* b) {
   const int k = B.k;
   std::vector<BasisChan> chans(k);
   for (int i = 0; i < k; ++i) {
-    fhesi_slots* s = new fhesi_slots();
-    s->ctx = c;
-    s->S = B.ch[i];
-    if (const int rc = slots_pow2_build(s)) { slots_release(s); return rc; }
-    c->live_handles++;
-    b->ch[i] = s;
+    FHESI_TRY(slots_make(c, B.ch[i], &b->ch[i]));          // (direct path: hm::slot_basis admits no other)
     const u64 p = B.primes[i];
     BasisChan& C = chans[i];
-    C.D = sp2_dev(s);
+    C.D = sp2_dev(b->ch[i]);
     C.one = {1u, (u32)((1ull << 32) / p)};
     const u64 r = (1ull << 32) % p;
     C.r32 = {(u32)r, (u32)((r << 32) / p)};
@@ -176,9 +171,7 @@ static int basis_build(fhesi_slots_basis* b) {
 }
 static int basis_shape(const fhesi_slots_basis* b, const char* what, i64 nvals, i64 count) {
   if (!b) FHESI_FAIL("null slot basis");
-  const i64 n = b->B.m / 2;
-  if (nvals < 1 || nvals > n) FHESI_FAIL("%s: %lld values per plaintext, the ring has %lld slots", what, (long long)nvals, (long long)n);
-  if (count < 0) FHESI_FAIL("negative count");
+  FHESI_TRY(slots_check_shape(what, nvals, count, b->B.m / 2));
   if (count > (1ll << 30)) FHESI_FAIL("%s: more than 2^30 plaintexts in one call", what);
   return 0;
 }
@@ -192,12 +185,6 @@ int slots_basis_embed_rows(fhesi_slots_basis* b, const i64* d_vals, int L_in, i6
   if (hipGetLastError() != hipSuccess) FHESI_FAIL("slot basis: kernel launch failed");
   return 0;
 }
-int slots_basis_residue_rows(fhesi_slots_basis* b, const i64* d_msg, i64 count, i64 nvals, u32* d_res) {
-  const u32 n = (u32)(b->B.m / 2);
-  slots_basis_decode<<<dim3((unsigned)count, (unsigned)b->B.k), sp2_threads(n), sp2_shmem(n), b->ctx->stream>>>(d_msg, d_res, nvals, count, (const BasisChan*)b->d_chan);
-  if (hipGetLastError() != hipSuccess) FHESI_FAIL("slot basis: kernel launch failed");
-  return 0;
-}
 int slots_basis_decode_rows(fhesi_slots_basis* b, const i64* d_msg, i64 count, i64 nvals, i64* d_vals) {
   FHESI_TRY(basis_shape(b, "DecodeSlots", nvals, count));
   if (!count) return 0;
@@ -205,10 +192,11 @@ int slots_basis_decode_rows(fhesi_slots_basis* b, const i64* d_msg, i64 count, i
   HIP_TRY(hipSetDevice(c->device));
   const SlotBasis& B = b->B;
   const i64 total = count * nvals;
+  const u32 n = (u32)(B.m / 2);
+  const int W = 2 * B.limbs;
   void* d_res;
   FHESI_TRY(ws_reserve(c, 8, (size_t)B.k * total * sizeof(u32), &d_res));
-  FHESI_TRY(slots_basis_residue_rows(b, d_msg, count, nvals, (u32*)d_res));
-  const int W = 2 * B.limbs;
+  slots_basis_decode<<<dim3((unsigned)count, (unsigned)B.k), sp2_threads(n), sp2_shmem(n), c->stream>>>(d_msg, (u32*)d_res, nvals, count, (const BasisChan*)b->d_chan);
   slots_basis_garner<<<(unsigned)((total + SB_GT - 1) / SB_GT), SB_GT, 0, c->stream>>>((const u32*)d_res, (u64*)d_vals, total, B.k, B.limbs, b->d_words + 2 * W, b->d_garner, b->d_words);
   if (hipGetLastError() != hipSuccess) FHESI_FAIL("slot basis: kernel launch failed");
   return 0;
@@ -282,31 +270,11 @@ extern "C" int fhesi_slots_basis_decode_dev(fhesi_slots_basis* b, const int64_t*
 extern "C" int fhesi_slots_basis_embed(fhesi_slots_basis* b, const int64_t* vals_host, int32_t L_in, int64_t nvals, int64_t count, int64_t* msg_host) {
   FHESI_TRY(basis_shape(b, "EmbedInSlots", nvals, count));
   if (L_in < 1 || L_in > SlotBasis::MAXL) FHESI_FAIL("EmbedInSlots: %d limbs per value, 1 .. %d are taken", L_in, SlotBasis::MAXL);
-  if (!count) return 0;
-  fhesi_ctx* c = b->ctx;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t bv = (size_t)count * nvals * L_in * 8, bm = (size_t)b->B.k * count * (b->B.m / 2) * 8;
-  void *d_vals, *d_msg;
-  FHESI_TRY(ws_reserve(c, 9, bv, &d_vals));
-  FHESI_TRY(ws_reserve(c, 5, bm, &d_msg));
-  HIP_TRY(hipMemcpyAsync(d_vals, vals_host, bv, hipMemcpyHostToDevice, c->stream));
-  FHESI_TRY(slots_basis_embed_rows(b, (const i64*)d_vals, L_in, nvals, count, (i64*)d_msg));
-  HIP_TRY(hipMemcpyAsync(msg_host, d_msg, bm, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return slots_stage_host(b->ctx, true, vals_host, msg_host, (size_t)count * nvals * L_in * 8, (size_t)b->B.k * count * (b->B.m / 2) * 8,
+                          [&](i64* d_vals, i64* d_msg) { return slots_basis_embed_rows(b, d_vals, L_in, nvals, count, d_msg); });
 }
 extern "C" int fhesi_slots_basis_decode(fhesi_slots_basis* b, const int64_t* msg_host, int64_t count, int64_t nvals, int64_t* vals_host) {
   FHESI_TRY(basis_shape(b, "DecodeSlots", nvals, count));
-  if (!count) return 0;
-  fhesi_ctx* c = b->ctx;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t bv = (size_t)count * nvals * b->B.limbs * 8, bm = (size_t)b->B.k * count * (b->B.m / 2) * 8;
-  void *d_vals, *d_msg;
-  FHESI_TRY(ws_reserve(c, 9, bv, &d_vals));
-  FHESI_TRY(ws_reserve(c, 5, bm, &d_msg));
-  HIP_TRY(hipMemcpyAsync(d_msg, msg_host, bm, hipMemcpyHostToDevice, c->stream));
-  FHESI_TRY(slots_basis_decode_rows(b, (const i64*)d_msg, count, nvals, (i64*)d_vals));
-  HIP_TRY(hipMemcpyAsync(vals_host, d_vals, bv, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return slots_stage_host(b->ctx, false, msg_host, vals_host, (size_t)count * nvals * b->B.limbs * 8, (size_t)b->B.k * count * (b->B.m / 2) * 8,
+                          [&](i64* d_vals, i64* d_msg) { return slots_basis_decode_rows(b, d_msg, count, nvals, d_vals); });
 }

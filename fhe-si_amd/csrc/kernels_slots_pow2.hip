@@ -113,16 +113,10 @@ int slots_pow2_run(fhesi_slots* s, bool embed, const i64* d_in, i64* d_out, i64 
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/fhesi_hip.h)
-static int sp2_path(const SlotSpace& S) { return S.direct ? 0 : S.naux; }
 extern "C" int fhesi_slots_plan_pow2(int64_t m, uint64_t p, int64_t generator, int64_t* total, int64_t* rows, int64_t* cols, uint64_t* rho0, int32_t* path, int32_t* e_out) {
   SlotSpace S;
   if (const char* why = hm::slot_space_pow2(m, p, generator, &S)) FHESI_FAIL("PlaintextSpace(m=%lld, p=%llu, g=%lld), two rows, refused: %s", (long long)m, (unsigned long long)p, (long long)generator, why);
-  if (total) *total = S.phim;
-  if (rows) *rows = S.rows;
-  if (cols) *cols = S.phim / S.rows;
-  if (rho0) *rho0 = S.rho0;
-  if (path) *path = sp2_path(S);
-  if (e_out) std::copy(S.exps.begin(), S.exps.end(), e_out);
+  slots_describe(S, total, nullptr, rows, cols, rho0, nullptr, path, e_out);
   return 0;
 }
 extern "C" int fhesi_slots_create_pow2(fhesi_ctx* c, uint64_t p, int64_t generator, fhesi_slots** out) {
@@ -131,21 +125,11 @@ extern "C" int fhesi_slots_create_pow2(fhesi_ctx* c, uint64_t p, int64_t generat
   if (!c) FHESI_FAIL("null context");
   SlotSpace S;                                             // the argument checks come first: a refused ring launches nothing
   if (const char* why = hm::slot_space_pow2(c->m, p, generator, &S)) FHESI_FAIL("PlaintextSpace(m=%lld, p=%llu, g=%lld), two rows, refused: %s", (long long)c->m, (unsigned long long)p, (long long)generator, why);
-  if (S.phim != c->phim) FHESI_FAIL("PlaintextSpace: phi(m) mismatch");
-  HIP_TRY(hipSetDevice(c->device));
-  fhesi_slots* s = new fhesi_slots();
-  s->ctx = c;
-  s->S = S;
-  if (const int rc = S.direct ? slots_pow2_build(s) : slots_build(s)) { slots_release(s); return rc; }
-  c->live_handles++;
-  *out = s;
-  return 0;
+  return slots_make(c, S, out);
 }
 extern "C" int fhesi_slots_shape(const fhesi_slots* s, int64_t* rows, int64_t* cols, int32_t* path) {
   if (!s) FHESI_FAIL("null slot space");
-  if (rows) *rows = s->S.rows;
-  if (cols) *cols = s->S.phim / s->S.rows;
-  if (path) *path = sp2_path(s->S);
+  slots_describe(s->S, nullptr, nullptr, rows, cols, nullptr, nullptr, path, nullptr);
   return 0;
 }
 // Which transform a two-row space runs: 0 the direct one (where the plan admits it), anything else the chirp.  Result-neutral: both compute

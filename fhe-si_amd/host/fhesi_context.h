@@ -82,25 +82,21 @@ class PlaintextSpace {
   // bound where the handle is made: the destructor (reached from ~FHEcontext in every program) then names no slot entry point, so a program
   // that never creates a slot space links against an ABI without them (the host-memory stand-in of the CPU-only harness)
   int (*release)(fhesi_slots*) = nullptr;
- public:
-  PlaintextSpace(fhesi_ctx* ctx, unsigned long p, unsigned generator) {        // Init(PhiX, p, generator) :53-56
-    ck(fhesi_slots_create(ctx, (uint64_t)p, (int64_t)generator, &h));
-    release = &fhesi_slots_free;
-    int64_t t = 0, u = 0; uint64_t r = 0; int32_t na = 0;
-    ck(fhesi_slots_info(h, &t, &u, &r, &na));
-    total = (long)t; usable = (long)u; rho0 = (unsigned long)r; phim = (long)t;
-  }
-  // the two-row space of a power-of-two ring (m = 2^k, k >= 3, p = 1 mod m, generator 3 or 5 mod 8; include/fhesi_hip.h): slot r Cols() + j
-  // sits on rho0^((-1)^r g^j mod m).  Not in the reference, whose single-generator walk asserts on these rings.
-  struct TwoRows {};
-  PlaintextSpace(fhesi_ctx* ctx, unsigned long p, unsigned generator, TwoRows) {
-    ck(fhesi_slots_create_pow2(ctx, (uint64_t)p, (int64_t)generator, &h));
+  // (an ordinary space reports one row)
+  void init(int rc) {
+    ck(rc);
     release = &fhesi_slots_free;
     int64_t t = 0, u = 0, rw = 0, cl = 0; uint64_t r = 0; int32_t na = 0, path = 0;
     ck(fhesi_slots_info(h, &t, &u, &r, &na));
     ck(fhesi_slots_shape(h, &rw, &cl, &path));
     total = (long)t; usable = (long)u; rho0 = (unsigned long)r; phim = (long)t; rows = (long)rw;
   }
+ public:
+  PlaintextSpace(fhesi_ctx* ctx, unsigned long p, unsigned generator) { init(fhesi_slots_create(ctx, (uint64_t)p, (int64_t)generator, &h)); }        // Init(PhiX, p, generator) :53-56
+  // the two-row space of a power-of-two ring (m = 2^k, k >= 3, p = 1 mod m, generator 3 or 5 mod 8; include/fhesi_hip.h): slot r Cols() + j
+  // sits on rho0^((-1)^r g^j mod m).  Not in the reference, whose single-generator walk asserts on these rings.
+  struct TwoRows {};
+  PlaintextSpace(fhesi_ctx* ctx, unsigned long p, unsigned generator, TwoRows) { init(fhesi_slots_create_pow2(ctx, (uint64_t)p, (int64_t)generator, &h)); }
   // m = 2^k with k >= 3 and p = 1 mod m: the rings whose slots form two rows
   static bool IsTwoRowRing(unsigned long m, unsigned long p) { return m >= 8 && (m & (m - 1)) == 0 && p % m == 1; }
   ~PlaintextSpace() { if (h) release(h); }

@@ -17,26 +17,11 @@ class FHESISecKey {
   size_t GetSize() const { return sKeys.size(); }
   // Decrypt for many unscaled 2-part ciphertexts in one device call (fhesi_decrypt_batch); same values as repeated Decrypt calls
   void DecryptBatch(std::vector<Plaintext>& ptxts, const std::vector<Ciphertext>& ctxts) const {
-    const long n = context.zMstar.phiM(), count = (long)ctxts.size(); const int nl = (int)((context.logQ + 63) / 64);
+    const long n = context.zMstar.phiM(), count = (long)ctxts.size();
     std::vector<int64_t> msg((size_t)count * n);
-    if (LazyCiphertexts() && count) {
-      // the ciphertexts as values in HBM (whatever was recorded for them runs now), gathered into one run of the arena
-      CtEngine& e = ct_engine(context);
-      std::vector<CtRef> vals; for (auto& c : ctxts) vals.push_back(c.device_value());
-      e.flush();
-      std::vector<int32_t> idx; for (auto& v : vals) { e.force(v); idx.push_back((int32_t)v->slot); }
-      const long run = e.alloc_run(count);
-      ck(fhesi_ct_gather_dev(e.h, e.pool(), idx.data(), count, e.words, e.ptr(run)));
-      int rc = fhesi_decrypt_batch(e.h, sKeys[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), e.ptr(run), nl, count, msg.data());
-      e.free_run(run, count);
-      ck(rc);
-    } else {
-      std::vector<uint64_t> host((size_t)count * 2 * n * nl);
-      for (long c = 0; c < count; ++c) for (int part = 0; part < 2; ++part) for (long j = 0; j < n; ++j) coeff(ctxts[c].GetPart((unsigned)part).poly, j).to_limbs(&host[((c * 2 + part) * n + j) * nl], nl);
-      void* dev; ck(fhesi_dev_alloc(context.handle(), host.size() * 8, &dev)); ck(fhesi_dev_upload(context.handle(), dev, host.data(), host.size() * 8));
-      ck(fhesi_decrypt_batch(context.handle(), sKeys[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), (const uint64_t*)dev, nl, count, msg.data()));
-      ck(fhesi_dev_free(context.handle(), dev));
-    }
+    ciphertexts_on_device(ctxts, [&](fhesi_ctx* h, const uint64_t* ct, int nl) {
+      return fhesi_decrypt_batch(h, sKeys[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), ct, nl, count, msg.data());
+    });
     ptxts.assign(count, Plaintext());
     for (long c = 0; c < count; ++c) ptxts[c].message.assign(msg.begin() + c * n, msg.begin() + (c + 1) * n);
   }
@@ -44,30 +29,42 @@ class FHESISecKey {
   // message polynomials never leave HBM.  vals[i] has nvals entries (0 = all phi(m) slots), the first min(nvals, usable or total) filled.
   void DecryptSlotsBatch(std::vector<std::vector<long>>& vals, const std::vector<Ciphertext>& ctxts, long nvals = 0, bool onlyUsable = true) const {
     const PlaintextSpace& ps = context.GetPlaintextSpace();
-    const long n = context.zMstar.phiM(), count = (long)ctxts.size(); const int nl = (int)((context.logQ + 63) / 64);
+    const long count = (long)ctxts.size();
     if (nvals <= 0) nvals = ps.GetTotalSlots();
     std::vector<int64_t> out((size_t)count * nvals);
-    if (LazyCiphertexts() && count) {
-      CtEngine& e = ct_engine(context);
-      std::vector<CtRef> v; for (auto& c : ctxts) v.push_back(c.device_value());
-      e.flush();
-      std::vector<int32_t> idx; for (auto& x : v) { e.force(x); idx.push_back((int32_t)x->slot); }
-      const long run = e.alloc_run(count);
-      ck(fhesi_ct_gather_dev(e.h, e.pool(), idx.data(), count, e.words, e.ptr(run)));
-      int rc = fhesi_decrypt_slots_batch(e.h, ps.handle(), sKeys[1].handle(), (int32_t)context.logQ, e.ptr(run), nl, count, nvals, onlyUsable ? 1 : 0, out.data());
-      e.free_run(run, count);
-      ck(rc);
-    } else if (count) {
-      std::vector<uint64_t> host((size_t)count * 2 * n * nl);
-      for (long c = 0; c < count; ++c) for (int part = 0; part < 2; ++part) for (long j = 0; j < n; ++j) coeff(ctxts[c].GetPart((unsigned)part).poly, j).to_limbs(&host[((c * 2 + part) * n + j) * nl], nl);
-      void* dev; ck(fhesi_dev_alloc(context.handle(), host.size() * 8, &dev)); ck(fhesi_dev_upload(context.handle(), dev, host.data(), host.size() * 8));
-      int rc = fhesi_decrypt_slots_batch(context.handle(), ps.handle(), sKeys[1].handle(), (int32_t)context.logQ, (const uint64_t*)dev, nl, count, nvals, onlyUsable ? 1 : 0, out.data());
-      fhesi_dev_free(context.handle(), dev);
-      ck(rc);
-    }
+    ciphertexts_on_device(ctxts, [&](fhesi_ctx* h, const uint64_t* ct, int nl) {
+      return fhesi_decrypt_slots_batch(h, ps.handle(), sKeys[1].handle(), (int32_t)context.logQ, ct, nl, count, nvals, onlyUsable ? 1 : 0, out.data());
+    });
     vals.assign(count, std::vector<long>());
     for (long c = 0; c < count; ++c) vals[c].assign(out.begin() + c * nvals, out.begin() + (c + 1) * nvals);
   }
+ private:
+  // the ciphertexts as one batch [count][2][phi(m)][nl] in HBM for one device call: gathered into a run of the arena when recording is on (they
+  // are values in HBM; whatever was recorded for them runs now), else packed and uploaded.  The run or buffer is released before the result is looked at.
+  template <class F> void ciphertexts_on_device(const std::vector<Ciphertext>& ctxts, F call) const {
+    const long n = context.zMstar.phiM(), count = (long)ctxts.size(); const int nl = (int)((context.logQ + 63) / 64);
+    if (!count) return;
+    if (LazyCiphertexts()) {
+      CtEngine& e = ct_engine(context);
+      std::vector<CtRef> vals; for (auto& c : ctxts) vals.push_back(c.device_value());
+      e.flush();
+      std::vector<int32_t> idx; for (auto& v : vals) { e.force(v); idx.push_back((int32_t)v->slot); }
+      const long run = e.alloc_run(count);
+      int rc = fhesi_ct_gather_dev(e.h, e.pool(), idx.data(), count, e.words, e.ptr(run));
+      if (!rc) rc = call(e.h, e.ptr(run), nl);
+      e.free_run(run, count);
+      ck(rc);
+      return;
+    }
+    std::vector<uint64_t> host((size_t)count * 2 * n * nl);
+    for (long c = 0; c < count; ++c) for (int part = 0; part < 2; ++part) poly_to_limbs(ctxts[c].GetPart((unsigned)part).poly, &host[((size_t)(c * 2 + part) * n) * nl], n, nl);
+    void* dev; ck(fhesi_dev_alloc(context.handle(), host.size() * 8, &dev));
+    int rc = fhesi_dev_upload(context.handle(), dev, host.data(), host.size() * 8);
+    if (!rc) rc = call(context.handle(), (const uint64_t*)dev, nl);
+    fhesi_dev_free(context.handle(), dev);
+    ck(rc);
+  }
+ public:
   void Decrypt(Plaintext& ptxt, const Ciphertext& ctxt) const {   // FHE-SI.cpp:93-119
     if (LazyCiphertexts() && !ctxt.isScaledUp() && ctxt.parts.resident() && sKeys.size() == 2) {
       // the ciphertext lives in HBM: the same dot product with (1, t), rounding and reduction as ONE device call on it (fhesi_decrypt_batch)
@@ -117,56 +114,28 @@ class FHESIPubKey {
   // Encrypt for many plaintexts in one device call (fhesi_encrypt_batch).  The randomness is drawn here, per plaintext, in the
   // order Encrypt draws it (r, noise of part 0, noise of part 1), so the ciphertexts equal those of repeated Encrypt calls.
   void EncryptBatch(std::vector<Ciphertext>& ctxts, const std::vector<Plaintext>& ptxts) const {
-    const long n = context.zMstar.phiM(), count = (long)ptxts.size(); const int nl = (int)((context.logQ + 63) / 64);
+    const long n = context.zMstar.phiM(), count = (long)ptxts.size();
     std::vector<int64_t> rnd((size_t)count * 3 * n), msg((size_t)count * n, 0);
     for (long c = 0; c < count; ++c) {
       for (long j = 0; j < n; ++j) rnd[(c * 3) * n + j] = RandomBnd(2L);
       for (int i = 0; i < 2; ++i) { ZZX e; sampleGaussian(e, n, context.stdev); for (long j = 0; j < n; ++j) rnd[(c * 3 + 1 + i) * n + j] = coeff(e, j).to_long(); }
       for (size_t k = 0; k < ptxts[c].message.size() && (long)k < n; ++k) msg[c * n + k] = ptxts[c].message[k];
     }
-    if (LazyCiphertexts() && count) {            // the ciphertexts stay in HBM, as consecutive slots of the arena
-      CtEngine& e = ct_engine(context); const long first = e.alloc_run(count);
-      int rc = fhesi_encrypt_batch(e.h, publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), rnd.data(), msg.data(), count, e.ptr(first), nl);
-      if (rc) { e.free_run(first, count); ck(rc); }
-      e.publish(first, count);
-      ctxts.assign(count, Ciphertext(context));
-      for (long c = 0; c < count; ++c) ctxts[c].set_device_value(e.wrap(first + c));
-      return;
-    }
-    void* dev; ck(fhesi_dev_alloc(context.handle(), (size_t)count * 2 * n * nl * 8, &dev));
-    ck(fhesi_encrypt_batch(context.handle(), publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), rnd.data(), msg.data(),
-                           count, (uint64_t*)dev, nl));
-    std::vector<uint64_t> host((size_t)count * 2 * n * nl);
-    ck(fhesi_dev_download(context.handle(), host.data(), dev, host.size() * 8)); ck(fhesi_dev_free(context.handle(), dev));
-    ctxts.assign(count, Ciphertext(context));
-    for (long c = 0; c < count; ++c) {
-      ctxts[c].Initialize(2, context);
-      for (int part = 0; part < 2; ++part) { ZZX poly; poly.rep.resize(n); for (long j = 0; j < n; ++j) poly.rep[j] = ZZ::from_limbs(&host[((c * 2 + part) * n + j) * nl], nl); poly.normalize(); ctxts[c][part].poly = poly; }
-    }
+    encrypt_on_device(ctxts, count, [&](fhesi_ctx* h, uint64_t* out, int nl) {
+      return fhesi_encrypt_batch(h, publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), rnd.data(), msg.data(), count, out, nl);
+    });
   }
   // ... with r and the noise drawn ON THE DEVICE from the counter-based generator (fhesi_encrypt_batch_seeded, csrc/philox.h): plaintext i
   // uses the streams of object index first + i, so a batch can be split or repeated anywhere and give the same ciphertexts
   // (no default index: an (seed, index) pair used twice repeats r, e0, e1 -- the difference of the two ciphertexts is delta (m1 - m2) in the clear)
   void EncryptBatchSeeded(std::vector<Ciphertext>& ctxts, const std::vector<Plaintext>& ptxts, SeedSequence& seq) const { EncryptBatchSeeded(ctxts, ptxts, seq.seed, seq.take(ptxts.size())); }
   void EncryptBatchSeeded(std::vector<Ciphertext>& ctxts, const std::vector<Plaintext>& ptxts, uint64_t seed, uint64_t first_obj) const {
-    const long n = context.zMstar.phiM(), count = (long)ptxts.size(); const int nl = (int)((context.logQ + 63) / 64);
+    const long n = context.zMstar.phiM(), count = (long)ptxts.size();
     std::vector<int64_t> msg((size_t)count * n, 0);
     for (long c = 0; c < count; ++c) for (size_t k = 0; k < ptxts[c].message.size() && (long)k < n; ++k) msg[c * n + k] = ptxts[c].message[k];
-    if (LazyCiphertexts() && count) {
-      CtEngine& e = ct_engine(context); const long first = e.alloc_run(count);
-      int rc = fhesi_encrypt_batch_seeded(e.h, publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), seed, first_obj, msg.data(), count, e.ptr(first), nl);
-      if (rc) { e.free_run(first, count); ck(rc); }
-      e.publish(first, count);
-      ctxts.assign(count, Ciphertext(context));
-      for (long c = 0; c < count; ++c) ctxts[c].set_device_value(e.wrap(first + c));
-      return;
-    }
-    void* dev; ck(fhesi_dev_alloc(context.handle(), (size_t)count * 2 * n * nl * 8, &dev));
-    ck(fhesi_encrypt_batch_seeded(context.handle(), publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), seed, first_obj, msg.data(), count, (uint64_t*)dev, nl));
-    std::vector<uint64_t> host((size_t)count * 2 * n * nl);
-    ck(fhesi_dev_download(context.handle(), host.data(), dev, host.size() * 8)); ck(fhesi_dev_free(context.handle(), dev));
-    ctxts.assign(count, Ciphertext(context));
-    for (long c = 0; c < count; ++c) { ctxts[c].Initialize(2, context); for (int part = 0; part < 2; ++part) limbs_to_poly(ctxts[c][part].poly, &host[((size_t)(c * 2 + part) * n) * nl], n, nl); }
+    encrypt_on_device(ctxts, count, [&](fhesi_ctx* h, uint64_t* out, int nl) {
+      return fhesi_encrypt_batch_seeded(h, publicKey[0].handle(), publicKey[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), seed, first_obj, msg.data(), count, out, nl);
+    });
   }
   // Plaintext(context, vals[i]) + Encrypt for a whole batch, the message polynomials embedded on the device and kept in HBM
   // (fhesi_encrypt_slots_batch_seeded); the same ciphertexts as EncryptBatchSeeded on the embedded plaintexts under the same (seed, index).

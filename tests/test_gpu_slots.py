@@ -1,5 +1,6 @@
 """GPU: plaintext slot packing on the device (fhesi_slots_*, the slot-valued Encrypt / Decrypt, the noise masks) through the C ABI against the
 model of tests/slots_model.py, which evaluates at roots and interpolates from the definition.  Exact."""
+import functools
 import json
 import os
 
@@ -11,20 +12,14 @@ import fhesi_pyref as R
 import oracle_lib as O
 import params as P
 import slots_model as M
+from slots_common import I, make, rand_pk
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 P31 = (1 << 31) - 1        # a 31-bit prime = 1 mod 22: 22 p^2 is above 2^59, which forces the two-prime convolution
 
 
-def I(v):
-    return [int(x) for x in v]
-
-
-def make(m, p, g, logQ=64):
-    primes, roots = P.chain_for(m, logQ, p)
-    ctx = F.Context(m, primes, roots)
-    return ctx, F.SlotSpace(ctx, p, g), M.slot_space(m, p, g)
+make = functools.partial(make, F.SlotSpace, M)
 
 
 @pytest.mark.parametrize("m,p,g", [(4, 5, 3), (9, 19, 2), (50, 101, 3), (22, 23, 7), (22, 67, 7), (2026, 2027, 3), (22, P31, 7)])
@@ -78,17 +73,6 @@ def test_large_rings_round_trip_and_sampled_slots(m, p):
     # Embed is linear
     a, b = vals[0:1], vals[1:2]
     assert np.array_equal(S.embed((a + b) % p, False), (S.embed(a, False) + S.embed(b, False)) % p)
-
-
-def rand_pk(ctx, primes, rng):
-    rows = P.rand_rows(rng, primes, ctx.phim, 2)
-    out = []
-    for r in range(2):
-        d = F.DoubleCRT(ctx)
-        for i in range(rows.shape[1]):
-            d.set_row(i, np.ascontiguousarray(rows[r, i]))
-        out.append(d)
-    return out
 
 
 @pytest.mark.parametrize("m,p,g,logQ", [(50, 101, 3, 90), (2026, 2027, 3, 128), (22, P31, 7, 100)])

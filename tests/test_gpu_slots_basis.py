@@ -14,18 +14,10 @@ import oracle_lib as O
 import params as P
 import slots_basis_model as MB
 import slots_pow2_model as M2
+from slots_common import I, View, context, device_keys, rand_pk
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def I(v):
-    return [int(x) for x in v]
-
-
-def context(m, logQ=64, p=65537):
-    primes, roots = P.chain_for(m, logQ, p)
-    return F.Context(m, primes, roots), primes
 
 
 def signed_values(rng, half, shape):
@@ -111,17 +103,6 @@ def test_fixtures():
         assert I(B.decode(np.array(c["msg"], dtype=np.int64)[:, None, :])[0]) == I(vals[0])
 
 
-def rand_pk(ctx, primes, rng):
-    rows = P.rand_rows(rng, primes, ctx.phim, 2)
-    out = []
-    for r in range(2):
-        d = F.DoubleCRT(ctx)
-        for i in range(rows.shape[1]):
-            d.set_row(i, np.ascontiguousarray(rows[r, i]))
-        out.append(d)
-    return out
-
-
 @pytest.mark.parametrize("m,primes,g,logQ", [(64, [257, 193, 449], 5, 90), (4096, MB.plan(4096, 100, 31, 3), 3, 128), (1 << 16, [65537, 786433], 3, 64)])
 def test_device_forms_and_fused_encrypt_decrypt(m, primes, g, logQ):
     ctx, chain = context(m, logQ, max(primes))
@@ -154,23 +135,6 @@ def test_device_forms_and_fused_encrypt_decrypt(m, primes, g, logQ):
         cts = ctx.upload(raw)
         plain = np.stack([ctx.decrypt_batch(pk1, logQ, primes[c], ctx.upload(raw[c * count:(c + 1) * count]), nl, count) for c in range(k)])
         assert np.array_equal(B.decrypt_batch(pk1, logQ, cts, nl, count, nvals, raw=True), B.decode(plain, nvals, raw=True))
-
-
-class View:
-    """part of a device buffer, for the calls that take one channel of a logical ciphertext"""
-
-    def __init__(self, buf, off):
-        self.ptr = F.binding._vp(buf.ptr.value + off)
-
-
-def device_keys(ctx, logQ, seed):
-    """t = sampleHWt(64), pk = (e + t c1, -c1), all on the device"""
-    n, nl = ctx.phim, (logQ + 63) // 64
-    sk1 = F.DoubleCRT(ctx).sample(0, 64, seed, 7)
-    c1 = F.DoubleCRT.from_poly(ctx, P.rand_limbs(np.random.default_rng(seed), (n,), nl, logQ))
-    pk0 = sk1.copy().op(c1, F.OP_MUL).op(F.DoubleCRT(ctx).sample(1, 0, seed, 9), F.OP_ADD)
-    pk1 = F.DoubleCRT.from_poly(ctx, O.ints_to_limbs([0] * n, 1)).op(c1, F.OP_SUB)
-    return sk1, pk0, pk1
 
 
 def test_big_integers_through_the_scheme_on_one_key_set():

@@ -1,6 +1,7 @@
 """GPU: the two-row slot spaces of the power-of-two rings (fhesi_slots_create_pow2: the direct negacyclic transform modulo p in LDS, the
 chirp where the plan picks it) through the C ABI against the model of tests/slots_pow2_model.py, which evaluates at roots and interpolates
 from the definition.  Exact."""
+import functools
 import json
 import os
 
@@ -12,6 +13,7 @@ import fhesi_pyref as R
 import oracle_lib as O
 import params as P
 import slots_pow2_model as M2
+from slots_common import I, device_keys, make, rand_pk
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -19,14 +21,7 @@ P31 = 2147473409           # 1 mod 2^10, just below 2^31: lazy values reach 2^32
 P32 = 2147493889           # 1 mod 2^10, just above 2^31: chirp, and m p^2 > 2^59 takes two auxiliary primes
 
 
-def I(v):
-    return [int(x) for x in v]
-
-
-def make(m, p, g, logQ=64):
-    primes, roots = P.chain_for(m, logQ, p)
-    ctx = F.Context(m, primes, roots)
-    return ctx, F.SlotSpace.pow2(ctx, p, g), M2.slot_space(m, p, g)
+make = functools.partial(make, F.SlotSpace.pow2, M2)
 
 
 @pytest.mark.parametrize("m,p,g", [(8, 17, 3), (16, 17, 5), (32, 97, 3), (64, 257, 5), (128, 257, 3), (256, 7681, 5), (1024, 12289, 3), (1024, P31, 3), (16, P32, 3), (64, P32, 5)])
@@ -133,17 +128,6 @@ def test_the_direct_path_is_refused_where_the_plan_does_not_admit_it():
         one_row.set_path(0)
 
 
-def rand_pk(ctx, primes, rng):
-    rows = P.rand_rows(rng, primes, ctx.phim, 2)
-    out = []
-    for r in range(2):
-        d = F.DoubleCRT(ctx)
-        for i in range(rows.shape[1]):
-            d.set_row(i, np.ascontiguousarray(rows[r, i]))
-        out.append(d)
-    return out
-
-
 @pytest.mark.parametrize("m,p,g,logQ", [(64, 257, 5, 90), (4096, 65537, 3, 128), (16, P32, 3, 100)])
 def test_device_forms_and_fused_encrypt_decrypt(m, p, g, logQ):
     primes, roots = P.chain_for(m, logQ, p)
@@ -171,16 +155,6 @@ def test_device_forms_and_fused_encrypt_decrypt(m, p, g, logQ):
         cts = ctx.upload(P.rand_limbs(rng, (count, 2, n), nl, logQ))
         plain = ctx.decrypt_batch(pk1, logQ, p, cts, nl, count)
         assert np.array_equal(S.decrypt_batch(pk1, logQ, cts, nl, count, nvals, only_usable), S.decode(plain, nvals, only_usable))
-
-
-def device_keys(ctx, logQ, seed):
-    """t = sampleHWt(64), pk = (e + t c1, -c1), all on the device"""
-    n, nl = ctx.phim, (logQ + 63) // 64
-    sk1 = F.DoubleCRT(ctx).sample(0, 64, seed, 7)
-    c1 = F.DoubleCRT.from_poly(ctx, P.rand_limbs(np.random.default_rng(seed), (n,), nl, logQ))
-    pk0 = sk1.copy().op(c1, F.OP_MUL).op(F.DoubleCRT(ctx).sample(1, 0, seed, 9), F.OP_ADD)
-    pk1 = F.DoubleCRT.from_poly(ctx, O.ints_to_limbs([0] * n, 1)).op(c1, F.OP_SUB)
-    return sk1, pk0, pk1
 
 
 def test_products_rotations_row_swap_total_sum_and_noise_through_the_scheme():
