@@ -4,8 +4,10 @@
 set -e
 name=$1; shift
 d=variants/obj_$name; mkdir -p $d
-for f in hostmath.cpp kernels_ntt.hip kernels_ew.hip kernels_crt.hip kernels_ct.hip kernels_sample.hip kernels_ksaux.hip kernels_aux32.hip kernels_tensor32.hip bluestein.hip comm.hip capi_ctx.hip capi_dcrt.hip capi_pipeline.hip capi_ct.hip; do
-  o=$d/${f%.*}.o
+# (the translation units are the Makefile's OBJS: a unit added there is built here too)
+for o in $(sed -n 's/^OBJS *= *//p' Makefile); do
+  f=${o%.o}.hip; [ -f $f ] || f=${o%.o}.cpp
+  o=$d/$o
   ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -Wno-unused-value "$@" -x hip -c $f -o $o ) &
 done
 wait

@@ -900,25 +900,43 @@ int ks32_build(fhesi_ctx* ctx, fhesi_ksk* k, const u64* d_kint, int W, int B, in
   return 0;
 }
 
+// What the three launchers of the dot product share.  The kernels take up to 160 KiB of dynamic LDS: the limit is raised once per kernel
+// (the caller's latch) and device.
+static int dot32_allow_lds(fhesi_ctx* ctx, const void* kernel, std::atomic<unsigned long long>& done) {
+  if (!(done.load() >> ctx->device & 1)) {
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    done.fetch_or(1ull << ctx->device);
+  }
+  return 0;
+}
+// The grid: `blocks` workgroups (the launcher's count) x groups of eight 64-element slices of a row x the four primes
+struct Dot32Geom { int lognsl /* log2 of the 64-element slices per row */, nsl8, sub_lg; };
+static int dot32_geom(fhesi_ctx* ctx, i64 blocks, Dot32Geom* g) {
+  const i64 nrow = aux32_row_len(ctx);
+  g->lognsl = hm::ilog2_ceil((u64)nrow) - 6;
+  g->nsl8 = (int)(nrow / 64 / 8);
+  if (blocks > 0x7fffffff || g->nsl8 > 65535) FHESI_FAIL("dot32: too many ciphertexts per call");
+  static_assert((kDigitSubCt & (kDigitSubCt - 1)) == 0, "sub-chunks of a power of two");
+  g->sub_lg = 0;
+  while (((i64)1 << g->sub_lg) < kDigitSubCt) ++g->sub_lg;
+  return 0;
+}
+// dot32_kernel4 folds through 2^32 mod p = 2^32 - 4p and needs it below 2^28 (true of every prime aux32_init picks for rows up to 2^19; any
+// other ring takes the LDS-tile kernels)
+static bool dot32_k4_prime_ok(u32 p) { return p < (1u << 30) && (u32)(0u - 4u * p) < (1u << 28); }
+
 // d_dig: tiled [4][n/64][count*ncol][64] u32; d_out: [count*2*NLB][4][n] u32
 template <int CT, int NW>
 static int launch_dot32_t(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out) {
   const size_t shmem = (size_t)ncol * CT * 32 * 4;
   static std::atomic<unsigned long long> attr_done{0};
-  if (!(attr_done.load() >> ctx->device & 1)) {
-    HIP_TRY(hipFuncSetAttribute((const void*)dot32_kernel2<CT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.fetch_or(1ull << ctx->device);
-  }
-  const i64 nrow = aux32_row_len(ctx);
-  const int lognsl = hm::ilog2_ceil((u64)nrow) - 6;              // log2 of the 64-element slices per row
-  const int ntiles = (int)((count + CT - 1) / CT), nsl8 = (int)(nrow / 64 / 8);
+  FHESI_TRY(dot32_allow_lds(ctx, (const void*)dot32_kernel2<CT, NW>, attr_done));
+  const int ntiles = (int)((count + CT - 1) / CT);
   const i64 blocks = (i64)8 * ntiles * 2;
-  if (blocks > 0x7fffffff || nsl8 > 65535) FHESI_FAIL("dot32: too many ciphertexts per call");
-  static_assert((kDigitSubCt & (kDigitSubCt - 1)) == 0, "sub-chunks of a power of two");
-  int sub_lg = 0;
-  while (((i64)1 << sub_lg) < kDigitSubCt) ++sub_lg;
+  Dot32Geom g;
+  FHESI_TRY(dot32_geom(ctx, blocks, &g));
   PROF_KERNEL(ctx, PROF_DOT, (dot32_kernel2<CT, NW>));
-  dot32_kernel2<CT, NW><<<dim3((unsigned)blocks, (unsigned)nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, nsl8, lognsl, sub_lg);
+  dot32_kernel2<CT, NW><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, g.nsl8, g.lognsl, g.sub_lg);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -927,19 +945,13 @@ static int launch_dot32_p(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, 
   const int ncp = ((ncol + NH - 1) / NH + 7) & ~7;                 // columns per part: whole 8-column pairs in every part but the last
   const size_t shmem = (size_t)ncp * CT * 32 * 4;
   static std::atomic<unsigned long long> attr_done{0};
-  if (!(attr_done.load() >> ctx->device & 1)) {
-    HIP_TRY(hipFuncSetAttribute((const void*)dot32_kernel2p<CT, NW, NH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.fetch_or(1ull << ctx->device);
-  }
-  const i64 nrow = aux32_row_len(ctx);
-  const int lognsl = hm::ilog2_ceil((u64)nrow) - 6;              // log2 of the 64-element slices per row
-  const int ntiles = (int)((count + CT - 1) / CT), nsl8 = (int)(nrow / 64 / 8);
+  FHESI_TRY(dot32_allow_lds(ctx, (const void*)dot32_kernel2p<CT, NW, NH>, attr_done));
+  const int ntiles = (int)((count + CT - 1) / CT);
   const i64 blocks = (i64)8 * ntiles * 2;
-  if (blocks > 0x7fffffff || nsl8 > 65535) FHESI_FAIL("dot32: too many ciphertexts per call");
-  int sub_lg = 0;
-  while (((i64)1 << sub_lg) < kDigitSubCt) ++sub_lg;
+  Dot32Geom g;
+  FHESI_TRY(dot32_geom(ctx, blocks, &g));
   PROF_KERNEL(ctx, PROF_DOT, (dot32_kernel2p<CT, NW, NH>));
-  dot32_kernel2p<CT, NW, NH><<<dim3((unsigned)blocks, (unsigned)nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, nsl8, lognsl, sub_lg, ncp);
+  dot32_kernel2p<CT, NW, NH><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, g.nsl8, g.lognsl, g.sub_lg, ncp);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -947,21 +959,15 @@ template <int NLBT, int CW, int KC, int PD, int NW = 8, int NSP = 1, int TAIL = 
 static int launch_dot32_k4(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out) {
   const size_t shmem = (size_t)2 * KC * 2 * NLBT * 64 * 4;
   static std::atomic<unsigned long long> attr_done{0};
-  if (!(attr_done.load() >> ctx->device & 1)) {
-    HIP_TRY(hipFuncSetAttribute((const void*)dot32_kernel4<NLBT, CW, KC, PD, NW, NSP, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_done.fetch_or(1ull << ctx->device);
-  }
+  FHESI_TRY(dot32_allow_lds(ctx, (const void*)dot32_kernel4<NLBT, CW, KC, PD, NW, NSP, TAIL>, attr_done));
   for (int a = 0; a < 4; ++a)
-    if ((u32)(0u - 4u * ctx->aux32->pr.p[a]) >= (1u << 28) || ctx->aux32->pr.p[a] >= (1u << 30)) FHESI_FAIL("dot32: prime %u outside the range of dot32_kernel4's fold", ctx->aux32->pr.p[a]);
-  const i64 nrow = aux32_row_len(ctx);
-  const int lognsl = hm::ilog2_ceil((u64)nrow) - 6;
-  const int ngroups = (int)((count + NW / NSP * CW - 1) / (NW / NSP * CW)), nsl8 = (int)(nrow / 64 / 8);
+    if (!dot32_k4_prime_ok(ctx->aux32->pr.p[a])) FHESI_FAIL("dot32: prime %u outside the range of dot32_kernel4's fold", ctx->aux32->pr.p[a]);
+  const int ngroups = (int)((count + NW / NSP * CW - 1) / (NW / NSP * CW));
   const i64 blocks = (i64)8 * ngroups;
-  if (blocks > 0x7fffffff || nsl8 > 65535) FHESI_FAIL("dot32: too many ciphertexts per call");
-  int sub_lg = 0;
-  while (((i64)1 << sub_lg) < kDigitSubCt) ++sub_lg;
+  Dot32Geom g;
+  FHESI_TRY(dot32_geom(ctx, blocks, &g));
   PROF_KERNEL(ctx, PROF_DOT, (dot32_kernel4<NLBT, CW, KC, PD, NW, NSP, TAIL>));
-  dot32_kernel4<NLBT, CW, KC, PD, NW, NSP, TAIL><<<dim3((unsigned)blocks, (unsigned)nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, count, d_out, ctx->aux32->pr, ngroups, lognsl, sub_lg);
+  dot32_kernel4<NLBT, CW, KC, PD, NW, NSP, TAIL><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, count, d_out, ctx->aux32->pr, ngroups, g.lognsl, g.sub_lg);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -970,14 +976,13 @@ int launch_dot32(fhesi_ctx* ctx, fhesi_ksk* k, const u32* d_dig, int ncol, i64 c
   if (!count) return 0;
   ProfScope prof(ctx, PROF_DOT, (double)count);
   // keys in LDS, digits in registers (dot32_kernel4): the limb counts of generated matrices at the benchmark rings
-  bool k4_primes = true;                    // dot32_kernel4 folds through 2^32 mod p = 2^32 - 4p and needs it below 2^28 (true of every prime aux32_init picks for rows up to 2^19; any other ring takes the LDS-tile kernels)
-  for (int a = 0; a < 4; ++a) k4_primes = k4_primes && ctx->aux32->pr.p[a] < (1u << 30) && (u32)(0u - 4u * ctx->aux32->pr.p[a]) < (1u << 28);
+  bool k4_primes = true;
+  for (int a = 0; a < 4; ++a) k4_primes = k4_primes && dot32_k4_prime_ok(ctx->aux32->pr.p[a]);
   if (ctx->opt.dot32_k4 && count >= 24 && k4_primes) {
     if (k->aux_rows == 7 && ncol % 12 == 6) return launch_dot32_k4<7, 6, 12, 3, 8, 1, 6>(ctx, k, d_dig, ncol, count, d_out);      // (66 columns = 5 x 12 + 6: the tail compiled on its own)
     if (k->aux_rows == 7) return launch_dot32_k4<7, 6, 12, 3>(ctx, k, d_dig, ncol, count, d_out);      // (measured: digit ring 2 / 3 / 4 steps ahead the same; 12 waves x 4 ciphertexts slower, profiles/r05_ab_dot_k4.txt)
     if (k->aux_rows == 8 && ncol % 12 == 6) return launch_dot32_k4<8, 4, 12, 3, 8, 1, 6>(ctx, k, d_dig, ncol, count, d_out);
     if (k->aux_rows == 8) return launch_dot32_k4<8, 4, 12, 3>(ctx, k, d_dig, ncol, count, d_out);      // (5 ciphertexts per lane: 160 bytes of spills -- odd counts leave the 64-bit pairs badly placed)
-    // 15 limbs (the stress ring): the 30 outputs split over two wave groups (with all 30 in one lane only 3 ciphertexts fit: 81 ms per 1024 against 37.6 for dot32_kernel2p)
     // (15 limbs -- the stress ring -- keep dot32_kernel2p: with all 30 outputs in one lane only 3 ciphertexts fit (81 ms per 1024 against 37.6); the
     // outputs split over two wave groups, NSP = 2, measured 37.8-42 ms in six configurations of ciphertexts per lane, ring depth, key lead and chunk
     // size against 37.5-38.2 -- profiles/r06_ab_stress_dot.txt; that instantiation left the library in round 6)

@@ -630,6 +630,39 @@ struct Garner32 { u32 p[4]; u32 c[6], cp[6]; u32 tw[4][2], twp[4][2]; };      //
 __device__ __forceinline__ u32 g32_mul(u32 y, u32 c, u32 cp, u32 p) { const u32 r = y * c - __umulhi(y, cp) * p; return r >= p ? r - p : r; }     // y any u32 -> [0, p)
 __device__ __forceinline__ u32 g32_mul_lazy(u32 y, u32 c, u32 cp, u32 p) { return y * c - __umulhi(y, cp) * p; }                               // y any u32 -> [0, 2p)
 __device__ __forceinline__ u32 g32_sub(u32 a, u32 b, u32 p) { return a + 2 * p - b; }      // a, b below 2p -> a - b + 2p in (0, 4p): only ever the argument of a g32_mul
+// Garner's mixed radix over the residues of the four auxiliary primes: x1 + p0 (x2 + p1 (x3 + p2 x4)), in [0, p0 p1 p2 p3)
+__device__ __forceinline__ u128 g32_garner(u32 v0, u32 v1, u32 v2, u32 v3, const Garner32& gc) {
+  const u32 p0 = gc.p[0], p1 = gc.p[1], p2 = gc.p[2], p3 = gc.p[3];
+  const u32 x1 = v0;                                                        // all four primes lie in (2^29, 2^30): a residue of one is below twice any other
+  // (inner products stay lazy, below 2p; the mixed-radix digits x2, x3, x4 themselves are reduced)
+  const u32 x2 = g32_mul(g32_sub(v1, x1, p1), gc.c[0], gc.cp[0], p1);
+  const u32 x3 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(v2, x1, p2), gc.c[1], gc.cp[1], p2), x2, p2), gc.c[2], gc.cp[2], p2);
+  const u32 x4 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(g32_mul_lazy(g32_sub(v3, x1, p3), gc.c[3], gc.cp[3], p3), x2, p3), gc.c[4], gc.cp[4], p3), x3, p3),
+                         gc.c[5], gc.cp[5], p3);
+  return (u128)((u64)x3 + (u64)p2 * x4) * ((u64)p0 * p1) + ((u64)x1 + (u64)p0 * x2);
+}
+// Coefficient j of a row S of nrow residues modulo p of a linear-convolution ring (fold_q != 0), folded into the ring on the residues: in [0, p).
+// (The callers keep the test for fold_q = 0 and take p from the kernel argument themselves: with either inside, the compiler orders the
+// loads of the run-time kernels differently.)
+__device__ __forceinline__ u32 g32_fold(const u32* __restrict__ row, i64 j, i64 n, i64 nrow, i64 fold_q, u32 p) {
+  u32 r;
+  if (fold_q > 0) {        // m = 2q':  S_j - S_(j+q') -+ (S_n - S_(n+q'))
+    const u32 s0 = row[j], s1 = row[j + fold_q], t0 = row[n], t1 = n + fold_q < nrow ? row[n + fold_q] : 0u;      // all below p
+    r = s0 + (p - s1) + ((j & 1) ? t0 + (p - t1) : t1 + (p - t0));                     // below 4p
+  } else {                 // m prime (offset -fold_q = m, n = m - 1):  S_j + S_(j+m) - S_(m-1)
+    const u32 s0 = row[j], s1 = j - fold_q < nrow ? row[j - fold_q] : 0u, t0 = row[n];
+    r = s0 + s1 + (p - t0);                                                               // below 3p
+  }
+  r = r >= 2 * p ? r - 2 * p : r;
+  return r >= p ? r - p : r;
+}
+// A centred limb sum V (two's complement, |V| < 2^119) made non-negative by + 2^119 and placed at bit bt < 64 of its first word: three words.
+// (Out-parameters: returned as a struct, the compile-time kernels schedule differently.)
+__device__ __forceinline__ void ks_limb_words(u128 V, int bt, u64& w0, u64& w1, u64& w2) {
+  V += (u128)1 << 119;                                           // non-negative, below 2^120
+  const u64 lo = (u64)V, hi = (u64)(V >> 64);
+  w0 = lo << bt; w1 = bt ? ((lo >> ((64 - bt) & 63)) | (hi << bt)) : hi; w2 = bt ? (hi >> ((64 - bt) & 63)) : 0;
+}
 // S = 1 (A32 only): the rows are the two sub-inverses A, B of 2^15-point rows as ntt32_inv_kernel3 leaves them -- coefficient e < 2^14 is
 // (A_e + B_e) / 2, coefficient e + 2^14 is (A_e - B_e) psi^-brv(1) / 2 (ntt32_tail_kernel's arithmetic, taken here in the loader: the rows are
 // read once instead of being rewritten by a pass of their own).
@@ -676,14 +709,7 @@ __global__ void __launch_bounds__(128) ks_recombine_kernel(const u64* __restrict
         v0 = tail(a0, b0, 0); v1 = tail(a1, b1, 1); v2 = tail(a2, b2, 2); v3 = tail(a3, b3, 3);
       }
       else { v0 = base32[(i64)(l * 4 + 0) * n]; v1 = base32[(i64)(l * 4 + 1) * n]; v2 = base32[(i64)(l * 4 + 2) * n]; v3 = base32[(i64)(l * 4 + 3) * n]; }
-      const u32 p0 = gc.p[0], p1 = gc.p[1], p2 = gc.p[2], p3 = gc.p[3];
-      const u32 x1 = v0;                                                        // all four primes lie in (2^29, 2^30): a residue of one is below twice any other
-      // (inner products stay lazy, below 2p; the mixed-radix digits x2, x3, x4 themselves are reduced)
-      const u32 x2 = g32_mul(g32_sub(v1, x1, p1), gc.c[0], gc.cp[0], p1);
-      const u32 x3 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(v2, x1, p2), gc.c[1], gc.cp[1], p2), x2, p2), gc.c[2], gc.cp[2], p2);
-      const u32 x4 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(g32_mul_lazy(g32_sub(v3, x1, p3), gc.c[3], gc.cp[3], p3), x2, p3), gc.c[4], gc.cp[4], p3), x3, p3),
-                             gc.c[5], gc.cp[5], p3);
-      V = (u128)((u64)x3 + (u64)p2 * x4) * ((u64)p0 * p1) + ((u64)x1 + (u64)p0 * x2);       // x1 + p0 (x2 + p1 (x3 + p2 x4)), below p0 p1 p2 p3
+      V = g32_garner(v0, v1, v2, v3, gc);
     } else {
     const u64 v0 = base[(i64)(l * 2 + 0) * n], v1 = base[(i64)(l * 2 + 1) * n];
     const u64 v0r = v0 >= q1 ? v0 - q1 : v0;
@@ -691,10 +717,9 @@ __global__ void __launch_bounds__(128) ks_recombine_kernel(const u64* __restrict
     V = (u128)q0 * t + v0;                                       // in [0, q_0 q_1)
     }
     if (V > half) V -= A;                                        // centred (two's complement in 128 bits)
-    V += (u128)1 << 119;                                         // non-negative, below 2^120
     const int s = B * l, wd = s >> 6, bt = s & 63;               // compile-time after unrolling
-    const u64 lo = (u64)V, hi = (u64)(V >> 64);
-    const u64 p0 = lo << bt, p1 = bt ? ((lo >> ((64 - bt) & 63)) | (hi << bt)) : hi, p2 = bt ? (hi >> ((64 - bt) & 63)) : 0;
+    u64 p0, p1, p2;
+    ks_limb_words(V, bt, p0, p1, p2);
     // the three words go into their limbs; the carries out of a limb are only COUNTED here and added in one pass below (a carry chain
     // through all the higher limbs per term was 40 % of the kernel)
     { const u64 s0 = x[wd] + p0; cnt[wd + 1] += s0 < p0 ? 1u : 0u; x[wd] = s0; }
@@ -771,26 +796,13 @@ __global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __
   // rows of nrow elements (nrow = n except on the linear-convolution rings, where the rows are the 2^14-point products)
   const u64* base = o + poly * NLB * 2 * nrow;
   const u32* base32 = reinterpret_cast<const u32*>(o) + poly * NLB * 4 * nrow;
-  // the centred integer at position `pos` of limb row l (two's complement in 128 bits)
+  // the two 60-bit chain primes only (the A32 instantiations go through fetch + g32_garner below): the centred integer at position `pos` of
+  // limb row l (two's complement in 128 bits)
   auto centred = [&](int l, i64 pos) -> u128 {
-    u128 V;
-    if (A32) {
-      const u32 v0 = base32[(i64)(l * 4 + 0) * nrow + pos], v1 = base32[(i64)(l * 4 + 1) * nrow + pos], v2 = base32[(i64)(l * 4 + 2) * nrow + pos],
-                v3 = base32[(i64)(l * 4 + 3) * nrow + pos];
-      const u32 p0 = gc.p[0], p1 = gc.p[1], p2 = gc.p[2], p3 = gc.p[3];
-      const u32 x1 = v0;
-      // (inner products stay lazy, below 2p; the mixed-radix digits x2, x3, x4 themselves are reduced)
-      const u32 x2 = g32_mul(g32_sub(v1, x1, p1), gc.c[0], gc.cp[0], p1);
-      const u32 x3 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(v2, x1, p2), gc.c[1], gc.cp[1], p2), x2, p2), gc.c[2], gc.cp[2], p2);
-      const u32 x4 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(g32_mul_lazy(g32_sub(v3, x1, p3), gc.c[3], gc.cp[3], p3), x2, p3), gc.c[4], gc.cp[4], p3), x3, p3),
-                             gc.c[5], gc.cp[5], p3);
-      V = (u128)((u64)x3 + (u64)p2 * x4) * ((u64)p0 * p1) + ((u64)x1 + (u64)p0 * x2);
-    } else {
-      const u64 v0 = base[(i64)(l * 2 + 0) * nrow + pos], v1 = base[(i64)(l * 2 + 1) * nrow + pos];
-      const u64 v0r = v0 >= q1 ? v0 - q1 : v0;
-      const u64 t = d_shoup(d_submod(v1, v0r, q1), q0inv, q0inv_sh, q1);
-      V = (u128)q0 * t + v0;
-    }
+    const u64 v0 = base[(i64)(l * 2 + 0) * nrow + pos], v1 = base[(i64)(l * 2 + 1) * nrow + pos];
+    const u64 v0r = v0 >= q1 ? v0 - q1 : v0;
+    const u64 t = d_shoup(d_submod(v1, v0r, q1), q0inv, q0inv_sh, q1);
+    u128 V = (u128)q0 * t + v0;
     if (V > half) V -= A;
     return V;
   };
@@ -803,36 +815,16 @@ __global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __
     for (int a = 0; a < 4; ++a) {
       const u32* __restrict__ row = base32 + (i64)(l * 4 + a) * nrow;
       if (!fold_q) { v[a] = row[j]; continue; }
-      const u32 p = gc.p[a];
-      u32 r;
-      if (fold_q > 0) {        // m = 2q':  S_j - S_(j+q') -+ (S_n - S_(n+q'))
-        const u32 s0 = row[j], s1 = row[j + fold_q], t0 = row[n], t1 = n + fold_q < nrow ? row[n + fold_q] : 0u;      // all below p
-        r = s0 + (p - s1) + ((j & 1) ? t0 + (p - t1) : t1 + (p - t0));                     // below 4p
-      } else {                 // m prime (offset -fold_q = m, n = m - 1):  S_j + S_(j+m) - S_(m-1)
-        const u32 s0 = row[j], s1 = j - fold_q < nrow ? row[j - fold_q] : 0u, t0 = row[n];
-        r = s0 + s1 + (p - t0);                                                               // below 3p
-      }
-      r = r >= 2 * p ? r - 2 * p : r;
-      v[a] = r >= p ? r - p : r;
+      v[a] = g32_fold(row, j, n, nrow, fold_q, gc.p[a]);
     }
-  };
-  auto garner = [&](const u32 (&v)[4]) -> u128 {
-    const u32 p0 = gc.p[0], p1 = gc.p[1], p2 = gc.p[2], p3 = gc.p[3];
-    const u32 x1 = v[0];
-    const u32 x2 = g32_mul(g32_sub(v[1], x1, p1), gc.c[0], gc.cp[0], p1);
-    const u32 x3 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(v[2], x1, p2), gc.c[1], gc.cp[1], p2), x2, p2), gc.c[2], gc.cp[2], p2);
-    const u32 x4 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(g32_mul_lazy(g32_sub(v[3], x1, p3), gc.c[3], gc.cp[3], p3), x2, p3), gc.c[4], gc.cp[4], p3), x3, p3),
-                           gc.c[5], gc.cp[5], p3);
-    u128 V = (u128)((u64)x3 + (u64)p2 * x4) * ((u64)p0 * p1) + ((u64)x1 + (u64)p0 * x2);
-    if (V > half) V -= A;
-    return V;
   };
   if (A32) fetch(0, cur);
   for (int l = 0; l < NLB; ++l) {
     u128 V;
     if (A32) {
       if (l + 1 < NLB) fetch(l + 1, nxt);
-      V = garner(cur);
+      V = g32_garner(cur[0], cur[1], cur[2], cur[3], gc);
+      if (V > half) V -= A;
 #pragma unroll
       for (int a = 0; a < 4; ++a) cur[a] = nxt[a];
     } else {
@@ -845,10 +837,9 @@ __global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __
         if (j & 1) V += top; else V -= top;
       }
     }
-    V += (u128)1 << 119;
     const int s = B * l, wd = s >> 6, bt = s & 63;
-    const u64 lo = (u64)V, hi = (u64)(V >> 64);
-    const u64 p0 = lo << bt, p1 = bt ? ((lo >> ((64 - bt) & 63)) | (hi << bt)) : hi, p2 = bt ? (hi >> ((64 - bt) & 63)) : 0;
+    u64 p0, p1, p2;
+    ks_limb_words(V, bt, p0, p1, p2);
     u64 carry = 0;
     for (int i = wd; i <= W; ++i) {
       const u64 add = i == wd ? p0 : (i == wd + 1 ? p1 : (i == wd + 2 ? p2 : 0));
@@ -911,21 +902,33 @@ static int garner32_consts(fhesi_ctx* ctx, Garner32* gc) {
   }
   return 0;
 }
+// The host constants of every launch path.  Two 60-bit chain primes: q0, q1, q0^-1 mod q1 with its Shoup quotient, A = q0 q1.  aux32: A = the
+// product of the four 30-bit auxiliary primes and their Garner32 (the kernels then read no chain prime: those words stay 0).  half = (A - 1) / 2.
+// tail: the rows arrive without the tail stage of their 2^15-point inverse, so Garner32 carries its constants too.
+struct RecombineConsts { u64 q0, q1, q0inv, q0inv_sh, half_hi, half_lo, a_hi, a_lo; Garner32 gc; };
+static int ks_recombine_consts(fhesi_ctx* ctx, bool aux32, bool tail, RecombineConsts* rc) {
+  *rc = RecombineConsts{};
+  u128 A;
+  if (aux32) {
+    if (garner32_consts(ctx, &rc->gc)) return 1;
+    A = (u128)((u64)rc->gc.p[0] * rc->gc.p[1]) * ((u64)rc->gc.p[2] * rc->gc.p[3]);
+  } else {
+    rc->q0 = ctx->q[0]; rc->q1 = ctx->q[1];
+    rc->q0inv = hm::invmod(rc->q0 % rc->q1, rc->q1); rc->q0inv_sh = hm::shoup(rc->q0inv, rc->q1);
+    A = (u128)rc->q0 * rc->q1;
+  }
+  if (tail && aux32_tail_consts(ctx, rc->gc.tw, rc->gc.twp)) return 1;
+  const u128 half = (A - 1) / 2;
+  rc->half_hi = (u64)(half >> 64); rc->half_lo = (u64)half; rc->a_hi = (u64)(A >> 64); rc->a_lo = (u64)A;
+  return 0;
+}
 template <int W, int LQ, int B, int NLB, bool A32, int S = 0>
 static int launch_ks_recombine_t(fhesi_ctx* ctx, const CrtTables* t, const fhesi_ksk* k, const u64* d_o, i64 npolys, u64* d_out, int nl_out) {
-  const u64 q0 = ctx->q[0], q1 = ctx->q[1];
-  const u64 inv = hm::invmod(q0 % q1, q1);
-  u128 A = (u128)q0 * q1;
-  Garner32 gc{};
-  if (A32) {
-    if (garner32_consts(ctx, &gc)) return 1;
-    A = (u128)((u64)gc.p[0] * gc.p[1]) * ((u64)gc.p[2] * gc.p[3]);
-  }
-  const u128 half = (A - 1) / 2;
+  RecombineConsts c;
+  FHESI_TRY(ks_recombine_consts(ctx, A32, S != 0, &c));
   dim3 grid((unsigned)((ctx->phim + 127) / 128), (unsigned)npolys);
-  if (S && aux32_tail_consts(ctx, gc.tw, gc.twp)) return 1;
-  ks_recombine_kernel<W, LQ, B, NLB, A32, S><<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, q0, q1, inv, hm::shoup(inv, q1), (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A,
-                                                                          k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, gc);
+  ks_recombine_kernel<W, LQ, B, NLB, A32, S><<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, c.q0, c.q1, c.q0inv, c.q0inv_sh, c.half_hi, c.half_lo, c.a_hi, c.a_lo,
+                                                                          k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1031,17 +1034,7 @@ __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __
         continue;
       }
       if (!fold_q) { v[a] = row[j]; continue; }
-      const u32 p = gc.p[a];
-      u32 r;
-      if (fold_q > 0) {        // m = 2q':  S_j - S_(j+q') -+ (S_n - S_(n+q'))
-        const u32 s0 = row[j], s1 = row[j + fold_q], t0 = row[n], t1 = n + fold_q < nrow ? row[n + fold_q] : 0u;
-        r = s0 + (p - s1) + ((j & 1) ? t0 + (p - t1) : t1 + (p - t0));
-      } else {                 // m prime:  S_j + S_(j+m) - S_(m-1)
-        const u32 s0 = row[j], s1 = j - fold_q < nrow ? row[j - fold_q] : 0u, t0 = row[n];
-        r = s0 + s1 + (p - t0);
-      }
-      r = r >= 2 * p ? r - 2 * p : r;
-      v[a] = r >= p ? r - p : r;
+      v[a] = g32_fold(row, j, n, nrow, fold_q, gc.p[a]);
     }
   };
   if constexpr (!FIX) fetch(0, cur);
@@ -1051,13 +1044,7 @@ __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __
 #pragma unroll
       for (int a = 0; a < 4; ++a) cur[a] = vin[l][a];
     } else if (l + 1 < NLB) fetch(l + 1, nxt);
-    const u32 p0 = gc.p[0], p1 = gc.p[1], p2 = gc.p[2], p3 = gc.p[3];
-    const u32 x1 = cur[0];
-    const u32 x2 = g32_mul(g32_sub(cur[1], x1, p1), gc.c[0], gc.cp[0], p1);
-    const u32 x3 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(cur[2], x1, p2), gc.c[1], gc.cp[1], p2), x2, p2), gc.c[2], gc.cp[2], p2);
-    const u32 x4 = g32_mul(g32_sub(g32_mul_lazy(g32_sub(g32_mul_lazy(g32_sub(cur[3], x1, p3), gc.c[3], gc.cp[3], p3), x2, p3), gc.c[4], gc.cp[4], p3), x3, p3),
-                           gc.c[5], gc.cp[5], p3);
-    u128 V = (u128)((u64)x3 + (u64)p2 * x4) * ((u64)p0 * p1) + ((u64)x1 + (u64)p0 * x2);
+    u128 V = g32_garner(cur[0], cur[1], cur[2], cur[3], gc);
     if (V > half) V -= A;
     V += (u128)1 << 119;
     if constexpr (!FIX) {
@@ -1138,13 +1125,10 @@ __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __
   for (int i = 0; i < NWORDS; ++i) if (i < nl_out) o[i] = x[i];
   for (int i = NWORDS; i < nl_out; ++i) o[i] = hbit ? ~0ull : 0ull;
 }
-static int garner32_consts(fhesi_ctx* ctx, Garner32* gc);
 static int launch_ks_recombine_centred(fhesi_ctx* ctx, const fhesi_ksk* k, const u64* d_o, i64 npolys, u64* d_out, int nl_out, bool tail_pending) {
-  Garner32 gc{};
-  if (garner32_consts(ctx, &gc)) return 1;
+  RecombineConsts c;
+  FHESI_TRY(ks_recombine_consts(ctx, true, tail_pending, &c));
   const int S = tail_pending ? 1 : 0;
-  if (S && aux32_tail_consts(ctx, gc.tw, gc.twp)) return 1;
-  const u128 A = (u128)((u64)gc.p[0] * gc.p[1]) * ((u64)gc.p[2] * gc.p[3]), half = (A - 1) / 2;
   const int LQ = k->aux_logQ, B = k->aux_limb_bits, NLB = k->aux_rows, NW = LQ <= 512 ? 8 : 16;
   if (LQ > 1024) FHESI_FAIL("key switch, centred limbs: logQ=%d above 1024", LQ);
   // start value: - sum_l 2^(119 + B l)  modulo 2^(64 NW)
@@ -1162,19 +1146,21 @@ static int launch_ks_recombine_centred(fhesi_ctx* ctx, const fhesi_ksk* k, const
   const i64 nrow = aux32_row_len(ctx);
   const i64 fold = k->aux_fold;
   dim3 grid((unsigned)((ctx->phim + 127) / 128), (unsigned)npolys);
+  void (*kern)(const u32*, i64, i64, i64, int, int, int, int, u64, u64, u64, u64, CentredConsts, u64*, int, Garner32);
   if (NW == 16 && LQ == 1024 && B == 72 && NLB == 15 && !fold)         // the stress ring with a generated matrix (rows of 2^15: the tail stage in the loader when S)
-    ks_recombine_centred_kernel<16, 15, 72, 1024><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
+    kern = ks_recombine_centred_kernel<16, 15, 72, 1024>;
   else if (NW == 8 && LQ == 512 && B == 74 && NLB == 7 && !fold && !S)      // the metric ring with a generated matrix
-    ks_recombine_centred_kernel<8, 7, 74, 512><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
+    kern = ks_recombine_centred_kernel<8, 7, 74, 512>;
   // (a compile-time instantiation <8, 8, 72, 512, FS = 1> for the reference drivers' ring at the metric's size, its residues fetched up front through the
   // run-time loader, was measured: 106 registers, 256 loads before the first Garner step -- crt class 8.7 -> 10.9 ms per step there, and the same
   // loader in front of the stress instantiation cost it 22.7 -> 26.8: the folds keep the run-time form, the compile-time forms their own loaders)
-  else if (S && fold && NW == 8 && fold > 0) ks_recombine_centred_kernel<8, 0, 0, 0, 1><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
-  else if (S && fold && NW == 8) ks_recombine_centred_kernel<8, 0, 0, 0, 2><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
-  else if (S && fold && fold > 0) ks_recombine_centred_kernel<16, 0, 0, 0, 1><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
-  else if (S && fold) ks_recombine_centred_kernel<16, 0, 0, 0, 2><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
-  else if (NW == 8) ks_recombine_centred_kernel<8><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
-  else ks_recombine_centred_kernel<16><<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, cc, d_out, nl_out, gc);
+  else if (S && fold && NW == 8 && fold > 0) kern = ks_recombine_centred_kernel<8, 0, 0, 0, 1>;
+  else if (S && fold && NW == 8) kern = ks_recombine_centred_kernel<8, 0, 0, 0, 2>;
+  else if (S && fold && fold > 0) kern = ks_recombine_centred_kernel<16, 0, 0, 0, 1>;
+  else if (S && fold) kern = ks_recombine_centred_kernel<16, 0, 0, 0, 2>;
+  else if (NW == 8) kern = ks_recombine_centred_kernel<8>;
+  else kern = ks_recombine_centred_kernel<16>;
+  kern<<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, c.half_hi, c.half_lo, c.a_hi, c.a_lo, cc, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1188,34 +1174,29 @@ bool ks_recombine_takes_tail(const fhesi_ctx* ctx, const CrtTables* t, const fhe
 }
 int launch_ks_recombine(fhesi_ctx* ctx, const CrtTables* t, const fhesi_ksk* k, const u64* d_o, i64 npolys, u64* d_out, int nl_out, bool tail_pending) {
   if (!npolys) return 0;
-  if (tail_pending != ks_recombine_takes_tail(ctx, t, k) && tail_pending) FHESI_FAIL("key switch: rows without their tail stage reached a recombination that does not take it");
-  if (k->aux_centred) { ProfScope prof(ctx, PROF_CRT, (double)npolys); return launch_ks_recombine_centred(ctx, k, d_o, npolys, d_out, nl_out, tail_pending); }
-  if (tail_pending) { ProfScope prof(ctx, PROF_CRT, (double)npolys); return launch_ks_recombine_t<34, 1024, 72, 30, true, 1>(ctx, t, k, d_o, npolys, d_out, nl_out); }
+  if (tail_pending && !ks_recombine_takes_tail(ctx, t, k)) FHESI_FAIL("key switch: rows without their tail stage reached a recombination that does not take it");
   ProfScope prof(ctx, PROF_CRT, (double)npolys);
+  if (k->aux_centred) return launch_ks_recombine_centred(ctx, k, d_o, npolys, d_out, nl_out, tail_pending);
   // compile-time instantiations for the shapes the benchmarks run (the plan of ks_limb_plan at the metric and stress chains) ...
-  if (!k->aux_fold && k->aux32 && t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15) return launch_ks_recombine_t<18, 512, 74, 15, true>(ctx, t, k, d_o, npolys, d_out, nl_out);
-  if (!k->aux32 && t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15) return launch_ks_recombine_t<18, 512, 74, 15, false>(ctx, t, k, d_o, npolys, d_out, nl_out);
-  if (!k->aux32 && t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30) return launch_ks_recombine_t<34, 1024, 72, 30, false>(ctx, t, k, d_o, npolys, d_out, nl_out);
-  if (!k->aux_fold && k->aux32 && t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30) return launch_ks_recombine_t<34, 1024, 72, 30, true>(ctx, t, k, d_o, npolys, d_out, nl_out);
+  int (*fixed)(fhesi_ctx*, const CrtTables*, const fhesi_ksk*, const u64*, i64, u64*, int) = nullptr;
+  if (tail_pending) fixed = launch_ks_recombine_t<34, 1024, 72, 30, true, 1>;      // (ks_recombine_takes_tail has checked the shape)
+  else if (!k->aux_fold && k->aux32 && t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15) fixed = launch_ks_recombine_t<18, 512, 74, 15, true>;
+  else if (!k->aux32 && t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15) fixed = launch_ks_recombine_t<18, 512, 74, 15, false>;
+  else if (!k->aux32 && t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30) fixed = launch_ks_recombine_t<34, 1024, 72, 30, false>;
+  else if (!k->aux_fold && k->aux32 && t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30) fixed = launch_ks_recombine_t<34, 1024, 72, 30, true>;
+  if (fixed) return fixed(ctx, t, k, d_o, npolys, d_out, nl_out);
   // ... and the run-time form for every other chain
-  const u64 q0 = ctx->q[0], q1 = ctx->q[1];
-  const u64 inv = hm::invmod(q0 % q1, q1);
-  u128 A = (u128)q0 * q1;
-  Garner32 gc{};
-  if (k->aux32) {
-    if (garner32_consts(ctx, &gc)) return 1;
-    A = (u128)((u64)gc.p[0] * gc.p[1]) * ((u64)gc.p[2] * gc.p[3]);
-  }
-  const u128 half = (A - 1) / 2;
+  RecombineConsts c;
+  FHESI_TRY(ks_recombine_consts(ctx, k->aux32, false, &c));
   const int W = t->W;
   dim3 grid((unsigned)((ctx->phim + 127) / 128), (unsigned)npolys);
   const i64 nrow = k->aux32 ? aux32_row_len(ctx) : ctx->phim;
-#define KS_GEN(MAXW, A32) ks_recombine_generic_kernel<MAXW, A32><<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, nrow, k->aux_fold, W, k->aux_logQ, k->aux_limb_bits, k->aux_rows, q0, q1, inv, hm::shoup(inv, q1), \
-      (u64)(half >> 64), (u64)half, (u64)(A >> 64), (u64)A, k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, gc)
-  if (W <= 20) { if (k->aux32) KS_GEN(20, true); else KS_GEN(20, false); }
-  else if (W <= 44) { if (k->aux32) KS_GEN(44, true); else KS_GEN(44, false); }
+  void (*kern)(const u64*, i64, i64, i64, int, int, int, int, u64, u64, u64, u64, u64, u64, u64, u64, const u64*, const u64*, const u64*, u64*, int, Garner32);
+  if (W <= 20) kern = k->aux32 ? ks_recombine_generic_kernel<20, true> : ks_recombine_generic_kernel<20, false>;
+  else if (W <= 44) kern = k->aux32 ? ks_recombine_generic_kernel<44, true> : ks_recombine_generic_kernel<44, false>;
   else FHESI_FAIL("key switch, limb mode: chain product of %d limbs exceeds the supported 44", W);
-#undef KS_GEN
+  kern<<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, nrow, k->aux_fold, W, k->aux_logQ, k->aux_limb_bits, k->aux_rows, c.q0, c.q1, c.q0inv, c.q0inv_sh,
+                                     c.half_hi, c.half_lo, c.a_hi, c.a_lo, k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
   return 0;
 }
