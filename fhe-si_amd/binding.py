@@ -45,8 +45,9 @@ ABI_SYMBOLS = [
     "fhesi_slots_basis_plan", "fhesi_slots_basis_check", "fhesi_slots_basis_create", "fhesi_slots_basis_free", "fhesi_slots_basis_info", "fhesi_slots_basis_channel",
     "fhesi_slots_basis_embed", "fhesi_slots_basis_decode", "fhesi_slots_basis_embed_dev", "fhesi_slots_basis_decode_dev",
     "fhesi_encrypt_int_slots_batch_seeded", "fhesi_decrypt_int_slots_batch", "fhesi_encrypt_noise_int_batch_seeded",
+    "fhesi_ctx_lin_class",
 ]
-ABI_VERSION = 7          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
+ABI_VERSION = 8          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8}
 
 
@@ -101,6 +102,7 @@ def _load():
         "fhesi_ctx_zms_idx": [_vp, _vp],
         "fhesi_ctx_phi_m": [_vp, _vp],
         "fhesi_ctx_sync": [_vp],
+        "fhesi_ctx_lin_class": [_vp, _i64, _vp, _vp, _vp],
         "fhesi_timer_start": [_vp],
         "fhesi_timer_stop": [_vp, _vp],
         "fhesi_cmod_fft": [_vp, _i32, _vp, _i32, _i64, _vp],
@@ -244,6 +246,14 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(_vp)
 
 
+def lin_class(m: int, ctx: "Context" = None):
+    """-> (offset, stride, lin_lg): the fold of the rings m = q^k, 2 q^k (q an odd prime) on the fused 30-bit paths, as a context on m would
+    take it (or as `ctx` took it); (0, 0, 0) for any other m.  Touches no device."""
+    off, st, lg = _i64(0), _i64(0), _i32(0)
+    _ck(_load().fhesi_ctx_lin_class(ctx.h if ctx is not None else None, int(m), C.byref(off), C.byref(st), C.byref(lg)))
+    return off.value, st.value, lg.value
+
+
 class Backend:
     @staticmethod
     def lib():
@@ -323,6 +333,10 @@ class Context:
         out = np.zeros(self.phim + 1, dtype=np.int64)
         _ck(_load().fhesi_ctx_phi_m(self.h, _p(out)))
         return out
+
+    def lin_class(self):
+        """-> (offset, stride, lin_lg) of the linear-convolution class this context took ((0, 0, 0): negacyclic or per-prime rows)."""
+        return lin_class(self.m, self)
 
     def timer_start(self):
         _ck(_load().fhesi_timer_start(self.h))

@@ -36,12 +36,12 @@ extern "C" int fhesi_ct_mul_poly_dev(fhesi_ctx* c, int32_t logQ, uint64_t* ct, i
   if (!count) return 0;
   const i64 n = c->phim;
   const int L = c->L;
-  // |coefficient of the product modulo Phi_m| <= growth * n * 2^(logQ-1) * max|other_j|, growth = 1 (X^n + 1), 2 (the two-term folds of prime and
-  // 2 x prime rings) or, conservatively, n for a general Phi_m
+  // |coefficient of the product modulo Phi_m| <= growth * n * 2^(logQ-1) * max|other_j|, growth = 1 (X^n + 1), 2 (the two-term folds of the rings
+  // m = q^k and 2 q^k, q an odd prime) or, conservatively, n for a general Phi_m
   u64 maxc = 0;
   for (i64 i = 0; i < (i64)npoly * n; ++i) { const i64 v = poly_host[i]; const u64 a = v < 0 ? (u64)(-(v + 1)) + 1 : (u64)v; if (a > maxc) maxc = a; }
   double bits = (logQ - 1) + std::log2((double)n) + (maxc ? std::log2((double)maxc) + 1e-9 : 0.0) + 1.0;
-  bits += c->pow2 ? 0.0 : ((c->lin_q || hm::is_prime((u64)c->m)) ? 1.0 : std::log2((double)n));
+  bits += c->pow2 ? 0.0 : (c->phi_two_term ? 1.0 : std::log2((double)n));
   double chain = 0.0;
   for (int i = 0; i < L; ++i) chain += std::log2((double)c->q[i]);
   if (bits + 1.0 >= chain) FHESI_FAIL("Ciphertext *= ZZX: the product needs %.0f bits, the chain holds %.0f", bits + 1.0, chain);

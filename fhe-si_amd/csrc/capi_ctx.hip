@@ -40,6 +40,22 @@ int upload_idx(fhesi_ctx* ctx, const std::vector<int>& idx, int** d_out) {
 }
 
 // --------------------------------------------------------------------------------------------- context
+// Rings whose products run as linear convolutions on padded power-of-two rows of 2^14 .. 2^20: m = Q or 2Q with Q = q^k, q an odd prime --
+// every m = p - 1 (safe prime p) and every prime m the reference admits (k = 1; m < 2^20, FHEContext.cpp:89; its drivers: Test_AddMul.cpp:131,
+// Test_Regression.cpp:122) and their prime powers (k >= 2: m = p - 1 for p = 19, 163, 251, 487, 1459, 2663, 39367, ...).  off = the fold's offset
+// (Q or m), s = q^(k-1) its stride, lg from 2 phi(m) - 1 <= 2^lg.  Rows up to 2^16 run the fused loaders, longer ones the simple path (head /
+// tail stages as passes of their own, ntt32_core.inc).  false: any other m (the chain path).
+static bool lin_ring_class(i64 m, i64* off, i64* s, bool* odd, int* lg) {
+  int k = 0;
+  const i64 qq = hm::prime_power_ring(m, &k);
+  if (!qq) return false;
+  const i64 Q = (m & 1) ? m : m / 2, st = Q / qq, phim = Q - st;
+  if (2 * phim - 1 > 64 * kAux32N) return false;
+  *off = Q; *s = st; *odd = (m & 1) != 0;
+  *lg = 14;
+  while (((i64)1 << *lg) < 2 * phim - 1) ++*lg;
+  return true;
+}
 extern "C" int32_t fhesi_abi_version(void) { return FHESI_ABI_VERSION; }
 extern "C" int fhesi_device_count(int32_t* count) {
   int c = 0;
@@ -146,18 +162,10 @@ extern "C" int fhesi_ctx_create(fhesi_ctx** out, int64_t m, int32_t nprimes, con
   c->phi = hm::cyclotomic(m);
   c->pow2 = (m & (m - 1)) == 0 && m >= 4;
   c->logn = c->pow2 ? hm::ilog2_ceil(c->phim) : 0;
-  if (!c->pow2 && 2 * c->phim - 1 <= 64 * kAux32N) {
-    // rings whose products run as linear convolutions on padded power-of-two rows of 2^14 .. 2^20: every m = p - 1 (safe prime p) and every
-    // prime m the reference admits (m < 2^20, FHEContext.cpp:89; its drivers: Test_AddMul.cpp:131, Test_Regression.cpp:122).  Rows up to 2^16
-    // run the fused loaders, longer ones the simple path (head / tail stages as passes of their own, ntt32_core.inc)
-    if (m % 2 == 0 && (m / 2) % 2 == 1 && hm::is_prime((u64)(m / 2))) c->lin_q = m / 2;
-    else if (m % 2 == 1 && m > 2 && hm::is_prime((u64)m)) { c->lin_q = m; c->lin_prime = true; }
-    if (c->lin_q) {
-      c->lin_lg = 14;
-      while (((i64)1 << c->lin_lg) < 2 * c->phim - 1) ++c->lin_lg;
-      // FHESI_LIN_LG: LONGER padded rows than the ring needs (a test hook: the long-row paths on rings small enough for the oracle)
-      if (const char* e = getenv("FHESI_LIN_LG")) { const int want = atoi(e); if (want > c->lin_lg && want <= 20) c->lin_lg = want; }
-    }
+  c->phi_two_term = !c->pow2 && hm::prime_power_ring(m, nullptr) != 0;      // (also the rings of the family beyond rows of 2^20, which lin_ring_class leaves to the chain path)
+  if (!c->pow2 && lin_ring_class(m, &c->lin_q, &c->lin_s, &c->lin_prime, &c->lin_lg)) {
+    // FHESI_LIN_LG: LONGER padded rows than the ring needs (a test hook: the long-row paths on rings small enough for the oracle)
+    if (const char* e = getenv("FHESI_LIN_LG")) { const int want = atoi(e); if (want > c->lin_lg && want <= 20) c->lin_lg = want; }
   }
   if (const char* e = getenv("FHESI_WS_POISON")) c->ws_poison = atoi(e) != 0;
   HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -359,6 +367,18 @@ extern "C" int fhesi_ctx_zms_idx(const fhesi_ctx* c, int32_t* out_m) {
 extern "C" int fhesi_ctx_phi_m(const fhesi_ctx* c, int64_t* o) {
   if (!c) FHESI_FAIL("null context");
   for (size_t i = 0; i < c->phi.size(); ++i) o[i] = c->phi[i];
+  return 0;
+}
+extern "C" int fhesi_ctx_lin_class(const fhesi_ctx* c, int64_t m, int64_t* offset, int64_t* stride, int32_t* lin_lg) {
+  i64 off = 0, st = 0;
+  int lg = 0;
+  bool odd = false;
+  if (c) { off = c->lin_q; st = c->lin_s; lg = c->lin_lg; }
+  else if (m < 2 || m > ((i64)1 << 20)) FHESI_FAIL("ring class: m=%lld outside [2, 2^20]", (long long)m);
+  else if (!lin_ring_class(m, &off, &st, &odd, &lg)) { off = st = 0; lg = 0; }      // (a power of two is not of the form: Q is odd)
+  if (offset) *offset = off;
+  if (stride) *stride = st;
+  if (lin_lg) *lin_lg = lg;
   return 0;
 }
 extern "C" int fhesi_ctx_sync(fhesi_ctx* c) { CHECK_CTX(c); HIP_TRY(hipStreamSynchronize(c->stream)); return 0; }

@@ -100,12 +100,17 @@ struct fhesi_ctx {
   int n_big_primes = 0;                // chain primes >= 2^48
   bool has_small_prime = false;        // some chain prime is below 2^48: the tile kernels transform its rows modulo q_tile (ntt_tile.inc)
   int logn = 0;                        // log2(phim) when pow2
-  // m = 2 q' with q' an odd prime (the reference's safe-prime rings, e.g. p = 8423) or m an odd prime, and 2 phi(m) - 1 <= 2^15: the
-  // integer products of the key switch and of the tensor half are LINEAR convolutions carried by the 2^14- or 2^15-point 32-bit
-  // transforms on zero-padded rows and folded afterwards, exactly, modulo X^q' + 1 and Phi_m = sum (-X)^i  (m = 2q':  out_j =
-  // S_j - S_(j+q') - (-1)^j S_(q'-1))  or modulo X^m - 1 and Phi_m = sum X^i  (m prime:  out_j = S_j + S_(j+m) - S_(m-1))
-  i64 lin_q = 0;                       // the fold's offset: q' (m = 2q') or m (m prime); 0 = not such a ring
-  bool lin_prime = false;              // m itself is the prime
+  // m = 2Q or m = Q with Q = q^k, q an odd prime (k = 1: the reference's safe-prime rings m = 2q', e.g. p = 8423, and the prime m), and
+  // 2 phi(m) - 1 <= 2^20: the integer products of the key switch and of the tensor half are LINEAR convolutions carried by the 32-bit
+  // transforms on zero-padded rows and folded afterwards, exactly, modulo X^Q + 1 (or X^m - 1) and Phi_m.  With s = q^(k-1), phi = (q - 1) s:
+  //   m = 2Q:  Phi_m = sum_{i<q} (-X^s)^i,  out_j = S_j - S_(j+Q) - (-1)^floor(j/s) S_(phi + j mod s)
+  //   m = Q:   Phi_m = sum_{i<q} X^(i s),   out_j = S_j + S_(j+m) - S_(phi + j mod s)
+  // (k = 1: s = 1, the third position is the fixed top phi and the sign (-1)^j)
+  i64 lin_q = 0;                       // the fold's offset: Q (m = 2Q) or m (m odd); 0 = not such a ring
+  bool lin_prime = false;              // m is odd (k = 1: m itself is the prime)
+  i64 lin_s = 0;                       // the fold's stride s = q^(k-1); 1 on the prime and 2 x prime rings
+  bool phi_two_term = false;           // m = q^k or 2 q^k for an odd prime q, whether or not the linear-convolution class took it (2 phi(m) - 1 may exceed 2^20): the
+                                       // remainder modulo Phi_m at most doubles a coefficient (Ciphertext *= ZZX sizes its product with it)
   int lin_lg = 0;                      // log2 of the padded rows: 14 .. 20
   std::vector<u64> q, root;
   std::vector<int> zms_idx;            // PAlgebra::zmsIdx (PAlgebra.cpp:50-52)
@@ -193,7 +198,7 @@ struct fhesi_ksk {
   int aux_key_bits = 0;                // nb of the matrix the table was built from (measured on the device at build time)
   int aux_long_opt = 0;                // option ks_long_keys at build time (a change rebuilds the table)
   bool aux32 = false;                  // the table holds residues modulo the four 30-bit primes of kernels_aux32.hip (u32, 2^14-point rows)
-  i64 aux_fold = 0;                    // q' when the rows are linear convolutions to be folded modulo X^q' + 1 and Phi_m (ctx->lin_q), -m for a prime m (modulo X^m - 1 and Phi_m), else 0
+  i64 aux_fold = 0;                    // lin_fold_pack(ctx->lin_q, ctx->lin_s, ctx->lin_prime) (lin_fold.h) when the rows are linear convolutions to be folded: Q for m = 2Q, -m for an odd m, plus (s - 1) 2^32 in magnitude; else 0
   u64* d_limb_consts = nullptr;        // [W+1] offset constant D, [2] floor(2^(64(W-2)+128) / P), then the quotient bound's bit count
 };
 struct KsLimbPlan { int W = 0, LQ = 0, B = 0, NLB = 0, mbits = 0; bool a32 = false; };
@@ -258,6 +263,7 @@ u64 mulmod(u64 a, u64 b, u64 q);
 u64 powmod(u64 a, u64 e, u64 q);
 u64 invmod(u64 a, u64 q);              // q prime
 bool is_prime(u64 n);
+i64 prime_power_ring(i64 m, int* k);   // q when m = q^k or 2 q^k (q an odd prime, k >= 1), else 0
 u64 shoup(u64 w, u64 q);
 u64 shoup63(u64 w, u64 q);             // floor(w 2^63 / q)
 u64 brv(u64 x, int bits);

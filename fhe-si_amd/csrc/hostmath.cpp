@@ -52,6 +52,22 @@ bool is_prime(u64 n) {
   return true;
 }
 
+// m = q^k or 2 q^k with q an odd prime, k >= 1: the rings whose Phi_m is Phi_q(+-X^s), s = q^(k-1) (PAlgebra.cpp:40-56 builds Phi_m for any m;
+// these are the ones whose remainder is a three-term fold).  Returns q (0: m is not of that form) and k.
+i64 prime_power_ring(i64 m, int* k) {
+  if (m < 3) return 0;
+  i64 Q = (m & 1) ? m : m / 2;
+  if (!(Q & 1) || Q < 3) return 0;
+  i64 q = 0;
+  for (i64 d = 3; d * d <= Q; d += 2) if (Q % d == 0) { q = d; break; }
+  if (!q) q = Q;                                   // Q itself is prime
+  int e = 0;
+  while (Q % q == 0) { Q /= q; ++e; }
+  if (Q != 1) return 0;
+  if (k) *k = e;
+  return q;
+}
+
 u64 shoup(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
 u64 shoup63(u64 w, u64 q) { return (u64)(((u128)w << 63) / q); }
 

@@ -11,6 +11,7 @@
 // residue of x modulo the full product P, so this kernel runs the mixed-radix recurrence with non-negative digits
 // (x stays in [0, P_k) ) and centres once at the end -- same value, no signed big-int arithmetic per step.
 #include "fhesi_internal.h"
+#include "lin_fold.h"
 
 // 128-bit value -> [0,q): hi * (2^64 mod q) + lo, each reduced by a Shoup step
 __device__ __forceinline__ u64 crt_fold128(u128 a, const PrimeConst& pc) {
@@ -642,17 +643,20 @@ __device__ __forceinline__ u128 g32_garner(u32 v0, u32 v1, u32 v2, u32 v3, const
   return (u128)((u64)x3 + (u64)p2 * x4) * ((u64)p0 * p1) + ((u64)x1 + (u64)p0 * x2);
 }
 // Coefficient j of a row S of nrow residues modulo p of a linear-convolution ring (fold_q != 0), folded into the ring on the residues: in [0, p).
+// With s = q^(k-1) the stride of the ring (m = 2Q or Q, Q = q^k), phi = (q - 1) s and S zero beyond degree 2 phi - 2:
+//   m = 2Q:  out_j = S_j - S_(j+Q) - (-1)^floor(j/s) S_(phi + j mod s)       (S_(phi + j mod s + Q) lies beyond degree 2 phi - 2: always zero)
+//   m odd:   out_j = S_j + S_(j+m) - S_(phi + j mod s)
+// off, top = phi + j mod s and odd = the parity of floor(j/s) come from lin_fold_pos, once per thread (they depend on neither prime nor limb);
+// the loads are unconditional: clamped index, masked value.
 // (The callers keep the test for fold_q = 0 and take p from the kernel argument themselves: with either inside, the compiler orders the
 // loads of the run-time kernels differently.)
-__device__ __forceinline__ u32 g32_fold(const u32* __restrict__ row, i64 j, i64 n, i64 nrow, i64 fold_q, u32 p) {
+__device__ __forceinline__ u32 g32_fold(const u32* __restrict__ row, i64 j, i64 nrow, i64 fold_q, u32 off, u32 top, bool odd, u32 p) {
+  const i64 e1 = j + off;
+  const bool in1 = e1 < nrow;
+  const u32 s0 = row[j], v1 = row[in1 ? e1 : 0], t0 = row[top], s1 = in1 ? v1 : 0u;      // all below p
   u32 r;
-  if (fold_q > 0) {        // m = 2q':  S_j - S_(j+q') -+ (S_n - S_(n+q'))
-    const u32 s0 = row[j], s1 = row[j + fold_q], t0 = row[n], t1 = n + fold_q < nrow ? row[n + fold_q] : 0u;      // all below p
-    r = s0 + (p - s1) + ((j & 1) ? t0 + (p - t1) : t1 + (p - t0));                     // below 4p
-  } else {                 // m prime (offset -fold_q = m, n = m - 1):  S_j + S_(j+m) - S_(m-1)
-    const u32 s0 = row[j], s1 = j - fold_q < nrow ? row[j - fold_q] : 0u, t0 = row[n];
-    r = s0 + s1 + (p - t0);                                                               // below 3p
-  }
+  if (fold_q > 0) r = s0 + (p - s1) + (odd ? t0 : p - t0);                                // below 3p
+  else r = s0 + s1 + (p - t0);                                                            // below 3p
   r = r >= 2 * p ? r - 2 * p : r;
   return r >= p ? r - p : r;
 }
@@ -807,15 +811,18 @@ __global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __
     return V;
   };
   // A32: the residues of the next limb are fetched while this one is recombined (the kernel waits on its loads), and on the
-  // linear-convolution rings the fold  S_j - S_(j+q') -+ (S_n - S_(n+q'))  is taken on the RESIDUES (it is linear and the plan keeps the
-  // combination below A / 2), so one Garner recombination per limb serves instead of four
+  // linear-convolution rings the fold (g32_fold) is taken on the RESIDUES (it is linear and the plan keeps the
+  // combination below A / 2), so one Garner recombination per limb serves instead of three
   u32 cur[4] = {0, 0, 0, 0}, nxt[4] = {0, 0, 0, 0};
+  u32 f_off = 0, f_top = 0;
+  bool f_odd = false;
+  if (fold_q) lin_fold_pos(fold_q, j, n, f_off, f_top, f_odd);
   auto fetch = [&](int l, u32 (&v)[4]) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const u32* __restrict__ row = base32 + (i64)(l * 4 + a) * nrow;
       if (!fold_q) { v[a] = row[j]; continue; }
-      v[a] = g32_fold(row, j, n, nrow, fold_q, gc.p[a]);
+      v[a] = g32_fold(row, j, nrow, fold_q, f_off, f_top, f_odd, gc.p[a]);
     }
   };
   if (A32) fetch(0, cur);
@@ -830,11 +837,11 @@ __global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __
     } else {
       V = centred(l, j);
       if (fold_q > 0) {      // (the two-prime auxiliary form never runs on a linear-convolution ring: ks_limb_plan)
-        // S (degree < 2n - 1) modulo X^q' + 1: R_j = S_j - S_(j+q');  modulo Phi_m = 1 - X + X^2 - ... + X^(q'-1) (degree n = q' - 1):
-        // out_j = R_j - (-1)^j R_n,  j < n   (Phi_m is monic, so this is the exact integer remainder)
-        const u128 top = centred(l, n) - centred(l, n + fold_q);
-        V -= centred(l, j + fold_q);
-        if (j & 1) V += top; else V -= top;
+        // S (degree < 2n - 1) modulo X^Q + 1: R_j = S_j - S_(j+Q);  modulo Phi_m = sum_{i<q} (-X^s)^i (degree n = Q - s):
+        // out_j = R_j - (-1)^floor(j/s) R_(n + j mod s),  j < n   (Phi_m is monic, so this is the exact integer remainder; S_(n + j mod s + Q) = 0)
+        const u128 top = centred(l, f_top);
+        if (j + f_off < nrow) V -= centred(l, j + f_off);
+        if (f_odd) V += top; else V -= top;
       }
     }
     const int s = B * l, wd = s >> 6, bt = s & 63;
@@ -941,8 +948,8 @@ static int launch_ks_recombine_t(fhesi_ctx* ctx, const CrtTables* t, const fhesi
 struct CentredConsts { u64 d[16]; };
 // NLBF, BF, LQF > 0: the limb count, limb width and logQ as compile-time constants (the metric ring's 7 x 74 bits, logQ = 512; plain rows only):
 // the limb loop unrolls, the bit offsets are static and all 4 NLBF residues of the coefficient are requested before the first is used.
-// FS = 1 (m = 2q'), 2 (m prime): rows of 2^15 on a linear-convolution ring, left as their two sub-inverses -- the fold and the tail stage are both
-// taken in the loader: the (up to) four positions a coefficient is folded from are worked out once (they do not depend on the limb or the prime),
+// FS = 1 (m = 2Q), 2 (m odd): rows of 2^15 on a linear-convolution ring, left as their two sub-inverses -- the fold and the tail stage are both
+// taken in the loader: the three positions a coefficient is folded from (g32_fold) are worked out once (they do not depend on the limb or the prime),
 // their sub-inverse pairs are loaded unconditionally, summed per half of the row with their signs and multiplied by the two tail constants.
 template <int NWORDS, int NLBF = 0, int BF = 0, int LQF = 0, int FS = 0>
 __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __restrict__ o32, i64 n, i64 nrow, i64 fold_q, int S /* 1: rows of 2^15 left as their two sub-inverses (the tail stage is taken here) */, int LQ_, int B_, int NLB_, u64 half_hi, u64 half_lo,
@@ -987,14 +994,16 @@ __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __
         }
     }
   }
-  constexpr int NT = FS == 1 ? 4 : 3;
+  constexpr int NT = 3;
   u32 eb[NT];
   bool up[NT], ok[NT], ng[NT];
+  u32 f_off = 0, f_top = 0;
+  bool f_odd = false;
+  if constexpr (!FIX) { if (fold_q) lin_fold_pos(fold_q, j, n, f_off, f_top, f_odd); }
   if constexpr (FS != 0) {
-    const i64 off = fold_q > 0 ? fold_q : -fold_q;
-    const i64 e[4] = {j, j + off, n, n + off};
-    // m = 2q':  S_j - S_(j+q') -+ (S_n - S_(n+q'))  (upper signs for even j);   m prime:  S_j + S_(j+m) - S_(m-1)
-    const bool sg[4] = {false, FS == 1, FS == 1 ? !(j & 1) : true, (j & 1) != 0};
+    const i64 e[3] = {j, j + f_off, f_top};
+    // m = 2Q:  S_j - S_(j+Q) - (-1)^floor(j/s) S_(phi + j mod s);   m odd:  S_j + S_(j+m) - S_(phi + j mod s)
+    const bool sg[3] = {false, FS == 1, FS == 1 ? !f_odd : true};
 #pragma unroll
     for (int k = 0; k < NT; ++k) {
       ok[k] = e[k] < nrow;
@@ -1034,7 +1043,7 @@ __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __
         continue;
       }
       if (!fold_q) { v[a] = row[j]; continue; }
-      v[a] = g32_fold(row, j, n, nrow, fold_q, gc.p[a]);
+      v[a] = g32_fold(row, j, nrow, fold_q, f_off, f_top, f_odd, gc.p[a]);
     }
   };
   if constexpr (!FIX) fetch(0, cur);

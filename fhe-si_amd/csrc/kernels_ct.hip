@@ -86,13 +86,14 @@ int launch_ct_add(fhesi_ctx* ctx, u64* d_dst, const u64* d_src, i64 ncoeffs, int
 // Ciphertext.cpp:54-59); its result is the INTEGER polynomial a(X^k) mod Phi_m (the coefficients, at most two input coefficients
 // added, stay far below half the chain product).  On the rings below that polynomial is a signed gather:
 //   m = 2n (power of two):  X^n = -1:              out_i = +-a_j,  j k = i or i + n (mod 2n)
-//   m = 2q', q' an odd prime (the reference's safe-prime rings), phi = q' - 1:  X^q' = -1 modulo X^q' + 1 = (X + 1) Phi_m,
-//       R_i = +-a_j with j k = i (mod q'), sign - when j k mod 2q' >= q';  out_i = R_i - (-1)^i R_(q'-1)   (Phi_m = sum (-X)^i, monic)
-//   m prime, phi = m - 1:   X^m = 1,  R_i = a_j with j k = i (mod m);  out_i = R_i - R_(m-1)   (Phi_m = sum X^i)
+//   m = 2Q, Q = q^k, q an odd prime (k = 1: the reference's safe-prime rings), s = q^(k-1), phi = Q - s:  X^Q = -1 modulo X^Q + 1,
+//       R_e = +-a_j with j k = e (mod Q), sign - when j k mod 2Q >= Q;  out_i = R_i - (-1)^floor(i/s) R_(phi + i mod s)   (Phi_m = sum_{i<q} (-X^s)^i, monic)
+//   m = Q odd, phi = m - s:   X^m = 1,  R_e = a_j with j k = e (mod m);  out_i = R_i - R_(phi + i mod s)   (Phi_m = sum_{i<q} X^(i s))
+//   (a_j = 0 for j >= phi.  s = 1: the fixed top phi = q' - 1 or m - 1 and the sign (-1)^i.)  Each output is at most two signed source coefficients,
 // so no row transform is needed at all: out = positive residue modulo 2^logQ, limb-major, as ByteDecompPart takes it (Ciphertext.cpp:94).
-// mode: 0 power of two, 1 m = 2 prime, 2 m prime.  in [npolys][n][nl_in] two's complement;  out [npolys][nlq][n] (logQ > 0), or the
+// mode: 0 power of two, 1 m = 2 q^k, 2 m = q^k; st = the stride s.  in [npolys][n][nl_in] two's complement;  out [npolys][nlq][n] (logQ > 0), or the
 // integers themselves, sign-extended, coefficient-major [npolys][n][nlq] (logQ = 0: toPoly of Ciphertext >>= without a key switch).
-__global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __restrict__ in, i64 n, int nl_in, i64 m, i64 kk, i64 kinv, int mode, int logQ,
+__global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __restrict__ in, i64 n, int nl_in, i64 m, i64 kk, i64 kinv, int mode, i64 st, int logQ,
                                                                  u64* __restrict__ out, int nlq) {
   const i64 poly = blockIdx.y;
   const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,22 +107,24 @@ __global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __re
     s1 = j < n ? 1 : -1;
   } else if (mode == 1) {
     const i64 q = m / 2;
-    auto term = [&](i64 e, i64& j, int& sg) {                        // the a_j with j k = e (mod q'), and its sign
+    const u32 b = st == 1 ? (u32)i : (u32)i / (u32)st;              // floor(i / s); i and s are below 2^20
+    auto term = [&](i64 e, i64& j, int& sg) {                        // the a_j with j k = e (mod Q), and its sign
       j = (i64)(((u128)e * (u128)(kinv % q)) % (u128)q);
-      if (j > q - 2) { sg = 0; j = 0; return; }
+      if (j >= n) { sg = 0; j = 0; return; }
       sg = ((i64)(((u128)j * (u128)kk) % (u128)m) >= q) ? -1 : 1;
     };
     term(i, j1, s1);
-    term(q - 1, j2, s2);
-    s2 = (i & 1) ? s2 : -s2;                                        // - (-1)^i R_(q'-1)
+    term(n + ((u32)i - b * (u32)st), j2, s2);
+    s2 = (b & 1) ? s2 : -s2;                                        // - (-1)^floor(i/s) R_(phi + i mod s)
   } else {
+    const u32 b = st == 1 ? (u32)i : (u32)i / (u32)st;
     auto term = [&](i64 e, i64& j, int& sg) {
       j = (i64)(((u128)e * (u128)kinv) % (u128)m);
-      sg = j > m - 2 ? 0 : 1;
+      sg = j >= n ? 0 : 1;
       if (!sg) j = 0;
     };
     term(i, j1, s1);
-    term(m - 1, j2, s2);
+    term(n + ((u32)i - b * (u32)st), j2, s2);
     s2 = -s2;
   }
   const u64* __restrict__ a1 = in + (poly * n + j1) * nl_in;
@@ -147,9 +150,9 @@ __global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __re
 int launch_ct_automorph_parts(fhesi_ctx* ctx, const u64* d_in, int nl_in, i64 npolys, i64 kk, int logQ, u64* d_parts, int nlq) {
   const i64 m = ctx->m, n = ctx->phim;
   int mode;
+  i64 st = 1;                         // the stride q^(k-1) of m = q^k, 2 q^k
   if (ctx->pow2) mode = 0;
-  else if (m % 2 == 0 && (m / 2) % 2 == 1 && hm::is_prime((u64)(m / 2)) && n == m / 2 - 1) mode = 1;
-  else if (hm::is_prime((u64)m) && n == m - 1) mode = 2;
+  else if (const i64 qq = hm::prime_power_ring(m, nullptr)) { mode = (m & 1) ? 2 : 1; st = ((m & 1) ? m : m / 2) / qq; }
   else return 2;
   if (!npolys) return 0;
   // k^-1 mod m (k in Z_m^*: checked by the caller)
@@ -161,7 +164,7 @@ int launch_ct_automorph_parts(fhesi_ctx* ctx, const u64* d_in, int nl_in, i64 np
     kinv = ((x0 % m) + m) % m;
   }
   dim3 grid((unsigned)((n + 255) / 256), (unsigned)npolys);
-  ct_automorph_parts_kernel<<<grid, 256, 0, ctx->stream>>>(d_in, n, nl_in, m, kk % m, kinv, mode, logQ, d_parts, nlq);
+  ct_automorph_parts_kernel<<<grid, 256, 0, ctx->stream>>>(d_in, n, nl_in, m, kk % m, kinv, mode, st, logQ, d_parts, nlq);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -21,6 +21,7 @@
 // primes instead of q_0, q_1 (kernels_aux32.hip: own 32-bit transforms, one multiply per multiply-add); this file then only plans
 // and builds.  Switches for A/B runs: FHESI_KS_DIRECT (per-prime dot product), FHESI_KS_RESIDUES, FHESI_KS_AUX60.
 #include "fhesi_internal.h"
+#include "lin_fold.h"
 #include <cmath>
 
 // 128-bit value -> [0,q)
@@ -300,7 +301,9 @@ bool ks_limb_plan(const fhesi_ctx* ctx, const CrtTables* t, int ncol, int digit_
   if (ctx->lin_q && !p.a32) return false;
   if (A >> 119 > 1) return false;                               // the +2^119 offset needs the auxiliary modulus below 2^120
   // ncol * n * 2^digit_bits bounds a coefficient of one limb product sum; on the linear-convolution rings the fold modulo X^q' + 1 and
-  // Phi_m combines four of them (C(j) - C(j+q') -+ (C(phi) - C(phi+q'))), each kept below A / 8 so that the combination stays below A / 2
+  // Phi_m combines three of them (C(j) -+ C(j+Q) -+ C(phi + j mod s)), each kept below A / 8 so that the combination stays below A / 2.  (The factor 4 is
+  // kept on purpose although three terms would do with 3: it is the plan the prime and 2 x prime rings have always had -- the same limb width B
+  // and limb count, so the same tables and bits -- and one bit of headroom costs nothing.)
   const u128 terms = ((u128)ncol * (u128)ctx->phim << digit_bits) * (ctx->lin_q ? 4 : 1);
   if (terms >> 50) return false;
   int B = 0;
@@ -443,7 +446,7 @@ int ksaux_build(fhesi_ctx* ctx, fhesi_ksk* k, int digit_bits, int logQ, int mode
   k->aux_centred = centred;
   k->aux_long_opt = ctx->opt.ks_long_keys;
   k->aux_key_bits = key_bits;
-  k->aux_fold = k->aux32 ? (ctx->lin_prime ? -ctx->lin_q : ctx->lin_q) : 0;      // (negative: the fold of a prime m)
+  k->aux_fold = k->aux32 && ctx->lin_q ? lin_fold_pack(ctx->lin_q, ctx->lin_s, ctx->lin_prime) : 0;      // (negative: the fold of an odd m)
   const int* d_slot = (const int*)(k->d_aux_consts + L);
   const i64 rows_per_a = (i64)R * 2 * ncol;
   if (!k->aux32)

@@ -32,6 +32,7 @@
 // fhesi_ct_mul_dev keeps the reference chain (its rows ARE visible).  Option tensor32 = 0 keeps the chain in the fused pipeline too; option
 // tensor_bits = 29 takes the primes below 2^29 (fewer range steps in the row transforms, one or two primes more: measured a tie).
 #include "fhesi_internal.h"
+#include "lin_fold.h"
 #include "ntt32_core.inc"
 #include <cmath>
 
@@ -590,13 +591,16 @@ __global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict_
 
 // The same conversion for any logQ <= 512 (words of 28 bits, rows of 2^14) and for the linear-convolution rings: the window [J0, J0 + NW)
 // of words and the bit positions are run-time values, so after the (compile-time indexed) accumulation and the carry pass the words go
-// through LDS, one column per thread, and the 64-bit limbs are cut from there.  fold_q = q' (m = 2q'): the residue of output coefficient j is
-//   r_j - r_(j+q') - (-1)^j r_(q'-1)   of the linear product's residues (modulo X^q' + 1, then modulo Phi_m = sum (-X)^i).
+// through LDS, one column per thread, and the 64-bit limbs are cut from there.  The fold (fold_off = lin_fold_pack: the offset Q or m and the stride
+// s = q^(k-1) of a ring m = 2Q or Q, Q = q^k; phi = (q - 1) s = n_out): the residue of output coefficient j is
+//   r_j - r_(j+Q) - (-1)^floor(j/s) r_(phi + j mod s)   (m = 2Q: modulo X^Q + 1, then modulo Phi_m = sum_{i<q} (-X^s)^i)
+//   r_j + r_(j+m) - r_(phi + j mod s)                   (m odd:  modulo X^m - 1, then modulo Phi_m = sum_{i<q} X^(i s))
+// of the linear product's residues; s = 1 is the fixed top phi and the sign (-1)^j of the prime and 2 x prime rings.
 // NWMAX = T32_GEN_NW with J0 from the host, or T32_GEN_NWX with J0 = 0 for the exact pass over flagged workgroups.
 // S = 1 (rows of 2^15 = the two sub-inverses A, B of ntt32_inv_kernel3): the coefficient at position e < 2^14 is (A_e + B_e) / 2, at e + 2^14
 // (A_e - B_e) psi^-brv(1) / 2; the two constants sit in cinv[2i], cinv[2i + 1] (times the CRT constant), so the positions of the lower and of
 // the upper half are summed separately and the residue is  lo c_lo + hi c_hi.
-// S and FOLD (0: none, 1: m = 2q', 2: m prime) are compile-time: the (up to) three positions a coefficient is folded from do not depend on the
+// S and FOLD (0: none, 1: m = 2Q, 2: m odd) are compile-time: the (up to) three positions a coefficient is folded from do not depend on the
 // prime, so their offsets, halves and signs are worked out once, the loads of a prime are unconditional (clamped index, masked value) and
 // independent of each other, and the multiply-adds run over all NWMAX words without a branch (words from NW upwards are never looked at; the
 // table is padded so that the reads stay inside it).  With the positions behind run-time branches and `if (l < NW)` around every word the
@@ -619,13 +623,16 @@ __global__ void __launch_bounds__(128) crt32_scale_generic_kernel(const u32* __r
   for (int l = 0; l < NWMAX; ++l) acc[l] = 0;
   u32 fsum = 0;
   if (active) {
-    // term 0: position j, +;  term 1: position j + off, - (m = 2q') or + (m prime);  term 2: position off - 1, -(-1)^j (m = 2q') or - (m prime)
+    // term 0: position j, +;  term 1: position j + off, - (m = 2Q) or + (m odd);  term 2: position phi + j mod s, -(-1)^floor(j/s) (m = 2Q) or - (m odd)
     constexpr int NT = FOLD ? 3 : 1;
     u32 eb[NT];
     bool up[NT], ok[NT], neg[NT];
     {
-      const i64 e[3] = {j, j + fold_off, fold_off - 1};
-      const bool ng[3] = {false, FOLD == 1, FOLD == 2 || !(j & 1)};
+      u32 f_off = 0, f_top = 0;
+      bool f_odd = false;
+      if (FOLD) lin_fold_pos(fold_off, j, n_out, f_off, f_top, f_odd);      // (j / s and j mod s once per thread, in 32 bits)
+      const i64 e[3] = {j, j + f_off, f_top};
+      const bool ng[3] = {false, FOLD == 1, FOLD == 2 || !f_odd};
 #pragma unroll
       for (int k = 0; k < NT; ++k) {
         ok[k] = e[k] < nrow;
@@ -662,8 +669,8 @@ __global__ void __launch_bounds__(128) crt32_scale_generic_kernel(const u32* __r
         u32 r = ri[eb[0]];
         if (FOLD) {
           const u32 b = ok[1] ? ri[eb[1]] : 0u, c = ri[eb[2]];
-          if (FOLD == 1) r = r + (p - b) + (neg[2] ? p - c : c);                    // r_j - r_(j+q') - (-1)^j r_(q'-1): below 4p
-          else r = r + b + (p - c);                                                  // r_j + r_(j+m) - r_(m-1): below 3p
+          if (FOLD == 1) r = r + (p - b) + (neg[2] ? p - c : c);                    // r_j - r_(j+Q) - (-1)^floor(j/s) r_(phi + j mod s): below 3p (mul_lazy32 takes any u32)
+          else r = r + b + (p - c);                                                  // r_j + r_(j+m) - r_(phi + j mod s): below 3p
         }
         y = mul_lazy32(r, cinv[2 * i], p);
         y = y >= p ? y - p : y;
@@ -818,7 +825,7 @@ static int t32_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npoly
   FHESI_TRY(ws_reserve(ctx, 6, (size_t)grid.x * grid.y, &d_fl));
   unsigned char* fl = (unsigned char*)d_fl;
   const int fold = !ctx->lin_q ? 0 : (ctx->lin_prime ? 2 : 1);
-  const i64 off = ctx->lin_q;
+  const i64 off = ctx->lin_q ? lin_fold_pack(ctx->lin_q, ctx->lin_s, false) : 0;      // (the kind of fold is the template argument)
   // (S, FOLD) compile-time; the first pass over 16 or 24 words, whichever holds the window
 #define T32_GEN_GO(NWM, SS, FF) do { \
     PROF_KERNEL(ctx, PROF_CRT, (crt32_scale_generic_kernel<NWM, false, SS, FF>)); \

@@ -41,10 +41,10 @@ const char* fhesi_last_error(void);
 int fhesi_device_count(int32_t* count);
 /* ABI revision of this header.  It changes whenever an existing entry point changes its parameters (revision 5:
  * fhesi_keyswitch_init_batch_seeded took its public_seed argument in round 4; revision 6 adds this query and
- * fhesi_host_stage_release).  A binding compiled or written against another revision must refuse to run: the Python binding
+ * fhesi_host_stage_release; revision 8 adds fhesi_ctx_lin_class).  A binding compiled or written against another revision must refuse to run: the Python binding
  * (fhe-si_amd/binding.py) and the C++ mirror (fhe-si_amd/host/fhesi_context.h) compare FHESI_ABI_VERSION with the library's
  * answer when they load it -- a stale ctypes table or mirror would otherwise link and silently shift arguments. */
-#define FHESI_ABI_VERSION 7
+#define FHESI_ABI_VERSION 8
 int32_t fhesi_abi_version(void);
 
 /* ---- context: FHEcontext::AddPrime (FHEContext.cpp:30-43) + Cmod::privateInit (CModulus.cpp:60-86) +
@@ -61,6 +61,12 @@ int32_t fhesi_ctx_nprimes(const fhesi_ctx* ctx);            /* FHEcontext::numPr
 int fhesi_ctx_prime(const fhesi_ctx* ctx, int32_t i, uint64_t* q, uint64_t* root);   /* ithPrime / getRoot */
 int fhesi_ctx_zms_idx(const fhesi_ctx* ctx, int32_t* out_m);                        /* PAlgebra::indexInZmstar table */
 int fhesi_ctx_phi_m(const fhesi_ctx* ctx, int64_t* out_phim_plus_1);                /* PAlgebra::PhimX coefficients */
+/* Which class of ring the fused 30-bit paths took (read-only).  Phi_m as PAlgebra::init builds it (PAlgebra.cpp:40-56) is a three-term fold
+ * exactly for m = Q or 2Q with Q = q^k, q an odd prime: Phi_m(X) = Phi_q(+-X^s), s = q^(k-1).  On those rings the integer products run as linear
+ * convolutions on zero-padded rows of 2^lin_lg points (14 .. 20, from 2 phi(m) - 1 <= 2^lin_lg) and are folded with offset = Q (m = 2Q) or m (m odd)
+ * and stride = s (1 for a prime or 2 x prime m).  offset = stride = lin_lg = 0: a power of two (negacyclic rows) or any other m (per-prime
+ * Bluestein rows).  ctx != NULL: what that context took (m is ignored); ctx == NULL: what a context on m would take -- no device is touched. */
+int fhesi_ctx_lin_class(const fhesi_ctx* ctx, int64_t m, int64_t* offset, int64_t* stride, int32_t* lin_lg);
 int fhesi_ctx_sync(fhesi_ctx* ctx);
 void* fhesi_ctx_stream(fhesi_ctx* ctx);                     /* the hipStream_t all work of this context runs on */
 /* Behaviour switches of one context (A/B measurements, test hooks).  Names: "ks_direct" (1 = per-chain-prime key-switch dot product, the
