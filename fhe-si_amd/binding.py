@@ -49,6 +49,10 @@ ABI_SYMBOLS = [
 ]
 ABI_VERSION = 8          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8}
+# name-only records (Context.prof_kernel_name; no stopwatch, so not in PROF_CLASSES): the closing kernel the last profiled launch ran
+# (class 13 is FHESI_PROF_NAME_DIGITS in the header; its key here is "digits_kernel" because prof_kernel_name takes the keys of both dictionaries
+# and "digits" is the timed class 5 of PROF_CLASSES)
+PROF_NAMES = {"crt_exact": 9, "ks_recombine": 10, "rns_generic": 11, "modswitch": 12, "digits_kernel": 13}
 
 
 class FhesiError(RuntimeError):
@@ -356,9 +360,9 @@ class Context:
         return n.value, u.value, ms.value
 
     def prof_kernel_name(self, cls: str) -> str:
-        """Demangled name of the kernel the last profiled launch of that class ran ('' if none)."""
+        """Demangled name of the kernel the last profiled launch of that class (of PROF_CLASSES or PROF_NAMES) ran ('' if none)."""
         buf = C.create_string_buffer(512)
-        _ck(_load().fhesi_prof_kernel_name(self.h, PROF_CLASSES[cls], buf, 512))
+        _ck(_load().fhesi_prof_kernel_name(self.h, PROF_CLASSES[cls] if cls in PROF_CLASSES else PROF_NAMES[cls], buf, 512))
         return buf.value.decode()
 
     def set_option(self, name: str, value: int):

@@ -417,9 +417,12 @@ extern "C" int fhesi_prof_read(fhesi_ctx* c, int32_t cls, int64_t* launches, dou
   return 0;
 }
 
+static_assert(FHESI_PROF_NAME_CRT_EXACT == PROF_NAME_CRT_EXACT && FHESI_PROF_NAME_KS_RECOMBINE == PROF_NAME_KS_RECOMBINE && FHESI_PROF_NAME_RNS_GENERIC == PROF_NAME_RNS_GENERIC &&
+              FHESI_PROF_NAME_MODSWITCH == PROF_NAME_MODSWITCH && FHESI_PROF_NAME_DIGITS == PROF_NAME_DIGITS && FHESI_PROF_NAME_DIGITS + 1 == PROF_NNAME,
+              "the name-only classes of include/fhesi_hip.h are those of fhesi_internal.h");
 extern "C" int fhesi_prof_kernel_name(fhesi_ctx* c, int32_t cls, char* out, size_t cap) {
   CHECK_CTX(c);
-  if (cls < 0 || cls >= PROF_NCLASS || !out || !cap) FHESI_FAIL("prof_kernel_name: bad argument");
+  if (cls < 0 || cls >= PROF_NNAME || !out || !cap) FHESI_FAIL("prof_kernel_name: bad argument");
   out[0] = 0;
   if (!c->prof_fn[cls]) return 0;
   const char* mangled = hipKernelNameRefByPtr(c->prof_fn[cls], c->stream);

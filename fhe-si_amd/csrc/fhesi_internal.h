@@ -63,6 +63,10 @@ struct fhesi_aux32;                    // four 30-bit auxiliary primes of the ke
 
 // per-kernel-class HIP-event stopwatch (bench.py's live kernel timing; off by default)
 enum { PROF_NTT_FWD = 0, PROF_NTT_INV = 1, PROF_RNS = 2, PROF_TENSOR = 3, PROF_CRT = 4, PROF_DIGITS = 5, PROF_DOT = 6, PROF_EW = 7, PROF_NTT_FWD_DIGITS_MAIN = 8, PROF_NCLASS = 9 };
+// name-only records behind the timed classes (fhesi_prof_kernel_name; no stopwatch of their own): which closing kernel of kernels_crt.hip the
+// last profiled launch ran -- the exact mixed-radix CRT (the sum form's clean-up included), the key-switch recombination, the run-time-width
+// RNS reduction, the modulus switch and the plain digit rows
+enum { PROF_NAME_CRT_EXACT = PROF_NCLASS, PROF_NAME_KS_RECOMBINE, PROF_NAME_RNS_GENERIC, PROF_NAME_MODSWITCH, PROF_NAME_DIGITS, PROF_NNAME };
 struct ProfRec { int cls; double units; hipEvent_t e0, e1; };
 
 // Behaviour switches of one context (fhesi_ctx_set_option).  The FHESI_* environment variables of the same meaning are read ONCE, when
@@ -256,6 +260,7 @@ struct ProfScope {
 // names the kernel of the launch that follows (only recorded while profiling is on)
 static inline void prof_kernel(fhesi_ctx* ctx, int cls, const void* host_stub) { if (ctx->prof_on) ctx->prof_fn[cls] = host_stub; }
 #define PROF_KERNEL(ctx, cls, ...) prof_kernel((ctx), (cls), (const void*)&__VA_ARGS__)
+static_assert(PROF_NNAME <= 16, "fhesi_ctx::prof_fn holds 16 entries");
 
 // --------------------------------------------------------------------------------- host number theory (hostmath.cpp)
 namespace hm {

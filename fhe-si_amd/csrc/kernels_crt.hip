@@ -198,6 +198,7 @@ int launch_rns_reduce(fhesi_ctx* ctx, const u64* d_limbs, int nlimbs, i64 ncoeff
   const size_t shmem = (size_t)nlimbs * 256 * sizeof(u64);
   if (shmem > 160 * 1024) FHESI_FAIL("rns_reduce: coefficients of %d limbs are too wide", nlimbs);
   HIP_TRY(hipFuncSetAttribute((const void*)rns_reduce_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  PROF_KERNEL(ctx, PROF_NAME_RNS_GENERIC, rns_reduce_kernel);
   rns_reduce_kernel<<<grid, 256, shmem, ctx->stream>>>(d_limbs, nlimbs, ncoeffs < n ? ncoeffs : n, n, npoly, d_sc, d_rows, nslots, d_prime_of_slot, ctx->d_pc, d_pow);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -507,6 +508,7 @@ static int launch_crt_t(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows, i
   static std::atomic<unsigned long long> attr_done{0};     // one bit per device: the attribute is per device
   if (!LQFIX && !(attr_done.load() >> ctx->device & 1)) { HIP_TRY(hipFuncSetAttribute((const void*)crt_kernel<MAXW, KFIX, WFIX, LQFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, MAXW * TB * 8)); attr_done.fetch_or(1ull << ctx->device); }
   dim3 grid((unsigned)((ctx->phim + TB - 1) / TB), (unsigned)npolys);
+  PROF_KERNEL(ctx, PROF_NAME_CRT_EXACT, (crt_kernel<MAXW, KFIX, WFIX, LQFIX>));
   crt_kernel<MAXW, KFIX, WFIX, LQFIX><<<grid, TB, shmem, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->nidx, t->W, t->d_idx, t->d_pow64, t->d_pinv, t->d_P,
                                                     t->d_halfP, ctx->d_pc, mode, positive, logQ, d_out, nl_out, d_block_flags);
   HIP_TRY(hipGetLastError());
@@ -934,6 +936,7 @@ static int launch_ks_recombine_t(fhesi_ctx* ctx, const CrtTables* t, const fhesi
   RecombineConsts c;
   FHESI_TRY(ks_recombine_consts(ctx, A32, S != 0, &c));
   dim3 grid((unsigned)((ctx->phim + 127) / 128), (unsigned)npolys);
+  PROF_KERNEL(ctx, PROF_NAME_KS_RECOMBINE, (ks_recombine_kernel<W, LQ, B, NLB, A32, S>));
   ks_recombine_kernel<W, LQ, B, NLB, A32, S><<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, c.q0, c.q1, c.q0inv, c.q0inv_sh, c.half_hi, c.half_lo, c.a_hi, c.a_lo,
                                                                           k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
@@ -1169,6 +1172,7 @@ static int launch_ks_recombine_centred(fhesi_ctx* ctx, const fhesi_ksk* k, const
   else if (S && fold) kern = ks_recombine_centred_kernel<16, 0, 0, 0, 2>;
   else if (NW == 8) kern = ks_recombine_centred_kernel<8>;
   else kern = ks_recombine_centred_kernel<16>;
+  prof_kernel(ctx, PROF_NAME_KS_RECOMBINE, (const void*)kern);
   kern<<<grid, 128, 0, ctx->stream>>>((const u32*)d_o, ctx->phim, nrow, fold, S, LQ, B, NLB, c.half_hi, c.half_lo, c.a_hi, c.a_lo, cc, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1204,6 +1208,7 @@ int launch_ks_recombine(fhesi_ctx* ctx, const CrtTables* t, const fhesi_ksk* k, 
   if (W <= 20) kern = k->aux32 ? ks_recombine_generic_kernel<20, true> : ks_recombine_generic_kernel<20, false>;
   else if (W <= 44) kern = k->aux32 ? ks_recombine_generic_kernel<44, true> : ks_recombine_generic_kernel<44, false>;
   else FHESI_FAIL("key switch, limb mode: chain product of %d limbs exceeds the supported 44", W);
+  prof_kernel(ctx, PROF_NAME_KS_RECOMBINE, (const void*)kern);
   kern<<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, nrow, k->aux_fold, W, k->aux_logQ, k->aux_limb_bits, k->aux_rows, c.q0, c.q1, c.q0inv, c.q0inv_sh,
                                      c.half_hi, c.half_lo, c.a_hi, c.a_lo, k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
@@ -1284,10 +1289,13 @@ int launch_modswitch_delta(fhesi_ctx* ctx, const u64* d_delta, int W, const u64*
   HIP_TRY(hipMemcpyAsync(d_c, consts_host, (size_t)3 * W * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));            // the caller's constant array may go away
   const unsigned grid = (unsigned)((ctx->phim + 127) / 128);
-  if (W <= 8) modswitch_delta_kernel<8><<<grid, 128, 0, ctx->stream>>>(d_delta, ctx->phim, W, (const u64*)d_c, p, u, d_e);
-  else if (W <= 24) modswitch_delta_kernel<24><<<grid, 128, 0, ctx->stream>>>(d_delta, ctx->phim, W, (const u64*)d_c, p, u, d_e);
-  else if (W <= 66) modswitch_delta_kernel<66><<<grid, 128, 0, ctx->stream>>>(d_delta, ctx->phim, W, (const u64*)d_c, p, u, d_e);
+  void (*kern)(const u64*, i64, int, const u64*, u64, u64, u64*);
+  if (W <= 8) kern = modswitch_delta_kernel<8>;
+  else if (W <= 24) kern = modswitch_delta_kernel<24>;
+  else if (W <= 66) kern = modswitch_delta_kernel<66>;
   else FHESI_FAIL("scaleDownToSet: dropped-prime product of %d limbs is too wide", W);
+  prof_kernel(ctx, PROF_NAME_MODSWITCH, (const void*)kern);
+  kern<<<grid, 128, 0, ctx->stream>>>(d_delta, ctx->phim, W, (const u64*)d_c, p, u, d_e);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1321,6 +1329,7 @@ int launch_digits(fhesi_ctx* ctx, const u64* d_parts, int nl, int logQ, int digi
   unsigned gx = (unsigned)((ctx->phim + 255) / 256);
   if (gx > 64) gx = 64;
   dim3 grid(gx, (unsigned)nd, (unsigned)npolys);
+  PROF_KERNEL(ctx, PROF_NAME_DIGITS, digits_kernel);
   digits_kernel<<<grid, 256, 0, ctx->stream>>>(d_parts, nl, ctx->phim, logQ, digit_bits, nd, ctx->L, d_rows, ctx->d_pc, only_below_q);
   HIP_TRY(hipGetLastError());
   return 0;

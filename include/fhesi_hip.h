@@ -98,7 +98,13 @@ enum { FHESI_PROF_NTT_FWD = 0, FHESI_PROF_NTT_INV = 1, FHESI_PROF_RNS = 2, FHESI
 int fhesi_prof_enable(fhesi_ctx* ctx, int32_t on);      /* also clears the records */
 int fhesi_prof_read(fhesi_ctx* ctx, int32_t kernel_class, int64_t* launches, double* units, double* total_ms);
 /* demangled name (as rocprofv3 prints it, without the argument list) of the kernel the most recent profiled launch of that class ran:
- * the roofline line of bench.py names kernels by what the library launched, not by string literals */
+ * the roofline line of bench.py names kernels by what the library launched, not by string literals.
+ * The classes from FHESI_PROF_NAME_CRT_EXACT on carry a name only (no stopwatch: fhesi_prof_read refuses them): which closing kernel of the
+ * big-integer conversions the last profiled launch ran -- the exact mixed-radix CRT (on its own or as the sum form's clean-up; FHESI_PROF_CRT
+ * keeps naming crt_sum_kernel / crt32_scale*), the key-switch recombination, the RNS reduction of coefficients wider than 20 limbs, the
+ * modulus switch and the plain digit rows.  The dispatch tests pin every branch of those launchers by these names. */
+enum { FHESI_PROF_NAME_CRT_EXACT = 9, FHESI_PROF_NAME_KS_RECOMBINE = 10, FHESI_PROF_NAME_RNS_GENERIC = 11, FHESI_PROF_NAME_MODSWITCH = 12,
+       FHESI_PROF_NAME_DIGITS = 13 };
 int fhesi_prof_kernel_name(fhesi_ctx* ctx, int32_t kernel_class, char* name_out, size_t name_cap);
 
 /* ---- Cmodulus::FFT / iFFT, one row (CModulus.h:165-166; CModulus.cpp:90-107, 110-132) */

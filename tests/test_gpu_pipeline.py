@@ -5,6 +5,7 @@ import pytest
 
 import fhe_si_amd as F
 import fhesi_pyref as R
+import ks_crafted as K
 import oracle_lib as O
 import params as P
 
@@ -409,14 +410,14 @@ def test_key_switch_on_safe_prime_rings(m, logQ):
     for q in primes:
         Pprod *= q
     mod, W, h, pb = 1 << logQ, L + 2, (Pprod - 1) // 2, Pprod.bit_length()
-    edge = [h, -h, h + 1, h - 1, 0, 1, -1, Pprod - 1, h + 2, 12345, -(1 << (pb * 4 // 7)), (1 << (pb - 8)) + 17]
+    edge = K.edge_values(Pprod)
+    assert edge[:4] == [h, -h, h + 1, h - 1] and edge[-1] == (1 << (pb - 8)) + 17
     for d, pos in ((1, 0), ((1 << 24) - 1, n - 1), ((1 << 24) - 1, n // 2))[(1 if m > 10000 else 0):(2 if m > 10000 else 3)]:
         tp = np.zeros((1, 3, L, n), dtype=np.uint64)
-        tp[0, 0] = orc.dcrt_from_poly(O.ints_to_limbs([0] * pos + [d * mod] + [0] * (n - 1 - pos), W))
+        tp[0, 0] = orc.dcrt_from_poly(K.monomial_limbs(n, W, pos, d * mod))
         ksm2 = ksm.copy()
         for r in range(2):
-            e = (edge[r:] + edge[:r]) * (n // len(edge) + 1)
-            ksm2[r, 0] = orc.dcrt_from_poly(O.ints_to_limbs(e[:n], W))
+            ksm2[r, 0] = orc.dcrt_from_poly(K.edge_limbs(edge, n, W, r))
         ksk2 = F.KeySwitchMatrix(ctx, 3, nd).upload(ksm2)
         dtp = ctx.upload(tp)
         out = ctx.alloc(2 * n * nl * 8)
