@@ -46,9 +46,11 @@ ABI_SYMBOLS = [
     "fhesi_slots_basis_embed", "fhesi_slots_basis_decode", "fhesi_slots_basis_embed_dev", "fhesi_slots_basis_decode_dev",
     "fhesi_encrypt_int_slots_batch_seeded", "fhesi_decrypt_int_slots_batch", "fhesi_encrypt_noise_int_batch_seeded",
     "fhesi_ctx_lin_class",
+    "fhesi_plain_create_slots", "fhesi_plain_create_poly", "fhesi_plain_free", "fhesi_plain_info", "fhesi_plain_sum_bits", "fhesi_ct_plain_sum_dev", "fhesi_ct_add_slots_dev",
 ]
-ABI_VERSION = 8          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
-PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8}
+ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
+PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8,
+                "plain_sum": 15}          # (numbered behind the name-only records below, which keep their public numbers)
 # name-only records (Context.prof_kernel_name; no stopwatch, so not in PROF_CLASSES): the closing kernel the last profiled launch ran
 # (class 13 is FHESI_PROF_NAME_DIGITS in the header; its key here is "digits_kernel" because prof_kernel_name takes the keys of both dictionaries
 # and "digits" is the timed class 5 of PROF_CLASSES)
@@ -219,6 +221,13 @@ def _load():
         "fhesi_encrypt_int_slots_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _vp, _i32, _i64, _i64, _vp, _i32],
         "fhesi_decrypt_int_slots_batch": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _vp],
         "fhesi_encrypt_noise_int_batch_seeded": [_vp, _vp, _vp, _vp, _i32, _u64, _u64, _i64, _vp, _i32],
+        "fhesi_plain_create_slots": [_vp, _vp, _i64, _i32, _i64, _vp],
+        "fhesi_plain_create_poly": [_vp, _vp, _i64, _vp],
+        "fhesi_plain_free": [_vp],
+        "fhesi_plain_info": [_vp, _vp, _vp, _vp],
+        "fhesi_plain_sum_bits": [_i64, _i32, _u64, _i64, _vp],
+        "fhesi_ct_plain_sum_dev": [_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp],
+        "fhesi_ct_add_slots_dev": [_vp, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _i64, _i32, _i64],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -503,9 +512,54 @@ class Context:
         weakref.finalize(buf, lambda: lib.fhesi_host_free(None, C.c_void_p(addr)))
         return arr
 
+    # ---- prepared plaintext operands (fhesi_plain): sums of ciphertext x plaintext products
+    def plain_from_poly(self, poly: np.ndarray) -> "Plain":
+        """poly [nw][phim] signed int64 coefficient polynomials (the operand of Ciphertext *= ZZX) -> a prepared handle."""
+        poly = np.ascontiguousarray(poly, dtype=np.int64).reshape(-1, self.phim)
+        h = _vp()
+        _ck(_load().fhesi_plain_create_poly(self.h, _p(poly), poly.shape[0], C.byref(h)))
+        return Plain(self, h)
+
+    def ct_plain_sum_dev(self, plain: "Plain", logQ: int, pool: DevBuf, npool: int, nlimbs: int, a_idx, b_idx, seg, out: DevBuf):
+        """out[g] = sum_{t in [seg[g], seg[g+1])} pool[a_idx[t]] (*) plain[b_idx[t]] on unscaled two-part ciphertexts; the arguments are checked
+        by the library (FhesiError names what it refuses)."""
+        ia, ib = np.ascontiguousarray(a_idx, dtype=np.int32), np.ascontiguousarray(b_idx, dtype=np.int32)
+        sg = np.ascontiguousarray(seg, dtype=np.int32)
+        _ck(_load().fhesi_ct_plain_sum_dev(self.h, plain.h, logQ, pool.ptr, npool, nlimbs, _p(ia), _p(ib), _p(sg), len(sg) - 1, out.ptr))
+
     def release_host_staging(self):
         """hand back the pinned + device staging ring the host-buffer calls keep between uses"""
         _ck(_load().fhesi_host_stage_release(self.h))
+
+
+def plain_sum_bits(m: int, logQ: int, maxabs: int, terms: int) -> float:
+    """Bits the chain product must exceed for a sum of `terms` ciphertext x plaintext products on the ring m: log2 of twice
+    terms * growth * phi(m) * 2^(logQ-1) * maxabs, growth = 1 (m a power of two), 2 (m = q^k, 2 q^k) or phi(m).  Touches no device."""
+    bits = C.c_double(0.0)
+    _ck(_load().fhesi_plain_sum_bits(int(m), int(logQ), int(maxabs), int(terms), C.byref(bits)))
+    return bits.value
+
+
+class Plain:
+    """nw prepared plaintext operands of one context (fhesi_plain): evaluation form over the whole chain, resident in HBM; made by
+    SlotSpace.plain / Context.plain_from_poly, read by any number of Context.ct_plain_sum_dev calls."""
+
+    def __init__(self, ctx: "Context", h):
+        self.ctx, self.h = ctx, h
+        nw, maxabs, p = _i64(0), _u64(0), _u64(0)
+        _ck(_load().fhesi_plain_info(self.h, C.byref(nw), C.byref(maxabs), C.byref(p)))
+        self.nw, self.maxabs, self.p = nw.value, maxabs.value, p.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            _load().fhesi_plain_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def slots_plan(m: int, p: int, generator: int) -> dict:
@@ -616,6 +670,18 @@ class SlotSpace:
         """Regression::GenerateNoise for `count` masks (slot 0 zero, the others uniform from (seed, index))."""
         _ck(_load().fhesi_encrypt_noise_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, count, out.ptr, nlimbs))
 
+    def plain(self, vals: np.ndarray, only_usable: bool = True) -> Plain:
+        """vals [nw][nvals] slot values -> a prepared handle for Context.ct_plain_sum_dev (embedded and transformed on the device)."""
+        vals = np.ascontiguousarray(np.atleast_2d(vals), dtype=np.int64)
+        h = _vp()
+        _ck(_load().fhesi_plain_create_slots(self.h, _p(vals), vals.shape[1], int(only_usable), vals.shape[0], C.byref(h)))
+        return Plain(self.ctx, h)
+
+    def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nparts: int, nlimbs: int, count: int, vals: np.ndarray, only_usable: bool = True):
+        """Ciphertext += Plaintext(vals) on unscaled ciphertexts; vals [nv][nvals] slot values, nv = 1 (one constant for all) or count."""
+        vals = np.ascontiguousarray(np.atleast_2d(vals), dtype=np.int64)
+        _ck(_load().fhesi_ct_add_slots_dev(self.ctx.h, self.h, logQ, ct.ptr, nparts, nlimbs, count, _p(vals), vals.shape[1], int(only_usable), vals.shape[0]))
+
 
 def slots_basis_plan(m: int, bits: int, prime_bits: int, generator: int) -> dict:
     """A slot basis for results of up to `bits` bits (host only): the largest primes = 1 mod m below 2^prime_bits, descending, until their
@@ -673,6 +739,13 @@ def unpack_limbs(limbs: np.ndarray) -> np.ndarray:
     for i in range(flat.shape[0]):
         flat[i] = int.from_bytes(raw[8 * L * i: 8 * L * (i + 1)], "little", signed=True)
     return out
+
+
+class _View:
+    """one channel's part of a [k][count] device buffer"""
+
+    def __init__(self, buf, off: int):
+        self.ptr = _vp(buf.ptr.value + off)
 
 
 class SlotBasis:
@@ -762,6 +835,31 @@ class SlotBasis:
         out = np.zeros((count, nvals, self.limbs), dtype=np.int64)
         _ck(_load().fhesi_decrypt_int_slots_batch(self.ctx.h, self.h, sk1.h, logQ, ct.ptr, nlimbs, count, nvals, _p(out)))
         return out if raw else unpack_limbs(out)
+
+    # prepared plaintext operands, channel by channel (no entry point of their own: channel c is an ordinary space modulo primes[c])
+    def _residues(self, vals, c: int) -> np.ndarray:
+        """integers (Python ints of any size or an integer array) [..][nvals] -> their residues modulo primes[c], int64"""
+        a = np.atleast_2d(np.asarray(vals))
+        if a.dtype == object:
+            return np.array([[int(v) % self.primes[c] for v in row] for row in a], dtype=np.int64)
+        return np.mod(a.astype(np.int64), np.int64(self.primes[c]))
+
+    def plain(self, vals) -> list:
+        """vals [nw][nvals] integers -> the k channel handles (channel c holds vals mod primes[c])."""
+        return [self.channel(c).plain(self._residues(vals, c)) for c in range(self.k)]
+
+    def ct_plain_sum_dev(self, plains, logQ: int, pool: DevBuf, npool: int, nlimbs: int, a_idx, b_idx, seg, out: DevBuf):
+        """Context.ct_plain_sum_dev per channel: pool [k][npool], out [k][ngroups] logical ciphertexts, plains from SlotBasis.plain."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        ngroups = len(seg) - 1
+        for c in range(self.k):
+            self.ctx.ct_plain_sum_dev(plains[c], logQ, _View(pool, c * npool * words), npool, nlimbs, a_idx, b_idx, seg, _View(out, c * ngroups * words))
+
+    def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nlimbs: int, count: int, vals):
+        """Ciphertext += integers, per channel: ct [k][count] two-part ciphertexts, vals [nv][nvals] integers, nv = 1 or count."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            self.channel(c).ct_add_slots_dev(logQ, _View(ct, c * count * words), 2, nlimbs, count, self._residues(vals, c))
 
     def encrypt_noise_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, count: int, out: DevBuf, nlimbs: int):
         """k masks per logical mask (slot 0 = 0 modulo P, the others uniform), object indices first_index .. first_index + k * count - 1."""

@@ -1,4 +1,4 @@
-// capi_ct.hip -- ciphertext algebra between multiplications, Encrypt / Decrypt batches, key generation (include/fhesi_hip.h)
+// capi_ct.hip -- ciphertext algebra between multiplications, Encrypt / Decrypt batches, prepared plaintext operands, key generation (include/fhesi_hip.h)
 #include "capi_common.h"
 
 // ---- coefficient-domain ciphertext algebra on device batches (kernels_ct.hip)
@@ -149,11 +149,11 @@ static int stage_msg_host(fhesi_ctx* c, const int64_t* msg_host, i64 count, i64*
   HIP_TRY(hipMemcpyAsync(*d_msg, msg_host, (size_t)count * c->phim * 8, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
-static int stage_msg_slots(fhesi_ctx* c, fhesi_slots* s, const int64_t* vals_host, i64 nvals, bool only_usable, i64 count, i64** d_msg) {      // [count][nvals] slot values
-  if (!s) FHESI_FAIL("Encrypt: null plaintext space");
-  if (s->ctx != c) FHESI_FAIL("Encrypt: the plaintext space belongs to another context");
-  if (!vals_host) FHESI_FAIL("Encrypt: null slot values");
-  FHESI_TRY(slots_check_shape("Encrypt", nvals, count, s->S.phim));
+static int stage_msg_slots(fhesi_ctx* c, fhesi_slots* s, const int64_t* vals_host, i64 nvals, bool only_usable, i64 count, i64** d_msg, const char* what = "Encrypt") {      // [count][nvals] slot values
+  if (!s) FHESI_FAIL("%s: null plaintext space", what);
+  if (s->ctx != c) FHESI_FAIL("%s: the plaintext space belongs to another context", what);
+  if (!vals_host) FHESI_FAIL("%s: null slot values", what);
+  FHESI_TRY(slots_check_shape(what, nvals, count, s->S.phim));
   if (!count) return 0;
   i64* d_vals;
   FHESI_TRY(msg_staging(c, count, d_msg));
@@ -315,6 +315,198 @@ extern "C" int fhesi_decrypt_int_slots_batch(fhesi_ctx* c, fhesi_slots_basis* b,
   FHESI_TRY(ws_i64(c, 9, bv, &d_vals));
   FHESI_TRY(slots_basis_decode_rows(b, d_msg, count, nvals, d_vals));
   return copy_out(c, vals_host, d_vals, bv);
+}
+
+// --------------------------------------------------------------------------------------------- prepared plaintext operands
+// fhesi_plain (include/fhesi_hip.h): the one core behind both constructors.  d_msg [nw][phi(m)] int64 message polynomials in HBM (a stage above
+// left them in workspace slot 5) -> DoubleCRT rows over all primes, owned by the handle.  Synchronises: the array the stage uploaded from is the
+// caller's again on return.
+static int plain_rows_dev(fhesi_ctx* c, const i64* d_msg, i64 nw, u64 maxabs, u64 p, fhesi_plain** out) {
+  const i64 n = c->phim;
+  const int L = c->L;
+  const std::vector<int> all = full_set(c);
+  fhesi_plain* w = new fhesi_plain();
+  w->ctx = c; w->nw = nw; w->maxabs = maxabs; w->p = p;
+  if (hipMalloc(&w->d_rows, (size_t)nw * L * n * 8) != hipSuccess) { (void)hipGetLastError(); delete w; FHESI_FAIL("prepared plaintext: hipMalloc of %zu bytes failed", (size_t)nw * L * n * 8); }
+  int rc = launch_rns_reduce(c, (const u64*)d_msg, 1, n, nw, 1, nullptr, w->d_rows, L, nullptr);      // one signed limb per coefficient
+  if (!rc) rc = row_fwd(c, w->d_rows, nw, L, nullptr, all.data());
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { fhesi_set_error("prepared plaintext: the transforms failed"); rc = 1; }
+  if (rc) { hipFree(w->d_rows); delete w; return rc; }
+  ++c->live_handles;
+  *out = w;
+  return 0;
+}
+extern "C" int fhesi_plain_create_slots(fhesi_slots* s, const int64_t* vals_host, int64_t nvals, int32_t only_usable, int64_t nw, fhesi_plain** out) {
+  if (!out) FHESI_FAIL("prepared plaintext: null output pointer");
+  *out = nullptr;
+  if (!s) FHESI_FAIL("prepared plaintext: null plaintext space");
+  fhesi_ctx* c = s->ctx;
+  CHECK_CTX(c);
+  if (nw < 1 || nw > 65535) FHESI_FAIL("prepared plaintext: %lld plaintexts per handle, 1 .. 65535 are taken", (long long)nw);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_slots(c, s, vals_host, nvals, only_usable != 0, nw, &d_msg, "prepared plaintext"));
+  return plain_rows_dev(c, d_msg, nw, s->S.p - 1, s->S.p, out);      // the embedding leaves coefficients in [0, p)
+}
+extern "C" int fhesi_plain_create_poly(fhesi_ctx* c, const int64_t* poly_host, int64_t nw, fhesi_plain** out) {
+  if (!out) FHESI_FAIL("prepared plaintext: null output pointer");
+  *out = nullptr;
+  CHECK_CTX(c);
+  if (!poly_host) FHESI_FAIL("prepared plaintext: null polynomial");
+  if (nw < 1 || nw > 65535) FHESI_FAIL("prepared plaintext: %lld plaintexts per handle, 1 .. 65535 are taken", (long long)nw);
+  u64 maxc = 0;
+  for (i64 i = 0; i < nw * c->phim; ++i) { const i64 v = poly_host[i]; const u64 a = v < 0 ? (u64)(-(v + 1)) + 1 : (u64)v; if (a > maxc) maxc = a; }
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_host(c, poly_host, nw, &d_msg));
+  return plain_rows_dev(c, d_msg, nw, maxc, 0, out);
+}
+extern "C" int fhesi_plain_free(fhesi_plain* w) {
+  if (!w) return 0;
+  hipSetDevice(w->ctx->device);
+  hipStreamSynchronize(w->ctx->stream);
+  --w->ctx->live_handles;
+  hipFree(w->d_rows);
+  delete w;
+  return 0;
+}
+extern "C" int fhesi_plain_info(const fhesi_plain* w, int64_t* nw, uint64_t* maxabs, uint64_t* p) {
+  if (!w) FHESI_FAIL("null prepared plaintext");
+  if (nw) *nw = w->nw;
+  if (maxabs) *maxabs = w->maxabs;
+  if (p) *p = w->p;
+  return 0;
+}
+// host only: no device, no context
+extern "C" int fhesi_plain_sum_bits(int64_t m, int32_t logQ, uint64_t maxabs, int64_t terms, double* bits) {
+  if (!bits) FHESI_FAIL("plain_sum_bits: null output");
+  if (m < 2 || m > ((i64)1 << 20)) FHESI_FAIL("plain_sum_bits: m=%lld outside [2, 2^20]", (long long)m);
+  if (logQ < 1) FHESI_FAIL("plain_sum_bits: logQ=%d", logQ);
+  if (terms < 0) FHESI_FAIL("plain_sum_bits: %lld terms", (long long)terms);
+  i64 n = 0;
+  hm::zms_idx(m, &n);
+  const bool pow2 = (m & (m - 1)) == 0 && m >= 4;      // the classes fhesi_ctx_create records (pow2, phi_two_term)
+  *bits = plain_sum_bits(n, pow2, !pow2 && hm::prime_power_ring(m, nullptr) != 0, logQ, maxabs, terms);
+  return 0;
+}
+
+// out[g] = sum_{t in [seg[g], seg[g+1])} pool[a_idx[t]] (*) w[b_idx[t]] on unscaled two-part ciphertexts (include/fhesi_hip.h).  The host plans
+// passes: groups [g, g2) whose distinct ciphertexts and whose sums both fit the rows one pass may hold; a single group with more distinct
+// ciphertexts than that is summed piecewise into the same rows.  The index lists of ALL passes are uploaded once, in front of the first launch.
+extern "C" int fhesi_ct_plain_sum_dev(fhesi_ctx* c, const fhesi_plain* w, int32_t logQ, const uint64_t* pool, int64_t npool, int32_t nlimbs,
+                                      const int32_t* a_idx, const int32_t* b_idx, const int32_t* seg, int64_t ngroups, uint64_t* out) {
+  CHECK_CTX(c);
+  if (!w) FHESI_FAIL("ct_plain_sum: null prepared plaintext");
+  if (w->ctx != c) FHESI_FAIL("ct_plain_sum: the prepared plaintext belongs to another context");
+  if (nlimbs < 1 || logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("ct_plain_sum: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
+  if (ngroups < 0 || npool < 0) FHESI_FAIL("ct_plain_sum: negative count");
+  if (!ngroups) return 0;
+  if (!seg || !out) FHESI_FAIL("ct_plain_sum: null argument");
+  if (seg[0] != 0) FHESI_FAIL("ct_plain_sum: seg must start at 0, got %d", seg[0]);
+  i64 tmax = 0;
+  for (i64 g = 0; g < ngroups; ++g) {
+    if (seg[g + 1] < seg[g]) FHESI_FAIL("ct_plain_sum: seg is not non-decreasing at group %lld (%d after %d)", (long long)g, seg[g + 1], seg[g]);
+    tmax = std::max<i64>(tmax, seg[g + 1] - seg[g]);
+  }
+  const i64 nterms = seg[ngroups];
+  if (nterms && (!a_idx || !b_idx || !pool)) FHESI_FAIL("ct_plain_sum: null argument");
+  for (i64 t = 0; t < nterms; ++t) {
+    if (a_idx[t] < 0 || a_idx[t] >= npool) FHESI_FAIL("ct_plain_sum: ciphertext index %d of term %lld out of range (pool of %lld)", a_idx[t], (long long)t, (long long)npool);
+    if (b_idx[t] < 0 || b_idx[t] >= w->nw) FHESI_FAIL("ct_plain_sum: plaintext index %d of term %lld out of range (%lld prepared)", b_idx[t], (long long)t, (long long)w->nw);
+  }
+  const i64 n = c->phim;
+  const int L = c->L;
+  const i64 ct_words = (i64)2 * n * nlimbs, row_words = (i64)2 * L * n;
+  {
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)ngroups * ct_words * 8, p0 = (uintptr_t)pool, p1 = p0 + (size_t)npool * ct_words * 8;
+    if (npool && o0 < p1 && p0 < o1) FHESI_FAIL("ct_plain_sum: out overlaps pool");
+  }
+  double chain = 0.0;
+  for (int i = 0; i < L; ++i) chain += std::log2((double)c->q[i]);
+  const double bits = plain_sum_bits(n, c->pow2, c->phi_two_term, logQ, w->maxabs, tmax);
+  if (bits >= chain) FHESI_FAIL("ct_plain_sum: a sum of %lld products needs %.0f bits, the chain holds %.0f", (long long)tmax, std::ceil(bits), std::floor(chain));
+  const std::vector<int> all = full_set(c);
+  CrtTables* t_all;
+  FHESI_TRY(get_crt_tables(c, all, &t_all));
+  // rows of one pass: the distinct ciphertexts' and the sums', about 4 GiB each (option "wave_operands": at most that many of either, for tests)
+  i64 cap = (i64)(4.0 * 1024 * 1024 * 1024 / ((double)row_words * 8));
+  if (cap > 32767) cap = 32767;                             // (the reduction and the CRT put two polynomials per ciphertext on grid.y)
+  if (c->opt.wave_operands > 0 && c->opt.wave_operands < cap) cap = c->opt.wave_operands;
+  if (cap < 1) cap = 1;
+  // ---- plan: per pass [distinct pool entries][local ciphertext slot per term][plaintext index per term][segment bounds] in one index array
+  struct Pass { i64 g, ng, nu, nt; size_t off; bool accumulate, close; };
+  std::vector<Pass> passes;
+  std::vector<int> ix;
+  std::map<int, int> slot_of;
+  auto add_pass = [&](i64 g, i64 ng, i64 t0, i64 t1, bool accumulate, bool close) {
+    Pass P{g, ng, 0, t1 - t0, ix.size(), accumulate, close};
+    slot_of.clear();
+    const size_t at = ix.size();
+    for (i64 t = t0; t < t1; ++t) if (slot_of.emplace(a_idx[t], (int)slot_of.size()).second) ix.push_back(a_idx[t]);
+    P.nu = (i64)(ix.size() - at);
+    for (i64 t = t0; t < t1; ++t) ix.push_back(slot_of[a_idx[t]]);
+    ix.insert(ix.end(), b_idx + t0, b_idx + t1);
+    if (ng == 1) { ix.push_back(0); ix.push_back((int)(t1 - t0)); }                        // (a piece of one group)
+    else for (i64 i = 0; i <= ng; ++i) ix.push_back(seg[g + i] - seg[g]);
+    passes.push_back(P);
+  };
+  {
+    std::set<int> seen, grp;
+    for (i64 g = 0; g < ngroups;) {
+      seen.clear();
+      i64 g2 = g;
+      while (g2 < ngroups && g2 - g < cap) {
+        grp.clear();
+        for (i64 t = seg[g2]; t < seg[g2 + 1]; ++t) if (!seen.count(a_idx[t])) grp.insert(a_idx[t]);
+        if (g2 > g && (i64)(seen.size() + grp.size()) > cap) break;
+        seen.insert(grp.begin(), grp.end());
+        ++g2;
+      }
+      if (g2 - g == 1 && (i64)seen.size() > cap) {
+        for (i64 t0 = seg[g]; t0 < seg[g + 1]; t0 += cap) { const i64 t1 = std::min<i64>(t0 + cap, seg[g + 1]); add_pass(g, 1, t0, t1, t0 != seg[g], t1 == seg[g + 1]); }
+      } else add_pass(g, g2 - g, seg[g], seg[g2], false, true);
+      g = g2;
+    }
+  }
+  void* d_ix;
+  FHESI_TRY(ws_reserve(c, 5, sizeof(int) * ix.size(), &d_ix));
+  HIP_TRY(hipMemcpyAsync(d_ix, ix.data(), sizeof(int) * ix.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));                 // the one synchronisation: ix lives on this frame, a_idx / b_idx / seg are read no more
+  i64 max_nu = 0, max_ng = 0;
+  for (const Pass& P : passes) { max_nu = std::max(max_nu, P.nu); max_ng = std::max(max_ng, P.ng); }
+  void *d_ops, *d_rows, *d_sum;
+  FHESI_TRY(ws_reserve(c, 7, (size_t)max_nu * ct_words * 8, &d_ops));
+  FHESI_TRY(ws_reserve(c, 0, (size_t)max_nu * row_words * 8, &d_rows));
+  FHESI_TRY(ws_reserve(c, 4, (size_t)max_ng * row_words * 8, &d_sum));
+  for (const Pass& P : passes) {
+    const int* dix = (const int*)d_ix + P.off;
+    if (P.nu) {
+      FHESI_TRY(launch_gather(c, (const u64*)pool, dix, P.nu, ct_words, (u64*)d_ops));
+      FHESI_TRY(launch_rns_reduce(c, (const u64*)d_ops, nlimbs, n, P.nu, 2, nullptr, (u64*)d_rows, L, nullptr));
+      FHESI_TRY(row_fwd(c, (u64*)d_rows, P.nu * 2, L, nullptr, all.data()));
+    }
+    FHESI_TRY(launch_plain_sum(c, (const u64*)d_rows, w->d_rows, dix + P.nu, dix + P.nu + P.nt, dix + P.nu + 2 * P.nt, P.ng, P.accumulate, (u64*)d_sum, (double)P.nt));
+    if (!P.close) continue;
+    FHESI_TRY(row_inv(c, (u64*)d_sum, P.ng * 2, L, nullptr, all.data()));
+    FHESI_TRY(launch_crt(c, t_all, (const u64*)d_sum, L, nullptr, P.ng * 2, 2, 0, logQ, (u64*)out + (size_t)P.g * ct_words, nlimbs));
+  }
+  return 0;
+}
+// Ciphertext::operator+=(const ZZX&) unscaled (Ciphertext.cpp:147-156) with the constant given as slot values: the embed stage, then the kernel
+// behind fhesi_ct_add_const_dev on the message polynomials where they are
+extern "C" int fhesi_ct_add_slots_dev(fhesi_ctx* c, fhesi_slots* s, int32_t logQ, uint64_t* ct, int32_t nparts, int32_t nlimbs, int64_t count,
+                                      const int64_t* vals_host, int64_t nvals, int32_t only_usable, int64_t nv) {
+  CHECK_CTX(c);
+  if (nparts < 1 || nlimbs < 1 || logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("Ciphertext += slots: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
+  if (count < 0) FHESI_FAIL("Ciphertext += slots: negative count");
+  if (nv != 1 && nv != count) FHESI_FAIL("Ciphertext += slots: %lld constants for %lld ciphertexts (one for all, or one each)", (long long)nv, (long long)count);
+  i64* d_msg = nullptr;
+  FHESI_TRY(stage_msg_slots(c, s, vals_host, nvals, only_usable != 0, nv, &d_msg, "Ciphertext += slots"));
+  const size_t n = (size_t)c->phim;
+  for (i64 done = 0; done < count; done += 65535) {
+    const i64 cnt = std::min<i64>(65535, count - done);
+    FHESI_TRY(launch_ct_add_const(c, (u64*)ct + (size_t)done * nparts * n * nlimbs, d_msg + (nv == 1 ? 0 : (size_t)done * n), nv == 1 ? 1 : (int)cnt, nparts, nlimbs, logQ, s->S.p, cnt));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));        // vals_host may be released on return
+  return 0;
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

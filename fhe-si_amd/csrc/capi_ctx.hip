@@ -404,7 +404,7 @@ extern "C" int fhesi_prof_enable(fhesi_ctx* c, int32_t on) {
 }
 extern "C" int fhesi_prof_read(fhesi_ctx* c, int32_t cls, int64_t* launches, double* units, double* total_ms) {
   CHECK_CTX(c);
-  if (cls < 0 || cls >= PROF_NCLASS) FHESI_FAIL("unknown kernel class %d", cls);
+  if (!prof_timed_class(cls)) FHESI_FAIL("unknown kernel class %d", cls);
   HIP_TRY(hipStreamSynchronize(c->stream));
   int64_t n = 0; double u = 0, ms = 0;
   for (auto& r : c->prof) {
@@ -418,11 +418,11 @@ extern "C" int fhesi_prof_read(fhesi_ctx* c, int32_t cls, int64_t* launches, dou
 }
 
 static_assert(FHESI_PROF_NAME_CRT_EXACT == PROF_NAME_CRT_EXACT && FHESI_PROF_NAME_KS_RECOMBINE == PROF_NAME_KS_RECOMBINE && FHESI_PROF_NAME_RNS_GENERIC == PROF_NAME_RNS_GENERIC &&
-              FHESI_PROF_NAME_MODSWITCH == PROF_NAME_MODSWITCH && FHESI_PROF_NAME_DIGITS == PROF_NAME_DIGITS && FHESI_PROF_NAME_DIGITS + 1 == PROF_NNAME,
+              FHESI_PROF_NAME_MODSWITCH == PROF_NAME_MODSWITCH && FHESI_PROF_NAME_DIGITS == PROF_NAME_DIGITS && FHESI_PROF_NAME_DIGITS + 1 == PROF_NNAME && FHESI_PROF_PLAIN_SUM == PROF_PLAIN_SUM,
               "the name-only classes of include/fhesi_hip.h are those of fhesi_internal.h");
 extern "C" int fhesi_prof_kernel_name(fhesi_ctx* c, int32_t cls, char* out, size_t cap) {
   CHECK_CTX(c);
-  if (cls < 0 || cls >= PROF_NNAME || !out || !cap) FHESI_FAIL("prof_kernel_name: bad argument");
+  if (cls < 0 || (cls >= PROF_NNAME && cls != PROF_PLAIN_SUM) || !out || !cap) FHESI_FAIL("prof_kernel_name: bad argument");
   out[0] = 0;
   if (!c->prof_fn[cls]) return 0;
   const char* mangled = hipKernelNameRefByPtr(c->prof_fn[cls], c->stream);

@@ -62,7 +62,8 @@ struct BluesteinTables;                // general-m path, defined in bluestein.h
 struct fhesi_aux32;                    // four 30-bit auxiliary primes of the key switch (kernels_aux32.hip), built on first use
 
 // per-kernel-class HIP-event stopwatch (bench.py's live kernel timing; off by default)
-enum { PROF_NTT_FWD = 0, PROF_NTT_INV = 1, PROF_RNS = 2, PROF_TENSOR = 3, PROF_CRT = 4, PROF_DIGITS = 5, PROF_DOT = 6, PROF_EW = 7, PROF_NTT_FWD_DIGITS_MAIN = 8, PROF_NCLASS = 9 };
+enum { PROF_NTT_FWD = 0, PROF_NTT_INV = 1, PROF_RNS = 2, PROF_TENSOR = 3, PROF_CRT = 4, PROF_DIGITS = 5, PROF_DOT = 6, PROF_EW = 7, PROF_NTT_FWD_DIGITS_MAIN = 8, PROF_NCLASS = 9,
+       PROF_PLAIN_SUM = 15 /* timed like the classes below PROF_NCLASS; numbered behind the name-only records, whose numbers are public */ };
 // name-only records behind the timed classes (fhesi_prof_kernel_name; no stopwatch of their own): which closing kernel of kernels_crt.hip the
 // last profiled launch ran -- the exact mixed-radix CRT (the sum form's clean-up included), the key-switch recombination, the run-time-width
 // RNS reduction, the modulus switch and the plain digit rows
@@ -167,7 +168,8 @@ struct fhesi_ctx {
   //   10 auxiliary-prime dot product output (kernels_ksaux.hip)      11 staging of host batches (fhesi_ct_mul_relin_batch)
   //   (the slot layer borrows 8 for its convolution buffer / basis residues, 9 for slot values and 5 for message polynomials -- slots_stage_host,
   //   the stage_msg_* functions in front of encrypt_rows_dev: before the transforms of an encryption start; what follows decrypt_rows_dev:
-  //   after those of a decryption are enqueued)
+  //   after those of a decryption are enqueued; fhesi_ct_plain_sum_dev takes the owners fhesi_ct_mul_sum_relin_dev takes: 7 gathered operands, 0 their
+  //   rows, 4 the sums, 5 the index lists of all passes)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -260,7 +262,8 @@ struct ProfScope {
 // names the kernel of the launch that follows (only recorded while profiling is on)
 static inline void prof_kernel(fhesi_ctx* ctx, int cls, const void* host_stub) { if (ctx->prof_on) ctx->prof_fn[cls] = host_stub; }
 #define PROF_KERNEL(ctx, cls, ...) prof_kernel((ctx), (cls), (const void*)&__VA_ARGS__)
-static_assert(PROF_NNAME <= 16, "fhesi_ctx::prof_fn holds 16 entries");
+static_assert(PROF_NNAME <= PROF_PLAIN_SUM && PROF_PLAIN_SUM < 16, "fhesi_ctx::prof_fn holds 16 entries");
+static inline bool prof_timed_class(int cls) { return (cls >= 0 && cls < PROF_NCLASS) || cls == PROF_PLAIN_SUM; }
 
 // --------------------------------------------------------------------------------- host number theory (hostmath.cpp)
 namespace hm {
@@ -376,6 +379,21 @@ template <class F> int slots_stage_host(fhesi_ctx* c, bool embed, const int64_t*
   return 0;
 }
 
+// --------------------------------------------------------------------------------- prepared plaintext operands (capi_ct.hip, kernels_plain.hip)
+// nw plaintext polynomials in evaluation form over the whole chain: made once, read by any number of fhesi_ct_plain_sum_dev calls
+struct fhesi_plain {
+  fhesi_ctx* ctx = nullptr;
+  i64 nw = 0;
+  u64 maxabs = 0;                      // bound on the magnitude of the coefficients the rows were made from (the capacity rule's operand)
+  u64 p = 0;                           // the slot space's plaintext modulus; 0 for the polynomial form
+  u64* d_rows = nullptr;               // [nw][L][phim] canonical residues
+};
+// log2 of 2 * terms * growth * n * 2^(logQ-1) * maxabs: the bits the chain product must exceed (0 for an empty or all-zero sum)
+double plain_sum_bits(i64 n, bool pow2, bool two_term, int logQ, u64 maxabs, i64 terms);
+constexpr int kPlainSumFold = 64;      // terms an accumulator of plain_sum_kernel takes between folds (derivation at the kernel)
+int launch_plain_sum(fhesi_ctx* ctx, const u64* d_ca /* [nu][2][L][n] */, const u64* d_w /* [nw][L][n] */, const int* d_slot_a, const int* d_slot_w, const int* d_seg,
+                     i64 ngroups, bool accumulate, u64* d_out /* [ngroups][2][L][n] */, double nterms);
+
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout
 // slot s is prime_of_slot[s] (nullptr = identity).  bitrev=false leaves the forward output / takes the inverse input in
@@ -484,5 +502,23 @@ __device__ __forceinline__ u64 d_barrett128(u64 hi, u64 lo, u64 q, u64 mu, u32 k
 __device__ __forceinline__ u64 d_mulmod(u64 a, u64 b, const PrimeConst& pc) {
   u64 hi = d_mulhi(a, b), lo = a * b;
   return d_barrett128(hi, lo, pc.q, pc.bar_mu, pc.bar_k);
+}
+// exact 128-bit multiply-accumulate and its reduction modulo q (dot_accum_kernel, tensor_sum_kernel, plain_sum_kernel): the caller folds
+// before the sum can reach 2^128
+struct Acc128 { u64 lo, hi; };
+__device__ __forceinline__ void acc_mad(Acc128& a, u64 x, u64 y) {
+  const u128 s = ((u128)a.hi << 64 | a.lo) + (u128)x * y;      // one 64x64->128 multiply-add: 4 v_mad_u64_u32
+  a.lo = (u64)s;
+  a.hi = (u64)(s >> 64);
+}
+__device__ __forceinline__ u64 acc_reduce(const Acc128& a, const PrimeConst& pc) {
+  const u64 q = pc.q;
+  const u64 h = d_shoup(a.hi, 1, pc.one_sh, q);              // hi mod q
+  const u64 t = d_shoup_lazy(h, pc.r64, pc.r64_sh, q);       // hi * 2^64 mod q, in [0,2q)
+  const u64 l = d_shoup_lazy(a.lo, 1, pc.one_sh, q);         // lo mod q, in [0,2q)
+  u64 r = t + l;                                              // < 4q
+  if (r >= pc.two_q) r -= pc.two_q;
+  if (r >= q) r -= q;
+  return r;
 }
 #endif

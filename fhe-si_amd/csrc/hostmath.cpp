@@ -2,6 +2,7 @@
 // Mirrors what FHEcontext / PAlgebra / Cmodulus compute at setup in the reference:
 //   PAlgebra::init (PAlgebra.cpp:40-56), Cyclotomic (NumbTh.cpp:142-158), ProbPrime check (FHEContext.cpp:34).
 #include "fhesi_internal.h"
+#include <cmath>
 
 #include <cstdarg>
 #include <cstring>
@@ -400,3 +401,14 @@ const char* slot_basis_plan(i64 m, int bits, int prime_bits, i64 g, std::vector<
 }
 
 }  // namespace hm
+
+// The capacity rule of a sum of ciphertext x plaintext products (fhesi_plain_sum_bits, fhesi_ct_plain_sum_dev): every coefficient of
+// sum_t part * w_t rem Phi_m is at most terms * growth * n * 2^(logQ-1) * maxabs in magnitude -- n products of a centred ciphertext
+// coefficient and a plaintext coefficient per term, and the remainder modulo Phi_m multiplies a coefficient by at most growth = 1 (X^n + 1),
+// 2 (the two-term folds of m = q^k, 2 q^k) or, conservatively, n (a general Phi_m), as Ciphertext *= ZZX sizes its product.  A centred
+// representative needs that bound below HALF the chain product: the bits returned are log2(2 * bound).
+double plain_sum_bits(i64 n, bool pow2, bool two_term, int logQ, u64 maxabs, i64 terms) {
+  if (!maxabs || terms < 1) return 0.0;
+  const double growth = pow2 ? 0.0 : (two_term ? 1.0 : std::log2((double)n));
+  return 1.0 + std::log2((double)terms) + growth + std::log2((double)n) + (double)(logQ - 1) + std::log2((double)maxabs);
+}

@@ -101,22 +101,7 @@ __global__ void __launch_bounds__(256) tensor2x2_kernel(const u64* __restrict__ 
 // accumulated as exact 128-bit integers and reduced once at the end.  The digit values may be lazy representatives (anything
 // below 4 q_tile + 2^32 < 2^63, which is what the fused digit transform stores): the launcher derives from that bound after how many
 // columns the accumulators have to be folded (every 63 columns for 60-bit primes: once per sum at the metric config's 66 columns).
-struct Acc128 { u64 lo, hi; };
-__device__ __forceinline__ void acc_mad(Acc128& a, u64 x, u64 y) {
-  const u128 s = ((u128)a.hi << 64 | a.lo) + (u128)x * y;      // one 64x64->128 multiply-add: 4 v_mad_u64_u32
-  a.lo = (u64)s;
-  a.hi = (u64)(s >> 64);
-}
-__device__ __forceinline__ u64 acc_reduce(const Acc128& a, const PrimeConst& pc) {
-  const u64 q = pc.q;
-  const u64 h = d_shoup(a.hi, 1, pc.one_sh, q);              // hi mod q
-  const u64 t = d_shoup_lazy(h, pc.r64, pc.r64_sh, q);       // hi * 2^64 mod q, in [0,2q)
-  const u64 l = d_shoup_lazy(a.lo, 1, pc.one_sh, q);         // lo mod q, in [0,2q)
-  u64 r = t + l;                                              // < 4q
-  if (r >= pc.two_q) r -= pc.two_q;
-  if (r >= q) r -= q;
-  return r;
-}
+// (Acc128 / acc_mad / acc_reduce: fhesi_internal.h, shared with kernels_plain.hip)
 // SUBORDER: the digit rows are in the sub-block order the head-fused transform of n = 2^15 leaves them in (evaluation 2j + sub at
 // [sub][j]): the two evaluations a lane works on come from the two halves of the row instead of from adjacent words.
 template <int CT_TILE, bool SUBORDER = false>

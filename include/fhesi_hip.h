@@ -33,6 +33,7 @@ typedef struct fhesi_ctx fhesi_ctx;     /* FHEcontext + vector<Cmodulus> + PAlge
 typedef struct fhesi_dcrt fhesi_dcrt;   /* one DoubleCRT object (DoubleCRT.h:83-365), rows resident in HBM */
 typedef struct fhesi_ksk fhesi_ksk;     /* one KeySwitchSI matrix (FHE-SI.cpp:206-208), resident in HBM */
 typedef struct fhesi_slots fhesi_slots; /* one PlaintextSpace (PlaintextSpace.h): slot <-> root tables and chirps of the DFT modulo the plaintext prime */
+typedef struct fhesi_plain fhesi_plain; /* nw prepared plaintext operands: DoubleCRT rows over the whole chain, resident in HBM */
 typedef struct fhesi_comm fhesi_comm;   /* one rank of a multi-GPU group: an RCCL communicator (ncclComm_t) over xGMI */
 
 enum { FHESI_OP_ADD = 0, FHESI_OP_SUB = 1, FHESI_OP_MUL = 2, FHESI_OP_DIV = 3, FHESI_OP_SET = 4 };
@@ -41,10 +42,10 @@ const char* fhesi_last_error(void);
 int fhesi_device_count(int32_t* count);
 /* ABI revision of this header.  It changes whenever an existing entry point changes its parameters (revision 5:
  * fhesi_keyswitch_init_batch_seeded took its public_seed argument in round 4; revision 6 adds this query and
- * fhesi_host_stage_release; revision 8 adds fhesi_ctx_lin_class).  A binding compiled or written against another revision must refuse to run: the Python binding
+ * fhesi_host_stage_release; revision 8 adds fhesi_ctx_lin_class; revision 9 adds the prepared plaintext operands, fhesi_plain_*).  A binding compiled or written against another revision must refuse to run: the Python binding
  * (fhe-si_amd/binding.py) and the C++ mirror (fhe-si_amd/host/fhesi_context.h) compare FHESI_ABI_VERSION with the library's
  * answer when they load it -- a stale ctypes table or mirror would otherwise link and silently shift arguments. */
-#define FHESI_ABI_VERSION 8
+#define FHESI_ABI_VERSION 9
 int32_t fhesi_abi_version(void);
 
 /* ---- context: FHEcontext::AddPrime (FHEContext.cpp:30-43) + Cmod::privateInit (CModulus.cpp:60-86) +
@@ -94,7 +95,9 @@ int fhesi_timer_stop(fhesi_ctx* ctx, float* elapsed_ms);
  * stream; read returns (#launches, units processed -- rows for the NTT classes, polynomials/ciphertexts otherwise --, total ms) */
 enum { FHESI_PROF_NTT_FWD = 0, FHESI_PROF_NTT_INV = 1, FHESI_PROF_RNS = 2, FHESI_PROF_TENSOR = 3, FHESI_PROF_CRT = 4,
        FHESI_PROF_DIGITS = 5, FHESI_PROF_DOT = 6, FHESI_PROF_EW = 7,
-       FHESI_PROF_NTT_FWD_DIGITS_MAIN = 8 /* the fused ByteDecomp + forward-NTT tile kernel alone; units = rows it transformed */ };
+       FHESI_PROF_NTT_FWD_DIGITS_MAIN = 8 /* the fused ByteDecomp + forward-NTT tile kernel alone; units = rows it transformed */,
+       FHESI_PROF_PLAIN_SUM = 15 /* plain_sum_kernel of fhesi_ct_plain_sum_dev; units = terms.  Numbered behind the name-only records below,
+                                    which keep the numbers revision 8 gave them; 14 stays unassigned */ };
 int fhesi_prof_enable(fhesi_ctx* ctx, int32_t on);      /* also clears the records */
 int fhesi_prof_read(fhesi_ctx* ctx, int32_t kernel_class, int64_t* launches, double* units, double* total_ms);
 /* demangled name (as rocprofv3 prints it, without the argument list) of the kernel the most recent profiled launch of that class ran:
@@ -419,6 +422,45 @@ int fhesi_decrypt_int_slots_batch(fhesi_ctx* ctx, fhesi_slots_basis* b, const fh
                                   int64_t nvals, int64_t* vals_host /* [count][nvals][limbs] */);
 int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* ctx, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
                                          int64_t count, uint64_t* out_dev /* [k][count] */, int32_t nlimbs);
+
+/* ---- prepared plaintext operands: a ciphertext combined with PLAINTEXT slot values on the device -- a mask, a model applied to encrypted data
+ * (y = sum_j theta_j o x_j + b), a diagonal of a plaintext matrix (fhe-si_amd/csrc/kernels_plain.hip, capi_ct.hip).  An extension of the mirror's
+ * Ciphertext *= ZZX / += ZZX for callers that hold slot values and reuse an operand many times.
+ *
+ * SCOPE.  Unscaled two-part ciphertexts [..][2][phi(m)][nlimbs], centred modulo 2^logQ.  A fhesi_plain owns nw <= 65535 plaintext polynomials in evaluation
+ * form over ALL chain primes, uint64 [nw][L][phi(m)] canonical residues in HBM: made once (embedding, reduction and forward transforms on the
+ * device; the message polynomials never visit the host), read by any number of calls.  It holds a pointer to its context and counts as one of its
+ * live handles, exactly as a fhesi_slots does (fhesi_ctx_destroy).
+ *   _create_slots: vals_host [nw][nvals] slot values of the space s (any fhesi_slots: single-generator, two-row, a channel of a basis), embedded as
+ *     fhesi_slots_embed does: message polynomials in [0, p).  Records maxabs = p - 1.
+ *   _create_poly:  poly_host [nw][phi(m)] SIGNED coefficient polynomials, the operand of Ciphertext::operator*=(const ZZX&).  Records maxabs = the
+ *     largest magnitude seen; p = 0.
+ * fhesi_ct_plain_sum_dev: for every group g,  out[g] = sum_{t in [seg[g], seg[g+1])} pool[a_idx[t]] (*) w[b_idx[t]].  Each product is
+ *   CiphertextPart::operator*=(ZZX) (Ciphertext.cpp:29-36: integer product, rem Phi_m, Reduce) on both parts, each sum Ciphertext::operator+=
+ *   unscaled (:123-134): bit for bit what fhesi_ct_mul_poly_dev on a copy of the operand and fhesi_ct_add_dev per term give.  Every distinct pool
+ *   entry is transformed once however many terms use it, the terms are accumulated exactly in the evaluation domain, and every GROUP is inverted
+ *   and reduced once.  a_idx, b_idx, seg are host arrays (seg[0] = 0, non-decreasing, ngroups + 1 entries), the caller's again on return; an empty
+ *   segment gives the zero ciphertext.  out_dev [ngroups][2][phi(m)][nlimbs] must not overlap pool_dev.
+ * CAPACITY.  Every coefficient of the integer sum is at most T growth n 2^(logQ-1) maxabs in magnitude: T the longest segment, n = phi(m), growth = 1
+ *   (m a power of two), 2 (m = q^k or 2 q^k, q an odd prime) or n (any other m), as fhesi_ct_mul_poly_dev sizes its product.  That bound must stay
+ *   below HALF the chain product: fhesi_plain_sum_bits returns log2 of twice the bound (0 for no terms or maxabs = 0), which must be below
+ *   sum_i log2 q_i.  Host only: no device, no context.
+ * REFUSED on the host before anything is launched, with the condition named and the context usable afterwards: a handle of another context, an
+ *   index outside the pool or the handle, seg not starting at 0 or decreasing, out overlapping pool, nvals outside 1 .. phi(m), coefficients that
+ *   cannot hold logQ, a sum the chain cannot hold (the message gives the bits needed and the bits of the chain), chain primes above 61 bits.
+ * fhesi_ct_add_slots_dev: Ciphertext::operator+=(const ZZX&) unscaled (Ciphertext.cpp:147-156) with the constant given as slot values
+ *   vals_host [nv][nvals], nv = 1 (one constant for every ciphertext) or count, embedded on the device; p is the space's.  Equals
+ *   fhesi_ct_add_const_dev(fhesi_slots_embed(vals)) bit for bit. */
+int fhesi_plain_create_slots(fhesi_slots* s, const int64_t* vals_host /* [nw][nvals] */, int64_t nvals, int32_t only_usable, int64_t nw, fhesi_plain** out);
+int fhesi_plain_create_poly(fhesi_ctx* ctx, const int64_t* poly_host /* [nw][phi(m)] */, int64_t nw, fhesi_plain** out);
+int fhesi_plain_free(fhesi_plain* w);
+int fhesi_plain_info(const fhesi_plain* w, int64_t* nw, uint64_t* maxabs, uint64_t* p /* 0 for the polynomial form */);
+int fhesi_plain_sum_bits(int64_t m, int32_t logQ, uint64_t maxabs, int64_t terms, double* bits);
+int fhesi_ct_plain_sum_dev(fhesi_ctx* ctx, const fhesi_plain* w, int32_t logQ, const uint64_t* pool_dev /* [npool][2][phi(m)][nlimbs] */, int64_t npool,
+                           int32_t nlimbs, const int32_t* a_idx, const int32_t* b_idx, const int32_t* seg, int64_t ngroups,
+                           uint64_t* out_dev /* [ngroups][2][phi(m)][nlimbs] */);
+int fhesi_ct_add_slots_dev(fhesi_ctx* ctx, fhesi_slots* s, int32_t logQ, uint64_t* ct_dev, int32_t nparts, int32_t nlimbs, int64_t count,
+                           const int64_t* vals_host /* [nv][nvals] */, int64_t nvals, int32_t only_usable, int64_t nv /* 1 or count */);
 
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
