@@ -164,28 +164,16 @@ int launch_ntt32_fwd(fhesi_ctx* ctx, u32* d_rows, i64 count, int nslots, int a0)
   if (!count) return 0;
   const fhesi_aux32* x = ctx->aux32;
   const int S = x->S;
-  if (S >= 2) {      // head stages as a pass of their own, at most 65535 rows (a multiple of nslots) per launch
-    const i64 nr = count * nslots, step = (65535 / nslots) * (i64)nslots;
-    for (i64 r0 = 0; r0 < nr; r0 += step) {
-      const unsigned ny = (unsigned)std::min(step, nr - r0);
-      u32* rp = d_rows + (r0 << (A32_LOGN + S));
-      if (S == 2) ntt32_head2_kernel<<<dim3(16, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_ht);
-      else if (S == 3) ntt32_headS_kernel<3><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs);
-      else if (S == 4) ntt32_headS_kernel<4><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs);
-      else if (S == 5) ntt32_headS_kernel<5><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs);
-      else ntt32_headS_kernel<6><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs);
-    }
-  }
+  if (S >= 2) { if (!launch_ntt32_head_pass(ctx->stream, S, d_rows, count * nslots, nslots, a0, x->d_p, x->d_ht, x->d_hs)) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S); }
   else if (S) ntt32_head_kernel<<<dim3(16, (unsigned)(count * nslots)), 256, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->hd);
   if (S) HIP_TRY(hipGetLastError());
   if (count > 0x7fffffff || (nslots << S) > 65535) FHESI_FAIL("ntt32: too many rows per launch");
   const dim3 grid((unsigned)count, (unsigned)(nslots << S));
-#define A32_PLAIN_GO(SS) do { PROF_KERNEL(ctx, PROF_NTT_FWD, ntt32_fwd_kernel3<false, SS>); ntt32_fwd_kernel3<false, SS><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_fwd, Dig32Src{}, x->hd); } while (0)
-  if (S == 3) A32_PLAIN_GO(3); else if (S == 4) A32_PLAIN_GO(4); else if (S == 5) A32_PLAIN_GO(5); else if (S == 6) A32_PLAIN_GO(6);
-#undef A32_PLAIN_GO
-  else if (S == 2) { PROF_KERNEL(ctx, PROF_NTT_FWD, ntt32_fwd_kernel3<false, 2>); ntt32_fwd_kernel3<false, 2><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_fwd, Dig32Src{}, x->hd); }
-  else if (S) { PROF_KERNEL(ctx, PROF_NTT_FWD, ntt32_fwd_kernel3<false, 1>); ntt32_fwd_kernel3<false, 1><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_fwd, Dig32Src{}, x->hd); }
-  else { PROF_KERNEL(ctx, PROF_NTT_FWD, ntt32_fwd_kernel3<false, 0>); ntt32_fwd_kernel3<false, 0><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_fwd, Dig32Src{}, x->hd); }
+  if (!a32_with_S<0, 6>(S, [&](auto s) {
+    constexpr int SS = decltype(s)::value;
+    PROF_KERNEL(ctx, PROF_NTT_FWD, ntt32_fwd_kernel3<false, SS>);
+    ntt32_fwd_kernel3<false, SS><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_fwd, Dig32Src{}, x->hd);
+  })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -204,18 +192,7 @@ int launch_ntt32_inv(fhesi_ctx* ctx, u32* d_rows, i64 count, int nslots, int a0,
   HIP_TRY(hipGetLastError());
   if (S >= 2 && !tail) FHESI_FAIL("ntt32: rows of 2^16 and longer have no consumer that takes their tail stages");
   if (S && tail) {
-    if (S >= 2) {
-      const i64 nr = count * nslots, step = (65535 / nslots) * (i64)nslots;
-      for (i64 r0 = 0; r0 < nr; r0 += step) {
-        const unsigned ny = (unsigned)std::min(step, nr - r0);
-        u32* rp = d_rows + (r0 << (A32_LOGN + S));
-        if (S == 2) ntt32_tail2_kernel<<<dim3(16, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_ht);
-        else if (S == 3) ntt32_tailS_kernel<3><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs, mont ? 1 : 0);
-        else if (S == 4) ntt32_tailS_kernel<4><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs, mont ? 1 : 0);
-        else if (S == 5) ntt32_tailS_kernel<5><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs, mont ? 1 : 0);
-        else ntt32_tailS_kernel<6><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, nslots, a0, x->d_p, x->d_hs, mont ? 1 : 0);
-      }
-    }
+    if (S >= 2) { if (!launch_ntt32_tail_pass(ctx->stream, S, d_rows, count * nslots, nslots, a0, x->d_p, x->d_ht, x->d_hs, mont ? 1 : 0)) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S); }
     else ntt32_tail_kernel<<<dim3(16, (unsigned)(count * nslots)), 256, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->hd);
     HIP_TRY(hipGetLastError());
   }
@@ -247,36 +224,42 @@ int launch_ntt32_fwd_digits(fhesi_ctx* ctx, const u64* d_parts, int nl, int digi
     FHESI_TRY(ws_reserve(ctx, 11, (size_t)units * 4 * ((size_t)A32_N << S) * 4, &tmp));
     u32* d_plain = (u32*)tmp;
     const dim3 hg(A32_N / 256, (unsigned)units);
-#define A32_DH(SS) do { if (wm) dig32_headS_kernel<SS, true><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->d_hs); else dig32_headS_kernel<SS, false><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->d_hs); } while (0)
-    if (S == 3) A32_DH(3); else if (S == 4) A32_DH(4); else if (S == 5) A32_DH(5); else A32_DH(6);
-#undef A32_DH
+    if (!a32_with_S<3, 6>(S, [&](auto s) {
+      constexpr int SS = decltype(s)::value;
+      if (wm) dig32_headS_kernel<SS, true><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->d_hs);
+      else dig32_headS_kernel<SS, false><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->d_hs);
+    })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
     HIP_TRY(hipGetLastError());
     // the sub-transforms read those rows and store the tiled layout the dot product reads (ntt32_fwd_kernel3<DIGITS, S >= 3>: row source)
     Dig32Src rs = src;
     rs.parts = reinterpret_cast<const u64*>(d_plain);
     const i64 blocks3 = (units + 7) / 8 * 8 * (4 << S);
     if (blocks3 > 0x7fffffff) FHESI_FAIL("ntt32: too many workgroups per launch");
-#define A32_ROWS_GO(SS) do { PROF_KERNEL(ctx, PROF_NTT_FWD_DIGITS_MAIN, (ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false>)); \
-    ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false><<<(unsigned)blocks3, A32_T, 0, ctx->stream>>>(d_out, units, 4, 0, x->pr, x->d_fwd, rs, x->hd); } while (0)
-    if (S == 3) A32_ROWS_GO(3); else if (S == 4) A32_ROWS_GO(4); else if (S == 5) A32_ROWS_GO(5); else A32_ROWS_GO(6);
-#undef A32_ROWS_GO
+    if (!a32_with_S<3, 6>(S, [&](auto s) {
+      constexpr int SS = decltype(s)::value;
+      PROF_KERNEL(ctx, PROF_NTT_FWD_DIGITS_MAIN, (ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false>));
+      ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false><<<(unsigned)blocks3, A32_T, 0, ctx->stream>>>(d_out, units, 4, 0, x->pr, x->d_fwd, rs, x->hd);
+    })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
     HIP_TRY(hipGetLastError());
     return 0;
   }
   const int PS = 4 << S;
   const i64 blocks = (units + 7) / 8 * 8 * PS;      // units dealt round-robin to the 8 XCDs, PS workgroups (primes x sub-blocks) each
   if (blocks > 0x7fffffff) FHESI_FAIL("ntt32: too many workgroups per launch");
-#define A32_DIG_GO(SS, PP, WW) do { PROF_KERNEL(ctx, PROF_NTT_FWD_DIGITS_MAIN, (ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW>)); \
-    ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW><<<(unsigned)blocks, A32_T, 0, ctx->stream>>>(d_out, npolys * nd, 4, 0, x->pr, x->d_fwd, src, x->hd); } while (0)
-#define A32_DIG_W(SS, PP) do { if (wm) A32_DIG_GO(SS, PP, true); else A32_DIG_GO(SS, PP, false); } while (0)
   if (S == 2 && !ctx->lin_q) FHESI_FAIL("ntt32: digit rows of 2^16 exist for the padded linear-convolution rings only");
-  if (S == 2) A32_DIG_W(2, true);
-  else if (S && ctx->lin_q) A32_DIG_W(1, true);
-  else if (S) A32_DIG_W(1, false);
-  else if (ctx->phim < A32_N) A32_DIG_W(0, true);
-  else A32_DIG_W(0, false);
-#undef A32_DIG_W
-#undef A32_DIG_GO
+  const bool pad = S ? ctx->lin_q != 0 : ctx->phim < A32_N;      // zero-padded rows: the linear-convolution rings, and rings shorter than a row of 2^14
+  if (!a32_with_S<0, 2>(S, [&](auto s) {
+    constexpr int SS = decltype(s)::value;
+    auto go = [&](auto pp, auto ww) {
+      constexpr bool PP = decltype(pp)::value, WW = decltype(ww)::value;
+      PROF_KERNEL(ctx, PROF_NTT_FWD_DIGITS_MAIN, (ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW>));
+      ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW><<<(unsigned)blocks, A32_T, 0, ctx->stream>>>(d_out, npolys * nd, 4, 0, x->pr, x->d_fwd, src, x->hd);
+    };
+    auto go_w = [&](auto pp) { if (wm) go(pp, std::true_type{}); else go(pp, std::false_type{}); };
+    if constexpr (SS == 2) go_w(std::true_type{});      // (rows of 2^16 are always padded: no other form is built)
+    else if (pad) go_w(std::true_type{});
+    else go_w(std::false_type{});
+  })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -378,167 +361,182 @@ __global__ void __launch_bounds__(256) ks32_retile_kernel(const u32* __restrict_
 // and the ragged end of one overlap the arithmetic of the other (with one 135 KB workgroup per CU the VALU sat idle 37 % of the time).
 // (The whole-slice form of round 2 -- one 135 KB workgroup per CU -- and the wave-group split for few limbs left the source in round 6: neither
 // is reached since dot32_kernel4 took the matrices with 7 or 8 limbs; profiles/HISTORY.md.)
-template <int CT, int NW>
-__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
-dot32_kernel2(const u32* __restrict__ k32, const u32* __restrict__ dig, int ncol, int NLB, i64 count,
-                                                         u32* __restrict__ out, Aux32Primes pr, int ntiles, int nsl8, int lognsl /* log2 of the 64-element slices per row */, int sub_lg /* log2 of the ciphertexts per sub-chunk of the tiled digit rows */) {
-  extern __shared__ __attribute__((aligned(16))) u32 dl32[];       // [ncol][CT][64 or 32 elements]
-  constexpr int LG = 5;
-  const u32 lane = threadIdx.x & 63;
-  const u32 ln = lane & 31;                        // element within the tile
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // grid: x = s_lo + 8 (tile + ntiles hf), y = s_hi, z = prime -- the same linear order as one flat index (workgroups 8 apart share an
-  // XCD), without the three integer divisions a flat index costs every wave (the SALU cannot divide: ~25 VALU instructions each)
+
+// ---- what the digit-tile kernels share (dot32_kernel2, dot32_kernel2p; the digit base and the output step also serve dot32_kernel4)
+// grid: x = s_lo + 8 (tile + ntiles hf), y = s_hi, z = prime -- the same linear order as one flat index (workgroups 8 apart share an
+// XCD), without the three integer divisions a flat index costs every wave (the SALU cannot divide: ~25 VALU instructions each)
+struct Dot32Place { u32 tile, hf; i64 slice, soff; int ct0, a; };       // tile of CT ciphertexts, half of the slice, 64-element slice and its first element, first ciphertext, prime
+template <int CT>
+__device__ __forceinline__ Dot32Place dot32_place(int ntiles) {
   const u32 s_lo = blockIdx.x & 7;
   u32 tile = blockIdx.x >> 3, hf = 0;
   if (tile >= (u32)ntiles) { hf = 1; tile -= (u32)ntiles; }
   const u32 s_hi = blockIdx.y;
-  const int a = (int)blockIdx.z;
-  const i64 slice = (i64)(s_hi * 8 + s_lo), soff = slice * 64 + hf * 32;
-  const int ct0 = (int)tile * CT;
-  const u32 p = pr.p[a], twop = 2 * p;
-#define DL32(k, c) (((((k) * CT) + (c)) << LG) + ln)
-  {
-    // One load instruction moves 1 KiB: lane i takes the 16 bytes = elements 4 (i & 15) .. + 3 of column k0 + (i >> 4) of one ciphertext
-    // (four consecutive columns of a ciphertext are contiguous in the tiled digit rows), reduces them and writes them with one
-    // conflict-free 16-byte LDS write; the arithmetic reads the CT ciphertexts of a column with CT 4-byte reads.
-    typedef u32 v4u __attribute__((ext_vector_type(4)));
-    const int sub = ct0 >> sub_lg, sub_ct = 1 << sub_lg, ct_in = ct0 & (sub_ct - 1);
-    const i64 rest = count - ((i64)sub << sub_lg), cnt_s = rest < sub_ct ? rest : (i64)sub_ct;
-    const u32* dbase = dig + ((i64)sub << sub_lg) * ncol * (((i64)4 << lognsl) * 64) + ((((i64)a << lognsl) + slice) * (cnt_s * ncol) + (i64)ct_in * ncol) * 64;
-    // (8 lanes per 128-byte half row; 16 consecutive lanes take the same column of TWO ciphertexts, which are adjacent in LDS.)
-    // Work split without divisions: NW / NCG waves share a group of ciphertexts and take its column quads round robin.
-    constexpr int TB = 6, CG = 2, NCG = CT / CG, WPG = NW / NCG;
-    static_assert(NW % NCG == 0, "waves per ciphertext group");
-    const int nq = (ncol + 3) >> 2;
-    const int cg = w % NCG, q0 = w / NCG;
-    const u32 e0 = 4 * (lane & 7), dk = lane >> 4, dc = (lane >> 3) & 1;
-    const u32 goff = hf * 32 + e0;
-    const int c = cg * CG + (int)dc;
-    const bool cok = ct0 + c < count;
-    for (int qb = q0; qb < nq; qb += WPG * TB) {
-      v4u v[TB];
+  const i64 slice = (i64)(s_hi * 8 + s_lo);
+  return Dot32Place{tile, hf, slice, slice * 64 + hf * 32, (int)tile * CT, (int)blockIdx.z};
+}
+// the digit columns of ciphertext ct in the tiled digit rows [sub-chunk][prime][slice][ciphertext * ncol + column][64] (launch_ntt32_fwd_digits)
+template <class T>
+__device__ __forceinline__ const u32* dot32_digit_base(const u32* dig, int ncol, i64 count, int lognsl, int sub_lg, int a, i64 slice, T ct) {
+  const T sub = ct >> sub_lg, sub_ct = (T)1 << sub_lg, ct_in = ct & (sub_ct - 1);
+  const i64 rest = count - ((i64)sub << sub_lg), cnt_s = rest < sub_ct ? rest : (i64)sub_ct;      // ciphertexts in this sub-chunk (the last one may be short)
+  return dig + ((i64)sub << sub_lg) * ncol * (((i64)4 << lognsl) * 64) + ((((i64)a << lognsl) + slice) * (cnt_s * ncol) + (i64)ct_in * ncol) * 64;
+}
+#define DL32(k, c) (((((k) * CT) + (c)) << 5) + ln)      // the tile: [column][CT][32 elements]
+// Columns kbeg .. kbeg + nc - 1 of the tile's CT ciphertexts (dbase: the first of them) into LDS, reduced below p.
+// One load instruction moves 1 KiB: lane i takes the 16 bytes = elements 4 (i & 15) .. + 3 of column k0 + (i >> 4) of one ciphertext
+// (four consecutive columns of a ciphertext are contiguous in the tiled digit rows), reduces them and writes them with one
+// conflict-free 16-byte LDS write; the arithmetic reads the CT ciphertexts of a column with CT 4-byte reads.
+// (8 lanes per 128-byte half row; 16 consecutive lanes take the same column of TWO ciphertexts, which are adjacent in LDS.)
+// Work split without divisions: NW / NCG waves share a group of ciphertexts and take its column quads round robin.
+template <int CT, int NW>
+__device__ __forceinline__ void dot32_tile_load(u32* dl32, const u32* dbase, int ncol, int kbeg, int nc, u32 lane, int w, u32 hf, int ct0, i64 count, u32 p) {
+  typedef u32 v4u __attribute__((ext_vector_type(4)));
+  constexpr int TB = 6, CG = 2, NCG = CT / CG, WPG = NW / NCG;
+  static_assert(NW % NCG == 0, "waves per ciphertext group");
+  const u32 twop = 2 * p;
+  const int nq = (nc + 3) >> 2;
+  const int cg = w % NCG, q0 = w / NCG;
+  const u32 e0 = 4 * (lane & 7), dk = lane >> 4, dc = (lane >> 3) & 1;
+  const u32 goff = hf * 32 + e0;
+  const int c = cg * CG + (int)dc;
+  const bool cok = ct0 + c < count;
+  for (int qb = q0; qb < nq; qb += WPG * TB) {
+    v4u v[TB];
 #pragma unroll
-      for (int u = 0; u < TB; ++u) {
-        const int q = qb + u * WPG, k = q * 4 + (int)dk;
-        v[u] = (q < nq && k < ncol && cok) ? __builtin_nontemporal_load(reinterpret_cast<const v4u*>(dbase + (((i64)c * ncol + k) << 6) + goff)) : v4u{0, 0, 0, 0};
-      }
+    for (int u = 0; u < TB; ++u) {
+      const int q = qb + u * WPG, k = q * 4 + (int)dk;
+      v[u] = (q < nq && k < nc && cok) ? __builtin_nontemporal_load(reinterpret_cast<const v4u*>(dbase + (((i64)c * ncol + kbeg + k) << 6) + goff)) : v4u{0, 0, 0, 0};
+    }
 #pragma unroll
-      for (int u = 0; u < TB; ++u) {
-        const int q = qb + u * WPG, k = q * 4 + (int)dk;
-        if (q < nq && k < ncol) {
-          v4u y = v[u];
+    for (int u = 0; u < TB; ++u) {
+      const int q = qb + u * WPG, k = q * 4 + (int)dk;
+      if (q < nq && k < nc) {
+        v4u y = v[u];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { u32 t = y[j]; t = t >= twop ? t - twop : t; y[j] = t >= p ? t - p : t; }
-          *reinterpret_cast<v4u*>(&dl32[((k * CT + c) << LG) + e0]) = y;
-        }
+        for (int j = 0; j < 4; ++j) { u32 t = y[j]; t = t >= twop ? t - twop : t; y[j] = t >= p ? t - p : t; }
+        *reinterpret_cast<v4u*>(&dl32[((k * CT + c) << 5) + e0]) = y;
       }
     }
   }
+}
+// One limb's sums over nc columns of the tile: tot[r][c] + 2^48 th[r][c] += sum_k kp_r[k] * tile[k][c]  (kp0 / kp1: the limb's two key rows at the
+// tile's first column, 64 words per column; ln: the lane's element of the tile).  Leaves every total below 2^48, so a further call -- the next
+// part of dot32_kernel2p -- starts like the first.
+template <int CT>
+__device__ __forceinline__ void dot32_sweep(const u32* dl32, u32 ln, const u32* kp0, const u32* kp1, int nc, u32 tile, u64 (&tot)[2][CT], u32 (&th)[2][CT]) {
+  auto fold = [&]() {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < CT; ++c) { th[r][c] += (u32)(tot[r][c] >> 48); tot[r][c] &= 0x0000ffffffffffffull; }
+  };
+  // Key words are fetched one 4-column chunk ahead into two register sets used alternately (no copies: with a copy at the end of
+  // the loop body the compiler waits for the fetch at the START of the body and the L2 latency is exposed once per chunk).
+  constexpr int CH = 4;
+  const int nfull = nc & ~(CH - 1), n2 = nc & ~(2 * CH - 1);
+  u32 xa[2][CH], xb[2][CH];
+  auto loadc = [&](u32 (&x)[2][CH], int k0) {
+#pragma unroll
+    for (int u = 0; u < CH; ++u) { x[0][u] = kp0[(k0 + u) << 6]; x[1][u] = kp1[(k0 + u) << 6]; }
+  };
+  // The 8-column pairs are taken in an order ROTATED by the tile number.  The workgroups of the 8 ciphertext tiles of a (slice, prime)
+  // run side by side on one XCD and stream the same key block; in the same order they all miss on the same lines at the same moment and
+  // every chunk arrives at HBM latency.  Rotated, each of them is the first reader of its own eighth: the whole block is requested in
+  // the first microsecond and everything after that is an L2 hit.
+  const int npair = n2 / (2 * CH);
+  int pst = npair > 1 ? (int)(tile & (0xffffffffu >> __builtin_clz((u32)npair - 1))) : 0;     // (tile mod npair without a division when npair is a power of two; any start is correct)
+  if (pst >= npair) pst -= npair;
+  auto pk = [&](int i) { int q = i + pst; if (q >= npair) q -= npair; return q * 2 * CH; };
+  if (npair) loadc(xa, pk(0)); else if (nfull) loadc(xa, 0);
+  for (int i = 0; i < npair; ++i) {
+    const int kb = pk(i);
+    loadc(xb, kb + CH);
+    // the digit words of column u + 1 are read from LDS while column u is multiplied, across the two key chunks (two or three columns
+    // ahead measured the same; left to itself the compiler reads a column right before its multiply-adds in the second chunk).  The
+    // next chunk of keys is fetched unconditionally -- after the last pair one unused chunk -- because a conditional fetch costs eight
+    // register moves per round and 16 registers (-2.5 % together with the prefetch: -4 %).
+    u32 d[2][CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) d[0][c] = dl32[DL32(kb, c)];
+#pragma unroll
+    for (int u = 0; u < 2 * CH; ++u) {
+      if (u == CH) loadc(xa, i + 1 < npair ? pk(i + 1) : (n2 < nfull ? n2 : 0));
+      if (u + 1 < 2 * CH) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) d[(u + 1) & 1][c] = dl32[DL32(kb + u + 1, c)];
+      }
+      const u32 x0 = u < CH ? xa[0][u & (CH - 1)] : xb[0][u & (CH - 1)], x1 = u < CH ? xa[1][u & (CH - 1)] : xb[1][u & (CH - 1)];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) { tot[0][c] += (u64)x0 * d[u & 1][c]; tot[1][c] += (u64)x1 * d[u & 1][c]; }
+    }
+    if (i & 1) fold();                               // 16 columns since the last fold
+  }
+  if (nfull & CH) {                                  // the 4-column chunk: its key words are in xa already
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+#pragma unroll
+      for (int c = 0; c < CT; ++c) { const u32 d = dl32[DL32(n2 + u, c)]; tot[0][c] += (u64)xa[0][u] * d; tot[1][c] += (u64)xa[1][u] * d; }
+    }
+  }
+  if ((nfull & (3 * CH)) != 0) fold();               // up to 12 columns pending, up to 3 more follow: fold here so that the tail starts below 2^48
+  for (int k = nfull; k < nc; ++k) {                 // at most 3 columns
+    const u32 x0 = kp0[k << 6], x1 = kp1[k << 6];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) { const u32 d = dl32[DL32(k, c)]; tot[0][c] += (u64)x0 * d; tot[1][c] += (u64)x1 * d; }
+  }
+  fold();                                            // at most 15 columns since the last one; leaves every total below 2^48
+}
+#undef DL32
+// v 2^-32 mod p, below p, by one Montgomery step (v < 2^32 p; mont = -p^-1 mod 2^32): m = v mont mod 2^32, (v + m p) / 2^32 < 2p.
+// The factor 2^-32 is undone by the inverse transform's final constant (ntt32_inv_kernel3, MONT) or by its tail pass.
+__device__ __forceinline__ u32 dot32_mont_out(u64 v, u32 mont, u32 p) {
+  const u32 mq = (u32)v * mont;
+  const u32 o = (u32)((v + (u64)mq * p) >> 32);
+  return min(o, o - p);                              // o < 2p: o - p wraps to a large value exactly when o < p
+}
+// limb l's 2 CT outputs of a tile: (th 2^48 + tot) 2^-32 mod p with v = tot + th (2^48 mod p) < 2^54 into out [ciphertext][r][limb][prime][row]
+template <int CT>
+__device__ __forceinline__ void dot32_tile_out(u32* out, const Dot32Place& g, int l, int NLB, i64 count, int lognsl, u32 ln, const u64 (&tot)[2][CT], const u32 (&th)[2][CT], u32 r48, u32 mont, u32 p) {
+  u32* obase = out + ((((i64)l * 4 + g.a) << (lognsl + 6)) + g.soff) + ln;
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int c = 0; c < CT; ++c)
+      if (g.ct0 + c < count)
+        __builtin_nontemporal_store(dot32_mont_out(tot[r][c] + (u64)th[r][c] * r48, mont, p), obase + (((i64)((g.ct0 + c) * 2 + r) * NLB * 4) << (lognsl + 6)));
+}
+
+template <int CT, int NW>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4, 4)))
+dot32_kernel2(const u32* __restrict__ k32, const u32* __restrict__ dig, int ncol, int NLB, i64 count,
+                                                         u32* __restrict__ out, Aux32Primes pr, int ntiles, int nsl8, int lognsl /* log2 of the 64-element slices per row */, int sub_lg /* log2 of the ciphertexts per sub-chunk of the tiled digit rows */) {
+  extern __shared__ __attribute__((aligned(16))) u32 dl32[];       // [ncol][CT][32 elements]
+  const u32 lane = threadIdx.x & 63;
+  const u32 ln = lane & 31;                        // element within the tile
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const Dot32Place g = dot32_place<CT>(ntiles);
+  const u32 p = pr.p[g.a];
+  dot32_tile_load<CT, NW>(dl32, dot32_digit_base(dig, ncol, count, lognsl, sub_lg, g.a, g.slice, g.ct0), ncol, 0, ncol, lane, w, g.hf, g.ct0, count, p);
   __syncthreads();
-  const u32 r48 = (u32)pr.r48[a];                 // 2^48 mod p: 30 bits, one multiply-add
-  const u32 mont = pr.mont[a];
-  constexpr int CW = CT, NWG = NW;      // ciphertexts per wave, waves per group
-  const int wl = w % NWG, c0 = (w / NWG) * CW;            // the wave's place in its group; first ciphertext of the group
-  for (int lw = wl; lw * 2 < NLB; lw += NWG) {
-    const int lraw = 2 * lw + (int)(lane >> 5);          // the upper lanes of the last wave may have no limb
-    const bool lok = lraw < NLB;
+  const u32 r48 = (u32)pr.r48[g.a];               // 2^48 mod p: 30 bits, one multiply-add
+  const u32 mont = pr.mont[g.a];
+  for (int lw = w; lw * 2 < NLB; lw += NW) {
+    const int l = 2 * lw + (int)(lane >> 5);
     // the half wave without a limb (15 limbs on 16 half waves) leaves the loop: its lanes are masked off for the multiply-adds instead of
     // repeating the neighbour's -- same issue slots, but the step runs at the power limit and idle lanes draw less
-    if (!lok) continue;
-    const int l = lok ? lraw : NLB - 1;
-    const u32* kp0 = k32 + (((((((i64)a * NLB + l) << lognsl) + slice) * 2) * ncol) << 6) + (hf * 32 + ln);      // row r = 0; row 1 follows after ncol slices
+    if (l >= NLB) continue;
+    const u32* kp0 = k32 + (((((((i64)g.a * NLB + l) << lognsl) + g.slice) * 2) * ncol) << 6) + (g.hf * 32 + ln);      // row r = 0; row 1 follows after ncol slices
     const u32* kp1 = kp0 + ((i64)ncol << 6);
-    u64 tot[2][CW];
-    u32 th[2][CW];
+    u64 tot[2][CT];
+    u32 th[2][CT];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-      for (int c = 0; c < CW; ++c) { tot[r][c] = 0; th[r][c] = 0; }
-    auto fold = [&]() {
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < CW; ++c) { th[r][c] += (u32)(tot[r][c] >> 48); tot[r][c] &= 0x0000ffffffffffffull; }
-    };
-    // Key words are fetched one 4-column chunk ahead into two register sets used alternately (no copies: with a copy at the end of
-    // the loop body the compiler waits for the fetch at the START of the body and the L2 latency is exposed once per chunk).
-    constexpr int CH = 4;
-    const int nfull = ncol & ~(CH - 1), n2 = ncol & ~(2 * CH - 1);
-    u32 xa[2][CH], xb[2][CH];
-    auto loadc = [&](u32 (&x)[2][CH], int k0) {
-#pragma unroll
-      for (int u = 0; u < CH; ++u) { x[0][u] = kp0[(k0 + u) << 6]; x[1][u] = kp1[(k0 + u) << 6]; }
-    };
-    auto macc = [&](const u32 (&x)[2][CH], int k0) {
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        u32 d[CW];
-#pragma unroll
-        for (int c = 0; c < CW; ++c) d[c] = dl32[DL32(k0 + u, c0 + c)];
-#pragma unroll
-        for (int c = 0; c < CW; ++c) { tot[0][c] += (u64)x[0][u] * d[c]; tot[1][c] += (u64)x[1][u] * d[c]; }
-      }
-    };
-    // The 8-column pairs are taken in an order ROTATED by the tile number.  The workgroups of the 8 ciphertext tiles of a (slice, prime)
-    // run side by side on one XCD and stream the same key block; in the same order they all miss on the same lines at the same moment and
-    // every chunk arrives at HBM latency.  Rotated, each of them is the first reader of its own eighth: the whole block is requested in
-    // the first microsecond and everything after that is an L2 hit.
-    const int npair = n2 / (2 * CH);
-    int pst = npair > 1 ? (int)(tile & (0xffffffffu >> __builtin_clz((u32)npair - 1))) : 0;     // (tile mod npair without a division when npair is a power of two; any start is correct)
-    if (pst >= npair) pst -= npair;
-    auto pk = [&](int i) { int q = i + pst; if (q >= npair) q -= npair; return q * 2 * CH; };
-    if (npair) loadc(xa, pk(0)); else if (nfull) loadc(xa, 0);
-    for (int i = 0; i < npair; ++i) {
-      const int kb = pk(i);
-      loadc(xb, kb + CH);
-      // the digit words of column u + 1 are read from LDS while column u is multiplied, across the two key chunks (two or three columns
-      // ahead measured the same; left to itself the compiler reads a column right before its multiply-adds in the second chunk).  The
-      // next chunk of keys is fetched unconditionally -- after the last pair one unused chunk -- because a conditional fetch costs eight
-      // register moves per round and 16 registers (-2.5 % together with the prefetch: -4 %).
-      u32 d[2][CW];
-#pragma unroll
-      for (int c = 0; c < CW; ++c) d[0][c] = dl32[DL32(kb, c0 + c)];
-#pragma unroll
-      for (int u = 0; u < 2 * CH; ++u) {
-        if (u == CH) loadc(xa, i + 1 < npair ? pk(i + 1) : (n2 < nfull ? n2 : 0));
-        if (u + 1 < 2 * CH) {
-#pragma unroll
-          for (int c = 0; c < CW; ++c) d[(u + 1) & 1][c] = dl32[DL32(kb + u + 1, c0 + c)];
-        }
-        const u32 x0 = u < CH ? xa[0][u & (CH - 1)] : xb[0][u & (CH - 1)], x1 = u < CH ? xa[1][u & (CH - 1)] : xb[1][u & (CH - 1)];
-#pragma unroll
-        for (int c = 0; c < CW; ++c) { tot[0][c] += (u64)x0 * d[u & 1][c]; tot[1][c] += (u64)x1 * d[u & 1][c]; }
-      }
-      if (i & 1) fold();                             // 16 columns since the last fold
-    }
-    const int kb = n2;
-    if (nfull & CH) { macc(xa, kb); }
-    if ((nfull & (3 * CH)) != 0) fold();             // up to 12 columns pending, up to 3 more follow: fold here so that the tail starts below 2^48
-    for (int k = nfull; k < ncol; ++k) {             // at most 3 columns
-      const u32 x0 = kp0[k << 6], x1 = kp1[k << 6];
-#pragma unroll
-      for (int c = 0; c < CW; ++c) { const u32 d = dl32[DL32(k, c0 + c)]; tot[0][c] += (u64)x0 * d; tot[1][c] += (u64)x1 * d; }
-    }
-    fold();                                          // at most 15 columns since the last one; leaves every total below 2^48
-    u32* obase = out + ((((i64)l * 4 + a) << (lognsl + 6)) + soff) + ln;
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        if (ct0 + c0 + c < count) {
-          // (th 2^48 + tot) 2^-32 mod p by one Montgomery step: v = tot + th (2^48 mod p) < 2^54, m = v (-p^-1) mod 2^32,
-          // (v + m p) / 2^32 < p + 2^22.  The factor 2^-32 is undone by the inverse transform's final constant (ntt32_inv_kernel, mont).
-          const u64 v = tot[r][c] + (u64)th[r][c] * r48;
-          const u32 mq = (u32)v * mont;
-          u32 o = (u32)((v + (u64)mq * p) >> 32);
-          o = min(o, o - p);                          // o < 2p: o - p wraps to a large value exactly when o < p
-          u32* q = obase + (((i64)((ct0 + c0 + c) * 2 + r) * NLB * 4) << (lognsl + 6));
-          if (lok) __builtin_nontemporal_store(o, q);
-        }
-      }
+      for (int c = 0; c < CT; ++c) { tot[r][c] = 0; th[r][c] = 0; }
+    dot32_sweep<CT>(dl32, ln, kp0, kp1, ncol, g.tile, tot, th);
+    dot32_tile_out<CT>(out, g, l, NLB, count, lognsl, ln, tot, th, r48, mont, p);
   }
-#undef DL32
 }
 
 // ---- dot32_kernel2 for MORE COLUMNS THAN ONE LDS TILE HOLDS (the stress ring: 129 columns x 8 ciphertexts x 128 bytes = 132 KB, where two
@@ -552,139 +550,34 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4,
 dot32_kernel2p(const u32* __restrict__ k32, const u32* __restrict__ dig, int ncol, int NLB, i64 count, u32* __restrict__ out, Aux32Primes pr, int ntiles, int nsl8,
                int lognsl, int sub_lg, int ncp /* columns per part: a multiple of 8 */) {
   extern __shared__ __attribute__((aligned(16))) u32 dl32[];       // [ncp][CT][32 elements]
-  constexpr int LG = 5;
   const u32 lane = threadIdx.x & 63, ln = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const u32 s_lo = blockIdx.x & 7;
-  u32 tile = blockIdx.x >> 3, hf = 0;
-  if (tile >= (u32)ntiles) { hf = 1; tile -= (u32)ntiles; }
-  const u32 s_hi = blockIdx.y;
-  const int a = (int)blockIdx.z;
-  const i64 slice = (i64)(s_hi * 8 + s_lo), soff = slice * 64 + hf * 32;
-  const int ct0 = (int)tile * CT;
-  const u32 p = pr.p[a], twop = 2 * p;
-#define DL32(k, c) (((((k) * CT) + (c)) << LG) + ln)
-  typedef u32 v4u __attribute__((ext_vector_type(4)));
-  const int sub = ct0 >> sub_lg, sub_ct = 1 << sub_lg, ct_in = ct0 & (sub_ct - 1);
-  const i64 rest = count - ((i64)sub << sub_lg), cnt_s = rest < sub_ct ? rest : (i64)sub_ct;
-  const u32* dbase = dig + ((i64)sub << sub_lg) * ncol * (((i64)4 << lognsl) * 64) + ((((i64)a << lognsl) + slice) * (cnt_s * ncol) + (i64)ct_in * ncol) * 64;
-  constexpr int TB = 6, CG = 2, NCG = CT / CG, WPG = NW / NCG;
-  static_assert(NW % NCG == 0, "waves per ciphertext group");
-  const int cg = w % NCG, q0 = w / NCG;
-  const u32 e0 = 4 * (lane & 7), dk = lane >> 4, dc = (lane >> 3) & 1;
-  const u32 goff = hf * 32 + e0;
-  const int cl = cg * CG + (int)dc;
-  const bool cok = ct0 + cl < count;
+  const Dot32Place g = dot32_place<CT>(ntiles);
+  const u32 p = pr.p[g.a];
+  const u32* dbase = dot32_digit_base(dig, ncol, count, lognsl, sub_lg, g.a, g.slice, g.ct0);
   // the wave's limbs: lanes 0..31 limb 2w, lanes 32..63 limb 2w + 1 (a half wave without a limb only helps with the tile loads)
   const int lraw = 2 * w + (int)(lane >> 5);
   const bool lok = lraw < NLB;
   const int l = lok ? lraw : NLB - 1;
-  const u32* kpa = k32 + (((((((i64)a * NLB + l) << lognsl) + slice) * 2) * ncol) << 6) + hf * 32 + ln;
-  const u32 r48 = (u32)pr.r48[a], mont = pr.mont[a];
-  constexpr int CW = CT;
-  u64 tot[2][CW];
-  u32 th[2][CW];
+  const u32* kpa = k32 + (((((((i64)g.a * NLB + l) << lognsl) + g.slice) * 2) * ncol) << 6) + g.hf * 32 + ln;
+  const u32 r48 = (u32)pr.r48[g.a], mont = pr.mont[g.a];
+  u64 tot[2][CT];
+  u32 th[2][CT];
 #pragma unroll
   for (int r = 0; r < 2; ++r)
 #pragma unroll
-    for (int c = 0; c < CW; ++c) { tot[r][c] = 0; th[r][c] = 0; }
-  auto fold = [&]() {
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < CW; ++c) { th[r][c] += (u32)(tot[r][c] >> 48); tot[r][c] &= 0x0000ffffffffffffull; }
-  };
+    for (int c = 0; c < CT; ++c) { tot[r][c] = 0; th[r][c] = 0; }
   for (int part = 0; part < NH; ++part) {
     const int kbeg = part * ncp, nc = (ncol - kbeg < ncp ? ncol - kbeg : ncp);
     if (part) __syncthreads();                       // every wave is done with the previous part's tile
-    {
-      const int nq = (nc + 3) >> 2;
-      for (int qb = q0; qb < nq; qb += WPG * TB) {
-        v4u v[TB];
-#pragma unroll
-        for (int u = 0; u < TB; ++u) {
-          const int q = qb + u * WPG, k = q * 4 + (int)dk;
-          v[u] = (q < nq && k < nc && cok) ? __builtin_nontemporal_load(reinterpret_cast<const v4u*>(dbase + (((i64)cl * ncol + kbeg + k) << 6) + goff)) : v4u{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int u = 0; u < TB; ++u) {
-          const int q = qb + u * WPG, k = q * 4 + (int)dk;
-          if (q < nq && k < nc) {
-            v4u y = v[u];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { u32 t = y[j]; t = t >= twop ? t - twop : t; y[j] = t >= p ? t - p : t; }
-            *reinterpret_cast<v4u*>(&dl32[((k * CT + cl) << LG) + e0]) = y;
-          }
-        }
-      }
-    }
+    dot32_tile_load<CT, NW>(dl32, dbase, ncol, kbeg, nc, lane, w, g.hf, g.ct0, count, p);
     __syncthreads();
     if (lok) {
       const u32* kp0 = kpa + ((i64)kbeg << 6);
-      const u32* kp1 = kp0 + ((i64)ncol << 6);
-      constexpr int CH = 4;
-      const int nfull = nc & ~(CH - 1), n2 = nc & ~(2 * CH - 1);
-      u32 xa[2][CH], xb[2][CH];
-      auto loadc = [&](u32 (&x)[2][CH], int k0) {
-#pragma unroll
-        for (int u = 0; u < CH; ++u) { x[0][u] = kp0[(k0 + u) << 6]; x[1][u] = kp1[(k0 + u) << 6]; }
-      };
-      const int npair = n2 / (2 * CH);
-      int pst = npair > 1 ? (int)(tile & (0xffffffffu >> __builtin_clz((u32)npair - 1))) : 0;
-      if (pst >= npair) pst -= npair;
-      auto pk = [&](int i) { int q = i + pst; if (q >= npair) q -= npair; return q * 2 * CH; };
-      if (npair) loadc(xa, pk(0)); else if (nfull) loadc(xa, 0);
-      for (int i = 0; i < npair; ++i) {
-        const int kb = pk(i);
-        loadc(xb, kb + CH);
-        u32 d[2][CW];
-#pragma unroll
-        for (int c = 0; c < CW; ++c) d[0][c] = dl32[DL32(kb, c)];
-#pragma unroll
-        for (int u = 0; u < 2 * CH; ++u) {
-          if (u == CH) loadc(xa, i + 1 < npair ? pk(i + 1) : (n2 < nfull ? n2 : 0));
-          if (u + 1 < 2 * CH) {
-#pragma unroll
-            for (int c = 0; c < CW; ++c) d[(u + 1) & 1][c] = dl32[DL32(kb + u + 1, c)];
-          }
-          const u32 x0 = u < CH ? xa[0][u & (CH - 1)] : xb[0][u & (CH - 1)], x1 = u < CH ? xa[1][u & (CH - 1)] : xb[1][u & (CH - 1)];
-#pragma unroll
-          for (int c = 0; c < CW; ++c) { tot[0][c] += (u64)x0 * d[u & 1][c]; tot[1][c] += (u64)x1 * d[u & 1][c]; }
-        }
-        if (i & 1) fold();                           // 16 columns since the last fold
-      }
-      if (nfull & CH) {
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-#pragma unroll
-          for (int c = 0; c < CW; ++c) { const u32 d = dl32[DL32(n2 + u, c)]; tot[0][c] += (u64)xa[0][u] * d; tot[1][c] += (u64)xa[1][u] * d; }
-        }
-      }
-      if ((nfull & (3 * CH)) != 0) fold();
-      for (int k = nfull; k < nc; ++k) {             // at most 3 columns
-        const u32 x0 = kp0[k << 6], x1 = kp1[k << 6];
-#pragma unroll
-        for (int c = 0; c < CW; ++c) { const u32 d = dl32[DL32(k, c)]; tot[0][c] += (u64)x0 * d; tot[1][c] += (u64)x1 * d; }
-      }
-      fold();                                        // every total below 2^48 again: the next part (or the epilogue) starts clean
+      dot32_sweep<CT>(dl32, ln, kp0, kp0 + ((i64)ncol << 6), nc, g.tile, tot, th);
     }
   }
-  if (lok) {
-    u32* obase = out + ((((i64)l * 4 + a) << (lognsl + 6)) + soff) + ln;
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < CW; ++c) {
-        if (ct0 + c < count) {
-          const u64 v = tot[r][c] + (u64)th[r][c] * r48;          // one Montgomery step, as in dot32_kernel2
-          const u32 mq = (u32)v * mont;
-          u32 o = (u32)((v + (u64)mq * p) >> 32);
-          o = min(o, o - p);
-          __builtin_nontemporal_store(o, obase + (((i64)((ct0 + c) * 2 + r) * NLB * 4) << (lognsl + 6)));
-        }
-      }
-  }
-#undef DL32
+  if (lok) dot32_tile_out<CT>(out, g, l, NLB, count, lognsl, ln, tot, th, r48, mont, p);
 }
 
 // ---- dot32_kernel4: the KEY words in LDS, the DIGIT words straight from memory into registers (round 5).
@@ -734,17 +627,14 @@ dot32_kernel4(const u32* __restrict__ k32, const u32* __restrict__ dig, int ncol
   const u32 r32 = 0u - 4u * p;                                    // 2^32 mod p for p in (2^32 / 5, 2^30): below 2^28 for every prime the launcher admits
   const int osel = w % NSP, o_base = osel * NO;                     // this wave's block of outputs
   const i64 ct0 = (i64)g * (NW / NSP * CW) + (i64)(w / NSP) * CW;
-  // the CW digit streams of this wave: scalar bases (the tiled digit rows [sub-chunk][prime][slice][ciphertext * ncol + column][64])
+  // the CW digit streams of this wave: scalar bases (dot32_digit_base)
   const u32* dbase[CW];
   bool live[CW];
 #pragma unroll
   for (int c = 0; c < CW; ++c) {
     const i64 ct = ct0 + c;
     live[c] = ct < count;
-    const i64 cc = live[c] ? ct : count - 1;                      // (a wave past the end repeats the last ciphertext's loads and stores nothing)
-    const i64 sub = cc >> sub_lg, ct_in = cc & (((i64)1 << sub_lg) - 1);
-    const i64 rest = count - (sub << sub_lg), cnt_s = rest < ((i64)1 << sub_lg) ? rest : ((i64)1 << sub_lg);
-    dbase[c] = dig + (sub << sub_lg) * ncol * (((i64)4 << lognsl) * 64) + ((((i64)a << lognsl) + slice) * (cnt_s * ncol) + ct_in * ncol) * 64;
+    dbase[c] = dot32_digit_base(dig, ncol, count, lognsl, sub_lg, a, slice, live[c] ? ct : count - 1);      // (a wave past the end repeats the last ciphertext's loads and stores nothing)
   }
   // key rows k32 [a][l][slice][r][column][64]: this wave fetches the rows of outputs o = w, w + 8, ... (o = 2 l + r); a wave without such an
   // output takes the last one again (same words, same LDS row: a benign double write)
@@ -870,10 +760,7 @@ _Pragma("unroll") \
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
       if (live[c]) {
-        const u64 v = acc[oo][c];                         // below 2^60 + 2^32
-        const u32 mq = (u32)v * mont;
-        u32 ov = (u32)((v + (u64)mq * p) >> 32);          // v 2^-32 mod p, below p + 2^28 + 1 < 2p
-        ov = min(ov, ov - p);
+        const u32 ov = dot32_mont_out(acc[oo][c], mont, p);      // acc is below 2^60 + 2^32: (v + m p) / 2^32 < p + 2^28 + 1 < 2p
         __builtin_nontemporal_store(ov, obase + (((i64)((ct0 + c) * 2 + (o & 1)) * NLBT * 4) << (lognsl + 6)));
       }
     }
@@ -926,34 +813,31 @@ static int dot32_geom(fhesi_ctx* ctx, i64 blocks, Dot32Geom* g) {
 static bool dot32_k4_prime_ok(u32 p) { return p < (1u << 30) && (u32)(0u - 4u * p) < (1u << 28); }
 
 // d_dig: tiled [4][n/64][count*ncol][64] u32; d_out: [count*2*NLB][4][n] u32
-template <int CT, int NW>
-static int launch_dot32_t(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out) {
-  const size_t shmem = (size_t)ncol * CT * 32 * 4;
-  static std::atomic<unsigned long long> attr_done{0};
-  FHESI_TRY(dot32_allow_lds(ctx, (const void*)dot32_kernel2<CT, NW>, attr_done));
+// The digit-tile launch: tiles of CT ciphertexts x tile_cols columns x 32 elements; `trailing` is dot32_kernel2p's ncp (dot32_kernel2 takes none).
+// attr_done: the kernel's own latch (one per instantiation, in the callers below).
+template <int CT, int NW, class K, class... Trailing>
+static int launch_dot32_tile(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out, K kernel, std::atomic<unsigned long long>& attr_done, int tile_cols, Trailing... trailing) {
+  const size_t shmem = (size_t)tile_cols * CT * 32 * 4;
+  FHESI_TRY(dot32_allow_lds(ctx, (const void*)kernel, attr_done));
   const int ntiles = (int)((count + CT - 1) / CT);
   const i64 blocks = (i64)8 * ntiles * 2;
   Dot32Geom g;
   FHESI_TRY(dot32_geom(ctx, blocks, &g));
-  PROF_KERNEL(ctx, PROF_DOT, (dot32_kernel2<CT, NW>));
-  dot32_kernel2<CT, NW><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, g.nsl8, g.lognsl, g.sub_lg);
+  prof_kernel(ctx, PROF_DOT, (const void*)kernel);
+  kernel<<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, g.nsl8, g.lognsl, g.sub_lg, trailing...);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+template <int CT, int NW>
+static int launch_dot32_t(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out) {
+  static std::atomic<unsigned long long> attr_done{0};
+  return launch_dot32_tile<CT, NW>(ctx, k, d_dig, ncol, count, d_out, &dot32_kernel2<CT, NW>, attr_done, ncol);
 }
 template <int CT, int NW, int NH>
 static int launch_dot32_p(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out) {
   const int ncp = ((ncol + NH - 1) / NH + 7) & ~7;                 // columns per part: whole 8-column pairs in every part but the last
-  const size_t shmem = (size_t)ncp * CT * 32 * 4;
   static std::atomic<unsigned long long> attr_done{0};
-  FHESI_TRY(dot32_allow_lds(ctx, (const void*)dot32_kernel2p<CT, NW, NH>, attr_done));
-  const int ntiles = (int)((count + CT - 1) / CT);
-  const i64 blocks = (i64)8 * ntiles * 2;
-  Dot32Geom g;
-  FHESI_TRY(dot32_geom(ctx, blocks, &g));
-  PROF_KERNEL(ctx, PROF_DOT, (dot32_kernel2p<CT, NW, NH>));
-  dot32_kernel2p<CT, NW, NH><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, k->aux_rows, count, d_out, ctx->aux32->pr, ntiles, g.nsl8, g.lognsl, g.sub_lg, ncp);
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_dot32_tile<CT, NW>(ctx, k, d_dig, ncol, count, d_out, &dot32_kernel2p<CT, NW, NH>, attr_done, ncp, ncp);
 }
 template <int NLBT, int CW, int KC, int PD, int NW = 8, int NSP = 1, int TAIL = 0>
 static int launch_dot32_k4(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out) {

@@ -765,25 +765,20 @@ static int t32_fwd(fhesi_ctx* ctx, const T32Config* c, u32* d_r, i64 npolys) {
   ProfScope prof(ctx, PROF_NTT_FWD, (double)(npolys * c->NP));
   if (npolys > 0x7fffffff) FHESI_FAIL("tensor32: too many rows per launch");
   const dim3 grid((unsigned)npolys, (unsigned)(c->NP << x->S));
-#define T32_FWD_GO(SS, PB) do { PROF_KERNEL(ctx, PROF_NTT_FWD, (ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB>)); \
-    ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB><<<grid, A32_T, 0, ctx->stream>>>(d_r, npolys, c->NP, 0, c->pr, x->d_fwd, Dig32Src{}, Aux32Head{}); } while (0)
-  if (x->S >= 3) {       // head stages of the plain rows as a pass of their own (at most 65535 rows, a multiple of NP, per launch)
-    const i64 nr = npolys * c->NP, step = (65535 / c->NP) * (i64)c->NP;
-    for (i64 r0 = 0; r0 < nr; r0 += step) {
-      const dim3 hg(A32_N / 256, (unsigned)std::min(step, nr - r0));
-      u32* rp = d_r + (r0 << (A32_LOGN + x->S));
-      if (x->S == 3) ntt32_headS_kernel<3><<<hg, 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs);
-      else if (x->S == 4) ntt32_headS_kernel<4><<<hg, 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs);
-      else if (x->S == 5) ntt32_headS_kernel<5><<<hg, 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs);
-      else ntt32_headS_kernel<6><<<hg, 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs);
-    }
+  // head stages of the plain rows as a pass of their own (rows of 2^16 take them in rns32_reduce)
+  if (x->S >= 3) {
+    if (!launch_ntt32_head_pass(ctx->stream, x->S, d_r, npolys * c->NP, c->NP, 0, x->d_p, x->d_ht, x->d_hs)) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
     HIP_TRY(hipGetLastError());
   }
-#define T32_FWD_S(PB) do { switch (x->S) { case 0: T32_FWD_GO(0, PB); break; case 1: T32_FWD_GO(1, PB); break; case 2: T32_FWD_GO(2, PB); break; case 3: T32_FWD_GO(3, PB); break; \
-    case 4: T32_FWD_GO(4, PB); break; case 5: T32_FWD_GO(5, PB); break; default: T32_FWD_GO(6, PB); break; } } while (0)
-  if (x->bits == 29) T32_FWD_S(29); else T32_FWD_S(30);
-#undef T32_FWD_S
-#undef T32_FWD_GO
+  if (!a32_with_S<0, 6>(x->S, [&](auto s) {
+    constexpr int SS = decltype(s)::value;
+    auto go = [&](auto pb) {
+      constexpr int PB = decltype(pb)::value;
+      PROF_KERNEL(ctx, PROF_NTT_FWD, (ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB>));
+      ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB><<<grid, A32_T, 0, ctx->stream>>>(d_r, npolys, c->NP, 0, c->pr, x->d_fwd, Dig32Src{}, Aux32Head{});
+    };
+    if (x->bits == 29) go(std::integral_constant<int, 29>{}); else go(std::integral_constant<int, 30>{});
+  })) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -837,16 +832,7 @@ static int t32_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npoly
     } } while (0)
   if (S >= 2) {      // rows of 2^16 and longer: the tail stages as a pass of their own over the sub-inverses (in place), then the fold from whole rows
     const fhesi_tensor32* x = ctx->tensor32;
-    const i64 nr = npolys * c->NP, step = (65535 / c->NP) * (i64)c->NP;
-    for (i64 r0 = 0; r0 < nr; r0 += step) {
-      const unsigned ny = (unsigned)std::min(step, nr - r0);
-      u32* rp = const_cast<u32*>(d_t) + (r0 << (A32_LOGN + S));
-      if (S == 2) ntt32_tail2_kernel<<<dim3(16, ny), 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_ht);
-      else if (S == 3) ntt32_tailS_kernel<3><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs, 0);
-      else if (S == 4) ntt32_tailS_kernel<4><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs, 0);
-      else if (S == 5) ntt32_tailS_kernel<5><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs, 0);
-      else ntt32_tailS_kernel<6><<<dim3(A32_N / 256, ny), 256, 0, ctx->stream>>>(rp, c->NP, 0, x->d_p, x->d_hs, 0);
-    }
+    if (!launch_ntt32_tail_pass(ctx->stream, S, const_cast<u32*>(d_t), npolys * c->NP, c->NP, 0, x->d_p, x->d_ht, x->d_hs, 0)) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
     HIP_TRY(hipGetLastError());
   }
   // (A compiled form of this kernel for the reference drivers' own shapes -- logQ, word window and limb positions as constants, the words in

@@ -3,6 +3,8 @@
 // (kernels_aux32.hip) and the tensor half of the fused multiplication through ~35 of them (kernels_tensor32.hip).
 // Included inside a translation unit after fhesi_internal.h; everything is static / templated.
 #pragma once
+#include <algorithm>
+#include <type_traits>
 
 struct Tw32 { u32 w, wp; };          // constant and floor(w 2^32 / p)
 struct Aux32Primes { u32 p[4]; u32 ninv[4], ninv_p[4]; u64 pinv64[4] /* floor((2^64 - 1) / p) */, r64[4] /* 2^64 mod p */, r48[4] /* 2^48 mod p */;
@@ -236,6 +238,38 @@ static __global__ void __launch_bounds__(256) ntt32_tailS_kernel(u32* __restrict
   }
 #pragma unroll
   for (int h = 0; h < (1 << S); ++h) g[(i64)h * A32_N + e] = v[h];
+}
+
+// ---- host side: the row-length exponent S as a compile-time constant, and the stand-alone head / tail passes
+// f(std::integral_constant<int, S>) for the run-time S in LO .. HI; f reads it as decltype(s)::value.  false, and f not called, for any other S
+template <int LO, int HI, class F>
+static inline bool a32_with_S(int S, F&& f) {
+  if (S == LO) { f(std::integral_constant<int, LO>{}); return true; }
+  if constexpr (LO < HI) return a32_with_S<LO + 1, HI>(S, f);
+  return false;
+}
+// nrows rows of 2^(14 + S) elements in launches of at most 65535 rows (grid.y), each a multiple of nslots: launch(first row, rows); false as soon as a launch says so
+template <class F>
+static inline bool a32_row_launches(u32* rows, i64 nrows, int nslots, int S, F&& launch) {
+  const i64 step = (65535 / nslots) * (i64)nslots;
+  for (i64 r0 = 0; r0 < nrows; r0 += step)
+    if (!launch(rows + (r0 << (A32_LOGN + S)), (unsigned)std::min(step, nrows - r0))) return false;
+  return true;
+}
+// The head stages of rows of 2^16 and longer (S >= 2) as a pass of their own, in place: row r belongs to prime a0 + r % nslots, nrows is a
+// multiple of nslots.  d_ht: the constants of S = 2 (ntt32_head2_kernel / ntt32_tail2_kernel), d_hs: the twiddles of S >= 3.  false: no such pass for this S
+static inline bool launch_ntt32_head_pass(hipStream_t stream, int S, u32* rows, i64 nrows, int nslots, int a0, const u32* d_p, const Tw32* d_ht, const Tw32* d_hs) {
+  return a32_row_launches(rows, nrows, nslots, S, [&](u32* rp, unsigned ny) {
+    if (S == 2) { ntt32_head2_kernel<<<dim3(16, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_ht); return true; }
+    return a32_with_S<3, 6>(S, [&](auto s) { ntt32_headS_kernel<decltype(s)::value><<<dim3(A32_N / 256, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_hs); });
+  });
+}
+// ... and the tail stages of the inverse over the sub-inverses; mont: the rows carry dot32's factor 2^-32, undone here (S >= 3; at S = 2 the sub-inverses undo it)
+static inline bool launch_ntt32_tail_pass(hipStream_t stream, int S, u32* rows, i64 nrows, int nslots, int a0, const u32* d_p, const Tw32* d_ht, const Tw32* d_hs, int mont) {
+  return a32_row_launches(rows, nrows, nslots, S, [&](u32* rp, unsigned ny) {
+    if (S == 2) { ntt32_tail2_kernel<<<dim3(16, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_ht); return true; }
+    return a32_with_S<3, 6>(S, [&](auto s) { ntt32_tailS_kernel<decltype(s)::value><<<dim3(A32_N / 256, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_hs, mont); });
+  });
 }
 
 // element at a 32-bit BYTE offset from a wave-uniform base: `global_load/store v, v_off, s[base]`.  The offset is made opaque so that the

@@ -337,8 +337,9 @@ def test_dot32_kernel4_totals(step, ncol):
 
 # ---------------------------------------------------------------------------------------------- dot32_kernel2 / dot32_kernel2p
 def dot2_model(digs, keys, p, ncp):
-    """one output of dot32_kernel2p (column parts of ncp columns; dot32_kernel2 = one part): 64-bit totals of products below p^2, folded into
-    48-bit units (the high part counted in a 32-bit word) every 16 columns, r48 = 2^48 mod p and one Montgomery step at the end"""
+    """one output of dot32_kernel2p (column parts of ncp columns; dot32_kernel2 = one part).  Each part is one call of dot32_sweep: 64-bit totals
+    of products below p^2, folded into 48-bit units (the high part counted in a 32-bit word) every 16 columns and at the end of the part, so
+    the next part starts below 2^48; then r48 = 2^48 mod p and one Montgomery step (dot32_tile_out, dot32_mont_out)"""
     r48 = (1 << 48) % p
     mont = (-pow(p, -1, 1 << 32)) & M32
     tot, th = 0, 0
@@ -346,7 +347,7 @@ def dot2_model(digs, keys, p, ncp):
     def add(k0, n):
         nonlocal tot
         for k in range(k0, k0 + n):
-            assert digs[k] < p and keys[k] < p               # (the tile loader reduces the lazy digit words before they enter LDS)
+            assert digs[k] < p and keys[k] < p               # (dot32_tile_load reduces the lazy digit words before they enter LDS)
             tot += digs[k] * keys[k]
             assert tot <= M64, "sixteen products on top of a folded total overflowed 64 bits"
 

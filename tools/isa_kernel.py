@@ -11,8 +11,11 @@ def is_ins(l):
 
 
 def kernels(path):
-    """{kernel symbol: its lines from the label to s_endpgm}; lines naming the translation unit's __hip_cuid_ symbol are dropped"""
+    """{kernel symbol: its lines from the label to s_endpgm}; lines naming the translation unit's __hip_cuid_ symbol are dropped, and local
+    labels and block names lose the function's ordinal in the translation unit (.LBB21_4 -> .LBB_4): it follows the order of instantiation, which host code sets;
+    the blanks in front of a trailing comment, which pad to a column after the label's width, shrink to one"""
     s = "\n".join(l for l in open(path).read().splitlines() if '__hip_cuid_' not in l)
+    s = re.sub(r'[ \t]+;', ' ;', re.sub(r'(\.L[A-Za-z]+|\bBB)\d+_(\d+)', r'\1_\2', s))      # (block names in the trailing comments too)
     out = {}
     for name in re.findall(r'^\t\.amdhsa_kernel (\S+)', s, re.M):
         start = re.search(r'^' + re.escape(name) + r':', s, re.M).start()
@@ -37,12 +40,8 @@ def compare(a, b):
 
 if sys.argv[1] == "--compare":
     sys.exit(compare(sys.argv[2], sys.argv[3]))
-s = open(sys.argv[1]).read()
 name = sys.argv[2]
-m = re.search(r'^(' + re.escape(name) + r'\S*):', s, re.M)
-start = m.start()
-end = s.index('s_endpgm', start)
-lines = s[start:end].splitlines()
+lines = next(v for k, v in kernels(sys.argv[1]).items() if k.startswith(name))      # the whole function, every s_endpgm of it
 ins = [l for l in lines if is_ins(l)]
 print("instructions:", len(ins))
 cnt = collections.Counter(l.split()[0] for l in ins)
