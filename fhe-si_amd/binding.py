@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "fhesi_encrypt_int_slots_batch_seeded", "fhesi_decrypt_int_slots_batch", "fhesi_encrypt_noise_int_batch_seeded",
     "fhesi_ctx_lin_class",
     "fhesi_plain_create_slots", "fhesi_plain_create_poly", "fhesi_plain_free", "fhesi_plain_info", "fhesi_plain_sum_bits", "fhesi_ct_plain_sum_dev", "fhesi_ct_add_slots_dev",
+    "fhesi_ct_noise_batch", "fhesi_decrypt_noise_batch", "fhesi_ct_noise_int_batch",
 ]
 ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8,
@@ -55,6 +56,11 @@ PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt":
 # (class 13 is FHESI_PROF_NAME_DIGITS in the header; its key here is "digits_kernel" because prof_kernel_name takes the keys of both dictionaries
 # and "digits" is the timed class 5 of PROF_CLASSES)
 PROF_NAMES = {"crt_exact": 9, "ks_recombine": 10, "rns_generic": 11, "modswitch": 12, "digits_kernel": 13}
+
+
+def _words_to_ints(words: np.ndarray) -> list:
+    """[count][nw] little-endian 64-bit words -> Python integers"""
+    return [sum(int(w) << (64 * i) for i, w in enumerate(row)) for row in words]
 
 
 class FhesiError(RuntimeError):
@@ -228,6 +234,9 @@ def _load():
         "fhesi_plain_sum_bits": [_i64, _i32, _u64, _i64, _vp],
         "fhesi_ct_plain_sum_dev": [_vp, _vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp],
         "fhesi_ct_add_slots_dev": [_vp, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _i64, _i32, _i64],
+        "fhesi_ct_noise_batch": [_vp, _vp, _i32, _u64, _vp, _i32, _i64, _vp, _vp],
+        "fhesi_decrypt_noise_batch": [_vp, _vp, _i32, _u64, _vp, _i32, _i64, _vp, _vp, _vp],
+        "fhesi_ct_noise_int_batch": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -442,6 +451,22 @@ class Context:
         msg = np.zeros((count, self.phim), dtype=np.int64)
         _ck(_load().fhesi_decrypt_batch(self.h, sk1.h, logQ, p, ct.ptr, nlimbs, count, _p(msg)))
         return msg
+
+    # ---- the noise budget of unscaled two-part ciphertexts (include/fhesi_hip.h: what is and is not measured)
+    def noise_budget(self, sk1: "DoubleCRT", logQ: int, p: int, ct: DevBuf, nlimbs: int, count: int, maxres: bool = False):
+        """budget [count] int32 = max(0, logQ - bitlen(max |residual|)); with maxres=True also the exact maxima as Python integers."""
+        budget = np.zeros(count, dtype=np.int32)
+        words = np.zeros((count, (logQ + 64) // 64), dtype=np.uint64) if maxres else None
+        _ck(_load().fhesi_ct_noise_batch(self.h, sk1.h, logQ, p, ct.ptr, nlimbs, count, _p(budget), _p(words) if maxres else None))
+        return (budget, _words_to_ints(words)) if maxres else budget
+
+    def decrypt_noise_batch(self, sk1: "DoubleCRT", logQ: int, p: int, ct: DevBuf, nlimbs: int, count: int, maxres: bool = False):
+        """(msg, budget[, maxres]) from one pass: msg is decrypt_batch's bit for bit."""
+        msg = np.zeros((count, self.phim), dtype=np.int64)
+        budget = np.zeros(count, dtype=np.int32)
+        words = np.zeros((count, (logQ + 64) // 64), dtype=np.uint64) if maxres else None
+        _ck(_load().fhesi_decrypt_noise_batch(self.h, sk1.h, logQ, p, ct.ptr, nlimbs, count, _p(msg), _p(budget), _p(words) if maxres else None))
+        return (msg, budget, _words_to_ints(words)) if maxres else (msg, budget)
 
     # ---- ciphertext algebra between multiplications (Matrix<Ciphertext> / Regression), batches resident in HBM
     def ct_add_dev(self, logQ: int, dst: DevBuf, src: DevBuf, nparts: int, nlimbs: int, count: int):
@@ -666,6 +691,10 @@ class SlotSpace:
         _ck(_load().fhesi_decrypt_slots_batch(self.ctx.h, self.h, sk1.h, logQ, ct.ptr, nlimbs, count, nvals, int(only_usable), _p(vals)))
         return vals
 
+    def noise_budget(self, sk1: "DoubleCRT", logQ: int, ct: DevBuf, nlimbs: int, count: int, maxres: bool = False):
+        """Context.noise_budget with this space's p."""
+        return self.ctx.noise_budget(sk1, logQ, self.p, ct, nlimbs, count, maxres)
+
     def encrypt_noise_batch_seeded(self, pk0: "DoubleCRT", pk1: "DoubleCRT", logQ: int, seed: int, first_index: int, count: int, out: DevBuf, nlimbs: int):
         """Regression::GenerateNoise for `count` masks (slot 0 zero, the others uniform from (seed, index))."""
         _ck(_load().fhesi_encrypt_noise_batch_seeded(self.ctx.h, self.h, pk0.h, pk1.h, logQ, seed, first_index, count, out.ptr, nlimbs))
@@ -835,6 +864,12 @@ class SlotBasis:
         out = np.zeros((count, nvals, self.limbs), dtype=np.int64)
         _ck(_load().fhesi_decrypt_int_slots_batch(self.ctx.h, self.h, sk1.h, logQ, ct.ptr, nlimbs, count, nvals, _p(out)))
         return out if raw else unpack_limbs(out)
+
+    def noise_budget(self, sk1: "DoubleCRT", logQ: int, ct: DevBuf, nlimbs: int, count: int):
+        """ct [k][count] -> (budgets [k][count] with p = primes[c] in channel c, their minimum over the channels [count])."""
+        budget = np.zeros((self.k, count), dtype=np.int32)
+        _ck(_load().fhesi_ct_noise_int_batch(self.ctx.h, self.h, sk1.h, logQ, ct.ptr, nlimbs, count, _p(budget)))
+        return budget, budget.min(axis=0)
 
     # prepared plaintext operands, channel by channel (no entry point of their own: channel c is an ordinary space modulo primes[c])
     def _residues(self, vals, c: int) -> np.ndarray:

@@ -244,17 +244,19 @@ extern "C" int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* c, fhesi_slots_ba
   return 0;
 }
 
-// FHESISecKey::Decrypt (FHE-SI.cpp:93-119) of `count` unscaled 2-part ciphertexts [count][2][phi(m)][nlimbs] in HBM: the one core behind every
-// Decrypt entry point.  Leaves round(p z / q) mod p in d_msg [count][phi(m)] (HBM) and returns; only enqueues, and reads no host array.
-static int decrypt_rows_dev(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count, i64* d_msg) {
+// FHESISecKey::Decrypt (FHE-SI.cpp:93-119) of `count` unscaled 2-part ciphertexts [count][2][phi(m)][nlimbs] in HBM, up to the rounding: leaves
+// z = c0 + c1 t (toPoly, the low logQ+1 bits kept) in workspace slot 2 as [count][phi(m)][nw] words.  The checks of every Decrypt entry point.
+static int decrypt_z_dev(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count, u64** d_zw, int* nw_out) {
   CHECK_CTX(c);
   if (!sk1 || sk1->ctx != c) FHESI_FAIL("Decrypt: secret key belongs to another context");
   if ((int)sk1->idx.size() != c->L) FHESI_FAIL("Decrypt: secret key must be defined over all primes");
   if (logQ < 1 || nlimbs < 1) FHESI_FAIL("Decrypt: bad shape");
   if (p < 2 || p >= (1ull << 62)) FHESI_FAIL("Decrypt: plaintext modulus out of range");
-  if (!count) return 0;
   const i64 n = c->phim;
   const int L = c->L, nw = (logQ + 1 + 63) / 64;
+  *nw_out = nw;
+  *d_zw = nullptr;
+  if (!count) return 0;
   const std::vector<int> all = full_set(c);
   void *d_rows, *d_z, *d_big;
   FHESI_TRY(ws_reserve(c, 0, (size_t)count * 2 * L * n * 8, &d_rows));
@@ -267,7 +269,17 @@ static int decrypt_rows_dev(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, u
   CrtTables* t;
   FHESI_TRY(get_crt_tables(c, all, &t));
   FHESI_TRY(launch_crt(c, t, (const u64*)d_z, L, nullptr, count, 0, 0, 0, (u64*)d_big, nw));                         // toPoly, low logQ+1 bits kept
-  return launch_decrypt_round(c, (const u64*)d_big, count * n, nw, logQ, p, d_msg);                                  // round(p z / q) mod p (:110-116)
+  *d_zw = (u64*)d_big;
+  return 0;
+}
+// ... and the rounding: the one core behind every Decrypt entry point.  Leaves round(p z / q) mod p in d_msg [count][phi(m)] (HBM) and returns;
+// only enqueues, and reads no host array.
+static int decrypt_rows_dev(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count, i64* d_msg) {
+  u64* d_zw;
+  int nw;
+  FHESI_TRY(decrypt_z_dev(c, sk1, logQ, p, ct_dev, nlimbs, count, &d_zw, &nw));
+  if (!count) return 0;
+  return launch_decrypt_round(c, d_zw, count * c->phim, nw, logQ, p, d_msg);                                         // round(p z / q) mod p (:110-116)
 }
 // ---- behind the core: the message staging in slot 5 for the core to fill; slot values, once the transforms of the decryption are enqueued,
 // in slot 9; the host copy and the synchronise every Decrypt entry point ends in
@@ -315,6 +327,78 @@ extern "C" int fhesi_decrypt_int_slots_batch(fhesi_ctx* c, fhesi_slots_basis* b,
   FHESI_TRY(ws_i64(c, 9, bv, &d_vals));
   FHESI_TRY(slots_basis_decode_rows(b, d_msg, count, nvals, d_vals));
   return copy_out(c, vals_host, d_vals, bv);
+}
+
+// ---- the noise budget (include/fhesi_hip.h): the same z, the rounding that keeps its remainder (launch_decrypt_noise).  Workspace slot 4 holds
+// [rows][nw] maxima, [rows] budgets, then the per-block maxima of one chunk of at most `count` ciphertexts; rows = count, or k count for a slot basis.
+struct NoiseWs { u64 *maxres, *part; int* budget; };
+// the rows in front of the rounding put two polynomials per ciphertext on grid.y: batches of at most kNoiseChunk ciphertexts, one after the other
+static const i64 kNoiseChunk = 32767;
+static int noise_ws(fhesi_ctx* c, int32_t logQ, i64 rows, i64 count, NoiseWs* w) {
+  if (logQ < 1) FHESI_FAIL("Decrypt: bad shape");
+  const size_t nw = (size_t)(logQ + 1 + 63) / 64, head = (size_t)rows * nw * 8 + (((size_t)rows * 4 + 7) & ~(size_t)7);
+  void* d;
+  FHESI_TRY(ws_reserve(c, 4, head + (size_t)std::min<i64>(count, kNoiseChunk) * noise_blocks(c) * nw * 8, &d));
+  w->maxres = (u64*)d;
+  w->budget = (int*)(w->maxres + (size_t)rows * nw);
+  w->part = (u64*)((char*)d + head);
+  return 0;
+}
+static int noise_rows_dev(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count, i64* d_msg, const NoiseWs& w, i64 row0) {
+  const i64 n = c->phim;
+  for (i64 done = 0; done < count || !done; done += kNoiseChunk) {              // (count = 0 still runs the checks)
+    const i64 cnt = std::min<i64>(kNoiseChunk, count - done);
+    u64* d_zw;
+    int nw;
+    FHESI_TRY(decrypt_z_dev(c, sk1, logQ, p, ct_dev + (size_t)done * 2 * n * nlimbs, nlimbs, cnt, &d_zw, &nw));
+    FHESI_TRY(launch_decrypt_noise(c, d_zw, cnt, nw, logQ, p, d_msg ? d_msg + done * n : nullptr, w.part, w.maxres + (row0 + done) * nw, w.budget + row0 + done));
+  }
+  return 0;
+}
+static int noise_copy_out(fhesi_ctx* c, int32_t logQ, const NoiseWs& w, i64 rows, int32_t* budget_host, uint64_t* maxres_host) {
+  const size_t nw = (size_t)(logQ + 1 + 63) / 64;
+  if (rows) HIP_TRY(hipMemcpyAsync(budget_host, w.budget, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+  if (rows && maxres_host) HIP_TRY(hipMemcpyAsync(maxres_host, w.maxres, (size_t)rows * nw * 8, hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
+extern "C" int fhesi_ct_noise_batch(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                                    int32_t* budget_host, uint64_t* maxres_host) {
+  CHECK_CTX(c);
+  if (count < 0) FHESI_FAIL("noise budget: negative count");
+  if (!budget_host) FHESI_FAIL("noise budget: null output");
+  NoiseWs w;
+  FHESI_TRY(noise_ws(c, logQ, count, count, &w));
+  FHESI_TRY(noise_rows_dev(c, sk1, logQ, p, ct_dev, nlimbs, count, nullptr, w, 0));
+  FHESI_TRY(noise_copy_out(c, logQ, w, count, budget_host, maxres_host));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int fhesi_decrypt_noise_batch(fhesi_ctx* c, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                                         int64_t* msg_host, int32_t* budget_host, uint64_t* maxres_host) {
+  CHECK_CTX(c);
+  if (count < 0) FHESI_FAIL("noise budget: negative count");
+  if (!msg_host || !budget_host) FHESI_FAIL("noise budget: null output");
+  NoiseWs w;
+  i64* d_msg;
+  FHESI_TRY(noise_ws(c, logQ, count, count, &w));
+  FHESI_TRY(msg_staging(c, count, &d_msg));
+  FHESI_TRY(noise_rows_dev(c, sk1, logQ, p, ct_dev, nlimbs, count, d_msg, w, 0));
+  FHESI_TRY(noise_copy_out(c, logQ, w, count, budget_host, maxres_host));
+  return copy_out(c, msg_host, d_msg, (size_t)count * c->phim * 8);
+}
+// ... over a slot basis: channel ch with p = p_ch on its part of ct_dev, the layout of fhesi_decrypt_int_slots_batch; budget_host [k][count]
+extern "C" int fhesi_ct_noise_int_batch(fhesi_ctx* c, fhesi_slots_basis* b, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                                        int32_t* budget_host) {
+  CHECK_CTX(c);
+  FHESI_TRY(basis_check(c, b, "noise budget", 1, count));
+  if (!budget_host) FHESI_FAIL("noise budget: null output");
+  NoiseWs w;
+  FHESI_TRY(noise_ws(c, logQ, b->B.k * count, count, &w));
+  for (int ch = 0; ch < b->B.k; ++ch)
+    FHESI_TRY(noise_rows_dev(c, sk1, logQ, b->B.primes[ch], ct_dev + (size_t)ch * count * 2 * c->phim * nlimbs, nlimbs, count, nullptr, w, ch * count));
+  FHESI_TRY(noise_copy_out(c, logQ, w, b->B.k * count, budget_host, nullptr));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // --------------------------------------------------------------------------------------------- prepared plaintext operands

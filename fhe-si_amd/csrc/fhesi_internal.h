@@ -162,14 +162,15 @@ struct fhesi_ctx {
   // grow-only workspace.  Slot owners (a slot may be reused by another owner only when the first one's data is dead):
   //   0 digit rows / product operands / encrypt rows    1 inverse-transform scratch (tProd copy, dot output, automorph rows)
   //   2 limb-major parts / small-coefficient staging    3 automorph source rows / encrypt public key
-  //   4 wave sums, per-call constants                    5 tProd of a chunk / message staging
+  //   4 wave sums, per-call constants, noise maxima      5 tProd of a chunk / message staging
   //   6 row transforms above 2^14 (two-pass, bit reversal)   7 Bluestein slot map / wave operands
   //   8 Bluestein convolution buffer, index lists        9 Bluestein inverse output, scalar lists (no Bluestein call in between)
   //   10 auxiliary-prime dot product output (kernels_ksaux.hip)      11 staging of host batches (fhesi_ct_mul_relin_batch)
   //   (the slot layer borrows 8 for its convolution buffer / basis residues, 9 for slot values and 5 for message polynomials -- slots_stage_host,
   //   the stage_msg_* functions in front of encrypt_rows_dev: before the transforms of an encryption start; what follows decrypt_rows_dev:
   //   after those of a decryption are enqueued; fhesi_ct_plain_sum_dev takes the owners fhesi_ct_mul_sum_relin_dev takes: 7 gathered operands, 0 their
-  //   rows, 4 the sums, 5 the index lists of all passes)
+  //   rows, 4 the sums, 5 the index lists of all passes; the noise entry points own 4 from the CRT of a decryption to their copy-out: the per-block
+  //   maxima of launch_decrypt_noise, then the maxima and budgets per ciphertext -- nothing in a decryption touches 4)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -440,6 +441,11 @@ int launch_encrypt_combine(fhesi_ctx* ctx, const u64* d_rows /* [count][3][L][n]
 int launch_add_scaled_msg(fhesi_ctx* ctx, u64* d_ct, const i64* d_msg, const u64* d_delta, i64 count, int nl, int logQ);
 int launch_decrypt_dot(fhesi_ctx* ctx, const u64* d_rows /* [count][2][L][n] */, const u64* d_t /* [L][n] */, i64 count, u64* d_out /* [count][L][n] */);
 int launch_decrypt_round(fhesi_ctx* ctx, const u64* d_z, i64 total, int nw, int logQ, u64 p, i64* d_out);
+// ... keeping the remainder too: per ciphertext the maximum of |(2 p z + q) mod 2q - q| (nw limbs) and the noise budget; d_msg may be null.
+// d_part: [count][noise_blocks][nw] words, every one written before it is read
+static inline i64 noise_blocks(const fhesi_ctx* ctx) { return (ctx->phim + 255) / 256; }
+int launch_decrypt_noise(fhesi_ctx* ctx, const u64* d_z /* [count][n][nw] */, i64 count, int nw, int logQ, u64 p, i64* d_msg /* [count][n] or null */, u64* d_part,
+                         u64* d_maxres /* [count][nw] */, int* d_budget /* [count] */);
 
 int launch_rows_mul_bcast(fhesi_ctx* ctx, u64* d_dst /* [ncols][L][n] */, const u64* d_a /* [ncols][L][n] */, const u64* d_t /* [L][n] */, i64 ncols);
 int launch_keygen_combine(fhesi_ctx* ctx, const u64* d_bcoef, int wb, const u64* d_scoef, int ws, const i64* d_err, i64 ncols, int nd, int digit_bits, int nl, int logQ, u64* d_out);

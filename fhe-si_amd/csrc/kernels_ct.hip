@@ -393,14 +393,12 @@ int launch_decrypt_dot(fhesi_ctx* ctx, const u64* d_rows, const u64* d_t, i64 co
 // Writing z = zh * 2q + zl with zl = z mod 2q in [0, 2q) gives floor(...) = 2 p zh + floor((2 p zl + q) / 2q), and the first
 // term vanishes modulo p: only the low logQ+1 bits of z matter, and the quotient is at most 2p.
 // z: [npolys][n][nw] two's complement truncated to nw = ceil((logQ+1)/64) limbs; out: [npolys][n]
+// limbs 0 .. nw-1 of 2 p zl + q in P, limb nw in `carry`
 template <int MAXNL>
-__global__ void __launch_bounds__(256) decrypt_round_kernel(const u64* __restrict__ z, i64 total, int nw, int logQ, u64 p, i64* __restrict__ out) {
-  const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= total) return;
+__device__ __forceinline__ void round_product(const u64* __restrict__ z, i64 j, int nw, int logQ, u64 p, u64 (&P)[MAXNL + 1], u64& carry) {
   const int top_bits = logQ + 1 - 64 * (nw - 1);                  // bits of zl in its top limb (1..64)
   const u64 twop = 2 * p;
-  u64 P[MAXNL + 1];
-  u64 carry = 0;
+  carry = 0;
 #pragma unroll
   for (int i = 0; i < MAXNL; ++i) {
     P[i] = 0;
@@ -420,7 +418,10 @@ __global__ void __launch_bounds__(256) decrypt_round_kernel(const u64* __restric
   for (int i = 0; i < MAXNL; ++i)
     if (i < nw && i >= wq) { const u64 s = P[i] + add; add = s < add; P[i] = s; }
   carry += add;
-  // bits from logQ+1 upward: at most 2p, fits one word
+}
+// bits from logQ+1 upward: at most 2p, fits one word
+template <int MAXNL>
+__device__ __forceinline__ u64 round_quotient(const u64 (&P)[MAXNL + 1], u64 carry, int nw, int logQ) {
   const int ws = (logQ + 1) >> 6, bs = (logQ + 1) & 63;
   u64 lo = 0, hi = 0;
 #pragma unroll
@@ -430,8 +431,16 @@ __global__ void __launch_bounds__(256) decrypt_round_kernel(const u64* __restric
   }
   if (ws == MAXNL) lo = carry;
   if (ws + 1 == MAXNL) hi = (nw == MAXNL) ? carry : hi;
-  const u64 t = bs ? ((lo >> bs) | (hi << (64 - bs))) : lo;
-  out[j] = (i64)(t % p);
+  return bs ? ((lo >> bs) | (hi << (64 - bs))) : lo;
+}
+template <int MAXNL>
+__global__ void __launch_bounds__(256) decrypt_round_kernel(const u64* __restrict__ z, i64 total, int nw, int logQ, u64 p, i64* __restrict__ out) {
+  const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= total) return;
+  u64 P[MAXNL + 1];
+  u64 carry;
+  round_product<MAXNL>(z, j, nw, logQ, p, P, carry);
+  out[j] = (i64)(round_quotient<MAXNL>(P, carry, nw, logQ) % p);
 }
 int launch_decrypt_round(fhesi_ctx* ctx, const u64* d_z, i64 total, int nw, int logQ, u64 p, i64* d_out) {
   if (!total) return 0;
@@ -441,6 +450,123 @@ int launch_decrypt_round(fhesi_ctx* ctx, const u64* d_z, i64 total, int nw, int 
   else if (nw <= 9) decrypt_round_kernel<9><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
   else if (nw <= 17) decrypt_round_kernel<17><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
   else decrypt_round_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- the noise of a ciphertext, from the same product: P = (2 p z + q) mod 2q is the remainder the rounding above throws away, r = P - q in
+// [-q, q) the decryption residual (invariant noise v = r / 2q in [-1/2, 1/2)).  |r| takes logQ+1 bits, nw limbs as z does: bit logQ of P set
+// means r >= 0 and |r| is P with that bit cleared; otherwise |r| = q - P, which is q at the half-way point P = 0.
+// The residual equals the true noise only while the true noise is below 1/2: past that the message has already rounded to a neighbour and the
+// residual measured is the distance to THAT message, so a budget of 0 reads "at or within one bit of failure", never "failed by this much".
+template <int MAXNL>
+__device__ __forceinline__ void round_residual(const u64 (&P)[MAXNL + 1], int nw, int logQ, u64 (&a)[MAXNL]) {
+  const int wq = logQ >> 6;                                       // (= nw - 1: the limb of bit logQ is the top limb)
+  const u64 qbit = 1ull << (logQ & 63), top_mask = (qbit << 1) - 1;
+  u64 nonneg = 0;
+#pragma unroll
+  for (int i = 0; i < MAXNL; ++i)
+    if (i == wq) nonneg = P[i] & qbit;
+  u64 borrow = 0;
+#pragma unroll
+  for (int i = 0; i < MAXNL; ++i) {
+    a[i] = 0;
+    if (i < nw) {
+      const u64 x = i == wq ? P[i] & top_mask : P[i];             // limb i of P mod 2q
+      const u64 qi = i == wq ? qbit : 0;
+      const u64 d = qi - x, d2 = d - borrow;
+      borrow = (qi < x) | (d < borrow);
+      a[i] = nonneg ? (i == wq ? x & ~qbit : x) : d2;
+    }
+  }
+}
+// Exact maximum of the block's nw-limb values without a multi-limb shuffle: the limbs are walked from the top, each round takes the 64-bit
+// maximum over the threads still level with the maximum so far (wave64 shuffles, then LDS across the waves), and the threads below it drop out.
+// Ties are harmless: tied threads hold the same limbs.  Thread 0 writes the nw limbs to `out`; every thread returns the maximum's bit length.
+template <int MAXNL, int NWAVES>
+__device__ __forceinline__ int block_limb_max(const u64 (&a)[MAXNL], int nw, u64* __restrict__ out) {
+  __shared__ u64 s[MAXNL][NWAVES];
+  bool level = true;
+  int bitlen = 0;
+#pragma unroll
+  for (int i = MAXNL - 1; i >= 0; --i)
+    if (i < nw) {
+      u64 v = level ? a[i] : 0;
+#pragma unroll
+      for (int o = 32; o; o >>= 1) { const u64 w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+      if (NWAVES > 1) {
+        if ((threadIdx.x & 63) == 0) s[i][threadIdx.x >> 6] = v;
+        __syncthreads();                                            // (round i has its own row of s: one barrier per round)
+#pragma unroll
+        for (int w = 0; w < NWAVES; ++w) { const u64 o = s[i][w]; v = o > v ? o : v; }
+      }
+      level = level && a[i] == v;
+      if (!bitlen && v) bitlen = 64 * i + 64 - __clzll((long long)v);
+      if (threadIdx.x == 0) out[i] = v;
+    }
+  return bitlen;
+}
+// z: [gridDim.y][n][nw] as decrypt_round_kernel takes it; msg: [gridDim.y][n] the same message bits, or null; part: [gridDim.y][gridDim.x][nw]
+// the maximum of |r| over the coefficients of each block
+template <int MAXNL>
+__global__ void __launch_bounds__(256) decrypt_noise_kernel(const u64* __restrict__ z, i64 n, int nw, int logQ, u64 p, i64* __restrict__ msg, u64* __restrict__ part) {
+  const i64 c = blockIdx.y;
+  const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
+  u64 a[MAXNL];
+#pragma unroll
+  for (int i = 0; i < MAXNL; ++i) a[i] = 0;
+  if (j < n) {
+    u64 P[MAXNL + 1];
+    u64 carry;
+    round_product<MAXNL>(z, c * n + j, nw, logQ, p, P, carry);
+    if (msg) msg[c * n + j] = (i64)(round_quotient<MAXNL>(P, carry, nw, logQ) % p);
+    round_residual<MAXNL>(P, nw, logQ, a);
+  }
+  block_limb_max<MAXNL, 4>(a, nw, part + (c * gridDim.x + blockIdx.x) * nw);
+}
+// part: [count][np][nw] -> maxres [count][nw], budget [count] = max(0, logQ - bitlen(maxres)); one wave per ciphertext, each lane keeping
+// the lexicographic maximum of the partials it strides over.  A launch boundary separates it from the kernel above: no atomics, no hand-off.
+template <int MAXNL>
+__global__ void __launch_bounds__(64) noise_budget_kernel(const u64* __restrict__ part, int np, int nw, int logQ, u64* __restrict__ maxres, int* __restrict__ budget) {
+  const i64 c = blockIdx.x;
+  u64 a[MAXNL];
+#pragma unroll
+  for (int i = 0; i < MAXNL; ++i) a[i] = 0;
+  for (int g = threadIdx.x; g < np; g += 64) {
+    const u64* x = part + (c * np + g) * nw;
+    u64 v[MAXNL];
+    bool decided = false, greater = false;
+#pragma unroll
+    for (int i = MAXNL - 1; i >= 0; --i) {
+      v[i] = 0;
+      if (i < nw) {
+        v[i] = x[i];
+        if (!decided && v[i] != a[i]) { decided = true; greater = v[i] > a[i]; }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MAXNL; ++i) a[i] = greater ? v[i] : a[i];
+  }
+  const int bitlen = block_limb_max<MAXNL, 1>(a, nw, maxres + c * nw);
+  if (threadIdx.x == 0) budget[c] = logQ > bitlen ? logQ - bitlen : 0;
+}
+int launch_decrypt_noise(fhesi_ctx* ctx, const u64* d_z, i64 count, int nw, int logQ, u64 p, i64* d_msg, u64* d_part, u64* d_maxres, int* d_budget) {
+  if (!count) return 0;
+  if (nw > 32) FHESI_FAIL("Decrypt: logQ=%d exceeds the supported 2047 bits", logQ);
+  if (count > 65535) FHESI_FAIL("Decrypt: more than 65535 ciphertexts per launch");
+  const i64 n = ctx->phim, np = noise_blocks(ctx);
+  {
+    const dim3 grid((unsigned)np, (unsigned)count);
+    if (nw <= 2) decrypt_noise_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
+    else if (nw <= 9) decrypt_noise_kernel<9><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
+    else if (nw <= 17) decrypt_noise_kernel<17><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
+    else decrypt_noise_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
+  }
+  const unsigned grid = (unsigned)count;
+  if (nw <= 2) noise_budget_kernel<2><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
+  else if (nw <= 9) noise_budget_kernel<9><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
+  else if (nw <= 17) noise_budget_kernel<17><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
+  else noise_budget_kernel<32><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
   HIP_TRY(hipGetLastError());
   return 0;
 }

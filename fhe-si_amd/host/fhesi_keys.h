@@ -82,6 +82,38 @@ class FHESISecKey {
     ptxt.message.assign(context.zMstar.phiM(), 0);
     for (long i = 0; i <= deg(z); ++i) { ZZ c = z.rep[i]; c *= ZZ(2L) * p; c += q; c /= q2; ptxt.message[i] = rem(c, p.to_long()); }
   }
+  // The noise budget of an unscaled two-part ciphertext (include/fhesi_hip.h, fhesi_ct_noise_batch: what is and is not measured): logQ minus the
+  // bit length of the largest decryption residual |(2 p z + q) mod 2q - q|, at least 0.  An extension of the mirror; for the holder of the key.
+  // Looking at the budget is looking at the ciphertext: whatever was recorded for it runs now, as for Decrypt.
+  long NoiseBudget(const Ciphertext& ctxt) const {
+    if (LazyCiphertexts() && !ctxt.isScaledUp() && ctxt.parts.resident() && sKeys.size() == 2) {
+      CtEngine& e = ct_engine(context); CtRef v = ctxt.parts.value(); e.force(v);
+      int32_t budget = 0;
+      ck(fhesi_ct_noise_batch(e.h, sKeys[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), e.ptr(v->slot), e.nl, 1, &budget, nullptr));
+      return budget;
+    }
+    return NoiseBudgetObjects(ctxt);
+  }
+  // ... of many ciphertexts in one device call
+  void NoiseBudgetBatch(std::vector<long>& budgets, const std::vector<Ciphertext>& ctxts) const {
+    const long count = (long)ctxts.size();
+    std::vector<int32_t> b((size_t)count);
+    ciphertexts_on_device(ctxts, [&](fhesi_ctx* h, const uint64_t* ct, int nl) {
+      return fhesi_ct_noise_batch(h, sKeys[1].handle(), (int32_t)context.logQ, (uint64_t)context.ModulusP().to_long(), ct, nl, count, b.data(), nullptr);
+    });
+    budgets.assign(b.begin(), b.end());
+  }
+  // ... from toPoly in ZZ, the way Decrypt's body above forms z: the same number, stated a second time
+  long NoiseBudgetObjects(const Ciphertext& ctxt) const {
+    std::vector<DoubleCRT> cp, sp;
+    for (size_t i = 0; i < sKeys.size(); ++i) { cp.push_back(DoubleCRT(ctxt.GetPart((unsigned)i).poly, context)); sp.push_back(sKeys[i]); }
+    DoubleCRT tmp(context); DotProduct(tmp, cp, sp);
+    ZZX z; tmp.toPoly(z);
+    ZZ p = context.ModulusP(), q = context.modulusQ, q2 = q * ZZ(2L);
+    long maxbits = 0;
+    for (long i = 0; i <= deg(z); ++i) { ZZ r = z.rep[i]; r *= ZZ(2L) * p; r += q; r %= q2; r -= q; maxbits = std::max(maxbits, r.bits()); }
+    return std::max(0L, (long)context.logQ - maxbits);
+  }
 };
 // One stream of on-device randomness (csrc/philox.h): the secret seed, the public seed of the key polynomials, and ONE monotonically
 // increasing object counter shared by every Encrypt and every KeySwitchSI that draws from it -- callers never pick indices, so a pair

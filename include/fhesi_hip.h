@@ -266,6 +266,23 @@ int fhesi_encrypt_batch(fhesi_ctx* ctx, const fhesi_dcrt* pk0, const fhesi_dcrt*
  *   msg_host [count][phi(m)] = round(p * (c0 + c1 t) / 2^logQ) mod p, floor((2 p z + q) / (2 q)) as in the reference. */
 int fhesi_decrypt_batch(fhesi_ctx* ctx, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
                         int64_t* msg_host);
+/* The NOISE BUDGET of unscaled 2-part ciphertexts, for the holder of the secret key: how far each is from decrypting wrongly.  An extension of
+ * the mirror (the reference only has the end-to-end predicate decrypt(f(enc x)) == f(x)).  With q = 2^logQ and z = c0 + c1 t as in Decrypt, per
+ * coefficient P = (2 p z + q) mod 2q is the remainder Decrypt's rounding throws away and r = P - q in [-q, q) the decryption RESIDUAL (the
+ * invariant noise is r / 2q in [-1/2, 1/2)).  Per ciphertext:
+ *   maxres = max over the phi(m) coefficients of |r|, exact, nw = ceil((logQ + 1) / 64) little-endian 64-bit words;
+ *   budget = max(0, logQ - bitlen(maxres)), bitlen(0) = 0: the noise may grow by a factor 2^budget and every coefficient still rounds to the
+ *            same message (maxres 2^budget < q whenever budget > 0).
+ * WHAT IS MEASURED.  The residual equals the true noise only while the true noise is below 1/2.  A ciphertext whose noise has passed 1/2 has
+ * already rounded to a neighbouring message and shows the distance to THAT one, which may look small.  So budget 0 means "at or within one bit
+ * of failure", a positive budget is meaningful for a ciphertext that was computed within its budget so far, and a budget that RISES along a
+ * computation is the sign that it failed in between.  Nothing here estimates noise without the key.
+ * One pass over z gives both results of fhesi_decrypt_noise_batch; its msg_host is fhesi_decrypt_batch's bit for bit.  Arguments and refusals are
+ * those of fhesi_decrypt_batch; maxres_host may be null.  Deterministic: no atomics, the result does not depend on the launch shape. */
+int fhesi_ct_noise_batch(fhesi_ctx* ctx, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                         int32_t* budget_host /* [count] */, uint64_t* maxres_host /* [count][nw] or null */);
+int fhesi_decrypt_noise_batch(fhesi_ctx* ctx, const fhesi_dcrt* sk1, int32_t logQ, uint64_t p, const uint64_t* ct_dev, int32_t nlimbs, int64_t count,
+                              int64_t* msg_host, int32_t* budget_host /* [count] */, uint64_t* maxres_host /* [count][nw] or null */);
 
 /* KeySwitchSI::Init (FHE-SI.cpp:153-209) for every column of a matrix in one call: k = the matrix (ncomp = components of the source
  * key: 3 for InitS2's (1, t, t^2), 2 for InitAutomorph), src[i] = the source key's DoubleCRT components, dst_t = dst[1].
@@ -422,6 +439,9 @@ int fhesi_decrypt_int_slots_batch(fhesi_ctx* ctx, fhesi_slots_basis* b, const fh
                                   int64_t nvals, int64_t* vals_host /* [count][nvals][limbs] */);
 int fhesi_encrypt_noise_int_batch_seeded(fhesi_ctx* ctx, fhesi_slots_basis* b, const fhesi_dcrt* pk0, const fhesi_dcrt* pk1, int32_t logQ, uint64_t seed, uint64_t first_index,
                                          int64_t count, uint64_t* out_dev /* [k][count] */, int32_t nlimbs);
+/* fhesi_ct_noise_batch channel by channel, channel c with p = p_c: a logical ciphertext is as good as its worst channel (the minimum over c) */
+int fhesi_ct_noise_int_batch(fhesi_ctx* ctx, fhesi_slots_basis* b, const fhesi_dcrt* sk1, int32_t logQ, const uint64_t* ct_dev /* [k][count] */, int32_t nlimbs, int64_t count,
+                             int32_t* budget_host /* [k][count] */);
 
 /* ---- prepared plaintext operands: a ciphertext combined with PLAINTEXT slot values on the device -- a mask, a model applied to encrypted data
  * (y = sum_j theta_j o x_j + b), a diagonal of a plaintext matrix (fhe-si_amd/csrc/kernels_plain.hip, capi_ct.hip).  An extension of the mirror's
