@@ -329,7 +329,7 @@ extern "C" int fhesi_ctx_destroy(fhesi_ctx* c) {
   for (auto& r : c->prof) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   c->prof.clear();
   bluestein_destroy(c);
-  for (auto& kv : c->crt_cache) { hipFree(kv.second->d_blob); if (kv.second->d_flags) hipFree(kv.second->d_flags); delete kv.second; }
+  for (auto& kv : c->crt_cache) { hipFree(kv.second->d_blob); delete kv.second; }
   for (auto& kv : c->pow64_cache) hipFree(kv.second);
   for (auto& kv : c->scalar_cache) hipFree(kv.second);
   aux32_free(c);

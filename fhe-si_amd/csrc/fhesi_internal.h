@@ -54,8 +54,6 @@ struct CrtTables {
   // tables of the sum form x = sum_i y_i M_i - kappa P (crt_sum_kernel): M_i = P / q_i, y_i = r_i c_i mod q_i, c_i = M_i^-1 mod q_i
   u64* d_M = nullptr;                  // [nidx][W]
   u64* d_cinv = nullptr;               // [nidx][3]   c_i, floor(c_i 2^128 / q_i) as (hi, lo)
-  mutable unsigned char* d_flags = nullptr;   // per-workgroup "recompute exactly" flags of the last launch (grow-only)
-  mutable size_t flags_cap = 0;
 };
 
 struct BluesteinTables;                // general-m path, defined in bluestein.hip
@@ -163,7 +161,10 @@ struct fhesi_ctx {
   //   0 digit rows / product operands / encrypt rows    1 inverse-transform scratch (tProd copy, dot output, automorph rows)
   //   2 limb-major parts / small-coefficient staging    3 automorph source rows / encrypt public key
   //   4 wave sums, per-call constants, noise maxima      5 tProd of a chunk / message staging
-  //   6 row transforms above 2^14 (two-pass, bit reversal)   7 Bluestein slot map / wave operands
+  //   6 row transforms above 2^14 (two-pass, bit reversal); the per-workgroup clean-up flags of the CRT kernels that decide most coefficients from a
+  //     sum and leave the rest to an exact pass (launch_crt_sum, crt32_scale_kernel): written by the first kernel once the inverse transform's use
+  //     of the slot is dead, read by the clean-up launched right behind it on the same stream -- per lane, like every slot
+  //   7 Bluestein slot map / wave operands
   //   8 Bluestein convolution buffer, index lists        9 Bluestein inverse output, scalar lists (no Bluestein call in between)
   //   10 auxiliary-prime dot product output (kernels_ksaux.hip)      11 staging of host batches (fhesi_ct_mul_relin_batch)
   //   (the slot layer borrows 8 for its convolution buffer / basis residues, 9 for slot values and 5 for message polynomials -- slots_stage_host,

@@ -600,22 +600,21 @@ static int launch_crt_sum(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows,
                           u64* d_out, int nl_out) {
   const int TB = 128;
   dim3 grid((unsigned)((ctx->phim + TB - 1) / TB), (unsigned)npolys);
-  const size_t need = (size_t)grid.x * grid.y;
-  if (need > t->flags_cap) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (t->d_flags) HIP_TRY(hipFree(t->d_flags));
-    HIP_TRY(hipMalloc(&t->d_flags, need));
-    t->flags_cap = need;
-  }
+  // the per-workgroup "recompute exactly" flags live in the workspace of the lane that runs this launch (like crt32_scale_kernel's,
+  // kernels_tensor32.hip): with option lanes = 2 both halves of a batch convert through the same tables at the same time, and a buffer kept
+  // with the tables would let one lane's first kernel overwrite the flags the other lane's clean-up has yet to read
+  void* d_fl;
+  FHESI_TRY(ws_reserve(ctx, 6, (size_t)grid.x * grid.y, &d_fl));
+  unsigned char* fl = (unsigned char*)d_fl;
   if (mode == 1) PROF_KERNEL(ctx, PROF_CRT, crt_sum_kernel<K, W, LQ, true>); else PROF_KERNEL(ctx, PROF_CRT, crt_sum_kernel<K, W, LQ, false>);
   if (mode == 1) crt_sum_kernel<K, W, LQ, true><<<grid, TB, 0, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->d_idx, t->d_M, t->d_cinv, t->d_P + (size_t)K * W,
-                                                                               ctx->d_pc, mode, d_out, nl_out, t->d_flags);
+                                                                               ctx->d_pc, mode, d_out, nl_out, fl);
   else crt_sum_kernel<K, W, LQ, false><<<grid, TB, 0, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->d_idx, t->d_M, t->d_cinv, t->d_P + (size_t)K * W,
-                                                                      ctx->d_pc, mode, d_out, nl_out, t->d_flags);
+                                                                      ctx->d_pc, mode, d_out, nl_out, fl);
   HIP_TRY(hipGetLastError());
   // exact clean-up of the flagged workgroups (normally none: every workgroup of this launch returns at once)
   if (ctx->opt.crt_skip_cleanup) return 0;      // test hook: shows that a crafted input really needs the clean-up
-  return launch_crt_t<K, K, W, LQ>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, 0, LQ, d_out, nl_out, t->d_flags);
+  return launch_crt_t<K, K, W, LQ>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, 0, LQ, d_out, nl_out, fl);
 }
 
 // ----------------------------------------------------------------------------------------- key switch, limb mode: recombination
