@@ -11,11 +11,14 @@
 //   ntt32_fwd_kernel3     the rows' forward transforms (ntt32_core.inc)
 //   ntt32_inv_kernel3<.., TENSOR>   element-wise products formed in the loader of the inverse transform (no tensor kernel, no rows
 //                         written in between)
-//   crt32_scale_kernel    x = sum_i y_i M_i - kappa M with M_i = M/p_i cut into words of 28 bits: y_i M_i[l] < 2^58, so the NP + 1 terms of
-//                         a word accumulate in 64 bits without carries; kappa from a 26-bit fixed-point sum; only the words from
-//                         28 * 14 = 392 bits upwards are formed -- the dropped part is below 2^429 and can change round(x / 2^512) only
-//                         when bits 448..511 of x + 2^511 are all ones: those workgroups are flagged and redone with every word
-//                         (EXACT), the pattern of crt_sum_kernel.
+//   crt32_scale_kernel    x = sum_i y_i M_i - kappa M with y_i = r_i (M/p_i)^-1 mod p_i and M_i = M/p_i cut into words of 28 bits: y_i M_i[l] < 2^58,
+//                         so the NP + 1 terms of a word accumulate in 64 bits without carries; kappa from a 26-bit fixed-point sum.  Rows of
+//                         2^14 arrive as y_i (T32_ROWS_CRT): the inverse transform's closing constants are (M/p_i)^-1 / n and that times the last
+//                         twiddle (T32Primes, per configuration), so the kernel starts at the multiply-adds.  Only the words from
+//                         28 * 16 = 448 bits upwards are formed -- the dropped part is below 64 * 2^30 * 2^448 = 2^484 and can change
+//                         round(x / 2^512) only when bits 484..511 of x + 2^511 are all ones (2^-27 per coefficient: about one workgroup in
+//                         three launches of 1024 products): those workgroups are flagged and redone with every word (EXACT), the pattern of
+//                         crt_sum_kernel.
 // Rows of 2^15 (n = 2^15, the stress shape: 70 primes for logQ = 1024): the head stage of the forward transform is taken inside
 // rns32_reduce_kernel<NL, true> (a thread converts coefficients j and j + 2^14 and stores the two butterfly outputs into the two sub-rows),
 // the tail of the inverse inside crt32_scale_kernel (its first multiplication takes (A + B) or (A - B) with the tail constant folded into
@@ -41,9 +44,9 @@ struct T32Config {
   u64 lift = 0;
   int nl = 0, logQ = 0, NP = 0, R = 28, WT = 0;
   bool generic = false;              // crt32_scale_generic_kernel (any logQ, fold) instead of the compiled shapes
-  T32Primes pr;
+  T32Primes pr;                      // pr.closing: the form this configuration's inverse leaves its rows in, and the only one its CRT kernels take (t32_crt)
   u32* d_rns = nullptr;              // [2][NP][2 nl + 6]: (s 2^(32k) mod p) k < 2 nl, -(s 2^(64 nl)) mod p, 2^32 mod p, floor(2^61 / p), p, head twiddle (w, w');  s = lift (class 0) or 1
-  Tw32* d_cinv = nullptr;            // [NP][2] (M / p_i)^-1 mod p_i  [times 1/2 | times psi^-brv(1) / 2: the tail of a 2^15-point inverse]
+  Tw32* d_cinv = nullptr;            // [NP][2] (M / p_i)^-1 mod p_i  [times 1/2 | times psi^-brv(1) / 2: the tail of a 2^15-point inverse]   (rows of 2^14: not read, pr.ninv carries it)
   u32* d_inv57 = nullptr;            // [NP] floor(2^57 / p_i)
   u32* d_Mw = nullptr;               // [NP + 1][WT]: M_i in words of R bits; row NP = 2^(R WT) - M
   ~T32Config() { hipFree(d_rns); hipFree(d_cinv); hipFree(d_inv57); hipFree(d_Mw); }
@@ -54,6 +57,7 @@ struct fhesi_tensor32 {
   std::vector<u32> primes;           // the primes with transform tables, largest first
   std::vector<Tw32> head, tail;      // per prime: psi^brv(1), psi^-brv(1)   (S = 1)
   std::vector<Tw32> head1;           // per prime: psi^brv(2), psi^brv(3)    (S = 2: the second head stage)
+  std::vector<u32> last;             // per prime: the twiddle of the inverse's last stage (S = 0: what entry 1 of d_inv held before the 1/n went in)
   Tw32* d_fwd = nullptr;             // [primes][2^S][2^14]
   Tw32* d_inv = nullptr;
   Tw32* d_ht = nullptr;              // S = 2: [primes][A32_HT] constants of the stand-alone tail pass (ntt32_tail2_kernel)
@@ -87,6 +91,21 @@ static u32 big_word(const Big& a, int l, int R) {          // word l of the radi
 static constexpr int T32_WT_512 = 38, T32_R_512 = 28;        // logQ = 512: words of 28 bits (up to 62 primes), 1064 bits per table row
 static constexpr int T32_WT_1024 = 82, T32_R_1024 = 26;      // logQ = 1024: words of 26 bits (up to 72 primes), 2132 bits per table row
 static constexpr int T32_GEN_NW = 24, T32_GEN_NWX = 40;      // generic kernel: words formed in the first pass / in the exact pass (logQ <= 512)
+static constexpr int T32_NP_28 = 62, T32_NP_26 = T32_MAXP;   // the most primes a table of 28-bit / 26-bit words is built for (t32_plan_search)
+// The first word the non-exact CRT pass forms.  A dropped word position l < J0 holds NP + 1 terms y_i M_i[l] (and kappa N[l]) with y_i, kappa
+// < 2^30 and the table word < 2^R, so everything below word J0 is less than (np_max + 1) 2^30 2^(R J0) <= 2^(tb + 30 + R J0), tb = bits of np_max + 1.
+// J0 is the largest value that keeps this at or below 2^(logQ - T32_WIN): the formed value F <= x < F + 2^(logQ - T32_WIN) then rounds like x unless
+// one carry into bit logQ - T32_WIN runs through to bit logQ - 1, i.e. unless bits logQ-28 .. logQ-1 of F + 2^(logQ-1) are all ones (the undecided test).
+// (tb >= 6 at both bounds, so R J0 <= logQ - 64 follows and the rounding limb of bits logQ-64 .. logQ-1 is always formed: asserted in the kernel.)
+static constexpr int T32_WIN = 28;
+__host__ __device__ constexpr int t32_j0(int LQ, int R, int np_max) {
+  int tb = 0;
+  while ((1 << tb) < np_max + 1) ++tb;
+  return LQ < T32_WIN + 30 + tb ? 0 : (LQ - T32_WIN - 30 - tb) / R;
+}
+static_assert(t32_j0(512, T32_R_512, T32_NP_28) == 16 && t32_j0(1024, T32_R_1024, T32_NP_26) == 36, "the compiled windows: words from bit 448 / 936");
+// undecided: bits logQ-28 .. logQ-1 of the rounding limb G (bits logQ-64 .. logQ-1 of F) read 0111...1, i.e. all ones once the rounding bit is added
+__device__ __forceinline__ int t32_undecided(u64 G) { return (G >> (64 - T32_WIN)) == (((u64)1 << (T32_WIN - 1)) - 1) ? 1 : 0; }
 
 struct T32Plan { int NP = 0; bool generic = false; };
 // The number of primes the tensor half needs (0: this shape does not run through it).
@@ -129,7 +148,7 @@ static T32Plan t32_plan_search(const fhesi_ctx* ctx, u64 p, int nlimbs, int logQ
   double chain = 0;
   for (int i = 0; i < ctx->L; ++i) chain += std::log2((double)ctx->q[i]);
   if (chain < TB + 1.5) return pl;
-  const int maxp = (compiled && logQ == 1024) ? T32_MAXP : 62;
+  const int maxp = (compiled && logQ == 1024) ? T32_NP_26 : T32_NP_28;
   // Primes of 30 bits keep M above 2^(TB + 3.5) (rounds 2-5).  Primes below 2^29 (option tensor_bits = 29) make do with 2^(TB + 1.5): |x / M| < 0.36
   // and the fixed-point sum behind kappa is short by less than NP 2^-25, so round(sum y_i / p_i) is still kappa -- 36 primes at the metric ring
   // (1043.5 bits for TB = 1042), 72 at the stress ring.
@@ -179,7 +198,7 @@ static int t32_ring(fhesi_ctx* ctx, const std::vector<u32>& primes) {
   const i64 n = (i64)A32_N << S;
   const size_t per_prime = (size_t)A32_N << S;
   std::vector<Tw32> hf((size_t)NP * per_prime, Tw32{0, 0}), hi((size_t)NP * per_prime, Tw32{0, 0}), ff((size_t)n), fi((size_t)n), ht((size_t)NP * A32_HT, Tw32{0, 0});
-  x->head.assign(NP, Tw32{0, 0}); x->tail.assign(NP, Tw32{0, 0}); x->head1.assign((size_t)NP * 2, Tw32{0, 0});
+  x->head.assign(NP, Tw32{0, 0}); x->tail.assign(NP, Tw32{0, 0}); x->head1.assign((size_t)NP * 2, Tw32{0, 0}); x->last.assign(NP, 0);
   for (int a = 0; a < NP; ++a) {
     const u64 p = primes[a];
     u64 psi = 0;
@@ -195,6 +214,7 @@ static int t32_ring(fhesi_ctx* ctx, const std::vector<u32>& primes) {
     if (!S) {
       std::transform(ff.begin(), ff.end(), hf.begin() + (size_t)a * per_prime, fwd_form);
       std::copy(fi.begin(), fi.end(), hi.begin() + (size_t)a * per_prime);
+      x->last[a] = fi[1].w;
     } else {
       // sub-block h runs stage s >= 1 of the row on its groups i = h 2^(s-1) + i':  own index m' + i' (m' = 2^(s-1))  <->  2 m' + h m' + i'  (as aux32_init)
       for (int h = 0; h < NS; ++h)
@@ -221,7 +241,8 @@ static int t32_ring(fhesi_ctx* ctx, const std::vector<u32>& primes) {
     }
   }
   // the inverse transform's last stage carries the final scaling (ntt32_inv_kernel3): entries 0 and 1 of every (prime, sub-block) table
-  // become 1/n and w / n, w = that sub-block's distance-16 twiddle (n = 2^14: the sub-transform's length)
+  // become 1/n and w / n, w = that sub-block's distance-16 twiddle (n = 2^14: the sub-transform's length).  (Rows of 2^14 do not read the pair:
+  // t32_config puts (M / p_i)^-1 / n and w (M / p_i)^-1 / n into T32Primes -- M depends on the configuration, this table does not.)
   for (size_t a = 0; a < primes.size(); ++a) {
     const u64 p = primes[a], ninv = hm::invmod((u64)A32_N % p, p);
     for (int h = 0; h < NS; ++h) {
@@ -270,7 +291,7 @@ static int t32_config(fhesi_ctx* ctx, u64 lift, int nlimbs, int logQ, i64 gmax, 
     const u64 p = primes[a];
     const u64 ninv = hm::invmod((u64)A32_N % p, p);     // of the 2^14-point (sub-)transform; the tail carries the other 1/2
     c->pr.p[a] = (u32)p;
-    c->pr.ninv[a] = (u32)ninv;
+    c->pr.ninv[a] = (u32)ninv;                          // (S = 0: times (M / p_i)^-1 below, once M is known)
     c->pr.ninv_p[a] = (u32)((ninv << 32) / p);
     c->pr.mu61[a] = (u32)(((u64)1 << (32 + t32_shift((u32)p))) / p);
     for (int cls = 0; cls < 2; ++cls) {
@@ -290,6 +311,7 @@ static int t32_config(fhesi_ctx* ctx, u64 lift, int nlimbs, int logQ, i64 gmax, 
     }
   }
   // CRT tables
+  c->pr.closing = S ? T32_ROWS_PLAIN : T32_ROWS_CRT;
   Big M{1};
   for (int a = 0; a < NP; ++a) M = big_mul_small(M, primes[a]);
   std::vector<Tw32> cinv((size_t)NP * 2);
@@ -300,6 +322,13 @@ static int t32_config(fhesi_ctx* ctx, u64 lift, int nlimbs, int logQ, i64 gmax, 
     const u64 p = primes[a];
     const u64 ci = hm::invmod(big_mod_small(Mi, p), p);
     auto tw = [&](u64 w) { return Tw32{(u32)w, (u32)((w << 32) / p)}; };
+    if (!S) {
+      // rows of 2^14: the product by ci is the inverse transform's own closing multiplication (ntt32_inv_kernel3, last stage: (X + Y) c and
+      // (X - Y)(w c) with c = ci / n), so its rows are y_i = x ci mod p_i, below p, and the CRT kernels multiply by nothing
+      const u64 cn = hm::mulmod(ci, c->pr.ninv[a], p), cw = hm::mulmod(cn, x->last[a], p);
+      c->pr.ninv[a] = (u32)cn; c->pr.ninv_p[a] = (u32)((cn << 32) / p);
+      c->pr.ninv_w[a] = (u32)cw; c->pr.ninv_w_p[a] = (u32)((cw << 32) / p);
+    }
     if (S != 1) cinv[(size_t)a * 2] = cinv[(size_t)a * 2 + 1] = tw(ci);      // (rows of 2^16: the tail stages are a pass of their own, ntt32_tail2_kernel)
     else {
       const u64 inv2 = (p + 1) / 2;
@@ -516,6 +545,7 @@ __global__ void __launch_bounds__(256) tensor_sum32_kernel(const u32* __restrict
 
 // ---------------------------------------------------------------------------------------------- residues -> round(x / 2^logQ) mod 2^logQ
 // rows [npolys][NP][n] (below p) -> out [npolys][LQ/64][n] limb-major positive residues (crt mode 1, kernels_crt.hip).
+// S = 0: the rows are y_i = x (M / p_i)^-1 mod p_i already (T32_ROWS_CRT, below p: the inverse transform's closing constants), cinv is not read.
 // S = 1: the rows are the two sub-inverses of 2^15-point rows; coefficient j < 2^14 is (A_j + B_j) / 2, coefficient j + 2^14 is
 // (A_j - B_j) psi^-brv(1) / 2 -- the constants are folded into the CRT constant of the first multiplication.
 template <int LQ, bool EXACT, int R, int WT, int S>
@@ -524,9 +554,14 @@ __global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict_
                                                            unsigned char* __restrict__ flags, int wm /* 1: out as 32-bit WORD rows [npolys][LQ/32][n] (what the 32-bit digit loader reads whole lines of) */) {
   static_assert((LQ & 63) == 0, "logQ a multiple of 64");
   constexpr int WU = (2 * LQ + R - 1) / R;            // words that reach below bit 2 logQ
-  constexpr int J0 = EXACT ? 0 : (LQ - 64 - 30 - 8) / R;     // first word formed: R J0 + 30 + log2(NP + 1) + 1 <= logQ - 64
+  constexpr int NPMAX = R == 28 ? T32_NP_28 : T32_NP_26;
+  constexpr int J0 = EXACT ? 0 : t32_j0(LQ, R, NPMAX);       // first word formed: the dropped part stays below bit logQ - 28 (t32_j0)
   constexpr int NW = WU - J0;
   static_assert(WU <= WT && J0 >= 0, "window");
+  static_assert(R == 28 || R == 26, "word widths the tables are built in");
+  static_assert(EXACT || ((u64)(NPMAX + 1) << 30) <= ((u64)1 << (LQ - T32_WIN - R * J0)), "dropped words stay below bit logQ - 28");
+  static_assert(EXACT || ((u64)(NPMAX + 1) << 30) > ((u64)1 << (LQ - T32_WIN - R * (J0 + 1) < 0 ? 0 : LQ - T32_WIN - R * (J0 + 1))), "... and J0 is the largest such");
+  static_assert(R * J0 <= LQ - 64, "the rounding limb is formed");
   const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
   if (EXACT && !flags[wg]) return;
   const i64 poly = blockIdx.y;
@@ -539,11 +574,12 @@ __global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict_
   u32 fsum = 0;
 #pragma unroll 2
   for (int i = 0; i < NP; ++i) {
-    const u32 p = pr.p[i];
-    u32 r = src[(i64)i * n];
-    if (S) { const u32 B = src[(i64)i * n + A32_N]; r = hi ? r + p - B : r + B; }
-    u32 y = mul_lazy32(r, cinv[2 * i + hi], p);
-    y = y >= p ? y - p : y;
+    u32 y = src[(i64)i * n];
+    if (S) {
+      const u32 p = pr.p[i], B = src[(i64)i * n + A32_N];
+      y = mul_lazy32(hi ? y + p - B : y + B, cinv[2 * i + hi], p);
+      y = y >= p ? y - p : y;
+    }
     fsum += __umulhi(y, inv57[i]);                    // (y / p) 2^25, low by less than one unit
     const u32* __restrict__ Mi = Mw + (i64)i * WT + J0;
 #pragma unroll
@@ -571,7 +607,7 @@ __global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict_
   };
   const u64 G = limb(LQ - 64);                         // bits logQ-64 .. logQ-1
   int undecided = 0;
-  if (!EXACT) undecided = (G == 0x7fffffffffffffffull) ? 1 : 0;
+  if (!EXACT) undecided = t32_undecided(G);
   u64 c = G >> 63;                                     // round half up: + bit logQ-1
   u64* __restrict__ o = out + poly * (LQ / 64) * n + j;
   u32* __restrict__ o32 = reinterpret_cast<u32*>(out) + poly * (LQ / 32) * n + j;
@@ -666,14 +702,25 @@ __global__ void __launch_bounds__(128) crt32_scale_generic_kernel(const u32* __r
         y = min(y, y - twop);
         y = min(y, y - p);
       } else {
+        // Whole rows, every value in [0, p), p < 2^30.  The fold adds three of them -- the row's own, p - b or b, and c or p - c (a position
+        // beyond the row gives b = 0, and p - 0 = p is still congruent to 0): at most 3p < 2^32, no wrap-around.
         u32 r = ri[eb[0]];
         if (FOLD) {
           const u32 b = ok[1] ? ri[eb[1]] : 0u, c = ri[eb[2]];
-          if (FOLD == 1) r = r + (p - b) + (neg[2] ? p - c : c);                    // r_j - r_(j+Q) - (-1)^floor(j/s) r_(phi + j mod s): below 3p (mul_lazy32 takes any u32)
-          else r = r + b + (p - c);                                                  // r_j + r_(j+m) - r_(phi + j mod s): below 3p
+          if (FOLD == 1) r = r + (p - b) + (neg[2] ? p - c : c);                    // r_j - r_(j+Q) - (-1)^floor(j/s) r_(phi + j mod s): in [0, 3p]
+          else r = r + b + (p - c);                                                  // r_j + r_(j+m) - r_(phi + j mod s): in [0, 3p)
         }
-        y = mul_lazy32(r, cinv[2 * i], p);
-        y = y >= p ? y - p : y;
+        if (pr.closing) {
+          // T32_ROWS_CRT (rows of 2^14): the values are y = x (M / p_i)^-1 mod p_i already, and the fold is linear, so the folded value IS the
+          // folded y modulo p.  It must be canonical: the multiply-adds need y < 2^30 (NP + 1 terms below 2^58 per 64-bit word) and kappa's sum
+          // takes y / p below 1.  [0, 3p] lies inside [0, 4p): one step to [0, 2p), one to [0, p).
+          if (FOLD) { r = min(r, r - twop); r = min(r, r - p); }
+          y = r;
+        } else {
+          // T32_ROWS_PLAIN (rows of 2^16 and longer, finished by their tail pass): the product by (M / p_i)^-1 (mul_lazy32 takes any u32)
+          y = mul_lazy32(r, cinv[2 * i], p);
+          y = y >= p ? y - p : y;
+        }
       }
       fsum += __umulhi(y, inv57[i]);
       const u32* __restrict__ Mi = Mw + (i64)i * WT + J0;
@@ -704,7 +751,7 @@ __global__ void __launch_bounds__(128) crt32_scale_generic_kernel(const u32* __r
       return v;
     };
     const u64 G = limb(LQ - 64);                         // bits logQ-64 .. logQ-1
-    if (!EXACT) undecided = (G == 0x7fffffffffffffffull) ? 1 : 0;
+    if (!EXACT) undecided = t32_undecided(G);
     u64 c = G >> 63;                                     // round half up: + bit logQ-1
     const int nlq = (LQ + 63) >> 6;
     u64* __restrict__ o = out + poly * nlq * n_out + j;
@@ -784,6 +831,7 @@ static int t32_fwd(fhesi_ctx* ctx, const T32Config* c, u32* d_r, i64 npolys) {
 }
 template <int LQ, int R, int WT, int S>
 static int t32_launch_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npolys, u64* d_parts, bool wm) {
+  if (c->NP > (R == 28 ? T32_NP_28 : T32_NP_26)) FHESI_FAIL("tensor32: %d primes exceed the bound the CRT window is derived from", c->NP);
   const i64 n = (i64)A32_N << S;
   const dim3 grid((unsigned)(n / 128), (unsigned)npolys);
   void* d_fl;
@@ -799,8 +847,13 @@ static int t32_launch_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i6
   return 0;
 }
 // d_t [npolys][NP][nrow] coefficient-form residues -> d_parts [npolys][ceil(logQ/64)][phi(m)]
-static int t32_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npolys, u64* d_parts, bool wm) {
+// form: what the caller's inverse transform left in d_t (the closing word of the T32Primes it was launched with).  The CRT kernels take one form
+// per row length -- T32_ROWS_CRT from rows of 2^14 (they multiply by nothing), T32_ROWS_PLAIN from longer rows (cinv carries the constant with
+// the tail's) -- and the other one would come out as a wrong ciphertext, silently: refused here.
+static int t32_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npolys, u32 form, u64* d_parts, bool wm) {
   const int S = ctx->tensor32->S, logQ = c->logQ;
+  const u32 takes = S ? T32_ROWS_PLAIN : T32_ROWS_CRT;
+  if (form != takes || c->pr.closing != takes) FHESI_FAIL("tensor32: rows in form %u (configuration: %u) handed to the CRT of rows of 2^%d, which takes form %u", form, c->pr.closing, A32_LOGN + S, takes);
   ProfScope prof(ctx, PROF_CRT, (double)npolys);
   if (!c->generic) {
     if (logQ == 512 && !S) return t32_launch_crt<512, T32_R_512, T32_WT_512, 0>(ctx, c, d_t, npolys, d_parts, wm);
@@ -808,11 +861,11 @@ static int t32_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npoly
     if (logQ == 1024 && !S) return t32_launch_crt<1024, T32_R_1024, T32_WT_1024, 0>(ctx, c, d_t, npolys, d_parts, wm);
     return t32_launch_crt<1024, T32_R_1024, T32_WT_1024, 1>(ctx, c, d_t, npolys, d_parts, wm);
   }
-  // the generic form: window from R J0 + 30 + log2(NP + 1) + 1 <= logQ - 64 up to bit 2 logQ
+  // the generic form: the same window at run time -- from the first word whose dropped part stays below bit logQ - 28 (t32_j0) up to bit 2 logQ
   const i64 n_out = ctx->phim, nrow = t32_nrow(ctx);
   const int WU = (2 * logQ + 27) / 28;
-  int J0 = (logQ - 64 - 38) / 28;
-  if (logQ < 64 + 38) J0 = 0;
+  if (c->NP > T32_NP_28) FHESI_FAIL("tensor32: %d primes exceed the bound the CRT window is derived from", c->NP);
+  const int J0 = t32_j0(logQ, 28, T32_NP_28);
   const int NW = WU - J0;
   if (NW > T32_GEN_NW || WU > T32_GEN_NWX || WU > c->WT) FHESI_FAIL("tensor32: logQ=%d outside the generic CRT window", logQ);
   const dim3 grid((unsigned)((n_out + 127) / 128), (unsigned)npolys);
@@ -873,7 +926,7 @@ int launch_tensor32(fhesi_ctx* ctx, u64 p, const u64* d_a, const u64* d_b, int n
     }
     HIP_TRY(hipGetLastError());
   }
-  return t32_crt(ctx, c, (const u32*)d_t, count * 3, d_parts, parts_wm);
+  return t32_crt(ctx, c, (const u32*)d_t, count * 3, c->pr.closing, d_parts, parts_wm);
 }
 
 // ---- sums of products per group (fhesi_ct_mul_sum_relin_dev)
@@ -920,5 +973,5 @@ int tensor32_sum_finish(fhesi_ctx* ctx, void* d_sum, i64 ng, u64* d_parts, bool 
     }
     HIP_TRY(hipGetLastError());
   }
-  return t32_crt(ctx, c, (const u32*)d_sum, ng * 3, d_parts, parts_wm);
+  return t32_crt(ctx, c, (const u32*)d_sum, ng * 3, c->pr.closing, d_parts, parts_wm);
 }

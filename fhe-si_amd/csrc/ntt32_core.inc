@@ -26,7 +26,11 @@ static constexpr int A32_HT = 8;
 static constexpr int T32_MAXP = 76;
 // mu61: floor(2^(32 + sh) / p) with sh = 29 for primes of 30 bits, sh = 28 for primes of 29 bits (t32_shift): the quotient estimate of a value
 // below 2^(32 + sh) is  umulhi(v >> sh, mu61), at most 2 short
-struct T32Primes { u32 p[T32_MAXP], ninv[T32_MAXP], ninv_p[T32_MAXP], mu61[T32_MAXP]; };
+// closing != 0 (rows of 2^14, T32_ROWS_CRT): the last stage of ntt32_inv_kernel3 takes its pair of constants from here instead of the shared
+// table's entries 0 and 1 -- ninv = (M / p_i)^-1 / n and ninv_w = that times the last stage's twiddle, each with its Shoup word: the rows leave
+// the inverse already multiplied by the CRT constant of their prime (which depends on the number of primes: per configuration, not per ring)
+struct T32Primes { u32 p[T32_MAXP], ninv[T32_MAXP], ninv_p[T32_MAXP], mu61[T32_MAXP], ninv_w[T32_MAXP], ninv_w_p[T32_MAXP]; u32 closing; };
+static constexpr u32 T32_ROWS_PLAIN = 0, T32_ROWS_CRT = 1;      // what a row of the tensor half's inverse holds: x / n, or x (M / p_i)^-1 / n
 __host__ __device__ __forceinline__ u32 t32_shift(u32 p) { return (p >> 29) ? 29u : 28u; }
 struct fhesi_aux32 {
   Aux32Primes pr;
@@ -821,7 +825,12 @@ __global__ void __launch_bounds__(A32_T, A32_INV_WAVES) ntt32_inv_kernel3(u32* _
     }
   }
   Tw32 tn, tnw;
-  if constexpr (MONT) { tn = Tw32{pr.ninv_m[a], pr.ninv_m_p[a]}; tnw = Tw32{pr.ninv_mw[a][h], pr.ninv_mw_p[a][h]}; } else { tn = tab[0]; tnw = tab[1]; }
+  if constexpr (MONT) { tn = Tw32{pr.ninv_m[a], pr.ninv_m_p[a]}; tnw = Tw32{pr.ninv_mw[a][h], pr.ninv_mw_p[a][h]}; }
+  else if constexpr (std::is_same<PR, T32Primes>::value) {
+    // the tensor half: the configuration's own pair (rows of 2^14: the CRT constant travels with 1/n), or the table's 1/n (longer rows)
+    if (pr.closing) { tn = Tw32{pr.ninv[a], pr.ninv_p[a]}; tnw = Tw32{pr.ninv_w[a], pr.ninv_w_p[a]}; } else { tn = tab[0]; tnw = tab[1]; }
+  }
+  else { tn = tab[0]; tnw = tab[1]; }
   auto mulc = [&](u32 y, Tw32 t) -> u32 {            // y any 32-bit value -> [0, 2p): quotient estimate, then y w - Q p as two chained multiply-adds
     const u32 Q = __umulhi(y, t.wp);
     return (u32)mad64(Q, 0u - p, mul64_s(y, t.w));
