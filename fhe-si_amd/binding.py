@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "fhesi_ctx_lin_class",
     "fhesi_plain_create_slots", "fhesi_plain_create_poly", "fhesi_plain_free", "fhesi_plain_info", "fhesi_plain_sum_bits", "fhesi_ct_plain_sum_dev", "fhesi_ct_add_slots_dev",
     "fhesi_ct_noise_batch", "fhesi_decrypt_noise_batch", "fhesi_ct_noise_int_batch",
+    "fhesi_ksk_hoist", "fhesi_ct_rotations_dev", "fhesi_ct_matvec_dev",
 ]
 ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8,
@@ -237,6 +238,9 @@ def _load():
         "fhesi_ct_noise_batch": [_vp, _vp, _i32, _u64, _vp, _i32, _i64, _vp, _vp],
         "fhesi_decrypt_noise_batch": [_vp, _vp, _i32, _u64, _vp, _i32, _i64, _vp, _vp, _vp],
         "fhesi_ct_noise_int_batch": [_vp, _vp, _vp, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_ksk_hoist": [_vp, _i64, _vp],
+        "fhesi_ct_rotations_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp, _i32],
+        "fhesi_ct_matvec_dev": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -552,6 +556,27 @@ class Context:
         sg = np.ascontiguousarray(seg, dtype=np.int32)
         _ck(_load().fhesi_ct_plain_sum_dev(self.h, plain.h, logQ, pool.ptr, npool, nlimbs, _p(ia), _p(ib), _p(sg), len(sg) - 1, out.ptr))
 
+    # ---- hoisted rotations: many automorphism key switches of one ciphertext (fhesi_ct_rotations_dev)
+    @staticmethod
+    def _hoisted_args(hoisted, ks):
+        ks = [int(k) for k in ks]
+        if len(hoisted) != len(ks):
+            raise ValueError("one matrix (or None, the identity) per k")
+        hs = (_vp * max(len(ks), 1))(*[h.h if h is not None else None for h in hoisted])
+        return hs, np.ascontiguousarray(ks, dtype=np.int64)
+
+    def ct_rotations_dev(self, hoisted, ks, logQ: int, src: DevBuf, nlimbs_in: int, count: int, out: DevBuf, nlimbs: int, decomp_bytes: int = 3):
+        """out[t][i] = Reduce((ApplyKeySwitch(hoisted[t], src[i])) >>= ks[t]): the rotations of every ciphertext by every k, the digits of a
+        ciphertext made once.  hoisted[t]: KeySwitchMatrix.hoist(ks[t]) of the matrix of the automorphism ks[t], or None with ks[t] = 1 (the
+        reduced copy).  out: [len(ks)][count][2][phim][nlimbs].  The library checks the arguments (FhesiError names what it refuses)."""
+        hs, ka = self._hoisted_args(hoisted, ks)
+        _ck(_load().fhesi_ct_rotations_dev(self.h, hs, _p(ka), len(ka), logQ, decomp_bytes, src.ptr, nlimbs_in, count, out.ptr, nlimbs))
+
+    def ct_matvec_dev(self, hoisted, ks, plain: "Plain", logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[i] = sum_t rot_t(src[i]) (*) plain[t]: ct_rotations_dev into a workspace pool, then ct_plain_sum_dev -- those calls' bits."""
+        hs, ka = self._hoisted_args(hoisted, ks)
+        _ck(_load().fhesi_ct_matvec_dev(self.h, hs, _p(ka), len(ka), plain.h, logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+
     def release_host_staging(self):
         """hand back the pinned + device staging ring the host-buffer calls keep between uses"""
         _ck(_load().fhesi_host_stage_release(self.h))
@@ -705,6 +730,25 @@ class SlotSpace:
         h = _vp()
         _ck(_load().fhesi_plain_create_slots(self.h, _p(vals), vals.shape[1], int(only_usable), vals.shape[0], C.byref(h)))
         return Plain(self.ctx, h)
+
+    # ---- hoisted rotations in slot terms: an amount t is the automorphism k = g^t mod m, as `>>=` takes it (t slots to the left in every row);
+    # "swap" is k = m - 1, the row swap of a two-row space
+    def rotation_k(self, amount) -> int:
+        if amount == "swap":
+            if self.rows != 2:
+                raise ValueError("only a two-row space swaps rows")
+            return self.ctx.m - 1
+        return pow(self.generator, int(amount), self.ctx.m)
+
+    def rotations(self, hoisted, amounts, logQ: int, src: DevBuf, nlimbs_in: int, count: int, out: DevBuf, nlimbs: int, decomp_bytes: int = 3):
+        """Context.ct_rotations_dev with k = rotation_k(amount): hoisted[t] is the matrix of that k, hoisted (KeySwitchMatrix.hoist), or None for
+        an amount whose k is 1 (no rotation).  out [len(amounts)][count] ciphertexts."""
+        self.ctx.ct_rotations_dev(hoisted, [self.rotation_k(a) for a in amounts], logQ, src, nlimbs_in, count, out, nlimbs, decomp_bytes)
+
+    def matvec(self, hoisted, amounts, plain: Plain, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[i] = sum_t rotate(src[i], amounts[t]) o plain[t] (Context.ct_matvec_dev): a matrix-vector product by diagonals, plain from
+        SlotSpace.plain with diagonal t in row t."""
+        self.ctx.ct_matvec_dev(hoisted, [self.rotation_k(a) for a in amounts], plain, logQ, src, nlimbs, count, out, decomp_bytes)
 
     def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nparts: int, nlimbs: int, count: int, vals: np.ndarray, only_usable: bool = True):
         """Ciphertext += Plaintext(vals) on unscaled ciphertexts; vals [nv][nvals] slot values, nv = 1 (one constant for all) or count."""
@@ -889,6 +933,18 @@ class SlotBasis:
         ngroups = len(seg) - 1
         for c in range(self.k):
             self.ctx.ct_plain_sum_dev(plains[c], logQ, _View(pool, c * npool * words), npool, nlimbs, a_idx, b_idx, seg, _View(out, c * ngroups * words))
+
+    def rotations(self, hoisted, amounts, logQ: int, src: DevBuf, nlimbs_in: int, count: int, out: DevBuf, nlimbs: int, decomp_bytes: int = 3):
+        """SlotSpace.rotations per channel (one key set serves every channel): src [k][count], out [k][len(amounts)][count] ciphertexts."""
+        win, wout = 2 * self.ctx.phim * nlimbs_in * 8, 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            self.channel(c).rotations(hoisted, amounts, logQ, _View(src, c * count * win), nlimbs_in, count, _View(out, c * len(amounts) * count * wout), nlimbs, decomp_bytes)
+
+    def matvec(self, hoisted, amounts, plains, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """SlotSpace.matvec per channel: src, out [k][count] logical ciphertexts, plains from SlotBasis.plain (diagonal t in row t)."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            self.channel(c).matvec(hoisted, amounts, plains[c], logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
 
     def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nlimbs: int, count: int, vals):
         """Ciphertext += integers, per channel: ct [k][count] two-part ciphertexts, vals [nv][nvals] integers, nv = 1 or count."""
@@ -1216,6 +1272,14 @@ class KeySwitchMatrix:
         c, b = C.c_int32(), C.c_int32()
         _ck(_load().fhesi_ksk_key_bits(self.h, C.byref(c), C.byref(b)))
         return bool(c.value), b.value
+
+    def hoist(self, k: int) -> "KeySwitchMatrix":
+        """The derived matrix sigma_k^-1(self) of the hoisted rotations (fhesi_ksk_hoist): self is the matrix of the automorphism k (source key
+        (1, s(X^k))); the result goes to Context.ct_rotations_dev / ct_matvec_dev with the same k and is an ordinary matrix everywhere else."""
+        out = KeySwitchMatrix.__new__(KeySwitchMatrix)
+        out.ctx, out.ncomp, out.ndigits, out.h, out.k = self.ctx, self.ncomp, self.ndigits, _vp(), int(k)
+        _ck(_load().fhesi_ksk_hoist(self.h, int(k), C.byref(out.h)))
+        return out
 
     def mark_dirty(self):
         """The rows were written through device_ptr (e.g. by a collective): derived tables are rebuilt at the next key switch."""

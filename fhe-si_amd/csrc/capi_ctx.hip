@@ -100,6 +100,7 @@ static const OptDesc kOptions[] = {
   {"tensor_bits", "FHESI_TENSOR_BITS", offsetof(CtxOptions, tensor_bits), false},
   {"dot32_k4", "FHESI_DOT32_K4", offsetof(CtxOptions, dot32_k4), false},
   {"parts_words", "FHESI_PARTS_WORDS", offsetof(CtxOptions, parts_words), false},
+  {"hoist_dot", "FHESI_HOIST_DOT", offsetof(CtxOptions, hoist_dot), false},
   {"automorph_rows", "FHESI_AUTOMORPH_ROWS", offsetof(CtxOptions, automorph_rows), false},
   {"ks_long_keys", "FHESI_KS_LONG_KEYS", offsetof(CtxOptions, ks_long_keys), false},
   {"host_chunk", "FHESI_HOST_CHUNK", offsetof(CtxOptions, host_chunk), true},

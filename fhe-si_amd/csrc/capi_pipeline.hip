@@ -99,42 +99,77 @@ extern "C" int fhesi_ct_mul_dev(fhesi_ctx* c, uint64_t p, const uint64_t* a, con
 }
 
 // ByteDecomp + DoubleCRT(digit polys) + DotProduct + toPoly + ReduceCoefficients (FHE-SI.cpp:244-256) from parts that are already
-// positive residues mod 2^logQ in limb-major layout [count*ncomp][nlq][n].  d_t: scratch for count*2 DoubleCRTs, needed by the per-prime
-// and the residue forms only (null: reserved here, workspace slot 1, when one of those runs -- the limb forms never touch it).
+// positive residues mod 2^logQ in limb-major layout [count*ncomp][nlq][n], in two halves: key_switch_digits leaves the digit rows in the
+// running form's layout (workspace slot 0) and reads no matrix; key_switch_finish is everything that does -- dot product, inverse rows and
+// recombination / CRT.  key_switch_tail runs one after the other; the hoisted rotations (below) run the first once and the second per matrix.
+// The form that runs for this matrix, with its auxiliary table built (ksaux_build borrows workspace slot 0: before any digit rows exist).
+static int key_switch_form(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, int* ks_mode_out) {
+  CrtTables* t;
+  FHESI_TRY(get_crt_tables(c, full_set(c), &t));
+  // Dot product through the two largest chain primes (kernels_ksaux.hip): 2 transforms per digit polynomial instead of L.
+  // option ks_direct keeps the per-prime dot product below (A/B measurements; also the path of every shape the other does not cover).
+  const int ks_mode = ksaux_mode(c, t, k->ncomp * k->ndigits, 8 * decomp_bytes, logQ);
+  fhesi_ksk* km = const_cast<fhesi_ksk*>(k);
+  km->last_form = ks_mode;
+  if (ks_mode != KS_MODE_DIRECT && (!k->aux_valid || k->aux_mode != ks_mode || k->aux_suborder != ntt_digits_suborder(c, 8 * decomp_bytes) || k->aux_logQ != logQ || k->aux_long_opt != c->opt.ks_long_keys))
+    FHESI_TRY(ksaux_build(c, km, 8 * decomp_bytes, logQ, ks_mode));
+  *ks_mode_out = ks_mode;
+  return 0;
+}
 // parts_wm: d_parts are 32-bit word rows (launch_tensor32 parts_wm) -- only the four-prime limb form reads those; the caller asks for them
 // only when ksaux_mode says that form runs.
-static int key_switch_tail(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, const u64* d_parts, int64_t count, u64* d_t,
-                           uint64_t* out, int32_t nlimbs, bool parts_wm = false) {
+static int key_switch_digits(fhesi_ctx* c, int ks_mode, int ncomp, int nd, int32_t logQ, int32_t decomp_bytes, const u64* d_parts, int64_t count, bool parts_wm, void** d_dig_out) {
   const i64 n = c->phim;
-  const int L = c->L, ncomp = k->ncomp, nd = k->ndigits, ncol = ncomp * nd, nlq = (logQ + 63) / 64;
+  const int L = c->L, ncol = ncomp * nd, nlq = (logQ + 63) / 64;
+  if (parts_wm && ks_mode != KS_MODE_LIMB32) FHESI_FAIL("key switch: word-major parts handed to a form that reads limb rows (internal)");
+  void* d_dig;
+  if (ks_mode == KS_MODE_LIMB32) {       // four 30-bit primes (kernels_aux32.hip): the buffer of the 60-bit forms, u32 rows (always 2^14 or 2^15 elements: four 4-byte residues = two 8-byte ones)
+    FHESI_TRY(ws_reserve(c, 0, (size_t)count * ncol * 2 * aux32_row_len(c) * 8, &d_dig));
+    FHESI_TRY(launch_ntt32_fwd_digits(c, d_parts, nlq, 8 * decomp_bytes, nd, count * ncomp, (u32*)d_dig, kDigitSubCt * ncol, parts_wm));
+  } else if (ks_mode != KS_MODE_DIRECT) {
+    FHESI_TRY(ws_reserve(c, 0, (size_t)count * ncol * 2 * n * 8, &d_dig));
+    FHESI_TRY(launch_ntt_fwd_digits(c, d_parts, nlq, logQ, 8 * decomp_bytes, nd, count * ncomp, (u64*)d_dig, 0, 2, 2));
+  } else {
+    // ByteDecomp + DoubleCRT(digit polys)   (Ciphertext.cpp:82-121, FHE-SI.cpp:244-249)
+    FHESI_TRY(ws_reserve(c, 0, (size_t)count * ncol * L * n * 8, &d_dig));
+    if (c->pow2) FHESI_TRY(launch_ntt_fwd_digits(c, d_parts, nlq, logQ, 8 * decomp_bytes, nd, count * ncomp, (u64*)d_dig));
+    else {
+      FHESI_TRY(launch_digits(c, d_parts, nlq, logQ, 8 * decomp_bytes, nd, count * ncomp, (u64*)d_dig));
+      const std::vector<int> all = full_set(c);
+      FHESI_TRY(row_fwd(c, (u64*)d_dig, count * ncol, L, nullptr, all.data()));
+    }
+  }
+  if (c->mark_mid) { HIP_TRY(hipEventRecord(c->ev_mid, c->stream)); c->mark_mid = false; }
+  *d_dig_out = d_dig;
+  return 0;
+}
+// the four-prime form behind its dot product: d_o [count*2*R][4][row] -> inverse rows -> recombination
+static int key_switch_close32(fhesi_ctx* c, const CrtTables* t, const fhesi_ksk* k, u32* d_o, int64_t count, bool mont, uint64_t* out, int32_t nlimbs) {
+  const bool fold_tail = ks_recombine_takes_tail(c, t, k);      // (rows of 2^15 at the stress chain: the inverse's tail stage runs in the recombination's loader)
+  FHESI_TRY(launch_ntt32_inv(c, d_o, count * 2 * k->aux_rows, 4, 0, mont, !fold_tail));
+  return launch_ks_recombine(c, t, k, (const u64*)d_o, count * 2, (u64*)out, nlimbs, fold_tail);
+}
+// d_t: scratch for count*2 DoubleCRTs, needed by the per-prime and the residue forms only (null: reserved here, workspace slot 1, when one of
+// those runs -- the limb forms never touch it).
+static int key_switch_finish(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, int32_t logQ, int32_t decomp_bytes, const void* d_dig, int64_t count, u64* d_t,
+                             uint64_t* out, int32_t nlimbs) {
+  const i64 n = c->phim;
+  const int L = c->L, ncol = k->ncomp * k->ndigits;
   const std::vector<int> all = full_set(c);
   CrtTables* t;
   FHESI_TRY(get_crt_tables(c, all, &t));
-  // Dot product through the two largest chain primes (kernels_ksaux.hip): 2 transforms per digit polynomial instead of L.
-  // option ks_direct keeps the per-prime dot product below (A/B measurements; also the path of every shape the other does not cover).
-  const int ks_mode = ksaux_mode(c, t, ncol, 8 * decomp_bytes, logQ);
-  const_cast<fhesi_ksk*>(k)->last_form = ks_mode;
-  if (parts_wm && ks_mode != KS_MODE_LIMB32) FHESI_FAIL("key switch: word-major parts handed to a form that reads limb rows (internal)");
   if (ks_mode != KS_MODE_DIRECT) {
     fhesi_ksk* km = const_cast<fhesi_ksk*>(k);
-    if (!k->aux_valid || k->aux_mode != ks_mode || k->aux_suborder != ntt_digits_suborder(c, 8 * decomp_bytes) || k->aux_logQ != logQ || k->aux_long_opt != c->opt.ks_long_keys) FHESI_TRY(ksaux_build(c, km, 8 * decomp_bytes, logQ, ks_mode));
     const int R = k->aux_rows;        // L chain-prime residues, or the limbs of the key's integer coefficients (limb mode)
-    const i64 nrow = k->aux32 ? aux32_row_len(c) : n;      // the 32-bit auxiliary rows always have 2^14 elements (four 4-byte residues = two 8-byte ones)
-    void *d_dig, *d_o;
-    FHESI_TRY(ws_reserve(c, 0, (size_t)count * ncol * 2 * nrow * 8, &d_dig));
+    const i64 nrow = k->aux32 ? aux32_row_len(c) : n;      // the 32-bit auxiliary rows always have 2^14 or 2^15 elements
+    if (k->aux32 != (ks_mode == KS_MODE_LIMB32)) FHESI_FAIL("key switch: the matrix's table does not match the running form (internal)");
+    void* d_o;
     FHESI_TRY(ws_reserve(c, 10, (size_t)count * 2 * R * 2 * nrow * 8, &d_o));
-    if (parts_wm && !k->aux32) FHESI_FAIL("key switch: word-major parts without the four-prime table (internal)");
-    if (k->aux32) {       // four 30-bit primes (kernels_aux32.hip): the same buffer sizes, u32 rows
-      FHESI_TRY(launch_ntt32_fwd_digits(c, d_parts, nlq, 8 * decomp_bytes, nd, count * ncomp, (u32*)d_dig, kDigitSubCt * ncol, parts_wm));
-      if (c->mark_mid) { HIP_TRY(hipEventRecord(c->ev_mid, c->stream)); c->mark_mid = false; }
+    if (k->aux32) {
       bool mont = true;                 // dot32_kernel2 leaves the factor 2^-32 of its Montgomery step; the matrix-core form does not
       FHESI_TRY(launch_dot32(c, km, (const u32*)d_dig, ncol, count, (u32*)d_o, &mont));
-      const bool fold_tail = ks_recombine_takes_tail(c, t, k);      // (rows of 2^15 at the stress chain: the inverse's tail stage runs in the recombination's loader)
-      FHESI_TRY(launch_ntt32_inv(c, (u32*)d_o, count * 2 * R, 4, 0, mont, !fold_tail));
-      return launch_ks_recombine(c, t, k, (const u64*)d_o, count * 2, (u64*)out, nlimbs, fold_tail);
+      return key_switch_close32(c, t, k, (u32*)d_o, count, mont, out, nlimbs);
     }
-    FHESI_TRY(launch_ntt_fwd_digits(c, d_parts, nlq, logQ, 8 * decomp_bytes, nd, count * ncomp, (u64*)d_dig, 0, 2, 2));
-    if (c->mark_mid) { HIP_TRY(hipEventRecord(c->ev_mid, c->stream)); c->mark_mid = false; }
     FHESI_TRY(launch_dot_aux(c, k, (const u64*)d_dig, ncol, count, (u64*)d_o));
     FHESI_TRY(launch_ntt_inv(c, (u64*)d_o, count * 2 * R, 2, (const int*)(k->d_aux_consts + L), !k->aux_suborder));
     if (k->aux_limb_bits) return launch_ks_recombine(c, t, k, (const u64*)d_o, count * 2, (u64*)out, nlimbs);
@@ -142,22 +177,21 @@ static int key_switch_tail(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32
     FHESI_TRY(launch_aux_crt(c, k, (const u64*)d_o, d_t, count * 2 * L));
     return launch_crt(c, t, d_t, L, nullptr, count * 2, 2, 0, logQ, (u64*)out, nlimbs);
   }
-  // ByteDecomp + DoubleCRT(digit polys)   (Ciphertext.cpp:82-121, FHE-SI.cpp:244-249)
   if (!d_t) { void* q; FHESI_TRY(ws_reserve(c, 1, (size_t)count * 2 * L * n * 8, &q)); d_t = (u64*)q; }
-  void* d_dig;
-  FHESI_TRY(ws_reserve(c, 0, (size_t)count * ncol * L * n * 8, &d_dig));
-  if (c->pow2) FHESI_TRY(launch_ntt_fwd_digits(c, d_parts, nlq, logQ, 8 * decomp_bytes, nd, count * ncomp, (u64*)d_dig));
-  else {
-    FHESI_TRY(launch_digits(c, d_parts, nlq, logQ, 8 * decomp_bytes, nd, count * ncomp, (u64*)d_dig));
-    FHESI_TRY(row_fwd(c, (u64*)d_dig, count * ncol, L, nullptr, all.data()));
-  }
-  if (c->mark_mid) { HIP_TRY(hipEventRecord(c->ev_mid, c->stream)); c->mark_mid = false; }
   // DotProduct with both key rows (FHE-SI.cpp:251-254)
   FHESI_TRY(launch_dot_accum(c, k->d_rows, (const u64*)d_dig, ncol, count, d_t, 0, 0, c->pow2 && ntt_digits_suborder(c, 8 * decomp_bytes)));
   // toPoly + ReduceCoefficients (FHE-SI.cpp:255-256)
   FHESI_TRY(row_inv(c, d_t, count * 2, L, nullptr, all.data()));
   FHESI_TRY(launch_crt(c, t, d_t, L, nullptr, count * 2, 2, 0, logQ, (u64*)out, nlimbs));
   return 0;
+}
+static int key_switch_tail(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, const u64* d_parts, int64_t count, u64* d_t,
+                           uint64_t* out, int32_t nlimbs, bool parts_wm = false) {
+  int ks_mode;
+  FHESI_TRY(key_switch_form(c, k, logQ, decomp_bytes, &ks_mode));
+  void* d_dig;
+  FHESI_TRY(key_switch_digits(c, ks_mode, k->ncomp, k->ndigits, logQ, decomp_bytes, d_parts, count, parts_wm, &d_dig));
+  return key_switch_finish(c, k, ks_mode, logQ, decomp_bytes, d_dig, count, d_t, out, nlimbs);
 }
 
 static int key_switch_args(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, int32_t nlimbs) {
@@ -269,6 +303,213 @@ extern "C" int fhesi_ct_automorph_key_switch_dev(fhesi_ctx* c, const fhesi_ksk* 
   // toPoly (centred modulo the whole chain), then Reduce(..., positive) of ByteDecompPart (Ciphertext.cpp:94)
   FHESI_TRY(launch_crt(c, t, d_rows, c->L, nullptr, count * ncomp, 3, 0, logQ, (u64*)d_parts, nlq));
   return key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, count, d_rows, out, nlimbs);
+}
+
+// --------------------------------------------------------------------------------------------- hoisted rotations
+// sigma_k is a ring map, so  sum_j sigma_k(D_j(c)) W_k[j] = sigma_k( sum_j D_j(c) W'_k[j] )  with W'_k = sigma_k^-1(W_k), every column, both rows
+// (DESIGN.md 9a): the digits of the UNTOUCHED ciphertext are decomposed and transformed once and serve every rotation; a rotation is one dot
+// product with its derived matrix, one inverse, one recombination and the signed gather of two polynomials.
+static i64 inv_mod_m(i64 k, i64 m) {            // k in Z_m^* (checked by the caller)
+  i64 a = k % m, b = m, x0 = 1, x1 = 0;
+  while (b) { const i64 q = a / b; i64 t = a - q * b; a = b; b = t; t = x0 - q * x1; x0 = x1; x1 = t; }
+  return ((x0 % m) + m) % m;
+}
+extern "C" int fhesi_ksk_hoist(const fhesi_ksk* k, int64_t kk, fhesi_ksk** out) {
+  if (!k || !out) FHESI_FAIL("ksk_hoist: null argument");
+  fhesi_ctx* c = k->ctx;
+  CHECK_CTX(c);
+  *out = nullptr;
+  if (k->ncomp != 2) FHESI_FAIL("ksk_hoist: the matrix has %d source components, a rotation matrix (source key (1, s(X^k))) has 2", k->ncomp);
+  if (kk <= 0 || kk >= c->m || c->zms_idx[kk] < 0) FHESI_FAIL("ksk_hoist: k=%lld is not in Zm*", (long long)kk);
+  fhesi_ksk* h;
+  FHESI_TRY(fhesi_ksk_create(c, k->ncomp, k->ndigits, &h));
+  // DoubleCRT::automorph by k^-1 on every evaluation row [2][ncol][L][phi(m)]: the same gather on every ring and for every prime
+  const i64 nrows = (i64)2 * k->ncomp * k->ndigits * c->L, kinv = inv_mod_m(kk, c->m), step = 32768;
+  int rc = 0;
+  for (i64 r0 = 0; r0 < nrows && !rc; r0 += step) rc = launch_automorph(c, h->d_rows + r0 * c->phim, k->d_rows + r0 * c->phim, std::min(step, nrows - r0), kinv);
+  if (rc) { fhesi_ksk_free(h); return rc; }
+  h->hoist_k = kk;
+  *out = h;
+  return 0;
+}
+
+// reduce_logq(Ciphertext >>= k) of count unscaled two-part ciphertexts: the signed gather where the ring has one (any input size: the gather's
+// two's complement sum is exact modulo 2^(64 nlimbs), a multiple of 2^logQ), the evaluation rows otherwise; k = 1 is the reduced copy
+static int rotation_close(fhesi_ctx* c, int64_t kk, int32_t logQ, const u64* src, int32_t nl_src, int64_t count, u64* out, int32_t nlimbs) {
+  if (!c->opt.automorph_rows) {
+    const int r = launch_ct_automorph_parts(c, src, nl_src, count * 2, kk, 0, out, nlimbs);
+    if (r == 1) return 1;
+    if (r == 0) return launch_ct_mul_long(c, out, count * 2 * c->phim, nlimbs, logQ, 1);      // (times one: the centred residue modulo 2^logQ, in place)
+  }
+  u64* d_rows;
+  FHESI_TRY(automorph_rows(c, kk, src, 2, nl_src, count, &d_rows));
+  CrtTables* t;
+  FHESI_TRY(get_crt_tables(c, full_set(c), &t));
+  return launch_crt(c, t, d_rows, c->L, nullptr, count * 2, 2, 0, logQ, out, nlimbs);
+}
+static int rotations_args(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes, int32_t nlimbs_in, int64_t count, int32_t nlimbs) {
+  if (nk < 0 || count < 0) FHESI_FAIL("ct_rotations: negative count");
+  if (nk && (!hoisted || !ks)) FHESI_FAIL("ct_rotations: null argument");
+  if (nlimbs_in < 1) FHESI_FAIL("ct_rotations: bad shape (%d input limbs)", nlimbs_in);
+  if (logQ < 1 || nlimbs < 1 || nlimbs * 64 < logQ) FHESI_FAIL("ct_rotations: output coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
+  if (nlimbs > 32) FHESI_FAIL("ct_rotations: ciphertext coefficients of %d limbs exceed the supported 32", nlimbs);
+  for (int t = 0; t < nk; ++t) {
+    const fhesi_ksk* k = hoisted[t];
+    if (!k) {
+      if (ks[t] != 1) FHESI_FAIL("ct_rotations: rotation %d has no matrix and k=%lld (only k = 1, the identity, goes without one)", t, (long long)ks[t]);
+      continue;
+    }
+    if (k->ctx != c) FHESI_FAIL("ct_rotations: the matrix of rotation %d belongs to another context", t);
+    if (!k->hoist_k) FHESI_FAIL("ct_rotations: the matrix of rotation %d was not made by fhesi_ksk_hoist", t);
+    if (k->hoist_k != ks[t]) FHESI_FAIL("ct_rotations: the matrix of rotation %d was hoisted for k=%lld, the call asks k=%lld", t, (long long)k->hoist_k, (long long)ks[t]);
+    FHESI_TRY(key_switch_args(c, k, logQ, decomp_bytes, nlimbs));
+  }
+  return 0;
+}
+// out[t][i], i < count, at out + (t * count + i) ciphertexts; every argument checked by the caller
+static int rotations_run(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                         int32_t nlimbs_in, int64_t count, uint64_t* out, int32_t nlimbs) {
+  const i64 n = c->phim;
+  const int nlq = (logQ + 63) / 64;
+  const size_t ct_in = (size_t)2 * n * nlimbs_in, ct_out = (size_t)2 * n * nlimbs;
+  CrtTables* t_all;
+  FHESI_TRY(get_crt_tables(c, full_set(c), &t_all));
+  // the matrices, with their tables built before any digit row exists (ksaux_build borrows the digits' workspace slot)
+  std::vector<int> keyed;
+  int ks_mode = -1, nd = 0;
+  for (int t = 0; t < nk; ++t) {
+    if (!hoisted[t]) continue;
+    int mode;
+    FHESI_TRY(key_switch_form(c, hoisted[t], logQ, decomp_bytes, &mode));
+    if (ks_mode >= 0 && mode != ks_mode) FHESI_FAIL("ct_rotations: matrices of one call run different forms (internal)");
+    ks_mode = mode; nd = hoisted[t]->ndigits;
+    keyed.push_back(t);
+  }
+  const int ncol = 2 * nd;
+  const int how = c->opt.hoist_dot;
+  if (how == 2 && !keyed.empty() && ks_mode != KS_MODE_LIMB32) FHESI_FAIL("ct_rotations: hoist_dot = 2 (the multi-matrix dot product) needs the four-prime limb form, this ring and chain run form %d", ks_mode);
+  const i64 chunk = std::min<i64>(16384, keyed.empty() ? std::max<i64>(count, 1) : batch_chunk(c, ncol, ks_mode == KS_MODE_LIMB32, count));      // (the gather puts two polynomials per ciphertext on grid.y)
+  // automatic, as measured at (2^15, logQ 512), 44 columns, 7 limbs (profiles/hoist_bench.json, profiles/hoist_crossover.json): the multi-matrix kernel is the
+  // faster one at every batch up to 64 ciphertexts whatever the number of matrices (a tile no deeper than the batch below 8; above, dot32_kernel4's groups of
+  // 48 ciphertexts leave a ragged last group), with 4 matrices up to 256 (3-5 %; with one matrix the per-matrix launch is 1-2 % ahead from 128 on), and at
+  // 1024 -- the batch dot32_kernel4 is tuned for -- the per-matrix launches win by 3-4 %
+  const i64 cmax = std::min(chunk, count);
+  const bool multi = ks_mode == KS_MODE_LIMB32 && (how == 2 || (how == 0 && (cmax <= 64 || (keyed.size() >= 4 && cmax <= 256))));
+  // groups of one table shape (limb count, limb width, centred or not, folded or not): one launch covers one shape
+  struct Group { std::vector<int> ts; };
+  std::vector<Group> groups;
+  if (multi) {
+    auto same = [&](const fhesi_ksk* a, const fhesi_ksk* b) {
+      return a->aux_rows == b->aux_rows && a->aux_limb_bits == b->aux_limb_bits && a->aux_centred == b->aux_centred && a->aux_fold == b->aux_fold &&
+             ks_recombine_takes_tail(c, t_all, a) == ks_recombine_takes_tail(c, t_all, b);
+    };
+    for (int t : keyed) {
+      Group* g = nullptr;
+      for (Group& q : groups) if (same(hoisted[q.ts[0]], hoisted[t])) { g = &q; break; }
+      if (!g) { groups.emplace_back(); g = &groups.back(); }
+      g->ts.push_back(t);
+    }
+  }
+  // matrices per launch: the dot outputs of (matrices x ciphertexts) stay within what a full chunk of the batch pipeline puts into workspace slot 10
+  const i64 full = keyed.empty() ? 1 : batch_chunk(c, ncol, ks_mode == KS_MODE_LIMB32, -1);
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    const u64* src = (const u64*)in + done * ct_in;
+    auto dst = [&](int t) { return (u64*)out + ((size_t)t * count + done) * ct_out; };
+    for (int t = 0; t < nk; ++t) if (!hoisted[t]) FHESI_TRY(rotation_close(c, 1, logQ, src, nlimbs_in, cnt, dst(t), nlimbs));
+    if (keyed.empty()) continue;
+    // ApplyKeySwitch on the unscaled ciphertext as it is: ByteDecomp needs the positive residues limb-major
+    void *d_parts, *d_dig, *d_pre;
+    FHESI_TRY(ws_reserve(c, 2, (size_t)cnt * 2 * nlq * n * 8, &d_parts));
+    int r = c->opt.automorph_rows ? 2 : launch_ct_automorph_parts(c, src, nlimbs_in, cnt * 2, 1, logQ, (u64*)d_parts, nlq);
+    if (r == 1) return 1;
+    if (r == 2) {
+      u64* d_rows;
+      FHESI_TRY(automorph_rows(c, 1, src, 2, nlimbs_in, cnt, &d_rows));
+      FHESI_TRY(launch_crt(c, t_all, d_rows, c->L, nullptr, cnt * 2, 3, 0, logQ, (u64*)d_parts, nlq));
+    }
+    FHESI_TRY(key_switch_digits(c, ks_mode, 2, nd, logQ, decomp_bytes, (const u64*)d_parts, cnt, false, &d_dig));
+    FHESI_TRY(ws_reserve(c, 4, (size_t)cnt * ct_out * 8, &d_pre));      // one rotation's key-switched ciphertexts, in front of their sigma_k
+    if (!multi) {
+      for (int t : keyed) {
+        FHESI_TRY(key_switch_finish(c, hoisted[t], ks_mode, logQ, decomp_bytes, d_dig, cnt, nullptr, (uint64_t*)d_pre, nlimbs));
+        FHESI_TRY(rotation_close(c, ks[t], logQ, (const u64*)d_pre, nlimbs, cnt, dst(t), nlimbs));
+      }
+      continue;
+    }
+    const i64 per = std::min<i64>(kDot32MultiMax, std::max<i64>(1, full / cnt));
+    std::vector<const fhesi_ksk*> batch;
+    for (const Group& g : groups) {
+      const fhesi_ksk* k0 = hoisted[g.ts[0]];
+      const int R = k0->aux_rows;
+      const size_t o_words = (size_t)cnt * 2 * R * 4 * aux32_row_len(c);      // u32 words of one matrix's outputs
+      const bool fold_tail = ks_recombine_takes_tail(c, t_all, k0);
+      for (size_t j0 = 0; j0 < g.ts.size(); j0 += (size_t)per) {
+        const int nj = (int)std::min<size_t>((size_t)per, g.ts.size() - j0);
+        batch.clear();
+        for (int j = 0; j < nj; ++j) batch.push_back(hoisted[g.ts[j0 + j]]);
+        void* d_o;
+        FHESI_TRY(ws_reserve(c, 10, (size_t)nj * o_words * 4, &d_o));
+        bool mont = true;
+        FHESI_TRY(launch_dot32_multi(c, batch.data(), nj, (const u32*)d_dig, ncol, cnt, (u32*)d_o, &mont));
+        FHESI_TRY(launch_ntt32_inv(c, (u32*)d_o, (i64)nj * cnt * 2 * R, 4, 0, mont, !fold_tail));
+        for (int j = 0; j < nj; ++j) {
+          const int t = g.ts[j0 + j];
+          FHESI_TRY(launch_ks_recombine(c, t_all, hoisted[t], (const u64*)((const u32*)d_o + (size_t)j * o_words), cnt * 2, (u64*)d_pre, nlimbs, fold_tail));
+          FHESI_TRY(rotation_close(c, ks[t], logQ, (const u64*)d_pre, nlimbs, cnt, dst(t), nlimbs));
+        }
+      }
+    }
+  }
+  return 0;
+}
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+extern "C" int fhesi_ct_rotations_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes,
+                                      const uint64_t* in, int32_t nlimbs_in, int64_t count, uint64_t* out, int32_t nlimbs) {
+  CHECK_CTX(c);
+  FHESI_TRY(rotations_args(c, hoisted, ks, nk, logQ, decomp_bytes, nlimbs_in, count, nlimbs));
+  if (!count || !nk) return 0;
+  if (!in || !out) FHESI_FAIL("ct_rotations: null argument");
+  if (ranges_overlap(in, (size_t)count * 2 * c->phim * nlimbs_in * 8, out, (size_t)nk * count * 2 * c->phim * nlimbs * 8)) FHESI_FAIL("ct_rotations: out overlaps in");
+  return rotations_run(c, hoisted, ks, nk, logQ, decomp_bytes, in, nlimbs_in, count, out, nlimbs);
+}
+// out[i] = sum_t rot_t(in[i]) (*) w[t]: the rotations of a chunk of ciphertexts into a pool in the workspace (slot 12), then fhesi_ct_plain_sum_dev
+// on the pool -- the composition itself, so its bits
+extern "C" int fhesi_ct_matvec_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, const fhesi_plain* w, int32_t logQ,
+                                   int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  if (nk < 1) FHESI_FAIL("ct_matvec: %d diagonals", nk);
+  FHESI_TRY(rotations_args(c, hoisted, ks, nk, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  if (!w) FHESI_FAIL("ct_matvec: null prepared plaintext");
+  if (w->ctx != c) FHESI_FAIL("ct_matvec: the prepared plaintext belongs to another context");
+  if (w->nw < nk) FHESI_FAIL("ct_matvec: %d rotations against %lld prepared diagonals", nk, (long long)w->nw);
+  double chain = 0.0;
+  for (int i = 0; i < c->L; ++i) chain += std::log2((double)c->q[i]);
+  const double bits = plain_sum_bits(c->phim, c->pow2, c->phi_two_term, logQ, w->maxabs, nk);
+  if (bits >= chain) FHESI_FAIL("ct_matvec: a sum of %d products needs %.0f bits, the chain holds %.0f", nk, std::ceil(bits), std::floor(chain));
+  if (!count) return 0;
+  if (!in || !out) FHESI_FAIL("ct_matvec: null argument");
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  if (ranges_overlap(in, (size_t)count * ct_words * 8, out, (size_t)count * ct_words * 8)) FHESI_FAIL("ct_matvec: out overlaps in");
+  // ciphertexts per pass: about 4 GiB of rotated ciphertexts
+  const i64 chunk = std::max<i64>(1, std::min<i64>(count, (i64)(4.0 * 1024 * 1024 * 1024 / ((double)nk * ct_words * 8))));
+  std::vector<int32_t> a_idx((size_t)chunk * nk), b_idx((size_t)chunk * nk), seg((size_t)chunk + 1);
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    void* d_pool;
+    FHESI_TRY(ws_reserve(c, 12, (size_t)nk * cnt * ct_words * 8, &d_pool));
+    FHESI_TRY(rotations_run(c, hoisted, ks, nk, logQ, decomp_bytes, in + (size_t)done * ct_words, nlimbs, cnt, (uint64_t*)d_pool, nlimbs));
+    for (i64 i = 0; i < cnt; ++i) {
+      seg[i] = (int32_t)(i * nk);
+      for (int t = 0; t < nk; ++t) { a_idx[i * nk + t] = (int32_t)(t * cnt + i); b_idx[i * nk + t] = t; }
+    }
+    seg[cnt] = (int32_t)(cnt * nk);
+    FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nk * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt, out + (size_t)done * ct_words));
+  }
+  return 0;
 }
 
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).

@@ -88,6 +88,7 @@ struct CtxOptions {
   int tensor32 = 1;         // 1: the fused pipeline's tensor half runs over 30-bit primes where that path applies (fhesi_ct_mul_relin_batch_dev)
   int tensor_bits = 30;     // 30: the tensor half's primes are the largest below 2^30; 29: below 2^29 -- lazy values have room up to 8p, so the row transforms skip 8 of 14 (forward) / 6 of 13 (inverse) range steps, for one or two primes more (36 instead of 35 at the metric ring)
   int dot32_k4 = 1;         // 1: key switch with 7 or 8 limbs and at least 24 ciphertexts per call runs dot32_kernel4 (keys in LDS, digits and accumulators in registers); 0: dot32_kernel2 (A/B)
+  int hoist_dot = 0;        // dot product of the hoisted rotations (fhesi_ct_rotations_dev): 1 = one launch of launch_dot32's choice per matrix on the shared digits; 2 = the multi-matrix kernel (dot32_kernel2m; four-prime form only); 0 = automatic
   int parts_words = 1;      // 1: inside the fused multiplication the scaled-down parts travel as 32-bit word rows (crt32_scale -> digit loader); 0 = 64-bit limb rows (A/B)
 };
 
@@ -172,6 +173,9 @@ struct fhesi_ctx {
   //   after those of a decryption are enqueued; fhesi_ct_plain_sum_dev takes the owners fhesi_ct_mul_sum_relin_dev takes: 7 gathered operands, 0 their
   //   rows, 4 the sums, 5 the index lists of all passes; the noise entry points own 4 from the CRT of a decryption to their copy-out: the per-block
   //   maxima of launch_decrypt_noise, then the maxima and budgets per ciphertext -- nothing in a decryption touches 4)
+  //   (the hoisted rotations, capi_pipeline.hip: 2 the positive residues of a chunk, 0 its digit rows -- alive across all matrices, which is why every table is
+  //   built before them --, 10 the dot outputs of the matrices of one launch, 4 one rotation's key-switched ciphertexts in front of their automorphism;
+  //   fhesi_ct_matvec_dev keeps the rotated ciphertexts of a chunk in 12 until fhesi_ct_plain_sum_dev has read them)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -194,6 +198,7 @@ struct fhesi_ksk {
   u64* d_aux_consts = nullptr;         // [L] q_0 q_1 mod q_i, then the int pair {0, 1} (prime_of_slot of auxiliary rows)
   bool aux_valid = false, aux_suborder = false;
   int aux_mode = 0;                    // KS_MODE_* the table was built for: rebuilt when the options select another form
+  i64 hoist_k = 0;                     // fhesi_ksk_hoist: the k of the automorphism whose inverse moved the rows (0: not a derived matrix)
   int last_form = -1;                  // KS_MODE_* of the last key switch with this matrix (fhesi_ksk_form)
   // limb mode (kernels_ksaux.hip): the table is built from the key polynomial's INTEGER coefficients (toPoly over the chain) cut into
   // aux_rows limbs of aux_limb_bits bits instead of from its aux_rows = L chain-prime residues; 0 = residue mode
@@ -240,6 +245,9 @@ bool aux32_applies(const fhesi_ctx* ctx);          // n = 2^14 or 2^15, or a rin
 i64 aux32_row_len(const fhesi_ctx* ctx);            // 2^15 for n = 2^15 and for linear-convolution rings with 2 phi(m) - 1 > 2^14, else 2^14
 static const i64 kAux32N = 1 << 14;                // row length of the 32-bit auxiliary transforms
 int launch_dot32(fhesi_ctx* ctx, fhesi_ksk* k, const u32* d_dig /* [count*ncol][4][n] */, int ncol, i64 count, u32* d_out /* [count*2*rows][4][n] */, bool* mont /* out: the rows carry 2^-32 */);
+// few ciphertexts against nk <= kDot32MultiMax matrices of one table shape in one launch (dot32_kernel2m): d_out [nk][count*2*rows][4][n]
+constexpr int kDot32MultiMax = 32;
+int launch_dot32_multi(fhesi_ctx* ctx, const fhesi_ksk* const* keys, int nk, const u32* d_dig, int ncol, i64 count, u32* d_out, bool* mont);
 enum { KS_MODE_DIRECT = 0, KS_MODE_LIMB32 = 1 /* four 30-bit primes, limbs */, KS_MODE_LIMB60 = 2 /* two largest chain primes, limbs */, KS_MODE_RESIDUE60 = 3 /* ..., residues */ };
 int ksaux_mode(fhesi_ctx* ctx, const CrtTables* t, int ncol, int digit_bits, int logQ);       // the form that runs for this chain, ring and option set
 int ksaux_build(fhesi_ctx* ctx, fhesi_ksk* k, int digit_bits, int logQ, int mode);

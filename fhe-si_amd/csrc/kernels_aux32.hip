@@ -392,7 +392,8 @@ __device__ __forceinline__ const u32* dot32_digit_base(const u32* dig, int ncol,
 template <int CT, int NW>
 __device__ __forceinline__ void dot32_tile_load(u32* dl32, const u32* dbase, int ncol, int kbeg, int nc, u32 lane, int w, u32 hf, int ct0, i64 count, u32 p) {
   typedef u32 v4u __attribute__((ext_vector_type(4)));
-  constexpr int TB = 6, CG = 2, NCG = CT / CG, WPG = NW / NCG;
+  constexpr int TB = 6, CG = 2, NCG = CT >= CG ? CT / CG : 1, WPG = NW / NCG;
+  constexpr bool kLone = CT < CG;                  // a tile of ONE ciphertext (dot32_kernel2m): the lanes of a group's second ciphertext sit out
   static_assert(NW % NCG == 0, "waves per ciphertext group");
   const u32 twop = 2 * p;
   const int nq = (nc + 3) >> 2;
@@ -400,7 +401,7 @@ __device__ __forceinline__ void dot32_tile_load(u32* dl32, const u32* dbase, int
   const u32 e0 = 4 * (lane & 7), dk = lane >> 4, dc = (lane >> 3) & 1;
   const u32 goff = hf * 32 + e0;
   const int c = cg * CG + (int)dc;
-  const bool cok = ct0 + c < count;
+  const bool cok = (!kLone || dc == 0) && ct0 + c < count;
   for (int qb = q0; qb < nq; qb += WPG * TB) {
     v4u v[TB];
 #pragma unroll
@@ -411,7 +412,7 @@ __device__ __forceinline__ void dot32_tile_load(u32* dl32, const u32* dbase, int
 #pragma unroll
     for (int u = 0; u < TB; ++u) {
       const int q = qb + u * WPG, k = q * 4 + (int)dk;
-      if (q < nq && k < nc) {
+      if (q < nq && k < nc && (!kLone || dc == 0)) {
         v4u y = v[u];
 #pragma unroll
         for (int j = 0; j < 4; ++j) { u32 t = y[j]; t = t >= twop ? t - twop : t; y[j] = t >= p ? t - p : t; }
@@ -578,6 +579,51 @@ dot32_kernel2p(const u32* __restrict__ k32, const u32* __restrict__ dig, int nco
     }
   }
   if (lok) dot32_tile_out<CT>(out, g, l, NLB, count, lognsl, ln, tot, th, r48, mont, p);
+}
+
+// ---- dot32_kernel2m: FEW CIPHERTEXTS AGAINST MANY MATRICES (the hoisted rotations, fhesi_ct_rotations_dev: the digits of one ciphertext meet
+// the derived matrix of every rotation).  dot32_kernel2 launched once per matrix loads and reduces the same digit tile once per matrix, and its
+// tile is 8 ciphertexts deep however few there are: with one ciphertext every LDS read and seven of eight multiply-adds serve rows of zeros.
+// Here a workgroup loads the tile of its CT ciphertexts ONCE (CT = 1, 2, 4, 8, picked from the count) and sweeps the tables of all nk matrices
+// of the launch, read through a table of pointers in the kernel's argument segment (no upload, no synchronisation in front of the launch: 10 us
+// that a single rotation of a single ciphertext would notice): the (matrix, limb pair) items go round the waves, so 7 limbs (4 pairs, half of
+// dot32_kernel2's waves idle) times 5 matrices keep all 8 waves busy.  Every key word is read once per ciphertext tile and feeds CT
+// multiply-adds per row -- with few ciphertexts the kernel runs at the speed of the key stream, and the small tile (8 KB at 66 columns, CT = 1)
+// leaves the CU to as many workgroups as the 128 registers of a wave admit, each with its own stream in flight.  Grid and placement as
+// dot32_kernel2: the tiles of one (slice, half, prime) side by side on an XCD, each matrix's line fetched there once.  All matrices of a launch
+// have NLB limbs and ncol columns (the caller groups them); out: [nk][count*2*NLB][4][n], matrix t at t * out_stride words.
+struct Dot32Keys { static constexpr int MAX = 32; const u32* k[MAX]; };      // the tables of one launch's matrices
+template <int CT, int NW>
+__global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4)))
+dot32_kernel2m(const Dot32Keys ktab, int nk, const u32* __restrict__ dig, int ncol, int NLB, i64 count, u32* __restrict__ out, i64 out_stride,
+               Aux32Primes pr, int ntiles, int nsl8, int lognsl, int sub_lg) {
+  extern __shared__ __attribute__((aligned(16))) u32 dl32[];       // [ncol][CT][32 elements]
+  const u32 lane = threadIdx.x & 63, ln = lane & 31;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const Dot32Place g = dot32_place<CT>(ntiles);
+  const u32 p = pr.p[g.a];
+  dot32_tile_load<CT, NW>(dl32, dot32_digit_base(dig, ncol, count, lognsl, sub_lg, g.a, g.slice, g.ct0), ncol, 0, ncol, lane, w, g.hf, g.ct0, count, p);
+  __syncthreads();
+  const u32 r48 = (u32)pr.r48[g.a], mont = pr.mont[g.a];
+  const int npair = (NLB + 1) >> 1;
+  int t = 0, lw = w;                               // item w, then every NW-th: (matrix t, limb pair lw), without a division
+  while (lw >= npair) { lw -= npair; ++t; }
+  while (t < nk) {
+    const int l = 2 * lw + (int)(lane >> 5);
+    if (l < NLB) {                                 // (an odd limb count leaves the last pair's second half wave idle, as in dot32_kernel2)
+      const u32* kp0 = ktab.k[t] + (((((((i64)g.a * NLB + l) << lognsl) + g.slice) * 2) * ncol) << 6) + (g.hf * 32 + ln);
+      u64 tot[2][CT];
+      u32 th[2][CT];
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) { tot[r][c] = 0; th[r][c] = 0; }
+      dot32_sweep<CT>(dl32, ln, kp0, kp0 + ((i64)ncol << 6), ncol, g.tile, tot, th);
+      dot32_tile_out<CT>(out + (i64)t * out_stride, g, l, NLB, count, lognsl, ln, tot, th, r48, mont, p);
+    }
+    lw += NW;
+    while (lw >= npair) { lw -= npair; ++t; }
+  }
 }
 
 // ---- dot32_kernel4: the KEY words in LDS, the DIGIT words straight from memory into registers (round 5).
@@ -854,6 +900,42 @@ static int launch_dot32_k4(fhesi_ctx* ctx, const fhesi_ksk* k, const u32* d_dig,
   dot32_kernel4<NLBT, CW, KC, PD, NW, NSP, TAIL><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, shmem, ctx->stream>>>((const u32*)k->d_aux, d_dig, ncol, count, d_out, ctx->aux32->pr, ngroups, g.lognsl, g.sub_lg);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+template <int CT, int NW>
+static int launch_dot32_m(fhesi_ctx* ctx, const Dot32Keys& ktab, int nk, int NLB, const u32* d_dig, int ncol, i64 count, u32* d_out) {
+  static std::atomic<unsigned long long> attr_done{0};
+  FHESI_TRY(dot32_allow_lds(ctx, (const void*)&dot32_kernel2m<CT, NW>, attr_done));
+  const int ntiles = (int)((count + CT - 1) / CT);
+  const i64 blocks = (i64)8 * ntiles * 2;
+  Dot32Geom g;
+  FHESI_TRY(dot32_geom(ctx, blocks, &g));
+  PROF_KERNEL(ctx, PROF_DOT, dot32_kernel2m<CT, NW>);
+  dot32_kernel2m<CT, NW><<<dim3((unsigned)blocks, (unsigned)g.nsl8, 4), NW * 64, (size_t)ncol * CT * 32 * 4, ctx->stream>>>(ktab, nk, d_dig, ncol, NLB, count, d_out, count * 2 * NLB * 4 * aux32_row_len(ctx),
+                                                                                                                           ctx->aux32->pr, ntiles, g.nsl8, g.lognsl, g.sub_lg);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// keys: nk <= kDot32MultiMax matrices with four-prime tables of the same limb count and ncol columns; d_out: [nk][count*2*NLB][4][n] u32
+int launch_dot32_multi(fhesi_ctx* ctx, const fhesi_ksk* const* keys, int nk, const u32* d_dig, int ncol, i64 count, u32* d_out, bool* mont) {
+  *mont = true;
+  if (!count || !nk) return 0;
+  static_assert(kDot32MultiMax == Dot32Keys::MAX, "matrices per launch");
+  if (nk > Dot32Keys::MAX) FHESI_FAIL("dot32: %d matrices in one launch (at most %d)", nk, Dot32Keys::MAX);
+  const int NLB = keys[0]->aux_rows;
+  Dot32Keys ktab{};
+  for (int j = 0; j < nk; ++j) {
+    if (!keys[j]->aux32 || keys[j]->aux_rows != NLB || keys[j]->ncomp * keys[j]->ndigits != ncol) FHESI_FAIL("dot32: matrices of different table shapes in one launch (internal)");
+    ktab.k[j] = (const u32*)keys[j]->d_aux;
+  }
+  ProfScope prof(ctx, PROF_DOT, (double)count * nk);
+  // the tile depth follows the count (a single ciphertext does not pay for eight) and the 80 KB that leave a CU two workgroups
+  int ct = count <= 1 ? 1 : (count <= 2 ? 2 : (count <= 4 ? 4 : 8));
+  while (ct > 1 && (size_t)ncol * ct * 128 > 80 * 1024) ct >>= 1;
+  if ((size_t)ncol * ct * 128 > 80 * 1024) FHESI_FAIL("dot32: %d columns do not fit the LDS tile", ncol);
+  if (ct == 1) return launch_dot32_m<1, 8>(ctx, ktab, nk, NLB, d_dig, ncol, count, d_out);
+  if (ct == 2) return launch_dot32_m<2, 8>(ctx, ktab, nk, NLB, d_dig, ncol, count, d_out);
+  if (ct == 4) return launch_dot32_m<4, 8>(ctx, ktab, nk, NLB, d_dig, ncol, count, d_out);
+  return launch_dot32_m<8, 8>(ctx, ktab, nk, NLB, d_dig, ncol, count, d_out);
 }
 int launch_dot32(fhesi_ctx* ctx, fhesi_ksk* k, const u32* d_dig, int ncol, i64 count, u32* d_out, bool* mont) {
   *mont = true;

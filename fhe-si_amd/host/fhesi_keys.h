@@ -343,6 +343,9 @@ class KeySwitchSI {
     automorphedKey.UpdateRepresentation(sKeys);
     InitAny(automorphedKey, s);
   }
+  // this matrix moved by sigma_k^-1, for HoistedRotations (many rotations of one ciphertext from one digit decomposition): declared here, defined
+  // in fhesi_hoist.h, which a caller includes on top of fhesi_host.h -- nothing in these headers calls it
+  class HoistedKey Hoisted(unsigned k) const;
   // ApplyKeySwitch (FHE-SI.cpp:241-260).  The reference's body -- ScaleDown, ByteDecomp, one DoubleCRT per digit polynomial, two DotProducts,
   // toPoly, ReduceCoefficients -- is ApplyKeySwitchObjects below, one object at a time (2 s per call at the metric ring: the digits alone
   // are 66 polynomials through the host).  ApplyKeySwitch itself hands the ciphertext to the fused device call with the matrix resident in

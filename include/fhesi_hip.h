@@ -76,7 +76,8 @@ void* fhesi_ctx_stream(fhesi_ctx* ctx);                     /* the hipStream_t a
  * chain primes), "tensor_bits" (30 / 29: the size of the tensor half's primes -- below 2^29 the row transforms skip half of their range steps
  * for one or two primes more; the integers formed are the same); layout switches that never change a result (round 5): "dot32_k4" (0 = the digit-tile dot product dot32_kernel2 where the
  * key-in-LDS form dot32_kernel4 would run), "parts_words" (0 = 64-bit limb rows between the tensor half and the digit loader),
- * "ks_long_keys", "host_chunk", "host_threads".
+ * "ks_long_keys", "host_chunk", "host_threads"; "hoist_dot" (the dot product of fhesi_ct_rotations_dev: 1 = one launch per matrix of what a plain key
+ * switch would run, 2 = the multi-matrix kernel, refused where the form is not the four-prime limb form, 0 = automatic; never changes a result).
  * The FHESI_<NAME> environment variables give the initial values, read once in fhesi_ctx_create -- never per call.  FHESI_LIN_LG (also read
  * there; a test hook) asks for LONGER zero-padded rows than a linear-convolution ring needs (15 .. 20: the fused loaders of rows of 2^15 / 2^16 and
  * the paths of rings with safe primes beyond 65 537, on rings small enough for an oracle).  FHESI_WS_POISON=1 (also a test hook) fills every
@@ -481,6 +482,40 @@ int fhesi_ct_plain_sum_dev(fhesi_ctx* ctx, const fhesi_plain* w, int32_t logQ, c
                            uint64_t* out_dev /* [ngroups][2][phi(m)][nlimbs] */);
 int fhesi_ct_add_slots_dev(fhesi_ctx* ctx, fhesi_slots* s, int32_t logQ, uint64_t* ct_dev, int32_t nparts, int32_t nlimbs, int64_t count,
                            const int64_t* vals_host /* [nv][nvals] */, int64_t nvals, int32_t only_usable, int64_t nv /* 1 or count */);
+
+/* ---- hoisted rotations: MANY automorphism key switches of ONE ciphertext -- the T rotations of a matrix-vector product by diagonals
+ * (fhe-si_amd/csrc/capi_pipeline.hip, dot32_kernel2m in kernels_aux32.hip).  sigma_k is a ring map, so for the key-switch matrix W_k
+ * of the automorphism k (source key (1, s(X^k)), target s: KeySwitchSI::InitAutomorph)
+ *     sum_j sigma_k(D_j(c)) W_k[j]  =  sigma_k( sum_j D_j(c) W'_k[j] ),     W'_k = sigma_k^-1(W_k)  (every column, both rows)
+ * modulo (Phi_m, 2^logQ): the digits D_j of the UNTOUCHED ciphertext are decomposed and transformed once and serve every rotation; a rotation then
+ * costs one dot product with its derived matrix, one inverse, one recombination and a signed gather of two polynomials.
+ *
+ * fhesi_ksk_hoist: out = a new matrix of k's shape and context whose rows are k's evaluation rows moved by kk^-1 mod m (on the device, any ring); it
+ *   remembers kk.  For every other entry point it is an ordinary matrix (fhesi_ksk_free / _bytes / _form / _key_bits / _download / a key switch with
+ *   it); its auxiliary tables are built at its first use, like any matrix's, and may take one limb more than the source's where sigma reduces modulo
+ *   Phi_m (m not a power of two).  It costs the memory of a second matrix: fhesi_ksk_bytes plus the table.  Refused: kk outside Z_m^*, a matrix with
+ *   other than 2 source components.
+ * fhesi_ct_rotations_dev: for t < nk, i < count
+ *       out[t][i] = Reduce( Ciphertext >>= ks[t]  of  ApplyKeySwitch(hoisted[t], in[i]) )        (centred modulo 2^logQ)
+ *   -- a ciphertext of the plaintext of in[i] moved by ks[t], under the same key, with noise of the same distribution as `>>= k; ApplyKeySwitch(W_k)`
+ *   gives.  NOT that path's bits: it decomposes sigma_k(c), this one applies sigma_k to the digits of c.  It IS, bit for bit,
+ *   fhesi_ct_automorph_key_switch_dev(hoisted[t], k = 1) followed by fhesi_ct_automorph_dev(ks[t]) and the reduction, whatever the option "hoist_dot"
+ *   says.  hoisted[t] == NULL with ks[t] == 1 is the identity: the reduced copy of the input (diagonal 0).  in_dev [count][2][phi(m)][nlimbs_in],
+ *   out_dev [nk][count][2][phi(m)][nlimbs], not overlapping.  All four forms of the key switch run it; in the four-prime limb form few ciphertexts
+ *   meet all matrices of one table shape in ONE launch of the dot product (matrices whose tables differ in limb count or width go in groups).
+ * fhesi_ct_matvec_dev: out[i] = sum_t<nk rot_t(in[i]) (*) w[t], w a fhesi_plain of nw >= nk diagonals (w[t] goes with ks[t]): bit for bit
+ *   fhesi_ct_rotations_dev into a pool followed by fhesi_ct_plain_sum_dev; the pool lives in the workspace, in chunks of ciphertexts.  The capacity
+ *   rule of fhesi_ct_plain_sum_dev (nk terms) is checked before anything is launched.
+ * REFUSED on the host with the condition named, the context usable afterwards: a matrix not made by fhesi_ksk_hoist or hoisted for another k than
+ *   ks[t]; a missing matrix with ks[t] != 1; a matrix of another context; digit count or limb capacity as for any key switch; out overlapping in;
+ *   a prepared plaintext of another context or with fewer than nk diagonals; a sum the chain cannot hold. */
+int fhesi_ksk_hoist(const fhesi_ksk* k, int64_t kk, fhesi_ksk** out);
+int fhesi_ct_rotations_dev(fhesi_ctx* ctx, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes,
+                           const uint64_t* in_dev /* [count][2][phi(m)][nlimbs_in] */, int32_t nlimbs_in, int64_t count,
+                           uint64_t* out_dev /* [nk][count][2][phi(m)][nlimbs] */, int32_t nlimbs);
+int fhesi_ct_matvec_dev(fhesi_ctx* ctx, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, const fhesi_plain* w /* nw >= nk diagonals */,
+                        int32_t logQ, int32_t decomp_bytes, const uint64_t* in_dev, int32_t nlimbs, int64_t count,
+                        uint64_t* out_dev /* [count][2][phi(m)][nlimbs] */);
 
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
