@@ -333,6 +333,7 @@ extern "C" int fhesi_ctx_destroy(fhesi_ctx* c) {
   for (auto& kv : c->crt_cache) { hipFree(kv.second->d_blob); delete kv.second; }
   for (auto& kv : c->pow64_cache) hipFree(kv.second);
   for (auto& kv : c->scalar_cache) hipFree(kv.second);
+  for (auto& kv : c->pow_scaled_cache) hipFree(kv.second);
   aux32_free(c);
   tensor32_free(c);
   for (int i = 0; i < FHESI_WS_SLOTS; ++i) if (c->lane_ws[i]) hipFree(c->lane_ws[i]);

@@ -358,8 +358,6 @@ extern "C" int fhesi_dcrt_remove_primes(fhesi_dcrt* d, const int32_t* prime_idx,
   return 0;
 }
 
-// magnitude of a non-negative big integer modulo a word (host scalars of the modulus-switching methods)
-static u64 bn_mag_mod(const std::vector<u64>& a, u64 q) { u64 r = 0; for (size_t i = a.size(); i-- > 0;) r = (u64)((((u128)r << 64) | a[i]) % q); return r; }
 static u64 inv_mod_word(u64 a, u64 p) {      // a^-1 mod p for any p > 1 with gcd(a, p) = 1 (NTL InvMod); 0 if not invertible
   __int128 t = 0, nt = 1, r = p, nr = a % p;
   while (nr) { const __int128 qq = r / nr; __int128 tmp = t - qq * nt; t = nt; nt = tmp; tmp = r - qq * nr; r = nr; nr = tmp; }
@@ -417,13 +415,13 @@ extern "C" int fhesi_dcrt_add_primes_and_scale(fhesi_dcrt* d, const int32_t* pri
   std::vector<u64> factor{1};
   double lf = 0.0;
   for (int i : add) { factor = hm::bn_mul_small(factor, c->q[i]); lf += std::log((double)c->q[i]); }
-  const u64 prodInv = inv_mod_word(bn_mag_mod(factor, p), p);
+  const u64 prodInv = inv_mod_word(hm::bn_mod_small(factor, p), p);
   if (!prodInv) FHESI_FAIL("addPrimesAndScale: product of the added primes is not invertible modulo p (InvMod)");
   factor = hm::bn_mul_small(factor, prodInv);
   lf += std::log((double)prodInv);
   if (!d->idx.empty()) {
     std::vector<u64> sc(d->idx.size());
-    for (size_t s = 0; s < d->idx.size(); ++s) sc[s] = bn_mag_mod(factor, c->q[d->idx[s]]);    // f = factor % qi (:190)
+    for (size_t s = 0; s < d->idx.size(); ++s) sc[s] = hm::bn_mod_small(factor, c->q[d->idx[s]]);    // f = factor % qi (:190)
     FHESI_TRY(dcrt_scale_rows(d, sc));                                                     // MulModPrecon loop (:193-196)
   }
   std::vector<int> uni(d->idx);
@@ -449,7 +447,7 @@ extern "C" int fhesi_dcrt_scale_down_to_set(fhesi_dcrt* d, const int32_t* prime_
   // diffProd and the scalars derived from it (:528, :538)
   std::vector<u64> D{1};
   for (int i : diff) D = hm::bn_mul_small(D, c->q[i]);
-  const u64 dp = bn_mag_mod(D, p);
+  const u64 dp = hm::bn_mod_small(D, p);
   const u64 u = inv_mod_word(dp, p);
   if (!u) FHESI_FAIL("scaleDownToSet: product of the dropped primes is not invertible modulo p (InvMod)");
   // *this *= (diffProd % p)   (:529) -- every row, the dropped ones included
@@ -483,7 +481,8 @@ extern "C" int fhesi_dcrt_scale_down_to_set(fhesi_dcrt* d, const int32_t* prime_
   if ((int)M.size() > W || (M.size() == (size_t)W && (M.back() >> 63))) FHESI_FAIL("scaleDownToSet: D p does not fit %d limbs", W);
   for (size_t i = 0; i < D.size(); ++i) consts[i] = D[i];
   for (size_t i = 0; i < M.size(); ++i) consts[W + i] = M[i];
-  for (int i = 0; i < W; ++i) consts[2 * W + i] = (consts[W + i] >> 1) | (i + 1 < W ? consts[W + i + 1] << 63 : 0);
+  const std::vector<u64> H = hm::bn_half(hm::bn_resized(M, W));
+  for (int i = 0; i < W; ++i) consts[2 * W + i] = H[i];
   FHESI_TRY(launch_modswitch_delta(c, (const u64*)d_delta, W, consts.data(), p, u, (u64*)d_e));
   // removePrimes(diff); *this += delta; *this /= diffProd   (:555-557)
   FHESI_TRY(dcrt_reindex(d, keep));
@@ -492,7 +491,7 @@ extern "C" int fhesi_dcrt_scale_down_to_set(fhesi_dcrt* d, const int32_t* prime_
   FHESI_TRY(row_fwd(c, (u64*)d_tmp, 1, Kk, d_pos, keep.data()));
   FHESI_TRY(launch_ew_op(c, d->d_rows, (const u64*)d_tmp, 1, Kk, d_pos, FHESI_OP_ADD));
   std::vector<u64> sc(Kk);
-  for (int s = 0; s < Kk; ++s) { const u64 q = c->q[keep[s]]; sc[s] = hm::invmod(bn_mag_mod(D, q), q); }
+  for (int s = 0; s < Kk; ++s) { const u64 q = c->q[keep[s]]; sc[s] = hm::invmod(hm::bn_mod_small(D, q), q); }
   FHESI_TRY(dcrt_scale_rows(d, sc));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;

@@ -7,6 +7,7 @@
 #include <string>
 #include <atomic>
 #include <vector>
+#include "hostbig.h"
 
 typedef uint64_t u64;
 typedef int64_t i64;
@@ -54,6 +55,7 @@ struct CrtTables {
   // tables of the sum form x = sum_i y_i M_i - kappa P (crt_sum_kernel): M_i = P / q_i, y_i = r_i c_i mod q_i, c_i = M_i^-1 mod q_i
   u64* d_M = nullptr;                  // [nidx][W]
   u64* d_cinv = nullptr;               // [nidx][3]   c_i, floor(c_i 2^128 / q_i) as (hi, lo)
+  std::vector<u64> P, halfP;           // host copies, W limbs each: the full product and (P-1)/2
 };
 
 struct BluesteinTables;                // general-m path, defined in bluestein.hip
@@ -140,7 +142,8 @@ struct fhesi_ctx {
   std::map<std::vector<long long>, std::pair<int, std::vector<uint32_t>>> t32_memo;      // t32_plan's answers: (lift, limbs, logQ, bits of the group size, option) -> (2 NP + generic, primes)
   std::map<std::vector<int>, CrtTables*> crt_cache;
   std::map<int, Shoup2*> pow64_cache;  // nlimbs -> device [L][nlimbs+1] table for rns_reduce
-  std::map<std::vector<u64>, u64*> scalar_cache;   // rns_reduce lift scalars (per-slot residues), keyed by the scalar list
+  std::map<std::vector<u64>, u64*> scalar_cache;   // rns_reduce lift scalars (per-slot residues), keyed by the scalar list and the slot count
+  std::map<std::pair<int, std::vector<u64>>, u64*> pow_scaled_cache;   // (nlimbs, lift scalars or {0}) -> [class][L][nlimbs+3] s 2^(64k) mod q and floor(2^128 / q)
   // second "lane" (stream + workspace): the batched ciphertext pipeline runs two half-batches concurrently so that one
   // half's HBM-bound kernels (dot, CRT loads) overlap the other half's VALU-bound NTTs
   hipStream_t lane_stream = nullptr;
@@ -216,6 +219,7 @@ struct fhesi_ksk {
 };
 struct KsLimbPlan { int W = 0, LQ = 0, B = 0, NLB = 0, mbits = 0; bool a32 = false; };
 bool ks_limb_plan(const fhesi_ctx* ctx, const CrtTables* t, int ncol, int digit_bits, int logQ, KsLimbPlan* plan, const u32* p32 /* the 30-bit primes, or null */);
+void ks_start_offset(std::vector<u64>& D, int B, int nlb);      // D -= sum_{l < nlb} 2^(119 + B l) at D's width: the start constant of both recombinations
 int launch_ks_recombine(fhesi_ctx* ctx, const CrtTables* t, const fhesi_ksk* k, const u64* d_o /* [npolys][aux_rows][2][n] */, i64 npolys, u64* d_out, int nl_out, bool tail_pending = false);
 bool ks_recombine_takes_tail(const fhesi_ctx* ctx, const CrtTables* t, const fhesi_ksk* k);
 int aux32_tail_consts(fhesi_ctx* ctx, uint32_t (*tw)[2], uint32_t (*twp)[2]);      // per auxiliary prime: (1/2, psi^-brv(1)/2) and their quotients
@@ -290,8 +294,7 @@ std::vector<int> zms_idx(i64 m, i64* phim);
 std::vector<i64> cyclotomic(i64 m);
 std::vector<i64> cyclotomic_cofactor(i64 m);     // (X^m - 1) / Phi_m
 bool is_primitive_2m_root(u64 root, i64 m, u64 q);
-u64 bn_mod(const u64* limbs, int nlimbs, u64 q);          // signed two's complement -> [0,q)  (role of NTL rem(ZZ,long))
-std::vector<u64> bn_mul_small(const std::vector<u64>& a, u64 b);   // non-negative
+// big integers (bn_mul_small, bn_mod_small, bn_mod, bn_bitlen, bn_shl, bn_sub, bn_ge, bn_half, pow64_table): hostbig.h
 // plaintext slots for p prime, p = 1 mod m, (Z/m)^* cyclic (PlaintextSpace::Init): slot j <-> root rho0^(exps[j]), exps[j] = g^j mod m
 struct SlotSpace {
   i64 m = 0, phim = 0, usable = 0;     // usable = 2^floor(log2 phi(m))  (PlaintextSpace.cpp:37-42)
@@ -496,6 +499,14 @@ __device__ __forceinline__ u64 d_shoup_lazy(u64 y, u64 w, u64 wp, u64 q) {
 __device__ __forceinline__ u64 d_shoup(u64 y, u64 w, u64 wp, u64 q) {
   u64 r = d_shoup_lazy(y, w, wp, q);
   return r >= q ? r - q : r;
+}
+// Reduce (Util.cpp:3-26) of limb i of a value modulo 2^logQ: sign-extend from bit logQ-1 (sbit = that bit: the centred residue) or clear
+// everything from bit logQ upwards (sbit = 0: the positive residue).  The one limb rule of every run-time store loop.
+__device__ __forceinline__ u64 reduce_limb(u64 val, int i, int logQ, u64 sbit) {
+  const int bits_left = logQ - 64 * i;
+  if (bits_left <= 0) return sbit ? ~0ull : 0ull;
+  if (bits_left < 64) { const u64 mask = (1ull << bits_left) - 1; return sbit ? (val | ~mask) : (val & mask); }
+  return val;
 }
 __device__ __forceinline__ u64 d_addmod(u64 a, u64 b, u64 q) { u64 s = a + b; return s >= q ? s - q : s; }
 __device__ __forceinline__ u64 d_submod(u64 a, u64 b, u64 q) { return a >= b ? a - b : a + q - b; }

@@ -1,0 +1,87 @@
+// hostbig.h -- the host's big integers: little-endian 64-bit limbs in a std::vector, non-negative unless a function says otherwise.
+// Host-only and free of HIP headers, so that a plain C++ program can test it (tests/host/test_hostbig.cpp); fhesi_internal.h includes it,
+// and every table builder of the library takes its wide constants from here.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace hm {
+typedef uint64_t bn_limb;
+typedef unsigned __int128 bn_wide;
+typedef std::vector<bn_limb> Big;
+
+// a * b, trimmed to its significant limbs (at least one)
+inline Big bn_mul_small(const Big& a, bn_limb b) {
+  Big r(a.size() + 1, 0);
+  bn_limb c = 0;
+  for (size_t i = 0; i < a.size(); ++i) {
+    const bn_wide s = (bn_wide)a[i] * b + c;
+    r[i] = (bn_limb)s;
+    c = (bn_limb)(s >> 64);
+  }
+  r[a.size()] = c;
+  while (r.size() > 1 && r.back() == 0) r.pop_back();
+  return r;
+}
+// the magnitude a[0..n) modulo a word q > 0
+inline bn_limb bn_mod_small(const bn_limb* a, int n, bn_limb q) {
+  bn_limb r = 0;
+  for (int i = n - 1; i >= 0; --i) r = (bn_limb)((((bn_wide)r << 64) | a[i]) % q);
+  return r;
+}
+inline bn_limb bn_mod_small(const Big& a, bn_limb q) { return bn_mod_small(a.data(), (int)a.size(), q); }
+// a signed two's complement value of n >= 1 limbs -> [0, q)  (role of NTL rem(ZZ, long))
+inline bn_limb bn_mod(const bn_limb* limbs, int n, bn_limb q) {
+  if (!(limbs[n - 1] >> 63)) return bn_mod_small(limbs, n, q);
+  Big mag(limbs, limbs + n);                      // the magnitude ~x + 1 (2^(64 n - 1) for the most negative value: it fits)
+  bn_limb c = 1;
+  for (int i = 0; i < n; ++i) { const bn_limb v = ~mag[i] + c; c = (c && v == 0); mag[i] = v; }
+  const bn_limb r = bn_mod_small(mag, q);
+  return r ? q - r : 0;
+}
+// bits of a: 0 for zero
+inline int bn_bitlen(const Big& a) {
+  for (int i = (int)a.size() - 1; i >= 0; --i)
+    if (a[i]) return 64 * i + 64 - __builtin_clzll(a[i]);
+  return 0;
+}
+// a <<= sh (sh >= 0) at a's own width: modulo 2^(64 a.size())
+inline void bn_shl(Big& a, int sh) {
+  const int n = (int)a.size(), w = sh >> 6, b = sh & 63;
+  Big r(n, 0);
+  for (int i = n - 1; i >= w; --i) r[i] = (a[i - w] << b) | ((b && i - w - 1 >= 0) ? (a[i - w - 1] >> (64 - b)) : 0);
+  a.swap(r);
+}
+// a -= b at a's own width: modulo 2^(64 a.size()); limbs b does not have count as zero, limbs of b beyond a's width are ignored
+inline void bn_sub(Big& a, const Big& b) {
+  bn_limb borrow = 0;
+  for (size_t i = 0; i < a.size(); ++i) {
+    const bn_limb bi = i < b.size() ? b[i] : 0, d = a[i] - bi, b1 = a[i] < bi, d2 = d - borrow, b2 = d < borrow;
+    a[i] = d2; borrow = b1 | b2;
+  }
+}
+// a >= b as magnitudes of any two widths
+inline bool bn_ge(const Big& a, const Big& b) {
+  for (size_t i = a.size() > b.size() ? a.size() : b.size(); i-- > 0;) {
+    const bn_limb ai = i < a.size() ? a[i] : 0, bi = i < b.size() ? b[i] : 0;
+    if (ai != bi) return ai > bi;
+  }
+  return true;
+}
+// floor(a / 2) at a's width: (P - 1) / 2 of an odd P
+inline Big bn_half(const Big& a) {
+  Big r(a.size(), 0);
+  for (size_t i = 0; i < a.size(); ++i) r[i] = (a[i] >> 1) | (i + 1 < a.size() ? a[i + 1] << 63 : 0);
+  return r;
+}
+// a at exactly n limbs (zero-filled; the caller knows that nothing significant is cut)
+inline Big bn_resized(Big a, size_t n) { a.resize(n, 0); return a; }
+// first * 2^(64 k) mod q for k < count: the weights of the limbs of a coefficient modulo a prime
+inline Big pow64_table(bn_limb q, int count, bn_limb first = 1) {
+  Big r((size_t)count);
+  const bn_limb b = (bn_limb)(((bn_wide)1 << 64) % q);
+  bn_limb cur = first % q;
+  for (int k = 0; k < count; ++k) { r[k] = cur; cur = (bn_limb)((bn_wide)cur * b % q); }
+  return r;
+}
+}  // namespace hm

@@ -301,41 +301,8 @@ const char* slot_space_pow2(i64 m, u64 p, i64 g, SlotSpace* out) {
   return nullptr;
 }
 
-u64 bn_mod(const u64* limbs, int nlimbs, u64 q) {
-  bool neg = limbs[nlimbs - 1] >> 63;
-  u64 r = 0;
-  if (!neg) {
-    for (int i = nlimbs - 1; i >= 0; --i) r = (u64)((((u128)r << 64) | limbs[i]) % q);
-    return r;
-  }
-  // magnitude = ~x + 1
-  std::vector<u64> mag(limbs, limbs + nlimbs);
-  u64 c = 1;
-  for (int i = 0; i < nlimbs; ++i) { u64 v = ~mag[i] + c; c = (c && v == 0); mag[i] = v; }
-  for (int i = nlimbs - 1; i >= 0; --i) r = (u64)((((u128)r << 64) | mag[i]) % q);
-  return r ? q - r : 0;
-}
-
-std::vector<u64> bn_mul_small(const std::vector<u64>& a, u64 b) {
-  std::vector<u64> r(a.size() + 1, 0);
-  u64 c = 0;
-  for (size_t i = 0; i < a.size(); ++i) {
-    u128 s = (u128)a[i] * b + c;
-    r[i] = (u64)s;
-    c = (u64)(s >> 64);
-  }
-  r[a.size()] = c;
-  while (r.size() > 1 && r.back() == 0) r.pop_back();
-  return r;
-}
-
 // ---- slot bases: k distinct primes p_c = 1 mod m on one two-row ring, P = prod p_c; a slot holds an integer modulo P, channel c its residue
 // modulo p_c in the two-row space of (m, p_c, g).  Scope = the direct transform of every channel: m = 2^3 .. 2^16, p_c < 2^31.
-static int bn_bitlen(const std::vector<u64>& a) {
-  for (int i = (int)a.size() - 1; i >= 0; --i)
-    if (a[i]) return 64 * i + 64 - __builtin_clzll(a[i]);
-  return 0;
-}
 static const char* basis_ring(i64 m, i64 g, u64* gm) {
   if (m < 1 || (m & (m - 1)) != 0) return "m is not a power of two (a slot basis lives on a two-row ring)";
   if (m < 8) return "m = 2^k with k < 3: no two-row space there";
@@ -372,8 +339,7 @@ const char* slot_basis(i64 m, const u64* primes, int k, i64 g, SlotBasis* out) {
   B.limbs = (bn_bitlen(P) + 1 + 63) / 64;
   P.resize(B.limbs, 0);
   B.P = P;
-  B.halfP.assign(B.limbs, 0);                                // floor(P / 2)
-  for (int i = 0; i < B.limbs; ++i) B.halfP[i] = (P[i] >> 1) | (i + 1 < B.limbs ? P[i + 1] << 63 : 0);
+  B.halfP = bn_half(P);                                      // floor(P / 2)
   B.garner.assign((size_t)k * k, 0);                         // [c][j], j < c: p_j^-1 mod p_c
   for (int c = 0; c < k; ++c)
     for (int j = 0; j < c; ++j) B.garner[(size_t)c * k + j] = invmod(primes[j] % primes[c], primes[c]);

@@ -12,6 +12,7 @@
 // (x stays in [0, P_k) ) and centres once at the end -- same value, no signed big-int arithmetic per step.
 #include "fhesi_internal.h"
 #include "lin_fold.h"
+#include "crt_wide.h"
 
 // 128-bit value -> [0,q): hi * (2^64 mod q) + lo, each reduced by a Shoup step
 __device__ __forceinline__ u64 crt_fold128(u128 a, const PrimeConst& pc) {
@@ -118,7 +119,8 @@ template <int NL>
 static void launch_rns_t(fhesi_ctx* ctx, dim3 grid, const u64* d_limbs, i64 ncoeffs, i64 n, int npoly, i64 pow_poly_stride, u64* d_rows, int nslots,
                          const int* d_prime_of_slot, const u64* d_pows) {
   PROF_KERNEL(ctx, PROF_RNS, rns_reduce_kernel_t<NL>);
-  rns_reduce_kernel_t<NL><<<grid, 256, 0, ctx->stream>>>(d_limbs, ncoeffs, n, npoly, pow_poly_stride, d_rows, nslots, d_prime_of_slot, ctx->d_pc, d_pows, ctx->L);
+  rns_reduce_kernel_t<NL><<<grid, 256, 0, ctx->stream>>>(d_limbs, ncoeffs, n, npoly, pow_poly_stride, d_rows, nslots, d_prime_of_slot, ctx->d_pc,
+                                                         d_pows, ctx->L);
 }
 
 int launch_rns_reduce(fhesi_ctx* ctx, const u64* d_limbs, int nlimbs, i64 ncoeffs, i64 count, int npoly, const u64* scalar_mul,
@@ -131,9 +133,8 @@ int launch_rns_reduce(fhesi_ctx* ctx, const u64* d_limbs, int nlimbs, i64 ncoeff
     std::vector<Shoup2> h((size_t)ctx->L * (nlimbs + 1));
     for (int l = 0; l < ctx->L; ++l) {
       const u64 q = ctx->q[l];
-      const u64 b = (u64)(((u128)1 << 64) % q);
-      u64 cur = 1 % q;
-      for (int k = 0; k <= nlimbs; ++k) { h[(size_t)l * (nlimbs + 1) + k] = {cur, hm::shoup(cur, q)}; cur = hm::mulmod(cur, b, q); }
+      const hm::Big pw = hm::pow64_table(q, nlimbs + 1);
+      for (int k = 0; k <= nlimbs; ++k) h[(size_t)l * (nlimbs + 1) + k] = {pw[k], hm::shoup(pw[k], q)};
     }
     HIP_TRY(hipMalloc(&d_pow, h.size() * sizeof(Shoup2)));
     HIP_TRY(hipMemcpyAsync(d_pow, h.data(), h.size() * sizeof(Shoup2), hipMemcpyHostToDevice, ctx->stream));
@@ -164,31 +165,29 @@ int launch_rns_reduce(fhesi_ctx* ctx, const u64* d_limbs, int nlimbs, i64 ncoeff
   u64* d_pows = nullptr;
   const i64 pow_stride = (i64)ctx->L * (nlimbs + 3);
   if (nlimbs <= 20) {
-    std::vector<u64> key;
-    if (scalar_mul) key.assign(scalar_mul, scalar_mul + npoly); else key.assign(1, 0);
-    key.push_back(0x7461626c65320000ull | (u64)nlimbs);          // tag: scaled power table (+ Barrett constant) of this limb count
-    auto pit = ctx->scalar_cache.find(key);
-    if (pit == ctx->scalar_cache.end()) {
+    const std::pair<int, std::vector<u64>> key(nlimbs, scalar_mul ? std::vector<u64>(scalar_mul, scalar_mul + npoly) : std::vector<u64>(1, 0));
+    auto pit = ctx->pow_scaled_cache.find(key);
+    if (pit == ctx->pow_scaled_cache.end()) {
       const int ncls = scalar_mul ? npoly : 1;
       std::vector<u64> h((size_t)ncls * pow_stride);
       for (int p = 0; p < ncls; ++p)
         for (int l = 0; l < ctx->L; ++l) {
           const u64 q = ctx->q[l];
-          const u64 b = (u64)(((u128)1 << 64) % q);
-          u64 cur = (scalar_mul && scalar_mul[p]) ? scalar_mul[p] % q : 1 % q;
+          const hm::Big pw = hm::pow64_table(q, nlimbs + 1, (scalar_mul && scalar_mul[p]) ? scalar_mul[p] : 1);
           u64* e = &h[(size_t)p * pow_stride + (size_t)l * (nlimbs + 3)];
-          for (int k = 0; k <= nlimbs; ++k) { e[k] = cur; cur = hm::mulmod(cur, b, q); }
+          for (int k = 0; k <= nlimbs; ++k) e[k] = pw[k];
           // floor(2^128 / q) = floor((2^128 - 1) / q) for odd q > 1
           const u128 mu = ~(u128)0 / q;
           e[nlimbs + 1] = (u64)mu; e[nlimbs + 2] = (u64)(mu >> 64);
         }
       HIP_TRY(hipMalloc(&d_pows, h.size() * 8));
       HIP_TRY(hipMemcpy(d_pows, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-      ctx->scalar_cache[key] = d_pows;
+      ctx->pow_scaled_cache[key] = d_pows;
     } else d_pows = pit->second;
   }
   const int npoly_cls = scalar_mul ? npoly : 1;
-#define RNS_CASE(NL) case NL: launch_rns_t<NL>(ctx, grid, d_limbs, nc, n, npoly_cls, pow_stride, d_rows, nslots, d_prime_of_slot, d_pows); HIP_TRY(hipGetLastError()); return 0;
+#define RNS_CASE(NL) case NL: launch_rns_t<NL>(ctx, grid, d_limbs, nc, n, npoly_cls, pow_stride, d_rows, nslots, d_prime_of_slot, d_pows); \
+    HIP_TRY(hipGetLastError()); return 0;
   switch (nlimbs) {
     RNS_CASE(1) RNS_CASE(2) RNS_CASE(3) RNS_CASE(4) RNS_CASE(5) RNS_CASE(6) RNS_CASE(7) RNS_CASE(8) RNS_CASE(9) RNS_CASE(10)
     RNS_CASE(11) RNS_CASE(12) RNS_CASE(13) RNS_CASE(14) RNS_CASE(15) RNS_CASE(16) RNS_CASE(17) RNS_CASE(18) RNS_CASE(19) RNS_CASE(20)
@@ -199,7 +198,8 @@ int launch_rns_reduce(fhesi_ctx* ctx, const u64* d_limbs, int nlimbs, i64 ncoeff
   if (shmem > 160 * 1024) FHESI_FAIL("rns_reduce: coefficients of %d limbs are too wide", nlimbs);
   HIP_TRY(hipFuncSetAttribute((const void*)rns_reduce_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   PROF_KERNEL(ctx, PROF_NAME_RNS_GENERIC, rns_reduce_kernel);
-  rns_reduce_kernel<<<grid, 256, shmem, ctx->stream>>>(d_limbs, nlimbs, ncoeffs < n ? ncoeffs : n, n, npoly, d_sc, d_rows, nslots, d_prime_of_slot, ctx->d_pc, d_pow);
+  rns_reduce_kernel<<<grid, 256, shmem, ctx->stream>>>(d_limbs, nlimbs, ncoeffs < n ? ncoeffs : n, n, npoly, d_sc, d_rows, nslots, d_prime_of_slot,
+                                                       ctx->d_pc, d_pow);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -217,6 +217,8 @@ int get_crt_tables(fhesi_ctx* ctx, const std::vector<int>& idx, CrtTables** out)
   const int W = (int)P[K].size() + 1;   // one spare limb for the sign / rounding carry
   CrtTables* t = new CrtTables();
   t->nidx = K; t->W = W; t->idx = idx;
+  t->P = hm::bn_resized(P[K], W);
+  t->halfP = hm::bn_half(t->P);         // (P-1)/2: P is odd
   // blob layout (u64 words): idx[K] (as u64) | pow64[K][W] (2 words each) | pinv[K] (2 words) | P[K+1][W] | halfP[W] | M[K][W] | cinv[K][3]
   const size_t n_idx = K, n_pow = (size_t)K * W * 2, n_pinv = (size_t)K * 2, n_P = (size_t)(K + 1) * W, n_half = W, n_M = (size_t)K * W, n_cinv = (size_t)K * 3;
   std::vector<u64> blob(n_idx + n_pow + n_pinv + n_P + n_half + n_M + n_cinv, 0);
@@ -228,25 +230,14 @@ int get_crt_tables(fhesi_ctx* ctx, const std::vector<int>& idx, CrtTables** out)
   for (int k = 0; k < K; ++k) {
     const u64 q = ctx->q[idx[k]];
     ((int*)b_idx)[k] = idx[k];
-    const u64 base = (u64)(((u128)1 << 64) % q);
-    u64 cur = 1 % q;
-    for (int j = 0; j < W; ++j) { b_pow[((size_t)k * W + j) * 2] = cur; b_pow[((size_t)k * W + j) * 2 + 1] = hm::shoup(cur, q); cur = hm::mulmod(cur, base, q); }
-    // P_k mod q_k
-    u64 pk = 0;
-    for (int j = (int)P[k].size() - 1; j >= 0; --j) pk = (u64)((((u128)pk << 64) | P[k][j]) % q);
-    const u64 inv = hm::invmod(pk, q);
+    const hm::Big pw = hm::pow64_table(q, W);
+    for (int j = 0; j < W; ++j) { b_pow[((size_t)k * W + j) * 2] = pw[j]; b_pow[((size_t)k * W + j) * 2 + 1] = hm::shoup(pw[j], q); }
+    const u64 inv = hm::invmod(hm::bn_mod_small(P[k], q), q);      // (P_k mod q_k)^-1
     b_pinv[k * 2] = inv; b_pinv[k * 2 + 1] = hm::shoup(inv, q);
   }
   for (int k = 0; k <= K; ++k)
     for (size_t j = 0; j < P[k].size(); ++j) b_P[(size_t)k * W + j] = P[k][j];
-  // halfP = (P-1)/2  (P odd)
-  {
-    std::vector<u64> h(W, 0);
-    for (size_t j = 0; j < P[K].size(); ++j) h[j] = P[K][j];
-    h[0] -= 1;   // P odd -> no borrow
-    for (int j = 0; j < W; ++j) h[j] = (h[j] >> 1) | (j + 1 < W ? h[j + 1] << 63 : 0);
-    for (int j = 0; j < W; ++j) b_half[j] = h[j];
-  }
+  for (int j = 0; j < W; ++j) b_half[j] = t->halfP[j];
   // sum-form tables
   {
     u64* b_M = b_half + n_half;
@@ -255,9 +246,7 @@ int get_crt_tables(fhesi_ctx* ctx, const std::vector<int>& idx, CrtTables** out)
       const u64 q = ctx->q[idx[i]];
       std::vector<u64> M{1};
       for (int k = 0; k < K; ++k) if (k != i) M = hm::bn_mul_small(M, ctx->q[idx[k]]);
-      u64 mi = 0;
-      for (int j = (int)M.size() - 1; j >= 0; --j) mi = (u64)((((u128)mi << 64) | M[j]) % q);
-      const u64 c = hm::invmod(mi, q);
+      const u64 c = hm::invmod(hm::bn_mod_small(M, q), q);
       for (size_t j = 0; j < M.size(); ++j) b_M[(size_t)i * W + j] = M[j];
       const u128 num = (u128)c << 64;
       const u64 hi = (u64)(num / q), rem = (u64)(num % q);
@@ -285,77 +274,19 @@ int get_crt_tables(fhesi_ctx* ctx, const std::vector<int>& idx, CrtTables** out)
 template <int MAXW, int WFIX, int LQFIX>
 __device__ __forceinline__ void crt_store_fixed(const u64 (&x)[MAXW], int mode, u64* __restrict__ out, i64 poly, i64 n, i64 j, int nl_out) {
   static_assert(WFIX > 0 && WFIX <= MAXW, "static epilogue needs a compile-time limb count");
-    constexpr int LQ = LQFIX, w = LQ >> 6, b = LQ & 63, sw = (LQ - 1) >> 6, sb = (LQ - 1) & 63;
-    const u64 sf = (x[WFIX - 1] >> 63) ? ~0ull : 0ull;
-#define XS(i) ((i) < WFIX ? x[(i) < WFIX ? (i) : 0] : sf)
-    const u64 hbit = (XS(sw) >> sb) & 1;           // bit logQ-1: the rounding carry (mode 1) / the sign of the centred residue (mode 2)
-    if (mode == 1) {
-      u64 carry = hbit;
-      u64* o = out + poly * nl_out * n + j;
+  constexpr int LQ = LQFIX, NLQ = (LQ + 63) >> 6;
+  const u64 sf = (x[WFIX - 1] >> 63) ? ~0ull : 0ull;
+  auto XS = [&](int i) -> u64 { return i < WFIX ? x[i < WFIX ? i : 0] : sf; };      // (static indices: every caller's loop unrolls)
+  if (mode == 1) crt_store_scaled<MAXW>(XS, LQ, out, poly, n, j, nl_out);
+  else if (mode == 3) crt_store_positive<MAXW>(XS, LQ, out, poly, n, j, nl_out);
+  else {
+    const u64 hbit = crt_round_bit(XS, LQ);
+    u64 v[MAXW];
 #pragma unroll
-      for (int i = 0; i < MAXW; ++i) {
-        if (i < nl_out) {
-          const u64 lo = XS(i + w), hi = XS(i + w + 1);
-          u64 val = b ? ((lo >> b) | (hi << ((64 - b) & 63))) : lo;
-          val += carry;
-          carry = (carry && val == 0);
-          const int bits_left = LQ - 64 * i;
-          if (bits_left < 64) val &= (bits_left <= 0) ? 0ull : ((1ull << (bits_left & 63)) - 1);
-          o[(i64)i * n] = val;
-        }
-      }
-      for (int i = MAXW; i < nl_out; ++i) o[(i64)i * n] = 0;
-    } else if (mode == 3) {
-      u64* o = out + poly * nl_out * n + j;
-#pragma unroll
-      for (int i = 0; i < MAXW; ++i) {
-        if (i < nl_out) {
-          u64 val = XS(i);
-          const int bits_left = LQ - 64 * i;
-          if (bits_left < 64) val &= (bits_left <= 0) ? 0ull : ((1ull << (bits_left & 63)) - 1);
-          o[(i64)i * n] = val;
-        }
-      }
-      for (int i = MAXW; i < nl_out; ++i) o[(i64)i * n] = 0;
-    } else {
-      // coefficient-major output.  Whole waves (n a multiple of 64; every caller runs one thread per coefficient in workgroups of whole waves and
-      // returns past the end before this point) whose caller holds exactly ceil(logQ / 64) limbs hand their 64 x NLQ limbs -- one contiguous
-      // block -- through LDS rows of their own and store 512 contiguous bytes per instruction; a lane's direct stores touch 32-64 cache lines
-      // per instruction for 8-16 bytes each (round 5, as ks_recombine_centred_kernel: -0.5 ms per 1024 there)
-      constexpr int NLQ = (LQ + 63) >> 6;
-      if (nl_out == NLQ && NLQ <= MAXW && (NLQ & (NLQ - 1)) == 0 && (n & 63) == 0 && (blockDim.x & 63) == 0) {
-        __shared__ u64 stg[4][64 * (NLQ + 1)];
-        const u32 lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & 3;
-        u64* __restrict__ st = stg[wv];
-        if (blockDim.x <= 256) {
-#pragma unroll
-          for (int i = 0; i < NLQ; ++i) {
-            u64 val = XS(i);
-            const int bits_left = LQ - 64 * i;
-            if (bits_left < 64) { const u64 mask = (1ull << (bits_left & 63)) - 1; val = hbit ? (val | ~mask) : (val & mask); }
-            st[lane * (NLQ + 1) + i] = val;
-          }
-          __builtin_amdgcn_wave_barrier();
-          u64* __restrict__ ow = out + (poly * n + (j - lane)) * NLQ;
-#pragma unroll
-          for (int k = 0; k < NLQ; ++k) { const u32 e = k * 64 + lane; ow[e] = st[(e / NLQ) * (NLQ + 1) + (e % NLQ)]; }
-          return;
-        }
-      }
-      u64* o = out + (poly * n + j) * nl_out;
-#pragma unroll
-      for (int i = 0; i < MAXW; ++i) {
-        if (i < nl_out) {
-          u64 val = XS(i);
-          const int bits_left = LQ - 64 * i;
-          if (bits_left <= 0) val = hbit ? ~0ull : 0ull;
-          else if (bits_left < 64) { const u64 mask = (1ull << (bits_left & 63)) - 1; val = hbit ? (val | ~mask) : (val & mask); }
-          o[i] = val;
-        }
-      }
-      for (int i = MAXW; i < nl_out; ++i) o[i] = hbit ? ~0ull : 0ull;
-    }
-#undef XS
+    for (int i = 0; i < MAXW; ++i) v[i] = reduce_limb(XS(i), i, LQ, hbit);
+    // (every caller runs one thread per coefficient in workgroups of whole waves and returns past the end before this point)
+    crt_store_coeff_major<NLQ, 4>(v, hbit, (blockDim.x & 63) == 0 && blockDim.x <= 256, out, poly, n, j, nl_out);
+  }
 }
 
 // One thread per coefficient.  MAXW = compile-time bound on the limb count (register array, static indices only);
@@ -420,30 +351,8 @@ __global__ void __launch_bounds__(128) crt_kernel(const u64* __restrict__ rows, 
     }
     // centre: if x > (P-1)/2 then x -= P   (DoubleCRT.cpp:375-376 / NumbTh.cpp:318; `positive` keeps [0,P), :392-395)
     if (!positive) {
-      bool gt = false, decided = false;
-#pragma unroll
-      for (int i = MAXW - 1; i >= 0; --i) {
-        if (i < W) {
-          const u64 h = halfP[i];
-          if (!decided && x[i] != h) { gt = x[i] > h; decided = true; }
-        }
-      }
-      if (gt) {
-        const u64* Pf = Ptab + (i64)K * W;
-        u64 borrow = 0;
-#pragma unroll
-        for (int i = 0; i < MAXW; ++i) {
-          if (i < W) {
-            const u64 p = Pf[i];
-            const u64 d = x[i] - p;
-            const u64 b1 = x[i] < p;
-            const u64 d2 = d - borrow;
-            const u64 b2 = d < borrow;
-            x[i] = d2;
-            borrow = b1 | b2;
-          }
-        }
-      }
+      const auto xw = wide_regs(x);
+      if (wide_gt(xw, halfP, W)) wide_sub(xw, Ptab + (i64)K * W, W);
     }
   }
   if constexpr (LQFIX > 0) {
@@ -456,48 +365,7 @@ __global__ void __launch_bounds__(128) crt_kernel(const u64* __restrict__ rows, 
     if (i < W) sx[i * blockDim.x + threadIdx.x] = x[i];
   // (each thread only reads back its own column: no barrier needed)
   if (!active) return;
-  const u64 sign_fill = (sx[(W - 1) * blockDim.x + threadIdx.x] >> 63) ? ~0ull : 0ull;
-  auto X = [&](int i) -> u64 { return i < W ? sx[i * blockDim.x + threadIdx.x] : sign_fill; };
-  if (mode == 0) {
-    u64* o = out + (poly * n + j) * nl_out;
-    for (int i = 0; i < nl_out; ++i) o[i] = X(i);
-  } else if (mode == 1) {
-    // y = floor((2x + q) / 2q) = (x >> logQ) + bit_{logQ-1}(x), q = 2^logQ (arithmetic shift = floor);
-    // keep the positive residue mod 2^logQ, limb-major [nl_out][n]
-    const int w = logQ >> 6, b = logQ & 63;
-    u64 carry = (X((logQ - 1) >> 6) >> ((logQ - 1) & 63)) & 1;
-    u64* o = out + poly * nl_out * n + j;
-    for (int i = 0; i < nl_out; ++i) {
-      const u64 lo = X(i + w), hi = X(i + w + 1);
-      u64 val = b ? ((lo >> b) | (hi << (64 - b))) : lo;
-      val += carry;
-      carry = (carry && val == 0);
-      const int bits_left = logQ - 64 * i;
-      if (bits_left < 64) val &= (bits_left <= 0) ? 0ull : ((1ull << bits_left) - 1);
-      o[(i64)i * n] = val;
-    }
-  } else if (mode == 3) {
-    // positive residue mod 2^logQ of the value itself, limb-major [nl_out][n]: what ByteDecompPart (Ciphertext.cpp:94) takes of
-    // an unscaled part (the key switch after Ciphertext::operator>>=, Regression.h:171-172)
-    u64* o = out + poly * nl_out * n + j;
-    for (int i = 0; i < nl_out; ++i) {
-      u64 val = X(i);
-      const int bits_left = logQ - 64 * i;
-      if (bits_left < 64) val &= (bits_left <= 0) ? 0ull : ((1ull << bits_left) - 1);
-      o[(i64)i * n] = val;
-    }
-  } else {
-    // centred residue mod 2^logQ, two's complement, coefficient-major
-    const u64 sbit = (X((logQ - 1) >> 6) >> ((logQ - 1) & 63)) & 1;
-    u64* o = out + (poly * n + j) * nl_out;
-    for (int i = 0; i < nl_out; ++i) {
-      u64 val = X(i);
-      const int bits_left = logQ - 64 * i;
-      if (bits_left <= 0) val = sbit ? ~0ull : 0ull;
-      else if (bits_left < 64) { const u64 mask = (1ull << bits_left) - 1; val = sbit ? (val | ~mask) : (val & mask); }
-      o[i] = val;
-    }
-  }
+  crt_store_rt(sx + threadIdx.x, blockDim.x, W, mode, logQ, out, poly, n, j, nl_out);
 }
 
 template <int MAXW, int KFIX = 0, int WFIX = 0, int LQFIX = 0>
@@ -506,11 +374,15 @@ static int launch_crt_t(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows, i
   const int TB = 128;
   const size_t shmem = LQFIX ? 0 : (size_t)t->W * TB * sizeof(u64);
   static std::atomic<unsigned long long> attr_done{0};     // one bit per device: the attribute is per device
-  if (!LQFIX && !(attr_done.load() >> ctx->device & 1)) { HIP_TRY(hipFuncSetAttribute((const void*)crt_kernel<MAXW, KFIX, WFIX, LQFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, MAXW * TB * 8)); attr_done.fetch_or(1ull << ctx->device); }
+  if (!LQFIX && !(attr_done.load() >> ctx->device & 1)) {
+    HIP_TRY(hipFuncSetAttribute((const void*)crt_kernel<MAXW, KFIX, WFIX, LQFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, MAXW * TB * 8));
+    attr_done.fetch_or(1ull << ctx->device);
+  }
   dim3 grid((unsigned)((ctx->phim + TB - 1) / TB), (unsigned)npolys);
   PROF_KERNEL(ctx, PROF_NAME_CRT_EXACT, (crt_kernel<MAXW, KFIX, WFIX, LQFIX>));
-  crt_kernel<MAXW, KFIX, WFIX, LQFIX><<<grid, TB, shmem, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->nidx, t->W, t->d_idx, t->d_pow64, t->d_pinv, t->d_P,
-                                                    t->d_halfP, ctx->d_pc, mode, positive, logQ, d_out, nl_out, d_block_flags);
+  crt_kernel<MAXW, KFIX, WFIX, LQFIX><<<grid, TB, shmem, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->nidx, t->W, t->d_idx, t->d_pow64,
+                                                                        t->d_pinv, t->d_P, t->d_halfP, ctx->d_pc, mode, positive, logQ, d_out, nl_out,
+                                                                        d_block_flags);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -575,15 +447,7 @@ __global__ void __launch_bounds__(128) crt_sum_kernel(const u64* __restrict__ ro
     const u32 kappa = kint + (u32)(f_hi >> 63);
     undecided |= (f_hi >= 0x7ffffffffffffffcull && f_hi < 0x8000000000000000ull) ? 1 : 0;
     // x[J0..J1) -= kappa * P[J0..J1)
-    u64 carry = 0, borrow = 0;
-#pragma unroll
-    for (int l = J0; l < J1; ++l) {
-      const u128 t = (u128)kappa * Pfull[l] + carry;
-      carry = (u64)(t >> 64);
-      const u64 tl = (u64)t, d = x[l] - tl, b1 = x[l] < tl, d2 = d - borrow, b2 = d < borrow;
-      x[l] = d2;
-      borrow = b1 | b2;
-    }
+    wide_mulsub(wide_regs(x), kappa, Pfull, J0, J1);
     if (HIGH) {
       // limbs below J0 were dropped: the limb holding bit logQ-1 may be off by a few units
       const u64 u = x[sw] + ((u64)1 << 63);
@@ -607,9 +471,10 @@ static int launch_crt_sum(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows,
   FHESI_TRY(ws_reserve(ctx, 6, (size_t)grid.x * grid.y, &d_fl));
   unsigned char* fl = (unsigned char*)d_fl;
   if (mode == 1) PROF_KERNEL(ctx, PROF_CRT, crt_sum_kernel<K, W, LQ, true>); else PROF_KERNEL(ctx, PROF_CRT, crt_sum_kernel<K, W, LQ, false>);
-  if (mode == 1) crt_sum_kernel<K, W, LQ, true><<<grid, TB, 0, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->d_idx, t->d_M, t->d_cinv, t->d_P + (size_t)K * W,
+  const u64* Pfull = t->d_P + (size_t)K * W;
+  if (mode == 1) crt_sum_kernel<K, W, LQ, true><<<grid, TB, 0, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->d_idx, t->d_M, t->d_cinv, Pfull,
                                                                                ctx->d_pc, mode, d_out, nl_out, fl);
-  else crt_sum_kernel<K, W, LQ, false><<<grid, TB, 0, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->d_idx, t->d_M, t->d_cinv, t->d_P + (size_t)K * W,
+  else crt_sum_kernel<K, W, LQ, false><<<grid, TB, 0, ctx->stream>>>(d_rows, ctx->phim, nslots_layout, d_slot_of, t->d_idx, t->d_M, t->d_cinv, Pfull,
                                                                       ctx->d_pc, mode, d_out, nl_out, fl);
   HIP_TRY(hipGetLastError());
   // exact clean-up of the flagged workgroups (normally none: every workgroup of this launch returns at once)
@@ -628,10 +493,15 @@ static int launch_crt_sum(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows,
 //   corrections, centring -- all exact integer arithmetic on W + 1 limbs -- then the mode-2 store of the sum-form kernel.
 // A32: the residues are those of the four 30-bit auxiliary primes (kernels_aux32.hip), [poly][NLB][4][n] u32, recombined by Garner's
 // mixed radix with the constants of Garner32; otherwise the two 60-bit chain primes, [poly][NLB][2][n] u64.
-struct Garner32 { u32 p[4]; u32 c[6], cp[6]; u32 tw[4][2], twp[4][2]; };      // tw: the tail of a 2^15-point inverse per prime (1/2 | psi^-brv(1) / 2) and its quotient (kernels with S = 1)      // c = {p0^-1 mod p1, p0^-1 mod p2, p1^-1 mod p2, p0^-1 mod p3, p1^-1 mod p3, p2^-1 mod p3} and floor(c 2^32 / p_j)
-__device__ __forceinline__ u32 g32_mul(u32 y, u32 c, u32 cp, u32 p) { const u32 r = y * c - __umulhi(y, cp) * p; return r >= p ? r - p : r; }     // y any u32 -> [0, p)
-__device__ __forceinline__ u32 g32_mul_lazy(u32 y, u32 c, u32 cp, u32 p) { return y * c - __umulhi(y, cp) * p; }                               // y any u32 -> [0, 2p)
-__device__ __forceinline__ u32 g32_sub(u32 a, u32 b, u32 p) { return a + 2 * p - b; }      // a, b below 2p -> a - b + 2p in (0, 4p): only ever the argument of a g32_mul
+// c = {p0^-1 mod p1, p0^-1 mod p2, p1^-1 mod p2, p0^-1 mod p3, p1^-1 mod p3, p2^-1 mod p3} and cp = floor(c 2^32 / p_j);
+// tw: the tail of a 2^15-point inverse per prime (1/2 | psi^-brv(1) / 2) and its quotient (kernels with S = 1)
+struct Garner32 { u32 p[4]; u32 c[6], cp[6]; u32 tw[4][2], twp[4][2]; };
+// y any u32 -> [0, p)
+__device__ __forceinline__ u32 g32_mul(u32 y, u32 c, u32 cp, u32 p) { const u32 r = y * c - __umulhi(y, cp) * p; return r >= p ? r - p : r; }
+// y any u32 -> [0, 2p)
+__device__ __forceinline__ u32 g32_mul_lazy(u32 y, u32 c, u32 cp, u32 p) { return y * c - __umulhi(y, cp) * p; }
+// a, b below 2p -> a - b + 2p in (0, 4p): only ever the argument of a g32_mul
+__device__ __forceinline__ u32 g32_sub(u32 a, u32 b, u32 p) { return a + 2 * p - b; }
 // Garner's mixed radix over the residues of the four auxiliary primes: x1 + p0 (x2 + p1 (x3 + p2 x4)), in [0, p0 p1 p2 p3)
 __device__ __forceinline__ u128 g32_garner(u32 v0, u32 v1, u32 v2, u32 v3, const Garner32& gc) {
   const u32 p0 = gc.p[0], p1 = gc.p[1], p2 = gc.p[2], p3 = gc.p[3];
@@ -674,7 +544,8 @@ __device__ __forceinline__ void ks_limb_words(u128 V, int bt, u64& w0, u64& w1, 
 template <int W, int LQ, int B, int NLB, bool A32, int S = 0>
 __global__ void __launch_bounds__(128) ks_recombine_kernel(const u64* __restrict__ o, i64 n, u64 q0, u64 q1, u64 q0inv, u64 q0inv_sh, u64 half_hi, u64 half_lo,
                                                            u64 a_hi, u64 a_lo, const u64* __restrict__ consts /* D[W+1], pinv lo, hi */,
-                                                           const u64* __restrict__ Pfull, const u64* __restrict__ halfP, u64* __restrict__ out, int nl_out, Garner32 gc) {
+                                                           const u64* __restrict__ Pfull, const u64* __restrict__ halfP, u64* __restrict__ out, int nl_out,
+                                                           Garner32 gc) {
   const i64 poly = blockIdx.y;
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
@@ -710,7 +581,8 @@ __global__ void __launch_bounds__(128) ks_recombine_kernel(const u64* __restrict
       if (PRE) { v0 = vin[l][0]; v1 = vin[l][1]; v2 = vin[l][2]; v3 = vin[l][3]; }
       else if (S) {
         const u32* r0 = base32 + (i64)(l * 4) * n;
-        const u32 a0 = r0[0], b0 = r0[1 << 14], a1 = r0[n], b1 = r0[n + (1 << 14)], a2 = r0[2 * n], b2 = r0[2 * n + (1 << 14)], a3 = r0[3 * n], b3 = r0[3 * n + (1 << 14)];
+        const u32 a0 = r0[0], b0 = r0[1 << 14], a1 = r0[n], b1 = r0[n + (1 << 14)], a2 = r0[2 * n], b2 = r0[2 * n + (1 << 14)], a3 = r0[3 * n],
+                  b3 = r0[3 * n + (1 << 14)];
         v0 = tail(a0, b0, 0); v1 = tail(a1, b1, 1); v2 = tail(a2, b2, 2); v3 = tail(a3, b3, 3);
       }
       else { v0 = base32[(i64)(l * 4 + 0) * n]; v1 = base32[(i64)(l * 4 + 1) * n]; v2 = base32[(i64)(l * 4 + 2) * n]; v3 = base32[(i64)(l * 4 + 3) * n]; }
@@ -741,6 +613,9 @@ __global__ void __launch_bounds__(128) ks_recombine_kernel(const u64* __restrict
     }
   }
   // x = S + 2^m P, below 2^(64 (W-1) + 63): x[W] = 0
+  // (this kernel keeps its own spelling of the quotient estimate, the multiply-subtract, the comparisons and the subtraction: through the
+  // shared steps of crt_wide.h it compiles to fewer exec-masked branches, 6 to 8 % fewer instructions, and measured 1.1 % slower on the metric
+  // ring with uniform keys -- profiles/crt_wide_refactor_ab.txt.  The algorithm is wide_qhat / wide_mulsub / wide_ge / wide_gt / wide_sub.)
   const u64 t0 = x[W - 2], t1 = x[W - 1], p0 = consts[W + 1], p1 = consts[W + 2];
   u128 mid = (u128)t1 * p0 + (u64)(((u128)t0 * p0) >> 64);
   const u128 add = (u128)t0 * p1;
@@ -788,9 +663,10 @@ __global__ void __launch_bounds__(128) ks_recombine_kernel(const u64* __restrict
 // x live in LDS (limb-major, one column per thread: run-time limb indices cost nothing there).  The compile-time instantiations above
 // serve the shapes the benchmarks run; this one makes limb mode (and the 30-bit auxiliary primes) available to every chain.
 template <int MAXW, bool A32>
-__global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __restrict__ o, i64 n, i64 nrow, i64 fold_q, int W, int LQ, int B, int NLB, u64 q0, u64 q1, u64 q0inv, u64 q0inv_sh,
-                                                                   u64 half_hi, u64 half_lo, u64 a_hi, u64 a_lo, const u64* __restrict__ consts /* D[W+1], pinv lo, hi */,
-                                                                   const u64* __restrict__ Pfull, const u64* __restrict__ halfP, u64* __restrict__ out, int nl_out, Garner32 gc) {
+__global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __restrict__ o, i64 n, i64 nrow, i64 fold_q, int W, int LQ, int B, int NLB,
+                                                                   u64 q0, u64 q1, u64 q0inv, u64 q0inv_sh, u64 half_hi, u64 half_lo, u64 a_hi, u64 a_lo,
+                                                                   const u64* __restrict__ consts /* D[W+1], pinv lo, hi */, const u64* __restrict__ Pfull,
+                                                                   const u64* __restrict__ halfP, u64* __restrict__ out, int nl_out, Garner32 gc) {
   __shared__ u64 xs[(MAXW + 1) * 128];
 #define X(i) xs[(i) * 128 + threadIdx.x]
   const i64 poly = blockIdx.y;
@@ -857,45 +733,12 @@ __global__ void __launch_bounds__(128) ks_recombine_generic_kernel(const u64* __
       carry = (u64)(sum >> 64);
     }
   }
-  const u64 t0 = X(W - 2), t1 = X(W - 1), pr0 = consts[W + 1], pr1 = consts[W + 2];
-  u128 mid = (u128)t1 * pr0 + (u64)(((u128)t0 * pr0) >> 64);
-  const u128 add = (u128)t0 * pr1;
-  const u128 mid2 = mid + add;
-  u128 qh = (u128)t1 * pr1 + (mid2 >> 64) + ((mid2 < add) ? ((u128)1 << 64) : 0);
-  const u64 qhat = (u64)qh;
-  {
-    u64 carry = 0, borrow = 0;
-    for (int i = 0; i < W; ++i) {
-      const u128 t = (u128)qhat * Pfull[i] + carry;
-      carry = (u64)(t >> 64);
-      const u64 xi = X(i), tl = (u64)t, d = xi - tl, b1 = xi < tl, d2 = d - borrow, b2 = d < borrow;
-      X(i) = d2;
-      borrow = b1 | b2;
-    }
-  }
-  auto ge = [&](const u64* __restrict__ c, bool strict) -> bool {      // x[0..W) >= c (or > c)
-    for (int i = W - 1; i >= 0; --i) { const u64 h = c[i], xi = X(i); if (xi != h) return xi > h; }
-    return !strict;
-  };
-  auto subP = [&]() {
-    u64 borrow = 0;
-    for (int i = 0; i < W; ++i) { const u64 pp = Pfull[i], xi = X(i), d = xi - pp, b1 = xi < pp, d2 = d - borrow, b2 = d < borrow; X(i) = d2; borrow = b1 | b2; }
-  };
-  if (ge(Pfull, false)) subP();
-  if (ge(Pfull, false)) subP();
-  if (ge(halfP, true)) subP();                                  // centre: x > (P-1)/2  ->  x - P   (DoubleCRT.cpp:375-376)
-  // mode-2 store: the centred residue modulo 2^logQ, two's complement, coefficient-major
-  const u64 sf = (X(W - 1) >> 63) ? ~0ull : 0ull;
-  const int sw = (LQ - 1) >> 6, sb = (LQ - 1) & 63;
-  const u64 hbit = ((sw < W ? X(sw) : sf) >> sb) & 1;
-  u64* op = out + (poly * n + j) * nl_out;
-  for (int i = 0; i < nl_out; ++i) {
-    u64 val = i < W ? X(i) : sf;
-    const int bits_left = LQ - 64 * i;
-    if (bits_left <= 0) val = hbit ? ~0ull : 0ull;
-    else if (bits_left < 64) { const u64 mask = (1ull << (bits_left & 63)) - 1; val = hbit ? (val | ~mask) : (val & mask); }
-    op[i] = val;
-  }
+  const WideCol<128> xw{xs + threadIdx.x};
+  wide_mulsub(xw, wide_qhat(X(W - 2), X(W - 1), consts[W + 1], consts[W + 2]), Pfull, 0, W);
+  if (wide_ge(xw, Pfull, W)) wide_sub(xw, Pfull, W);
+  if (wide_ge(xw, Pfull, W)) wide_sub(xw, Pfull, W);
+  if (wide_gt(xw, halfP, W)) wide_sub(xw, Pfull, W);              // centre: x > (P-1)/2  ->  x - P   (DoubleCRT.cpp:375-376)
+  crt_store_rt(xs + threadIdx.x, 128, W, 2, LQ, out, poly, n, j, nl_out);
 #undef X
 }
 
@@ -936,8 +779,9 @@ static int launch_ks_recombine_t(fhesi_ctx* ctx, const CrtTables* t, const fhesi
   FHESI_TRY(ks_recombine_consts(ctx, A32, S != 0, &c));
   dim3 grid((unsigned)((ctx->phim + 127) / 128), (unsigned)npolys);
   PROF_KERNEL(ctx, PROF_NAME_KS_RECOMBINE, (ks_recombine_kernel<W, LQ, B, NLB, A32, S>));
-  ks_recombine_kernel<W, LQ, B, NLB, A32, S><<<grid, 128, 0, ctx->stream>>>(d_o, ctx->phim, c.q0, c.q1, c.q0inv, c.q0inv_sh, c.half_hi, c.half_lo, c.a_hi, c.a_lo,
-                                                                          k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W, t->d_halfP, d_out, nl_out, c.gc);
+  ks_recombine_kernel<W, LQ, B, NLB, A32, S><<<grid, 128, 0, ctx->stream>>>(
+      d_o, ctx->phim, c.q0, c.q1, c.q0inv, c.q0inv_sh, c.half_hi, c.half_lo, c.a_hi, c.a_lo, k->d_limb_consts, t->d_P + (size_t)t->nidx * t->W,
+      t->d_halfP, d_out, nl_out, c.gc);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -954,7 +798,9 @@ struct CentredConsts { u64 d[16]; };
 // taken in the loader: the three positions a coefficient is folded from (g32_fold) are worked out once (they do not depend on the limb or the prime),
 // their sub-inverse pairs are loaded unconditionally, summed per half of the row with their signs and multiplied by the two tail constants.
 template <int NWORDS, int NLBF = 0, int BF = 0, int LQF = 0, int FS = 0>
-__global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __restrict__ o32, i64 n, i64 nrow, i64 fold_q, int S /* 1: rows of 2^15 left as their two sub-inverses (the tail stage is taken here) */, int LQ_, int B_, int NLB_, u64 half_hi, u64 half_lo,
+__global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __restrict__ o32, i64 n, i64 nrow, i64 fold_q,
+                                                                   int S /* 1: rows of 2^15 left as their two sub-inverses (the tail stage is taken here) */,
+                                                                   int LQ_, int B_, int NLB_, u64 half_hi, u64 half_lo,
                                                                    u64 a_hi, u64 a_lo, CentredConsts cc, u64* __restrict__ out, int nl_out, Garner32 gc) {
   constexpr bool FIX = NLBF > 0;
   const int LQ = FIX ? LQF : LQ_, B = FIX ? BF : B_, NLB = FIX ? NLBF : NLB_;
@@ -1104,37 +950,9 @@ __global__ void __launch_bounds__(128) ks_recombine_centred_kernel(const u32* __
   u64 hbit = 0;
 #pragma unroll
   for (int i = 0; i < NWORDS; ++i) if (i == sw) hbit = (x[i] >> sb) & 1;
-  u64* o = out + (poly * n + j) * nl_out;
 #pragma unroll
-  for (int i = 0; i < NWORDS; ++i) {
-    u64 val = x[i];
-    const int bits_left = LQ - 64 * i;
-    if (bits_left <= 0) val = hbit ? ~0ull : 0ull;
-    else if (bits_left < 64) { const u64 mask = (1ull << (bits_left & 63)) - 1; val = hbit ? (val | ~mask) : (val & mask); }
-    x[i] = val;
-  }
-  // Coefficient-major output: a lane owns NWORDS consecutive 8-byte limbs, so a direct store instruction of the wave touches 32-64 cache lines
-  // for 8-16 bytes each.  When the wave is whole (n a multiple of 64) and the caller's limb count is the kernel's, the wave's 64 x NWORDS limbs --
-  // one contiguous block of memory -- pass through its own LDS rows (stride NWORDS + 1: conflict-free) and leave 512 contiguous bytes per
-  // store instruction (round 5: the kernel was 43 % VALU busy at 3.7 TB/s).
-  if (nl_out == NWORDS && (n & 63) == 0) {
-    __shared__ u64 stg[2][64 * (NWORDS + 1)];
-    const u32 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u64* __restrict__ st = stg[wv];
-#pragma unroll
-    for (int i = 0; i < NWORDS; ++i) st[lane * (NWORDS + 1) + i] = x[i];
-    __builtin_amdgcn_wave_barrier();
-    u64* __restrict__ ow = out + (poly * n + (j - lane)) * NWORDS;      // the wave's block
-#pragma unroll
-    for (int k = 0; k < NWORDS; ++k) {
-      const u32 e = k * 64 + lane, tl = e / NWORDS, ii = e % NWORDS;   // (NWORDS a power of two: shifts)
-      ow[e] = st[tl * (NWORDS + 1) + ii];
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < NWORDS; ++i) if (i < nl_out) o[i] = x[i];
-  for (int i = NWORDS; i < nl_out; ++i) o[i] = hbit ? ~0ull : 0ull;
+  for (int i = 0; i < NWORDS; ++i) x[i] = reduce_limb(x[i], i, LQ, hbit);
+  crt_store_coeff_major<NWORDS, 2>(x, hbit, true, out, poly, n, j, nl_out);
 }
 static int launch_ks_recombine_centred(fhesi_ctx* ctx, const fhesi_ksk* k, const u64* d_o, i64 npolys, u64* d_out, int nl_out, bool tail_pending) {
   RecombineConsts c;
@@ -1144,21 +962,15 @@ static int launch_ks_recombine_centred(fhesi_ctx* ctx, const fhesi_ksk* k, const
   if (LQ > 1024) FHESI_FAIL("key switch, centred limbs: logQ=%d above 1024", LQ);
   // start value: - sum_l 2^(119 + B l)  modulo 2^(64 NW)
   CentredConsts cc{};
-  {
-    std::vector<u64> D((size_t)NW, 0);
-    for (int l = 0; l < NLB; ++l) {
-      const int bit = 119 + B * l;
-      if (bit >= 64 * NW) continue;
-      u64 borrow = (u64)1 << (bit & 63);
-      for (int i = bit >> 6; i < NW && borrow; ++i) { const u64 v = D[i]; D[i] = v - borrow; borrow = v < borrow ? 1 : 0; }
-    }
-    for (int i = 0; i < NW; ++i) cc.d[i] = D[i];
-  }
+  std::vector<u64> D((size_t)NW, 0);
+  ks_start_offset(D, B, NLB);
+  for (int i = 0; i < NW; ++i) cc.d[i] = D[i];
   const i64 nrow = aux32_row_len(ctx);
   const i64 fold = k->aux_fold;
   dim3 grid((unsigned)((ctx->phim + 127) / 128), (unsigned)npolys);
   void (*kern)(const u32*, i64, i64, i64, int, int, int, int, u64, u64, u64, u64, CentredConsts, u64*, int, Garner32);
-  if (NW == 16 && LQ == 1024 && B == 72 && NLB == 15 && !fold)         // the stress ring with a generated matrix (rows of 2^15: the tail stage in the loader when S)
+  // the stress ring with a generated matrix (rows of 2^15: the tail stage in the loader when S)
+  if (NW == 16 && LQ == 1024 && B == 72 && NLB == 15 && !fold)
     kern = ks_recombine_centred_kernel<16, 15, 72, 1024>;
   else if (NW == 8 && LQ == 512 && B == 74 && NLB == 7 && !fold && !S)      // the metric ring with a generated matrix
     kern = ks_recombine_centred_kernel<8, 7, 74, 512>;
@@ -1186,16 +998,21 @@ bool ks_recombine_takes_tail(const fhesi_ctx* ctx, const CrtTables* t, const fhe
 }
 int launch_ks_recombine(fhesi_ctx* ctx, const CrtTables* t, const fhesi_ksk* k, const u64* d_o, i64 npolys, u64* d_out, int nl_out, bool tail_pending) {
   if (!npolys) return 0;
-  if (tail_pending && !ks_recombine_takes_tail(ctx, t, k)) FHESI_FAIL("key switch: rows without their tail stage reached a recombination that does not take it");
+  if (tail_pending && !ks_recombine_takes_tail(ctx, t, k))
+    FHESI_FAIL("key switch: rows without their tail stage reached a recombination that does not take it");
   ProfScope prof(ctx, PROF_CRT, (double)npolys);
   if (k->aux_centred) return launch_ks_recombine_centred(ctx, k, d_o, npolys, d_out, nl_out, tail_pending);
   // compile-time instantiations for the shapes the benchmarks run (the plan of ks_limb_plan at the metric and stress chains) ...
   int (*fixed)(fhesi_ctx*, const CrtTables*, const fhesi_ksk*, const u64*, i64, u64*, int) = nullptr;
   if (tail_pending) fixed = launch_ks_recombine_t<34, 1024, 72, 30, true, 1>;      // (ks_recombine_takes_tail has checked the shape)
-  else if (!k->aux_fold && k->aux32 && t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15) fixed = launch_ks_recombine_t<18, 512, 74, 15, true>;
-  else if (!k->aux32 && t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15) fixed = launch_ks_recombine_t<18, 512, 74, 15, false>;
-  else if (!k->aux32 && t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30) fixed = launch_ks_recombine_t<34, 1024, 72, 30, false>;
-  else if (!k->aux_fold && k->aux32 && t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30) fixed = launch_ks_recombine_t<34, 1024, 72, 30, true>;
+  else {
+    const bool metric = t->W == 18 && k->aux_logQ == 512 && k->aux_limb_bits == 74 && k->aux_rows == 15;
+    const bool stress = t->W == 34 && k->aux_logQ == 1024 && k->aux_limb_bits == 72 && k->aux_rows == 30;
+    if (!k->aux_fold && k->aux32 && metric) fixed = launch_ks_recombine_t<18, 512, 74, 15, true>;
+    else if (!k->aux32 && metric) fixed = launch_ks_recombine_t<18, 512, 74, 15, false>;
+    else if (!k->aux32 && stress) fixed = launch_ks_recombine_t<34, 1024, 72, 30, false>;
+    else if (!k->aux_fold && k->aux32 && stress) fixed = launch_ks_recombine_t<34, 1024, 72, 30, true>;
+  }
   if (fixed) return fixed(ctx, t, k, d_o, npolys, d_out, nl_out);
   // ... and the run-time form for every other chain
   RecombineConsts c;
@@ -1227,7 +1044,8 @@ int launch_crt(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows, int nslots
     if (t->nidx == 18 && W == 18 && logQ == 512) return launch_crt_sum<18, 18, 512>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, d_out, nl_out);
     if (t->nidx == 35 && W == 34 && logQ == 1024) return launch_crt_sum<35, 34, 1024>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, d_out, nl_out);
   }
-  if (t->nidx == 18 && W == 18 && logQ == 512 && mode != 0) return launch_crt_t<18, 18, 18, 512>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, positive, logQ, d_out, nl_out);
+  if (t->nidx == 18 && W == 18 && logQ == 512 && mode != 0)
+    return launch_crt_t<18, 18, 18, 512>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, positive, logQ, d_out, nl_out);
   if (t->nidx == 18 && W == 18) return launch_crt_t<18, 18, 18>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, positive, logQ, d_out, nl_out);
   if (W <= 4) return launch_crt_t<4>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, positive, logQ, d_out, nl_out);
   if (W <= 8) return launch_crt_t<8>(ctx, t, d_rows, nslots_layout, d_slot_of, npolys, mode, positive, logQ, d_out, nl_out);
@@ -1246,7 +1064,8 @@ int launch_crt(fhesi_ctx* ctx, const CrtTables* t, const u64* d_rows, int nslots
 //   floor(D p / 2) -- exact integer arithmetic on W limbs per coefficient, the same bits as the reference's big-integer loop.
 // consts: D[W], M = D p [W], floor(M / 2) [W].  delta / e: [n][W] two's complement, coefficient-major.
 template <int MAXW>
-__global__ void __launch_bounds__(128) modswitch_delta_kernel(const u64* __restrict__ delta, i64 n, int W, const u64* __restrict__ consts, u64 p, u64 u, u64* __restrict__ e) {
+__global__ void __launch_bounds__(128) modswitch_delta_kernel(const u64* __restrict__ delta, i64 n, int W, const u64* __restrict__ consts, u64 p, u64 u,
+    u64* __restrict__ e) {
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   u64 d[MAXW], x[MAXW];
@@ -1275,9 +1094,8 @@ __global__ void __launch_bounds__(128) modswitch_delta_kernel(const u64* __restr
   }
   if (x[W - 1] >> 63) { u64 c = 0; for (int i = 0; i < W; ++i) { const u128 s = (u128)x[i] + M[i] + c; x[i] = (u64)s; c = (u64)(s >> 64); } }
   // x in [0, M): subtract M when x > floor(M / 2)
-  int cmp = 0;
-  for (int i = W - 1; i >= 0 && !cmp; --i) if (x[i] != H[i]) cmp = x[i] < H[i] ? -1 : 1;
-  if (cmp > 0) { u64 br = 0; for (int i = 0; i < W; ++i) { const u128 s = (u128)x[i] - M[i] - br; x[i] = (u64)s; br = (u64)(s >> 64) & 1; } }
+  const WideCol<1> xw{x};
+  if (wide_gt(xw, H, W)) wide_sub(xw, M, W);
   for (int i = 0; i < W; ++i) e[j * W + i] = x[i];
 }
 

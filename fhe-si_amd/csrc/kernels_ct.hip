@@ -5,14 +5,7 @@
 // ciphertexts (tProd) are residue rows [count][3][L][phi(m)].  All kernels are streaming (HBM-bound) integer work.
 #include "fhesi_internal.h"
 
-// Reduce (Util.cpp:3-26): sign-extend from bit logQ-1 (centred) or clear everything above it (positive)
-__device__ __forceinline__ u64 reduce_limb(u64 val, int i, int logQ, u64 sbit) {
-  const int bits_left = logQ - 64 * i;
-  if (bits_left <= 0) return sbit ? ~0ull : 0ull;
-  if (bits_left < 64) { const u64 mask = (1ull << bits_left) - 1; return sbit ? (val | ~mask) : (val & mask); }
-  return val;
-}
-
+// (Reduce, Util.cpp:3-26, of one limb: reduce_limb in fhesi_internal.h)
 // Ciphertext::operator+= for unscaled ciphertexts (Ciphertext.cpp:123-134): parts[i] += other.parts[i]; ReduceCoefficients
 template <int MAXNL>
 __global__ void __launch_bounds__(256) ct_add_kernel(u64* __restrict__ dst, const u64* __restrict__ src, i64 ncoeffs, int nl, int logQ) {
@@ -93,8 +86,8 @@ int launch_ct_add(fhesi_ctx* ctx, u64* d_dst, const u64* d_src, i64 ncoeffs, int
 // so no row transform is needed at all: out = positive residue modulo 2^logQ, limb-major, as ByteDecompPart takes it (Ciphertext.cpp:94).
 // mode: 0 power of two, 1 m = 2 q^k, 2 m = q^k; st = the stride s.  in [npolys][n][nl_in] two's complement;  out [npolys][nlq][n] (logQ > 0), or the
 // integers themselves, sign-extended, coefficient-major [npolys][n][nlq] (logQ = 0: toPoly of Ciphertext >>= without a key switch).
-__global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __restrict__ in, i64 n, int nl_in, i64 m, i64 kk, i64 kinv, int mode, i64 st, int logQ,
-                                                                 u64* __restrict__ out, int nlq) {
+__global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __restrict__ in, i64 n, int nl_in, i64 m, i64 kk, i64 kinv, int mode, i64 st,
+                                                                 int logQ, u64* __restrict__ out, int nlq) {
   const i64 poly = blockIdx.y;
   const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -188,7 +181,8 @@ int launch_ct_mul_long(fhesi_ctx* ctx, u64* d_ct, i64 ncoeffs, int nl, int logQ,
 // one constant for the whole batch).  Only the quotient modulo 2^logQ matters; it is formed limb by limb from the top by 128 / 64-bit
 // long division of |other_j| 2^logQ, and a negative constant takes -(q + [remainder != 0]) (floor, not truncation).
 template <int MAXNL>
-__global__ void __launch_bounds__(256) ct_add_const_kernel(u64* __restrict__ ct, const i64* __restrict__ poly, int npoly, i64 n, int nparts, int nl, int logQ, u64 p) {
+__global__ void __launch_bounds__(256) ct_add_const_kernel(u64* __restrict__ ct, const i64* __restrict__ poly, int npoly, i64 n, int nparts, int nl, int logQ,
+                                                           u64 p) {
   const i64 c = blockIdx.y;
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
@@ -287,8 +281,8 @@ int launch_segment_sum(fhesi_ctx* ctx, const u64* d_in, const int* d_seg, i64 ng
   if (gx > 64) gx = 64;
   for (i64 done = 0; done < ngroups; done += 65535) {
     const i64 cnt = ngroups - done < 65535 ? ngroups - done : 65535;
-    segment_sum_kernel<<<dim3(gx, (unsigned)(ncomp * ctx->L), (unsigned)cnt), 256, 0, ctx->stream>>>(d_in, d_seg + done, d_out + done * ncomp * ctx->L * ctx->phim,
-                                                                                                    ncomp * ctx->L, ctx->phim, ctx->d_pc, ctx->L);
+    segment_sum_kernel<<<dim3(gx, (unsigned)(ncomp * ctx->L), (unsigned)cnt), 256, 0, ctx->stream>>>(
+        d_in, d_seg + done, d_out + done * ncomp * ctx->L * ctx->phim, ncomp * ctx->L, ctx->phim, ctx->d_pc, ctx->L);
   }
   HIP_TRY(hipGetLastError());
   return 0;
@@ -317,7 +311,8 @@ int launch_encrypt_combine(fhesi_ctx* ctx, const u64* d_rows, const u64* d_pk, i
   if (gx > 64) gx = 64;
   for (i64 done = 0; done < count; done += 65535) {
     const i64 cnt = count - done < 65535 ? count - done : 65535;
-    encrypt_combine_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_rows + done * 3 * ctx->L * ctx->phim, d_pk, d_out + done * 2 * ctx->L * ctx->phim,
+    encrypt_combine_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_rows + done * 3 * ctx->L * ctx->phim, d_pk,
+                                                                                               d_out + done * 2 * ctx->L * ctx->phim,
                                                                                               ctx->L, ctx->phim, ctx->d_pc);
   }
   HIP_TRY(hipGetLastError());
@@ -327,7 +322,8 @@ int launch_encrypt_combine(fhesi_ctx* ctx, const u64* d_rows, const u64* d_pk, i
 // ---- ctxt[0] += delta * msg; ReduceCoefficients (FHE-SI.cpp:31-35).  ct: [count][2][n][nl]; msg: [count][n] small non-negative;
 // delta = floor(2^logQ / p) as nl limbs.  The product is taken modulo 2^(64 nl), exact modulo 2^logQ.
 template <int MAXNL>
-__global__ void __launch_bounds__(256) add_scaled_msg_kernel(u64* __restrict__ ct, const i64* __restrict__ msg, const u64* __restrict__ delta, i64 n, int nl, int logQ) {
+__global__ void __launch_bounds__(256) add_scaled_msg_kernel(u64* __restrict__ ct, const i64* __restrict__ msg, const u64* __restrict__ delta, i64 n, int nl,
+                                                             int logQ) {
   const i64 c = blockIdx.y;
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
@@ -382,7 +378,8 @@ int launch_decrypt_dot(fhesi_ctx* ctx, const u64* d_rows, const u64* d_t, i64 co
   if (gx > 64) gx = 64;
   for (i64 done = 0; done < count; done += 65535) {
     const i64 cnt = count - done < 65535 ? count - done : 65535;
-    decrypt_dot_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_rows + done * 2 * ctx->L * ctx->phim, d_t, d_out + done * ctx->L * ctx->phim, ctx->L,
+    decrypt_dot_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_rows + done * 2 * ctx->L * ctx->phim, d_t,
+                                                                                           d_out + done * ctx->L * ctx->phim, ctx->L,
                                                                                           ctx->phim, ctx->d_pc);
   }
   HIP_TRY(hipGetLastError());
@@ -509,7 +506,8 @@ __device__ __forceinline__ int block_limb_max(const u64 (&a)[MAXNL], int nw, u64
 // z: [gridDim.y][n][nw] as decrypt_round_kernel takes it; msg: [gridDim.y][n] the same message bits, or null; part: [gridDim.y][gridDim.x][nw]
 // the maximum of |r| over the coefficients of each block
 template <int MAXNL>
-__global__ void __launch_bounds__(256) decrypt_noise_kernel(const u64* __restrict__ z, i64 n, int nw, int logQ, u64 p, i64* __restrict__ msg, u64* __restrict__ part) {
+__global__ void __launch_bounds__(256) decrypt_noise_kernel(const u64* __restrict__ z, i64 n, int nw, int logQ, u64 p, i64* __restrict__ msg,
+                                                            u64* __restrict__ part) {
   const i64 c = blockIdx.y;
   const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
   u64 a[MAXNL];
@@ -527,7 +525,8 @@ __global__ void __launch_bounds__(256) decrypt_noise_kernel(const u64* __restric
 // part: [count][np][nw] -> maxres [count][nw], budget [count] = max(0, logQ - bitlen(maxres)); one wave per ciphertext, each lane keeping
 // the lexicographic maximum of the partials it strides over.  A launch boundary separates it from the kernel above: no atomics, no hand-off.
 template <int MAXNL>
-__global__ void __launch_bounds__(64) noise_budget_kernel(const u64* __restrict__ part, int np, int nw, int logQ, u64* __restrict__ maxres, int* __restrict__ budget) {
+__global__ void __launch_bounds__(64) noise_budget_kernel(const u64* __restrict__ part, int np, int nw, int logQ, u64* __restrict__ maxres,
+                                                          int* __restrict__ budget) {
   const i64 c = blockIdx.x;
   u64 a[MAXNL];
 #pragma unroll
@@ -596,8 +595,9 @@ int launch_rows_mul_bcast(fhesi_ctx* ctx, u64* d_dst, const u64* d_a, const u64*
 //   bcoef: [ncol][n][wb] two's complement (toPoly of b), scoef: [nsrc][n][ws] (toPoly of the source key components), err: [ncol][n];
 //   out: [ncol][n][nl] centred modulo 2^logQ.  Only the bits below logQ of every term matter, so all arithmetic is modulo 2^(64 nl).
 template <int MAXNL>
-__global__ void __launch_bounds__(256) keygen_combine_kernel(const u64* __restrict__ bcoef, int wb, const u64* __restrict__ scoef, int ws, const i64* __restrict__ err,
-                                                              i64 n, int nd, int digit_bits, int nl, int logQ, u64* __restrict__ out) {
+__global__ void __launch_bounds__(256) keygen_combine_kernel(const u64* __restrict__ bcoef, int wb, const u64* __restrict__ scoef, int ws,
+                                                             const i64* __restrict__ err, i64 n, int nd, int digit_bits, int nl, int logQ,
+                                                             u64* __restrict__ out) {
   const i64 col = blockIdx.y;
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
@@ -630,7 +630,8 @@ __global__ void __launch_bounds__(256) keygen_combine_kernel(const u64* __restri
   for (int i = 0; i < MAXNL; ++i)
     if (i < nl) o[i] = reduce_limb(v[i], i, logQ, sb);
 }
-int launch_keygen_combine(fhesi_ctx* ctx, const u64* d_bcoef, int wb, const u64* d_scoef, int ws, const i64* d_err, i64 ncols, int nd, int digit_bits, int nl, int logQ, u64* d_out) {
+int launch_keygen_combine(fhesi_ctx* ctx, const u64* d_bcoef, int wb, const u64* d_scoef, int ws, const i64* d_err, i64 ncols, int nd, int digit_bits, int nl,
+                          int logQ, u64* d_out) {
   if (!ncols) return 0;
   if (nl > 32) FHESI_FAIL("KeySwitchSI::Init: coefficients of %d limbs exceed the supported 32", nl);
   const dim3 grid((unsigned)((ctx->phim + 255) / 256), (unsigned)ncols);

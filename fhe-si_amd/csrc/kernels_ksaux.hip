@@ -223,7 +223,8 @@ __global__ void __launch_bounds__(NW * 64) dot_aux_kernel(const u64* __restrict_
     for (int c = 0; c < CT; ++c)
 #pragma unroll
       for (int r = 0; r < R; ++r)
-        tot[c][r] = (((u128)th[c][r][0] << 64) | tl[c][r][0]) + ((((u128)th[c][r][1] << 64) | tl[c][r][1]) << 30) + ((((u128)th[c][r][2] << 64) | tl[c][r][2]) << 60);
+        tot[c][r] = (((u128)th[c][r][0] << 64) | tl[c][r][0]) + ((((u128)th[c][r][1] << 64) | tl[c][r][1]) << 30) +
+                    ((((u128)th[c][r][2] << 64) | tl[c][r][2]) << 60);
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       if (ct0 + c < count) {
@@ -309,10 +310,7 @@ bool ks_limb_plan(const fhesi_ctx* ctx, const CrtTables* t, int ncol, int digit_
   int B = 0;
   while (B < 100 && (((A / 2) >> (B + 1)) > terms)) ++B;        // the largest B with terms * 2^B < A / 2
   if (B <= 64) return false;                                    // (the limb-scatter kernels cut limbs of 65..100 bits)
-  std::vector<u64> P{1};
-  for (int i = 0; i < ctx->L; ++i) P = hm::bn_mul_small(P, ctx->q[i]);
-  int pbits = (int)(P.size() - 1) * 64;
-  for (u64 top = P.back(); top; top >>= 1) ++pbits;
+  const int pbits = hm::bn_bitlen(t->P);                        // (t holds the whole chain: nidx = L)
   p.W = t->W; p.LQ = logQ; p.B = B; p.NLB = (pbits + B - 1) / B;
   if ((p.NLB - 1) * p.B + 120 > 64 * (p.W + 1)) return false;   // x = D + sum (V_l + 2^119) 2^(B l) fits W + 1 limbs
   if (logQ < 1 || logQ > 64 * (p.W - 1)) return false;
@@ -324,23 +322,17 @@ bool ks_limb_plan(const fhesi_ctx* ctx, const CrtTables* t, int ncol, int digit_
   return true;
 }
 
-// host big integers (little-endian u64 limbs, fixed width) for the limb mode's constants
-static void bn_shl(std::vector<u64>& a, int sh) {
-  const int n = (int)a.size(), w = sh >> 6, b = sh & 63;
-  std::vector<u64> r(n, 0);
-  for (int i = n - 1; i >= w; --i) r[i] = (a[i - w] << b) | ((b && i - w - 1 >= 0) ? (a[i - w - 1] >> (64 - b)) : 0);
-  a.swap(r);
-}
-static void bn_sub(std::vector<u64>& a, const std::vector<u64>& b) {          // a -= b  (mod 2^(64 n))
-  u64 borrow = 0;
-  for (size_t i = 0; i < a.size(); ++i) {
-    const u64 bi = i < b.size() ? b[i] : 0, d = a[i] - bi, b1 = a[i] < bi, d2 = d - borrow, b2 = d < borrow;
-    a[i] = d2; borrow = b1 | b2;
+// The + 2^119 that makes every limb sum V_l non-negative (ks_limb_words, ks_recombine_centred_kernel) is taken off the recombination's start
+// value once: D -= sum_{l < nlb} 2^(119 + B l) modulo 2^(64 D.size()).  A term at or beyond D's width vanishes modulo it: the centred
+// recombination forms only the words below bit logQ and relies on that; on the W + 1 limbs of the general limbs ks_limb_plan's fit check
+// ((NLB - 1) B + 120 <= 64 (W + 1)) keeps every term inside.
+void ks_start_offset(std::vector<u64>& D, int B, int nlb) {
+  std::vector<u64> off(D.size(), 0);                   // the terms are distinct bits: their sum is their union
+  for (int l = 0; l < nlb; ++l) {
+    const int bit = 119 + B * l;
+    if (bit < 64 * (int)D.size()) off[bit >> 6] |= (u64)1 << (bit & 63);
   }
-}
-static bool bn_ge(const std::vector<u64>& a, const std::vector<u64>& b) {
-  for (int i = (int)a.size() - 1; i >= 0; --i) { const u64 bi = i < (int)b.size() ? b[i] : 0; if (a[i] != bi) return a[i] > bi; }
-  return true;
+  hm::bn_sub(D, off);
 }
 
 // builds k->d_aux from k->d_rows (device work only; the caller holds the context's stream)
@@ -355,7 +347,8 @@ int ksaux_build(fhesi_ctx* ctx, fhesi_ksk* k, int digit_bits, int logQ, int mode
   KsLimbPlan plan;
   if (mode == KS_MODE_DIRECT) FHESI_FAIL("key switch: no auxiliary-prime table for the direct path");
   const bool limb = mode != KS_MODE_RESIDUE60 && ks_limb_plan(ctx, t, ncol, digit_bits, logQ, &plan, mode == KS_MODE_LIMB32 ? aux32_primes(ctx) : nullptr);
-  if ((mode != KS_MODE_RESIDUE60) != limb || (limb && plan.a32 != (mode == KS_MODE_LIMB32))) FHESI_FAIL("key switch: the limb plan does not match the selected form");
+  if ((mode != KS_MODE_RESIDUE60) != limb || (limb && plan.a32 != (mode == KS_MODE_LIMB32)))
+    FHESI_FAIL("key switch: the limb plan does not match the selected form");
   int R = limb ? plan.NLB : L;                                // output rows per (ciphertext, key row, auxiliary prime)
   bool centred = false;
   int key_bits = 0;
@@ -377,7 +370,8 @@ int ksaux_build(fhesi_ctx* ctx, fhesi_ksk* k, int digit_bits, int logQ, int mode
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
   void* tmp;
-  FHESI_TRY(ws_reserve(ctx, 0, std::max(k->bytes, (size_t)R * 2 * ncol * aux32_row_len(ctx) * 4), &tmp));      // the key rows, later one auxiliary prime's table rows
+  // the key rows, later one auxiliary prime's table rows
+  FHESI_TRY(ws_reserve(ctx, 0, std::max(k->bytes, (size_t)R * 2 * ncol * aux32_row_len(ctx) * 4), &tmp));
   HIP_TRY(hipMemcpyAsync(tmp, k->d_rows, k->bytes, hipMemcpyDeviceToDevice, ctx->stream));
   if (ctx->pow2) FHESI_TRY(launch_ntt_inv(ctx, (u64*)tmp, 2 * ncol, L, nullptr, true));
   else FHESI_TRY(launch_bluestein_inv(ctx, (u64*)tmp, 2 * ncol, L, all.data()));          // Cmod::iFFT of every key row on a general-m ring
@@ -395,10 +389,7 @@ int ksaux_build(fhesi_ctx* ctx, fhesi_ksk* k, int digit_bits, int logQ, int mode
       rc = launch_crt(ctx, t, (const u64*)tmp, L, nullptr, 2 * ncol, 0, 0, 0, kint, W);
       if (!rc) rc = ks32_key_bits(ctx, kint, (i64)2 * ncol * n, W, &key_bits);
       if (!rc) {
-        std::vector<u64> P{1};
-        for (int i = 0; i < L; ++i) P = hm::bn_mul_small(P, ctx->q[i]);
-        int pbits = (int)(P.size() - 1) * 64;
-        for (u64 top = P.back(); top; top >>= 1) ++pbits;
+        const int pbits = hm::bn_bitlen(t->P);
         const int nlc = std::max(1, (key_bits + plan.B - 1) / plan.B);
         // |S| <= terms 2^nb  (terms = ncol n 2^digit_bits, x 4 on the folded rings: mbits - 1 bits)  must stay below P / 2
         if (nlc < plan.NLB && plan.mbits + key_bits + 1 < pbits && logQ <= 1024) { centred = true; R = nlc; }
@@ -416,21 +407,18 @@ int ksaux_build(fhesi_ctx* ctx, fhesi_ksk* k, int digit_bits, int logQ, int mode
     hipFree(kint);
     if (rc) FHESI_FAIL("key switch, limb mode: building the limb table failed");
     // constants of the recombination kernel: D = 2^(mbits-1) P - sum_l 2^(119 + B l)  (W+1 limbs), floor(2^(64(W-2)+128) / P)
-    std::vector<u64> P{1};
-    for (int i = 0; i < L; ++i) P = hm::bn_mul_small(P, ctx->q[i]);
-    std::vector<u64> D(W + 1, 0);
-    for (size_t i = 0; i < P.size(); ++i) D[i] = P[i];
-    bn_shl(D, plan.mbits - 1);
-    for (int l = 0; l < R; ++l) { std::vector<u64> o(W + 1, 0); const int bit = 119 + plan.B * l; o[bit >> 6] = (u64)1 << (bit & 63); bn_sub(D, o); }
+    std::vector<u64> D = hm::bn_resized(t->P, W + 1);
+    hm::bn_shl(D, plan.mbits - 1);
+    ks_start_offset(D, plan.B, R);
     // restoring division of 2^e by P, e = 64 (W-2) + 128
     const int e = 64 * (W - 2) + 128;
-    std::vector<u64> rem(W + 1, 0), Pw(W + 1, 0), quo(3, 0);
-    for (size_t i = 0; i < P.size(); ++i) Pw[i] = P[i];
+    std::vector<u64> rem(W + 1, 0), quo(3, 0);
+    const std::vector<u64>& Pw = t->P;
     for (int bit = e; bit >= 0; --bit) {
-      bn_shl(rem, 1);
+      hm::bn_shl(rem, 1);
       if (bit == e) rem[0] |= 1;
       quo[2] = (quo[2] << 1) | (quo[1] >> 63); quo[1] = (quo[1] << 1) | (quo[0] >> 63); quo[0] <<= 1;
-      if (bn_ge(rem, Pw)) { bn_sub(rem, Pw); quo[0] |= 1; }
+      if (hm::bn_ge(rem, Pw)) { hm::bn_sub(rem, Pw); quo[0] |= 1; }
     }
     if (quo[2]) FHESI_FAIL("key switch, limb mode: reciprocal of the chain product does not fit 128 bits");
     std::vector<u64> h(D);
@@ -509,7 +497,8 @@ int launch_aux_crt(fhesi_ctx* ctx, const fhesi_ksk* k, const u64* d_o, u64* d_ds
   const u128 half = ((u128)q0 * q1 - 1) / 2;
   ProfScope prof(ctx, PROF_EW, (double)nrows);
   dim3 grid((unsigned)((n + 255) / 256 > 64 ? 64 : (n + 255) / 256), (unsigned)nrows);
-  aux_crt_kernel<<<grid, 256, 0, ctx->stream>>>(d_o, d_dst, n, ctx->L, ctx->d_pc, q0, q1, inv, hm::shoup(inv, q1), k->d_aux_consts, (u64)(half >> 64), (u64)half);
+  aux_crt_kernel<<<grid, 256, 0, ctx->stream>>>(d_o, d_dst, n, ctx->L, ctx->d_pc, q0, q1, inv, hm::shoup(inv, q1), k->d_aux_consts,
+                                                (u64)(half >> 64), (u64)half);
   HIP_TRY(hipGetLastError());
   return 0;
 }

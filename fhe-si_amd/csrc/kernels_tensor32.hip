@@ -77,9 +77,7 @@ void tensor32_free(fhesi_ctx* ctx) {
 }
 
 // ---------------------------------------------------------------------------------------------- host big integers (little-endian u64 limbs)
-typedef std::vector<u64> Big;
-static Big big_mul_small(const Big& a, u64 b) { return hm::bn_mul_small(a, b); }
-static u64 big_mod_small(const Big& a, u64 q) { u128 r = 0; for (size_t i = a.size(); i-- > 0;) r = ((r << 64) | a[i]) % q; return (u64)r; }
+using hm::Big;
 static u32 big_word(const Big& a, int l, int R) {          // word l of the radix-2^R form
   const int bit = R * l, w = bit >> 6, o = bit & 63;
   u64 v = (size_t)w < a.size() ? a[w] >> o : 0;
@@ -313,14 +311,14 @@ static int t32_config(fhesi_ctx* ctx, u64 lift, int nlimbs, int logQ, i64 gmax, 
   // CRT tables
   c->pr.closing = S ? T32_ROWS_PLAIN : T32_ROWS_CRT;
   Big M{1};
-  for (int a = 0; a < NP; ++a) M = big_mul_small(M, primes[a]);
+  for (int a = 0; a < NP; ++a) M = hm::bn_mul_small(M, primes[a]);
   std::vector<Tw32> cinv((size_t)NP * 2);
   std::vector<u32> inv57(NP), Mw((size_t)(NP + 1) * WT + 64);        // (padded: the generic kernel multiplies a fixed number of words per row, whatever the window)
   for (int a = 0; a < NP; ++a) {
     Big Mi{1};
-    for (int b = 0; b < NP; ++b) if (b != a) Mi = big_mul_small(Mi, primes[b]);
+    for (int b = 0; b < NP; ++b) if (b != a) Mi = hm::bn_mul_small(Mi, primes[b]);
     const u64 p = primes[a];
-    const u64 ci = hm::invmod(big_mod_small(Mi, p), p);
+    const u64 ci = hm::invmod(hm::bn_mod_small(Mi, p), p);
     auto tw = [&](u64 w) { return Tw32{(u32)w, (u32)((w << 32) / p)}; };
     if (!S) {
       // rows of 2^14: the product by ci is the inverse transform's own closing multiplication (ntt32_inv_kernel3, last stage: (X + Y) c and

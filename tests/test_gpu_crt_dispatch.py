@@ -147,6 +147,15 @@ row("stress-centred-limbs", {"ks_recombine": "ks_recombine_centred_kernel<16, 15
 row("aux60-stress-chain", {"ks_recombine": "ks_recombine_kernel<34, 1024, 72, 30, false, 0>", "crt": "crt_sum_kernel<35, 34, 1024, true>"}, "ks_big", m=1 << 16, logQ=1024, p=65537,
     centred=False, form=2, options={"ks_aux60": 1})
 
+# More output limbs than the value has (nl_extra: every row above asks for ceil(logQ / 64)): the sign fill beyond bit logQ, and on whole waves
+# the direct stores beside the staged path.  One row per store body of kernels_crt.hip (crt_wide.h), at the smallest ring that reaches it.
+row("wide-out-runtime-epilogue", {"crt_exact": crt_bucket(4)}, "ks_small", m=M_CHAIN, W=4, logQ=100, matrix="uniform", form=0, nl_extra=1)
+row("wide-out-runtime-epilogue-mode3", {"crt_exact": crt_bucket(4)}, "automorph", W=4, logQ=100, nl_extra=1)
+row("wide-out-fixed-store", {"crt": "crt_sum_kernel<18, 18, 512, false>", "crt_exact": "crt_kernel<18, 18, 18, 512>"}, "ks_small", m=M_CHAIN, nprimes=18, logQ=512,
+    matrix="uniform", form=0, nl_extra=1)
+row("wide-out-generic-recombination", {"ks_recombine": "ks_recombine_generic_kernel<20, false>"}, "ks_small", m=4096, logQ=128, matrix="uniform", form=2, nl_extra=1)
+row("wide-out-centred", {"ks_recombine": "ks_recombine_centred_kernel<8, 0, 0, 0, 0>"}, "ks_big", m=1 << 15, logQ=300, centred=True, form=1, nl_extra=1)
+
 
 # ---------------------------------------------------------------------------------------------------------------------------------- runners
 @functools.lru_cache(maxsize=None)
@@ -267,13 +276,13 @@ def generated_like(orc, rng, n, L, ncol, logQ):
     return ksm
 
 
-def run_ks_small(names, m, logQ, matrix, form, p=23, W=0, nprimes=0, options=None, crafted=True):
+def run_ks_small(names, m, logQ, matrix, form, p=23, W=0, nprimes=0, options=None, crafted=True, nl_extra=0):
     """fhesi_apply_key_switch_dev (ScaleDown = CRT mode 1, then the recombination or the per-prime form's CRT mode 2) against the oracle"""
     primes, roots = small_chain(m, logQ, p, W, nprimes)
     ctx, orc = F.Context(m, primes, roots), O.Oracle(m, primes, roots)
     if m > 2000 and m & (m - 1):
         orc.set_bluestein_fft(True)
-    n, L, nd, nl = ctx.phim, ctx.L, R.ndigits(logQ), (logQ + 63) // 64
+    n, L, nd, nl = ctx.phim, ctx.L, R.ndigits(logQ), (logQ + 63) // 64 + nl_extra
     for o, v in (options or {}).items():
         ctx.set_option(o, v)
     rng = np.random.default_rng(m + logQ + L)
@@ -309,12 +318,12 @@ def run_ks_small(names, m, logQ, matrix, form, p=23, W=0, nprimes=0, options=Non
         assert np.array_equal(out.download((2, 2, n, nl))[0], orc.apply_key_switch(ksm, t1[0], logQ, nl)), (d, pos)
 
 
-def run_automorph(names, logQ, W=0, nprimes=0, p=23):
+def run_automorph(names, logQ, W=0, nprimes=0, p=23, nl_extra=0):
     """fhesi_ct_automorph_key_switch_dev on evaluation rows (option automorph_rows): toPoly + the positive residue modulo 2^logQ = CRT mode 3"""
     m, k = M_CHAIN, 3
     primes, roots = small_chain(m, logQ, p, W, nprimes)
     ctx, orc = F.Context(m, primes, roots), O.Oracle(m, primes, roots)
-    n, L, nd, nl = ctx.phim, ctx.L, R.ndigits(logQ), (logQ + 63) // 64
+    n, L, nd, nl = ctx.phim, ctx.L, R.ndigits(logQ), (logQ + 63) // 64 + nl_extra
     rng = np.random.default_rng(logQ + L)
     ksm = np.stack([P.rand_rows(rng, primes, n, 2 * nd) for _ in range(2)])
     ksk = F.KeySwitchMatrix(ctx, 2, nd).upload(ksm)
@@ -347,12 +356,12 @@ def run_modswitch(names, W, p=23):
     assert d.index_set() == [0] and np.array_equal(d.rows()[0], want[0])
 
 
-def run_ks_big(names, m, logQ, centred, form, p=23, options=None):
+def run_ks_big(names, m, logQ, centred, form, p=23, options=None, nl_extra=0):
     """A matrix generated on the device (KeySwitchSI::Init) with the crafted column written over column 0, on rings where one oracle call takes minutes:
     the fused form against the per-prime form of the same matrix (one dot product per chain prime, the reference's structure)."""
     primes, roots = P.chain_for(m, logQ, p, 1, 60)
     ctx = F.Context(m, primes, roots)
-    n, L, nd, nl = ctx.phim, ctx.L, R.ndigits(logQ), (logQ + 63) // 64
+    n, L, nd, nl = ctx.phim, ctx.L, R.ndigits(logQ), (logQ + 63) // 64 + nl_extra
     Wl, ncol = L + 2, 3 * nd
     rng = np.random.default_rng(m + logQ)
     one = np.zeros((n, 1), dtype=np.uint64)
