@@ -49,7 +49,9 @@ ABI_SYMBOLS = [
     "fhesi_plain_create_slots", "fhesi_plain_create_poly", "fhesi_plain_free", "fhesi_plain_info", "fhesi_plain_sum_bits", "fhesi_ct_plain_sum_dev", "fhesi_ct_add_slots_dev",
     "fhesi_ct_noise_batch", "fhesi_decrypt_noise_batch", "fhesi_ct_noise_int_batch",
     "fhesi_ksk_hoist", "fhesi_ct_rotations_dev", "fhesi_ct_matvec_dev",
+    "fhesi_ct_rot_sum_dev", "fhesi_matvec_bsgs_plan", "fhesi_ct_matvec_bsgs_dev",
 ]
+ROT_SUM_MAX_TERMS = 16   # FHESI_ROT_SUM_MAX_TERMS: the terms one launch of the rotated-sum kernel takes (more terms chain launches)
 ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
 PROF_CLASSES = {"ntt_fwd": 0, "ntt_inv": 1, "rns_reduce": 2, "tensor": 3, "crt": 4, "digits": 5, "dot": 6, "ew": 7, "ntt_fwd_digits_main": 8,
                 "plain_sum": 15}          # (numbered behind the name-only records below, which keep their public numbers)
@@ -241,6 +243,9 @@ def _load():
         "fhesi_ksk_hoist": [_vp, _i64, _vp],
         "fhesi_ct_rotations_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp, _i32],
         "fhesi_ct_matvec_dev": [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_ct_rot_sum_dev": [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp],
+        "fhesi_matvec_bsgs_plan": [_i64, _vp, _vp],
+        "fhesi_ct_matvec_bsgs_dev": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -577,9 +582,32 @@ class Context:
         hs, ka = self._hoisted_args(hoisted, ks)
         _ck(_load().fhesi_ct_matvec_dev(self.h, hs, _p(ka), len(ka), plain.h, logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
 
+    # ---- baby-step/giant-step matrix-vector products (fhesi_ct_rot_sum_dev, fhesi_ct_matvec_bsgs_dev)
+    def ct_rot_sum_dev(self, ks, logQ: int, base, pre: DevBuf, count: int, nlimbs: int, out: DevBuf):
+        """out[i] = Reduce(base[i] + sum_t (pre[t][i] >>= ks[t])): pre [len(ks)][count][2][phim][nlimbs]; base a buffer of count ciphertexts or None;
+        out may be base.  The words of ct_automorph_dev per term, ct_add_dev and the reduction."""
+        ka = np.ascontiguousarray([int(k) for k in ks], dtype=np.int64)
+        _ck(_load().fhesi_ct_rot_sum_dev(self.h, _p(ka) if len(ka) else None, len(ka), logQ, base.ptr if base is not None else None, pre.ptr, count, nlimbs, out.ptr))
+
+    def ct_matvec_bsgs_dev(self, baby_hoisted, kb, giant_hoisted, kg, nk: int, plain: "Plain", logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf,
+                           decomp_bytes: int = 3):
+        """out[i] = Reduce(sum_g rot_kg[g](sum_j rot_kb[j](src[i]) (*) plain[g B + j])), B = len(kb), G = len(kg), (G - 1) B < nk <= G B: the words of
+        ct_rotations_dev for the babies, ct_plain_sum_dev with G groups per ciphertext, ct_rotations_dev per giant and ct_add_dev.  plain[g B + j] holds
+        the diagonal g B + j rotated back by the giant step g (SlotSpace.bsgs_diagonals)."""
+        hb, ka = self._hoisted_args(baby_hoisted, kb)
+        hg, kc = self._hoisted_args(giant_hoisted, kg)
+        _ck(_load().fhesi_ct_matvec_bsgs_dev(self.h, hb, _p(ka), len(ka), hg, _p(kc), len(kc), nk, plain.h, logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+
     def release_host_staging(self):
         """hand back the pinned + device staging ring the host-buffer calls keep between uses"""
         _ck(_load().fhesi_host_stage_release(self.h))
+
+
+def matvec_bsgs_plan(nk: int) -> tuple:
+    """(B, G) for nk diagonals: the B that minimises (B - 1) + (G - 1) with G = ceil(nk / B), of equal sums the larger B.  Touches no device."""
+    b, g = _i32(0), _i32(0)
+    _ck(_load().fhesi_matvec_bsgs_plan(int(nk), C.byref(b), C.byref(g)))
+    return b.value, g.value
 
 
 def plain_sum_bits(m: int, logQ: int, maxabs: int, terms: int) -> float:
@@ -749,6 +777,31 @@ class SlotSpace:
         """out[i] = sum_t rotate(src[i], amounts[t]) o plain[t] (Context.ct_matvec_dev): a matrix-vector product by diagonals, plain from
         SlotSpace.plain with diagonal t in row t."""
         self.ctx.ct_matvec_dev(hoisted, [self.rotation_k(a) for a in amounts], plain, logQ, src, nlimbs, count, out, decomp_bytes)
+
+    # ---- baby-step/giant-step products: diagonal g B + j meets the baby rotation j inside the giant rotation g B, so it is rotated back by g B in the clear
+    def rotate_values(self, vals: np.ndarray, amount: int) -> np.ndarray:
+        """vals [..][total] slot values moved `amount` slots to the left in every row (negative: to the right): what `>>= g^amount` does to a plaintext."""
+        v = np.asarray(vals)
+        if v.shape[-1] != self.total:
+            raise ValueError(f"rotate_values: {v.shape[-1]} values per plaintext, the space has {self.total} slots")
+        rows = self.rows if self.rows == 2 else 1
+        shaped = v.reshape(v.shape[:-1] + (rows, self.total // rows))
+        return np.roll(shaped, -int(amount), axis=-1).reshape(v.shape)
+
+    def bsgs_diagonals(self, diags: np.ndarray, B: int) -> np.ndarray:
+        """diags [T][total] -> the operands of matvec_bsgs: row g B + j is rotate_values(diags[g B + j], -g B)."""
+        d = np.asarray(diags)
+        return np.stack([self.rotate_values(d[t], -(t // B) * B) for t in range(d.shape[0])])
+
+    def matvec_bsgs(self, baby, giant, B: int, plain: Plain, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[i] = sum_t rotate(src[i], t) o d_t for t < plain.nw (Context.ct_matvec_bsgs_dev): baby[j] the hoisted matrix of g^j (j < B; None at j = 0),
+        giant[i] that of g^(i B) (None at i = 0), plain = self.plain(self.bsgs_diagonals(d, B))."""
+        nk = plain.nw
+        G = (nk + B - 1) // B
+        if len(baby) != B or len(giant) != G:
+            raise ValueError(f"matvec_bsgs: {nk} diagonals in steps of {B} take {B} baby and {G} giant matrices, got {len(baby)} and {len(giant)}")
+        self.ctx.ct_matvec_bsgs_dev(baby, [self.rotation_k(j) for j in range(B)], giant, [self.rotation_k(i * B) for i in range(G)], nk, plain, logQ, src, nlimbs,
+                                    count, out, decomp_bytes)
 
     def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nparts: int, nlimbs: int, count: int, vals: np.ndarray, only_usable: bool = True):
         """Ciphertext += Plaintext(vals) on unscaled ciphertexts; vals [nv][nvals] slot values, nv = 1 (one constant for all) or count."""
@@ -945,6 +998,13 @@ class SlotBasis:
         words = 2 * self.ctx.phim * nlimbs * 8
         for c in range(self.k):
             self.channel(c).matvec(hoisted, amounts, plains[c], logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
+
+    def matvec_bsgs(self, baby, giant, B: int, plains, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """SlotSpace.matvec_bsgs per channel: src, out [k][count] logical ciphertexts, plains = SlotBasis.plain of the diagonals that
+        channel(0).bsgs_diagonals rotated back (the rotation moves slots, whatever the prime)."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            self.channel(c).matvec_bsgs(baby, giant, B, plains[c], logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
 
     def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nlimbs: int, count: int, vals):
         """Ciphertext += integers, per channel: ct [k][count] two-part ciphertexts, vals [nv][nvals] integers, nv = 1 or count."""

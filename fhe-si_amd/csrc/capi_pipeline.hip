@@ -512,6 +512,152 @@ extern "C" int fhesi_ct_matvec_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted
   return 0;
 }
 
+// --------------------------------------------------------------------------------------------- baby-step/giant-step matrix-vector products
+// out[i] = Reduce(base[i] + sum_t Ciphertext >>= ks[t] of pre[t][i]), pre[t] at pre + t * term_stride words: ct_rot_sum_kernel where the ring has the signed
+// gather, the composition -- rotation_close per term into workspace slot 15, launch_ct_add -- where it has not or option automorph_rows asks for the
+// evaluation rows.  The same words either way.  Every argument checked by the caller; out may be base.
+static_assert(FHESI_ROT_SUM_MAX_TERMS == kRotSumMax, "terms of one rotated-sum launch");
+static int rot_sum_run(fhesi_ctx* c, const int64_t* ks, int32_t nk, int32_t logQ, const u64* base, const u64* pre, i64 term_stride, int64_t count, int32_t nlimbs, u64* out) {
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  bool composed = c->opt.automorph_rows != 0;
+  for (i64 done = 0; done < count && !composed; done += 16384) {      // (two polynomials per ciphertext on grid.y)
+    const i64 cnt = std::min<i64>(16384, count - done);
+    const int r = launch_ct_rot_sum(c, ks, nk, logQ, base ? base + done * ct_words : nullptr, pre + done * ct_words, term_stride, cnt * 2, nlimbs, out + done * ct_words);
+    if (r == 1) return 1;
+    if (r == 2) composed = true;      // (said at the first chunk, before anything is launched)
+  }
+  if (!composed) return 0;
+  const i64 chunk = 256;              // (the evaluation rows of a chunk: workspace slots 1 and 3)
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    u64* o = out + done * ct_words;
+    bool have = base != nullptr;
+    if (base && base != out) HIP_TRY(hipMemcpyAsync(o, base + done * ct_words, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));
+    for (int t = 0; t < nk; ++t) {
+      const u64* src = pre + (i64)t * term_stride + done * ct_words;
+      if (!have) { FHESI_TRY(rotation_close(c, ks[t], logQ, src, nlimbs, cnt, o, nlimbs)); have = true; continue; }
+      void* d_term;
+      FHESI_TRY(ws_reserve(c, 15, (size_t)cnt * ct_words * 8, &d_term));
+      FHESI_TRY(rotation_close(c, ks[t], logQ, src, nlimbs, cnt, (u64*)d_term, nlimbs));
+      FHESI_TRY(launch_ct_add(c, o, (const u64*)d_term, cnt * 2 * c->phim, nlimbs, logQ));
+    }
+  }
+  return 0;
+}
+extern "C" int fhesi_ct_rot_sum_dev(fhesi_ctx* c, const int64_t* ks, int32_t nk, int32_t logQ, const uint64_t* base, const uint64_t* pre, int64_t count, int32_t nlimbs,
+                                    uint64_t* out) {
+  CHECK_CTX(c);
+  if (nk < 1) FHESI_FAIL("ct_rot_sum: %d terms", nk);
+  if (count < 0) FHESI_FAIL("ct_rot_sum: negative count");
+  if (!ks) FHESI_FAIL("ct_rot_sum: null argument");
+  if (nlimbs < 1 || nlimbs > 32) FHESI_FAIL("ct_rot_sum: ciphertext coefficients of %d limbs are outside the supported 1..32", nlimbs);
+  if (logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("ct_rot_sum: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
+  for (int t = 0; t < nk; ++t)
+    if (ks[t] <= 0 || ks[t] >= c->m || c->zms_idx[ks[t]] < 0) FHESI_FAIL("ct_rot_sum: k=%lld of term %d is not in Zm*", (long long)ks[t], t);
+  if (!count) return 0;
+  if (!pre || !out) FHESI_FAIL("ct_rot_sum: null argument");
+  const size_t ct_bytes = (size_t)2 * c->phim * nlimbs * 8;
+  if (ranges_overlap(pre, (size_t)nk * count * ct_bytes, out, (size_t)count * ct_bytes)) FHESI_FAIL("ct_rot_sum: out overlaps pre");
+  if (base && base != out && ranges_overlap(base, (size_t)count * ct_bytes, out, (size_t)count * ct_bytes)) FHESI_FAIL("ct_rot_sum: out overlaps base without being base");
+  return rot_sum_run(c, ks, nk, logQ, base, pre, (i64)count * (i64)(ct_bytes / 8), count, nlimbs, out);
+}
+
+// host only: the B that minimises the key switches (B - 1) + (G - 1), G = ceil(nk / B); of equal sums the larger B -- baby steps are the hoisted, cheaper ones
+extern "C" int fhesi_matvec_bsgs_plan(int64_t nk, int32_t* baby, int32_t* giant) {
+  if (nk < 1 || nk > ((i64)1 << 20)) FHESI_FAIL("matvec_bsgs_plan: %lld diagonals outside [1, 2^20]", (long long)nk);
+  if (!baby || !giant) FHESI_FAIL("matvec_bsgs_plan: null output");
+  i64 best = 0, cost = -1;
+  for (i64 b = 1; b <= nk; ++b) {
+    const i64 g = (nk + b - 1) / b, s = b + g - 2;
+    if (cost < 0 || s <= cost) { cost = s; best = b; }
+  }
+  *baby = (int32_t)best;
+  *giant = (int32_t)((nk + best - 1) / best);
+  return 0;
+}
+
+// ApplyKeySwitch(k, src[i]) of count unscaled two-part ciphertexts as they are, no automorphism: what rotations_run computes in front of sigma_k, one matrix at
+// a time (its table built by the caller's key_switch_form, in front of any digit rows)
+static int key_switch_plain_run(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, int32_t logQ, int32_t decomp_bytes, const u64* in, int32_t nlimbs, int64_t count, u64* out) {
+  const i64 n = c->phim;
+  const int nlq = (logQ + 63) / 64, nd = k->ndigits;
+  const size_t ct_words = (size_t)2 * n * nlimbs;
+  CrtTables* t_all;
+  FHESI_TRY(get_crt_tables(c, full_set(c), &t_all));
+  const i64 chunk = std::min<i64>(16384, batch_chunk(c, 2 * nd, ks_mode == KS_MODE_LIMB32, count));
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    const u64* src = in + done * ct_words;
+    void *d_parts, *d_dig;
+    FHESI_TRY(ws_reserve(c, 2, (size_t)cnt * 2 * nlq * n * 8, &d_parts));
+    const int r = c->opt.automorph_rows ? 2 : launch_ct_automorph_parts(c, src, nlimbs, cnt * 2, 1, logQ, (u64*)d_parts, nlq);
+    if (r == 1) return 1;
+    if (r == 2) {
+      u64* d_rows;
+      FHESI_TRY(automorph_rows(c, 1, src, 2, nlimbs, cnt, &d_rows));
+      FHESI_TRY(launch_crt(c, t_all, d_rows, c->L, nullptr, cnt * 2, 3, 0, logQ, (u64*)d_parts, nlq));
+    }
+    FHESI_TRY(key_switch_digits(c, ks_mode, 2, nd, logQ, decomp_bytes, (const u64*)d_parts, cnt, false, &d_dig));
+    FHESI_TRY(key_switch_finish(c, k, ks_mode, logQ, decomp_bytes, d_dig, cnt, nullptr, out + done * ct_words, nlimbs));
+  }
+  return 0;
+}
+
+// out[i] = Reduce( sum_g rot_kg[g]( sum_j rot_kb[j](in[i]) (*) w[g B + j] ) )  (include/fhesi_hip.h): per chunk of ciphertexts the baby rotations from one digit
+// set into the pool (slot 12), ONE plaintext sum with G groups per ciphertext (slot 13), one key switch per giant into its slice of slot 14, one rotated sum
+extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted,
+                                        const int64_t* kg, int32_t G, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                                        int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  if (B < 1 || G < 1) FHESI_FAIL("ct_matvec_bsgs: %d baby steps and %d giant steps (at least 1 of each)", B, G);
+  if ((i64)nk <= (i64)(G - 1) * B || (i64)nk > (i64)G * B) FHESI_FAIL("ct_matvec_bsgs: %d diagonals outside (%lld, %lld], what %d giant steps of %d baby steps cover", nk, (long long)(G - 1) * B, (long long)G * B, G, B);
+  FHESI_TRY(rotations_args(c, baby_hoisted, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(rotations_args(c, giant_hoisted, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  if (!w) FHESI_FAIL("ct_matvec_bsgs: null prepared plaintext");
+  if (w->ctx != c) FHESI_FAIL("ct_matvec_bsgs: the prepared plaintext belongs to another context");
+  if (w->nw < nk) FHESI_FAIL("ct_matvec_bsgs: %d rotations against %lld prepared diagonals", nk, (long long)w->nw);
+  const int nb = std::min(B, nk);      // (G = 1 with a ragged group: the babies past nk are not run)
+  double chain = 0.0;
+  for (int i = 0; i < c->L; ++i) chain += std::log2((double)c->q[i]);
+  const double bits = plain_sum_bits(c->phim, c->pow2, c->phi_two_term, logQ, w->maxabs, nb);
+  if (bits >= chain) FHESI_FAIL("ct_matvec_bsgs: a sum of %d products needs %.0f bits, the chain holds %.0f", nb, std::ceil(bits), std::floor(chain));
+  if (!count) return 0;
+  if (!in || !out) FHESI_FAIL("ct_matvec_bsgs: null argument");
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  if (ranges_overlap(in, (size_t)count * ct_words * 8, out, (size_t)count * ct_words * 8)) FHESI_FAIL("ct_matvec_bsgs: out overlaps in");
+  // the giants' tables before any digit row exists, as rotations_run builds its matrices'
+  std::vector<int> g_mode((size_t)G, -1);
+  for (int g = 0; g < G; ++g) if (giant_hoisted[g]) FHESI_TRY(key_switch_form(c, giant_hoisted[g], logQ, decomp_bytes, &g_mode[g]));
+  // ciphertexts per pass: about 4 GiB of rotated ciphertexts, of inner sums and of key-switched sums each
+  const i64 chunk = std::max<i64>(1, std::min<i64>(count, (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(nb, G) * ct_words * 8))));
+  std::vector<int32_t> a_idx((size_t)chunk * nk), b_idx((size_t)chunk * nk), seg((size_t)chunk * G + 1);
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    void *d_pool, *d_inner, *d_pre;
+    FHESI_TRY(ws_reserve(c, 12, (size_t)nb * cnt * ct_words * 8, &d_pool));
+    FHESI_TRY(ws_reserve(c, 13, (size_t)G * cnt * ct_words * 8, &d_inner));
+    FHESI_TRY(ws_reserve(c, 14, (size_t)G * cnt * ct_words * 8, &d_pre));
+    FHESI_TRY(rotations_run(c, baby_hoisted, kb, nb, logQ, decomp_bytes, in + (size_t)done * ct_words, nlimbs, cnt, (uint64_t*)d_pool, nlimbs));
+    // group g * cnt + i = sum_j pool[j][i] (*) w[g B + j]
+    i64 at = 0;
+    for (int g = 0; g < G; ++g)
+      for (i64 i = 0; i < cnt; ++i) {
+        seg[(size_t)g * cnt + i] = (int32_t)at;
+        for (int j = 0; j < B && g * B + j < nk; ++j, ++at) { a_idx[at] = (int32_t)(j * cnt + i); b_idx[at] = g * B + j; }
+      }
+    seg[(size_t)G * cnt] = (int32_t)at;
+    FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nb * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt * G, (uint64_t*)d_inner));
+    for (int g = 0; g < G; ++g) {
+      const u64* inner = (const u64*)d_inner + (size_t)g * cnt * ct_words;
+      u64* pre = (u64*)d_pre + (size_t)g * cnt * ct_words;
+      if (!giant_hoisted[g]) HIP_TRY(hipMemcpyAsync(pre, inner, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));      // (k = 1: the sum itself)
+      else FHESI_TRY(key_switch_plain_run(c, giant_hoisted[g], g_mode[g], logQ, decomp_bytes, inner, nlimbs, cnt, pre));
+    }
+    FHESI_TRY(rot_sum_run(c, kg, G, logQ, nullptr, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, (u64*)out + (size_t)done * ct_words));
+  }
+  return 0;
+}
+
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).
 // Every distinct operand of a chunk is brought to evaluation form ONCE (a matrix entry or a minor typically feeds many products),
 // the products are formed and summed per group in one pass (tensor_sum_kernel), then the groups are key-switched together.

@@ -19,7 +19,7 @@ void fhesi_set_error(const char* fmt, ...);
 #define FHESI_FAIL(...) do { fhesi_set_error(__VA_ARGS__); return 1; } while (0)
 #define HIP_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { fhesi_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return 1; } } while (0)
 #define FHESI_OP_SET_ 4
-#define FHESI_WS_SLOTS 13
+#define FHESI_WS_SLOTS 16
 #define FHESI_TRY(expr) do { int r__ = (expr); if (r__) return r__; } while (0)
 
 // --------------------------------------------------------------------------------- per-prime device constants
@@ -178,7 +178,9 @@ struct fhesi_ctx {
   //   maxima of launch_decrypt_noise, then the maxima and budgets per ciphertext -- nothing in a decryption touches 4)
   //   (the hoisted rotations, capi_pipeline.hip: 2 the positive residues of a chunk, 0 its digit rows -- alive across all matrices, which is why every table is
   //   built before them --, 10 the dot outputs of the matrices of one launch, 4 one rotation's key-switched ciphertexts in front of their automorphism;
-  //   fhesi_ct_matvec_dev keeps the rotated ciphertexts of a chunk in 12 until fhesi_ct_plain_sum_dev has read them)
+  //   fhesi_ct_matvec_dev keeps the rotated ciphertexts of a chunk in 12 until fhesi_ct_plain_sum_dev has read them; fhesi_ct_matvec_bsgs_dev keeps the baby
+  //   rotations there too, the inner sums of a chunk in 13 and the giants' key-switched ciphertexts in 14 -- neither the plaintext sum nor a key switch touches
+  //   those --, and the composed form of the rotated sum keeps one rotated term in 15)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -447,6 +449,9 @@ int launch_sample_keygen(fhesi_ctx* ctx, u64* d_a, i64* d_err, i64 ncol, int nl,
 int launch_sample_poly(fhesi_ctx* ctx, i64* d_poly /* [n] */, int kind /* 0 sampleHWt(param), 1 sampleGaussian */, i64 param, u64 seed, u64 obj);
 int launch_ct_add_const(fhesi_ctx* ctx, u64* d_ct /* [count][nparts][n][nl] */, const i64* d_poly /* [npoly][n] */, int npoly, int nparts, int nl, int logQ, u64 p, i64 count);
 int launch_ct_automorph_parts(fhesi_ctx* ctx, const u64* d_in /* [npolys][n][nl_in] */, int nl_in, i64 npolys, i64 kk, int logQ, u64* d_parts /* [npolys][nlq][n] */, int nlq);   // 2: ring not covered
+constexpr int kRotSumMax = 16;      // terms of one ct_rot_sum_kernel launch: their (k, k^-1) pairs travel in the argument segment (FHESI_ROT_SUM_MAX_TERMS)
+int launch_ct_rot_sum(fhesi_ctx* ctx, const i64* ks, int nk, int logQ, const u64* d_base /* [npolys][n][nl] or null; may be d_out */, const u64* d_pre /* term t at + t * term_stride */,
+                      i64 term_stride, i64 npolys, int nl, u64* d_out);   // 2: ring not covered
 int launch_gather(fhesi_ctx* ctx, const u64* d_pool, const int* d_idx, i64 count, i64 words, u64* d_out);
 int launch_segment_sum(fhesi_ctx* ctx, const u64* d_in, const int* d_seg, i64 ngroups, int ncomp, u64* d_out);
 int launch_encrypt_combine(fhesi_ctx* ctx, const u64* d_rows /* [count][3][L][n] */, const u64* d_pk /* [2][L][n] */, i64 count, u64* d_out /* [count][2][L][n] */);

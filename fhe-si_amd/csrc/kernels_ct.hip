@@ -86,14 +86,10 @@ int launch_ct_add(fhesi_ctx* ctx, u64* d_dst, const u64* d_src, i64 ncoeffs, int
 // so no row transform is needed at all: out = positive residue modulo 2^logQ, limb-major, as ByteDecompPart takes it (Ciphertext.cpp:94).
 // mode: 0 power of two, 1 m = 2 q^k, 2 m = q^k; st = the stride s.  in [npolys][n][nl_in] two's complement;  out [npolys][nlq][n] (logQ > 0), or the
 // integers themselves, sign-extended, coefficient-major [npolys][n][nlq] (logQ = 0: toPoly of Ciphertext >>= without a key switch).
-__global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __restrict__ in, i64 n, int nl_in, i64 m, i64 kk, i64 kinv, int mode, i64 st,
-                                                                 int logQ, u64* __restrict__ out, int nlq) {
-  const i64 poly = blockIdx.y;
-  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  // term 1: s1 a[j1], term 2: s2 a[j2]  (s = 0: absent)
-  i64 j1 = 0, j2 = 0;
-  int s1 = 0, s2 = 0;
+// The sources of output coefficient i of a(X^k) mod Phi_m: term 1 is s1 a[j1], term 2 is s2 a[j2]  (s = 0: absent, its j = 0).  kk, kinv = k, k^-1 mod m.
+__device__ __forceinline__ void automorph_sources(i64 i, i64 n, i64 m, i64 kk, i64 kinv, int mode, i64 st, i64& j1, int& s1, i64& j2, int& s2) {
+  j1 = 0; j2 = 0;
+  s1 = 0; s2 = 0;
   if (mode == 0) {
     const i64 j = (i64)(((u128)i * (u128)kinv) % (u128)m);          // j k = i (mod 2n)
     j1 = j < n ? j : j - n;
@@ -120,6 +116,15 @@ __global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __re
     term(n + ((u32)i - b * (u32)st), j2, s2);
     s2 = -s2;
   }
+}
+__global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __restrict__ in, i64 n, int nl_in, i64 m, i64 kk, i64 kinv, int mode, i64 st,
+                                                                 int logQ, u64* __restrict__ out, int nlq) {
+  const i64 poly = blockIdx.y;
+  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  i64 j1, j2;
+  int s1, s2;
+  automorph_sources(i, n, m, kk, kinv, mode, st, j1, s1, j2, s2);
   const u64* __restrict__ a1 = in + (poly * n + j1) * nl_in;
   const u64* __restrict__ a2 = in + (poly * n + j2) * nl_in;
   const u64 ext1 = (a1[nl_in - 1] >> 63) ? ~0ull : 0ull, ext2 = (a2[nl_in - 1] >> 63) ? ~0ull : 0ull;
@@ -159,6 +164,82 @@ int launch_ct_automorph_parts(fhesi_ctx* ctx, const u64* d_in, int nl_in, i64 np
   dim3 grid((unsigned)((n + 255) / 256), (unsigned)npolys);
   ct_automorph_parts_kernel<<<grid, 256, 0, ctx->stream>>>(d_in, n, nl_in, m, kk % m, kinv, mode, st, logQ, d_parts, nlq);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- a sum of rotated ciphertexts, out = Reduce_logQ(base + sum_t sigma_{k_t}(pre_t)): the closing step of a baby-step/giant-step matrix-vector
+// product (fhesi_ct_matvec_bsgs_dev).  Every term is the signed gather above, summed in registers in two's complement modulo 2^(64 nl)
+// (exact modulo 2^logQ, which divides it), then ONE centred reduction as ct_add_kernel does it: one read per term and one write, where the composition
+// (gather, reduction, addition per term) makes about seven passes.  The (k, k^-1) pairs travel in the argument segment: nothing is uploaded in front of
+// the launch.  pre_t = pre + t * term_stride, [npolys][n][nl]; base (null: none) and out [npolys][n][nl].  A thread reads base and writes out at its own
+// coefficient only, so out may be base (which is why neither is __restrict__); out must not overlap pre.
+struct RotSumKeys { static constexpr int MAX = kRotSumMax; i64 k[MAX], kinv[MAX]; };
+template <int MAXNL>
+__global__ void __launch_bounds__(256) ct_rot_sum_kernel(const RotSumKeys keys, int nt, const u64* base, const u64* __restrict__ pre, i64 term_stride, i64 n, int nl,
+                                                         i64 m, int mode, i64 st, int logQ, u64* out) {
+  const i64 poly = blockIdx.y;
+  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const i64 at = (poly * n + i) * nl;
+  u64 x[MAXNL];
+#pragma unroll
+  for (int w = 0; w < MAXNL; ++w) x[w] = (base && w < nl) ? base[at + w] : 0;
+  for (int t = 0; t < nt; ++t) {
+    i64 j1, j2;
+    int s1, s2;
+    automorph_sources(i, n, m, keys.k[t], keys.kinv[t], mode, st, j1, s1, j2, s2);
+    const u64* __restrict__ a1 = pre + t * term_stride + (poly * n + j1) * nl;
+    const u64* __restrict__ a2 = pre + t * term_stride + (poly * n + j2) * nl;
+    const u64 f1 = s1 < 0 ? ~0ull : 0ull, f2 = s2 < 0 ? ~0ull : 0ull;      // a negated term: ~a + 1
+    const u64 k1 = s1 ? ~0ull : 0ull, k2 = s2 ? ~0ull : 0ull;              // an absent term: 0
+    u64 carry = (s1 < 0 ? 1 : 0) + (s2 < 0 ? 1 : 0);
+#pragma unroll
+    for (int w = 0; w < MAXNL; ++w)
+      if (w < nl) {
+        const u64 x1 = (a1[w] ^ f1) & k1, x2 = (a2[w] ^ f2) & k2;
+        const u128 sum = (u128)x[w] + x1 + x2 + carry;
+        x[w] = (u64)sum;
+        carry = (u64)(sum >> 64);
+      }
+  }
+  u64 sb = 0;
+#pragma unroll
+  for (int w = 0; w < MAXNL; ++w)
+    if (w == (logQ - 1) >> 6) sb = (x[w] >> ((logQ - 1) & 63)) & 1;
+#pragma unroll
+  for (int w = 0; w < MAXNL; ++w)
+    if (w < nl) out[at + w] = reduce_limb(x[w], w, logQ, sb);
+}
+// 0 = launched (nk > kRotSumMax terms: a chain of launches with base = out); 2 = this ring is not covered (the caller runs the composition).
+// ks in Z_m^* and nl in 1..32 holding logQ: checked by the caller; npolys <= 65535.
+int launch_ct_rot_sum(fhesi_ctx* ctx, const i64* ks, int nk, int logQ, const u64* d_base, const u64* d_pre, i64 term_stride, i64 npolys, int nl, u64* d_out) {
+  const i64 m = ctx->m, n = ctx->phim;
+  int mode;
+  i64 st = 1;
+  if (ctx->pow2) mode = 0;
+  else if (const i64 qq = hm::prime_power_ring(m, nullptr)) { mode = (m & 1) ? 2 : 1; st = ((m & 1) ? m : m / 2) / qq; }
+  else return 2;
+  if (!npolys || nk < 1) return 0;
+  if (nl < 1 || nl > 32) FHESI_FAIL("ciphertext coefficients of %d limbs exceed the supported 32", nl);
+  const dim3 grid((unsigned)((n + 255) / 256), (unsigned)npolys);
+  for (int t0 = 0; t0 < nk; t0 += kRotSumMax) {
+    const int nt = nk - t0 < kRotSumMax ? nk - t0 : kRotSumMax;
+    RotSumKeys keys{};
+    for (int t = 0; t < nt; ++t) {
+      i64 a = ks[t0 + t] % m, b = m, x0 = 1, x1 = 0;
+      while (b) { const i64 qq = a / b; i64 r = a - qq * b; a = b; b = r; r = x0 - qq * x1; x0 = x1; x1 = r; }
+      if (a != 1) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)ks[t0 + t]);
+      keys.k[t] = ks[t0 + t] % m;
+      keys.kinv[t] = ((x0 % m) + m) % m;
+    }
+    const u64* base = t0 ? d_out : d_base;
+    const u64* pre = d_pre + (i64)t0 * term_stride;
+    if (nl <= 2) ct_rot_sum_kernel<2><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
+    else if (nl <= 8) ct_rot_sum_kernel<8><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
+    else if (nl <= 16) ct_rot_sum_kernel<16><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
+    else ct_rot_sum_kernel<32><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
+    HIP_TRY(hipGetLastError());
+  }
   return 0;
 }
 

@@ -517,6 +517,36 @@ int fhesi_ct_matvec_dev(fhesi_ctx* ctx, const fhesi_ksk* const* hoisted, const i
                         int32_t logQ, int32_t decomp_bytes, const uint64_t* in_dev, int32_t nlimbs, int64_t count,
                         uint64_t* out_dev /* [count][2][phi(m)][nlimbs] */);
 
+/* ---- baby-step/giant-step matrix-vector products on the hoisted rotations (capi_pipeline.hip, ct_rot_sum_kernel in kernels_ct.hip).
+ * With T = B G diagonals and t = g B + j
+ *     sum_t d_t (*) rot_t(x)  =  sum_{g<G} rot_{gB}( sum_{j<B} rot_{-gB}(d_{gB+j}) (*) rot_j(x) ):
+ * B - 1 baby rotations of x from ONE digit decomposition, G plaintext sums over diagonals rotated in the clear, G - 1 further key switches and one
+ * sum of rotated ciphertexts -- about 2 sqrt(T) matrices and key switches where fhesi_ct_matvec_dev takes T of each.
+ *
+ * fhesi_ct_rot_sum_dev: out[i] = Reduce( base[i] + sum_t<nk  Ciphertext >>= ks[t]  of  pre[t][i] )  (centred modulo 2^logQ), i < count two-part
+ *   ciphertexts of nlimbs limbs; base_dev NULL: no base.  Bit for bit fhesi_ct_automorph_dev(ks[t]) per term, fhesi_ct_add_dev, and the reduction.
+ *   On m = 2^k, q^k and 2 q^k one kernel reads every term once and writes once (FHESI_ROT_SUM_MAX_TERMS terms per launch, more terms chain launches);
+ *   on other rings, or with option "automorph_rows", the library runs the composition itself: the same words.  out_dev may be base_dev.
+ *   REFUSED on the host with the condition named: out overlapping pre, or overlapping base without being base; a k outside Z_m^*; nlimbs outside
+ *   1..32 or too few for logQ; nk < 1.
+ * fhesi_matvec_bsgs_plan (host only): the B that minimises (B - 1) + (G - 1) with G = ceil(nk / B); of equal sums the larger B (baby steps are the
+ *   hoisted, cheaper ones).
+ * fhesi_ct_matvec_bsgs_dev:
+ *       out[i] = Reduce( sum_{g<G} rot_kg[g]( sum_{j<B, gB+j<nk} rot_kb[j](in[i]) (*) w[gB+j] ) )
+ *   rot_k exactly what fhesi_ct_rotations_dev gives for (matrix, k); a NULL matrix with k = 1 is the identity; the last group may be ragged:
+ *   (G - 1) B < nk <= G B.  DEFINED as, and word for word equal to, fhesi_ct_rotations_dev for the babies, fhesi_ct_plain_sum_dev with G groups per
+ *   ciphertext, fhesi_ct_rotations_dev with nk = 1 per giant, fhesi_ct_add_dev; with G = 1 it is fhesi_ct_matvec_dev.  The caller rotates the
+ *   diagonals in the clear: w[gB+j] holds rot_{-gB}(d_{gB+j}) (SlotSpace.bsgs_diagonals in the Python binding).  The capacity rule of
+ *   fhesi_ct_plain_sum_dev is checked with min(B, nk) terms, the longest inner sum.  Everything between in and out lives in the workspace, in chunks
+ *   of ciphertexts.  REFUSED as fhesi_ct_matvec_dev refuses, and: B or G below 1; nk outside ((G - 1) B, G B]. */
+#define FHESI_ROT_SUM_MAX_TERMS 16
+int fhesi_ct_rot_sum_dev(fhesi_ctx* ctx, const int64_t* ks, int32_t nk, int32_t logQ, const uint64_t* base_dev /* [count][2][phi(m)][nlimbs] or NULL */,
+                         const uint64_t* pre_dev /* [nk][count][2][phi(m)][nlimbs] */, int64_t count, int32_t nlimbs, uint64_t* out_dev);
+int fhesi_matvec_bsgs_plan(int64_t nk, int32_t* baby, int32_t* giant);
+int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* ctx, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted,
+                             const int64_t* kg, int32_t G, int32_t nk, const fhesi_plain* w /* nw >= nk, term t = g*B + j */, int32_t logQ,
+                             int32_t decomp_bytes, const uint64_t* in_dev, int32_t nlimbs, int64_t count, uint64_t* out_dev);
+
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
  * fhesi_comm_init_all: one process, one host thread per GPU -- ncclCommInitAll over `devices`, comms_out[r] is rank r's handle.
