@@ -1,5 +1,6 @@
 // capi_ct.hip -- ciphertext algebra between multiplications, Encrypt / Decrypt batches, prepared plaintext operands, key generation (include/fhesi_hip.h)
 #include "capi_common.h"
+#include "wave_plan.h"
 
 // ---- coefficient-domain ciphertext algebra on device batches (kernels_ct.hip)
 extern "C" int fhesi_ct_add_dev(fhesi_ctx* c, int32_t logQ, uint64_t* dst, const uint64_t* src, int32_t nparts, int32_t nlimbs, int64_t count) {
@@ -42,8 +43,7 @@ extern "C" int fhesi_ct_mul_poly_dev(fhesi_ctx* c, int32_t logQ, uint64_t* ct, i
   for (i64 i = 0; i < (i64)npoly * n; ++i) { const i64 v = poly_host[i]; const u64 a = v < 0 ? (u64)(-(v + 1)) + 1 : (u64)v; if (a > maxc) maxc = a; }
   double bits = (logQ - 1) + std::log2((double)n) + (maxc ? std::log2((double)maxc) + 1e-9 : 0.0) + 1.0;
   bits += c->pow2 ? 0.0 : (c->phi_two_term ? 1.0 : std::log2((double)n));
-  double chain = 0.0;
-  for (int i = 0; i < L; ++i) chain += std::log2((double)c->q[i]);
+  const double chain = chain_bits(c);
   if (bits + 1.0 >= chain) FHESI_FAIL("Ciphertext *= ZZX: the product needs %.0f bits, the chain holds %.0f", bits + 1.0, chain);
   const std::vector<int> all = full_set(c);
   CrtTables* t;
@@ -503,8 +503,7 @@ extern "C" int fhesi_ct_plain_sum_dev(fhesi_ctx* c, const fhesi_plain* w, int32_
     const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)ngroups * ct_words * 8, p0 = (uintptr_t)pool, p1 = p0 + (size_t)npool * ct_words * 8;
     if (npool && o0 < p1 && p0 < o1) FHESI_FAIL("ct_plain_sum: out overlaps pool");
   }
-  double chain = 0.0;
-  for (int i = 0; i < L; ++i) chain += std::log2((double)c->q[i]);
+  const double chain = chain_bits(c);
   const double bits = plain_sum_bits(n, c->pow2, c->phi_two_term, logQ, w->maxabs, tmax);
   if (bits >= chain) FHESI_FAIL("ct_plain_sum: a sum of %lld products needs %.0f bits, the chain holds %.0f", (long long)tmax, std::ceil(bits), std::floor(chain));
   const std::vector<int> all = full_set(c);
@@ -515,59 +514,27 @@ extern "C" int fhesi_ct_plain_sum_dev(fhesi_ctx* c, const fhesi_plain* w, int32_
   if (cap > 32767) cap = 32767;                             // (the reduction and the CRT put two polynomials per ciphertext on grid.y)
   if (c->opt.wave_operands > 0 && c->opt.wave_operands < cap) cap = c->opt.wave_operands;
   if (cap < 1) cap = 1;
-  // ---- plan: per pass [distinct pool entries][local ciphertext slot per term][plaintext index per term][segment bounds] in one index array
-  struct Pass { i64 g, ng, nu, nt; size_t off; bool accumulate, close; };
-  std::vector<Pass> passes;
-  std::vector<int> ix;
-  std::map<int, int> slot_of;
-  auto add_pass = [&](i64 g, i64 ng, i64 t0, i64 t1, bool accumulate, bool close) {
-    Pass P{g, ng, 0, t1 - t0, ix.size(), accumulate, close};
-    slot_of.clear();
-    const size_t at = ix.size();
-    for (i64 t = t0; t < t1; ++t) if (slot_of.emplace(a_idx[t], (int)slot_of.size()).second) ix.push_back(a_idx[t]);
-    P.nu = (i64)(ix.size() - at);
-    for (i64 t = t0; t < t1; ++t) ix.push_back(slot_of[a_idx[t]]);
-    ix.insert(ix.end(), b_idx + t0, b_idx + t1);
-    if (ng == 1) { ix.push_back(0); ix.push_back((int)(t1 - t0)); }                        // (a piece of one group)
-    else for (i64 i = 0; i <= ng; ++i) ix.push_back(seg[g + i] - seg[g]);
-    passes.push_back(P);
-  };
-  {
-    std::set<int> seen, grp;
-    for (i64 g = 0; g < ngroups;) {
-      seen.clear();
-      i64 g2 = g;
-      while (g2 < ngroups && g2 - g < cap) {
-        grp.clear();
-        for (i64 t = seg[g2]; t < seg[g2 + 1]; ++t) if (!seen.count(a_idx[t])) grp.insert(a_idx[t]);
-        if (g2 > g && (i64)(seen.size() + grp.size()) > cap) break;
-        seen.insert(grp.begin(), grp.end());
-        ++g2;
-      }
-      if (g2 - g == 1 && (i64)seen.size() > cap) {
-        for (i64 t0 = seg[g]; t0 < seg[g + 1]; t0 += cap) { const i64 t1 = std::min<i64>(t0 + cap, seg[g + 1]); add_pass(g, 1, t0, t1, t0 != seg[g], t1 == seg[g + 1]); }
-      } else add_pass(g, g2 - g, seg[g], seg[g2], false, true);
-      g = g2;
-    }
-  }
+  // ---- plan (wave_plan.h): the passes and, in one index array, per pass [distinct pool entries][local ciphertext slot per term][plaintext index per term][segment bounds]
+  const WavePlan plan = wave_plan(a_idx, b_idx, seg, ngroups, cap, cap, false);
+  const std::vector<int>& ix = plan.ix;
   void* d_ix;
   FHESI_TRY(ws_reserve(c, 5, sizeof(int) * ix.size(), &d_ix));
   HIP_TRY(hipMemcpyAsync(d_ix, ix.data(), sizeof(int) * ix.size(), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));                 // the one synchronisation: ix lives on this frame, a_idx / b_idx / seg are read no more
   i64 max_nu = 0, max_ng = 0;
-  for (const Pass& P : passes) { max_nu = std::max(max_nu, P.nu); max_ng = std::max(max_ng, P.ng); }
+  for (const WavePass& P : plan.passes) { max_nu = std::max<i64>(max_nu, P.nua); max_ng = std::max<i64>(max_ng, P.ng); }
   void *d_ops, *d_rows, *d_sum;
   FHESI_TRY(ws_reserve(c, 7, (size_t)max_nu * ct_words * 8, &d_ops));
   FHESI_TRY(ws_reserve(c, 0, (size_t)max_nu * row_words * 8, &d_rows));
   FHESI_TRY(ws_reserve(c, 4, (size_t)max_ng * row_words * 8, &d_sum));
-  for (const Pass& P : passes) {
+  for (const WavePass& P : plan.passes) {
     const int* dix = (const int*)d_ix + P.off;
-    if (P.nu) {
-      FHESI_TRY(launch_gather(c, (const u64*)pool, dix, P.nu, ct_words, (u64*)d_ops));
-      FHESI_TRY(launch_rns_reduce(c, (const u64*)d_ops, nlimbs, n, P.nu, 2, nullptr, (u64*)d_rows, L, nullptr));
-      FHESI_TRY(row_fwd(c, (u64*)d_rows, P.nu * 2, L, nullptr, all.data()));
+    if (P.nua) {
+      FHESI_TRY(launch_gather(c, (const u64*)pool, dix, P.nua, ct_words, (u64*)d_ops));
+      FHESI_TRY(launch_rns_reduce(c, (const u64*)d_ops, nlimbs, n, P.nua, 2, nullptr, (u64*)d_rows, L, nullptr));
+      FHESI_TRY(row_fwd(c, (u64*)d_rows, P.nua * 2, L, nullptr, all.data()));
     }
-    FHESI_TRY(launch_plain_sum(c, (const u64*)d_rows, w->d_rows, dix + P.nu, dix + P.nu + P.nt, dix + P.nu + 2 * P.nt, P.ng, P.accumulate, (u64*)d_sum, (double)P.nt));
+    FHESI_TRY(launch_plain_sum(c, (const u64*)d_rows, w->d_rows, dix + P.nua, dix + P.nua + P.nt, dix + P.nua + 2 * P.nt, P.ng, P.accumulate, (u64*)d_sum, (double)P.nt));
     if (!P.close) continue;
     FHESI_TRY(row_inv(c, (u64*)d_sum, P.ng * 2, L, nullptr, all.data()));
     FHESI_TRY(launch_crt(c, t_all, (const u64*)d_sum, L, nullptr, P.ng * 2, 2, 0, logQ, (u64*)out + (size_t)P.g * ct_words, nlimbs));

@@ -288,7 +288,7 @@ extern "C" int fhesi_dcrt_automorph(fhesi_dcrt* d, int64_t k) {
   if (d->coeff_form) FHESI_FAIL("DoubleCRT call on a SingleCRT handle");
   fhesi_ctx* c = d->ctx;
   CHECK_CTX(c);
-  if (k <= 0 || k >= c->m || c->zms_idx[k] < 0) FHESI_FAIL("DoubleCRT::automorph: k not in Zm*");     // DoubleCRT.cpp:442-443
+  if (!in_zm_star(c, k)) FHESI_FAIL("DoubleCRT::automorph: k not in Zm*");     // DoubleCRT.cpp:442-443
   const i64 K = (i64)d->idx.size();
   if (!K) return 0;
   void* tmp;

@@ -1,6 +1,7 @@
 // capi_pipeline.hip -- the key-switch matrix and the fused ciphertext multiplication + key switch, per stage and per batch (include/fhesi_hip.h)
 #include "capi_common.h"
 #include "copy_pool.h"
+#include "wave_plan.h"
 
 // --------------------------------------------------------------------------------------------- key-switch matrix
 extern "C" int fhesi_ksk_create(fhesi_ctx* c, int32_t ncomp, int32_t ndigits, fhesi_ksk** out) {
@@ -149,21 +150,21 @@ static int key_switch_close32(fhesi_ctx* c, const CrtTables* t, const fhesi_ksk*
   FHESI_TRY(launch_ntt32_inv(c, d_o, count * 2 * k->aux_rows, 4, 0, mont, !fold_tail));
   return launch_ks_recombine(c, t, k, (const u64*)d_o, count * 2, (u64*)out, nlimbs, fold_tail);
 }
-// d_t: scratch for count*2 DoubleCRTs, needed by the per-prime and the residue forms only (null: reserved here, workspace slot 1, when one of
-// those runs -- the limb forms never touch it).
-static int key_switch_finish(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, int32_t logQ, int32_t decomp_bytes, const void* d_dig, int64_t count, u64* d_t,
-                             uint64_t* out, int32_t nlimbs) {
+// The per-prime and the residue forms need scratch for count*2 DoubleCRTs: workspace slot 1, reserved here (the limb forms never touch it).  Whatever a
+// caller kept in slot 1 -- the scaled-up tProd, the automorphism's rows -- is dead by then: it was read into the parts in front of the digit rows.
+// apply_key_switch_consume sizes slot 1 for max(ncomp, 2) parts, so the later reservation never regrows it.
+static int key_switch_finish(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, int32_t logQ, int32_t decomp_bytes, const void* d_dig, int64_t count, uint64_t* out, int32_t nlimbs) {
   const i64 n = c->phim;
   const int L = c->L, ncol = k->ncomp * k->ndigits;
   const std::vector<int> all = full_set(c);
   CrtTables* t;
   FHESI_TRY(get_crt_tables(c, all, &t));
+  void *d_o = nullptr, *d_t;
   if (ks_mode != KS_MODE_DIRECT) {
     fhesi_ksk* km = const_cast<fhesi_ksk*>(k);
     const int R = k->aux_rows;        // L chain-prime residues, or the limbs of the key's integer coefficients (limb mode)
     const i64 nrow = k->aux32 ? aux32_row_len(c) : n;      // the 32-bit auxiliary rows always have 2^14 or 2^15 elements
     if (k->aux32 != (ks_mode == KS_MODE_LIMB32)) FHESI_FAIL("key switch: the matrix's table does not match the running form (internal)");
-    void* d_o;
     FHESI_TRY(ws_reserve(c, 10, (size_t)count * 2 * R * 2 * nrow * 8, &d_o));
     if (k->aux32) {
       bool mont = true;                 // dot32_kernel2 leaves the factor 2^-32 of its Montgomery step; the matrix-core form does not
@@ -173,25 +174,23 @@ static int key_switch_finish(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, int3
     FHESI_TRY(launch_dot_aux(c, k, (const u64*)d_dig, ncol, count, (u64*)d_o));
     FHESI_TRY(launch_ntt_inv(c, (u64*)d_o, count * 2 * R, 2, (const int*)(k->d_aux_consts + L), !k->aux_suborder));
     if (k->aux_limb_bits) return launch_ks_recombine(c, t, k, (const u64*)d_o, count * 2, (u64*)out, nlimbs);
-    if (!d_t) { void* q; FHESI_TRY(ws_reserve(c, 1, (size_t)count * 2 * L * n * 8, &q)); d_t = (u64*)q; }
-    FHESI_TRY(launch_aux_crt(c, k, (const u64*)d_o, d_t, count * 2 * L));
-    return launch_crt(c, t, d_t, L, nullptr, count * 2, 2, 0, logQ, (u64*)out, nlimbs);
   }
-  if (!d_t) { void* q; FHESI_TRY(ws_reserve(c, 1, (size_t)count * 2 * L * n * 8, &q)); d_t = (u64*)q; }
-  // DotProduct with both key rows (FHE-SI.cpp:251-254)
-  FHESI_TRY(launch_dot_accum(c, k->d_rows, (const u64*)d_dig, ncol, count, d_t, 0, 0, c->pow2 && ntt_digits_suborder(c, 8 * decomp_bytes)));
-  // toPoly + ReduceCoefficients (FHE-SI.cpp:255-256)
-  FHESI_TRY(row_inv(c, d_t, count * 2, L, nullptr, all.data()));
-  FHESI_TRY(launch_crt(c, t, d_t, L, nullptr, count * 2, 2, 0, logQ, (u64*)out, nlimbs));
-  return 0;
+  FHESI_TRY(ws_reserve(c, 1, (size_t)count * 2 * L * n * 8, &d_t));
+  if (ks_mode != KS_MODE_DIRECT) FHESI_TRY(launch_aux_crt(c, k, (const u64*)d_o, (u64*)d_t, count * 2 * L));
+  else {
+    // DotProduct with both key rows (FHE-SI.cpp:251-254), toPoly
+    FHESI_TRY(launch_dot_accum(c, k->d_rows, (const u64*)d_dig, ncol, count, (u64*)d_t, 0, 0, c->pow2 && ntt_digits_suborder(c, 8 * decomp_bytes)));
+    FHESI_TRY(row_inv(c, (u64*)d_t, count * 2, L, nullptr, all.data()));
+  }
+  // ReduceCoefficients (FHE-SI.cpp:255-256)
+  return launch_crt(c, t, (const u64*)d_t, L, nullptr, count * 2, 2, 0, logQ, (u64*)out, nlimbs);
 }
-static int key_switch_tail(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, const u64* d_parts, int64_t count, u64* d_t,
-                           uint64_t* out, int32_t nlimbs, bool parts_wm = false) {
+static int key_switch_tail(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, const u64* d_parts, int64_t count, uint64_t* out, int32_t nlimbs, bool parts_wm = false) {
   int ks_mode;
   FHESI_TRY(key_switch_form(c, k, logQ, decomp_bytes, &ks_mode));
   void* d_dig;
   FHESI_TRY(key_switch_digits(c, ks_mode, k->ncomp, k->ndigits, logQ, decomp_bytes, d_parts, count, parts_wm, &d_dig));
-  return key_switch_finish(c, k, ks_mode, logQ, decomp_bytes, d_dig, count, d_t, out, nlimbs);
+  return key_switch_finish(c, k, ks_mode, logQ, decomp_bytes, d_dig, count, out, nlimbs);
 }
 
 static int key_switch_args(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, int32_t nlimbs) {
@@ -203,8 +202,8 @@ static int key_switch_args(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32
   return 0;
 }
 
-// d_t: the scaled-up ciphertexts [count][ncomp][L][n], with room for max(ncomp, 2) parts per ciphertext; consumed (transformed in place,
-// then reused for the dot product's rows)
+// d_t: the scaled-up ciphertexts [count][ncomp][L][n] in workspace slot 1, with room for max(ncomp, 2) parts per ciphertext; consumed (transformed
+// in place; key_switch_finish then takes the slot for the dot product's rows)
 static int apply_key_switch_consume(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, u64* d_t, int64_t count, uint64_t* out, int32_t nlimbs) {
   const i64 n = c->phim;
   const int L = c->L, ncomp = k->ncomp, nlq = (logQ + 63) / 64;
@@ -216,7 +215,7 @@ static int apply_key_switch_consume(fhesi_ctx* c, const fhesi_ksk* k, int32_t lo
   void* d_parts;
   FHESI_TRY(ws_reserve(c, 2, (size_t)count * ncomp * nlq * n * 8, &d_parts));
   FHESI_TRY(launch_crt(c, t, (const u64*)d_t, L, nullptr, count * ncomp, 1, 0, logQ, (u64*)d_parts, nlq));
-  return key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, count, d_t, out, nlimbs);
+  return key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, count, out, nlimbs);
 }
 
 extern "C" int fhesi_apply_key_switch_dev(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, int32_t decomp_bytes, const uint64_t* tprod, int64_t count,
@@ -235,8 +234,8 @@ extern "C" int fhesi_apply_key_switch_dev(fhesi_ctx* c, const fhesi_ksk* k, int3
 // Ciphertext::operator>>= (Ciphertext.cpp:264-269 -> CiphertextPart::operator>>= :54-59: DoubleCRT(poly) >>= k; toPoly) for a batch
 // of unscaled ciphertexts, rows left in d_rows [count*nparts][L][n] in coefficient (post-iFFT) form ready for the CRT.
 static int automorph_rows(fhesi_ctx* c, int64_t kk, const uint64_t* in, int32_t nparts, int32_t nlimbs_in, int64_t count, u64** d_rows_out) {
-  const i64 n = c->phim, m = c->m;
-  if (kk <= 0 || kk >= m || c->zms_idx[kk] < 0) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);     // DoubleCRT.cpp:442-443
+  const i64 n = c->phim;
+  if (!in_zm_star(c, kk)) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);
   const int L = c->L;
   const std::vector<int> all = full_set(c);
   const i64 nrows = count * nparts * L;
@@ -250,18 +249,39 @@ static int automorph_rows(fhesi_ctx* c, int64_t kk, const uint64_t* in, int32_t 
   *d_rows_out = (u64*)d_b;
   return 0;
 }
+// The front half of a key switch of unscaled ciphertexts: sigma_kk of the count * nparts polynomials at src as positive residues mod 2^logQ, limb-major
+// (what ByteDecomp reads), in workspace slot 2.  On power-of-two, prime-power and 2 x prime-power rings a(X^k) mod Phi_m is a signed gather of the
+// coefficients, no row transform (kernels_ct.hip); on the others, and under option automorph_rows, the evaluation rows: toPoly (centred modulo the
+// whole chain), then Reduce(..., positive) of ByteDecompPart (Ciphertext.cpp:94).  kk must be in Zm*.
+static int unscaled_parts(fhesi_ctx* c, int64_t kk, const u64* src, int32_t nparts, int32_t nlimbs_in, int64_t count, int32_t logQ, u64** d_parts_out) {
+  const int nlq = (logQ + 63) / 64;
+  void* d_parts;
+  FHESI_TRY(ws_reserve(c, 2, (size_t)count * nparts * nlq * c->phim * 8, &d_parts));
+  *d_parts_out = (u64*)d_parts;
+  const int r = c->opt.automorph_rows ? 2 : launch_ct_automorph_parts(c, src, nlimbs_in, count * nparts, kk, logQ, (u64*)d_parts, nlq);
+  if (r != 2) return r;
+  u64* d_rows;
+  FHESI_TRY(automorph_rows(c, kk, src, nparts, nlimbs_in, count, &d_rows));
+  CrtTables* t;
+  FHESI_TRY(get_crt_tables(c, full_set(c), &t));
+  return launch_crt(c, t, d_rows, c->L, nullptr, count * nparts, 3, 0, logQ, (u64*)d_parts, nlq);
+}
+// ... of two-part ciphertexts as they are (k = 1), on to the digit rows of the running form (slot 0): what a hoisted matrix is applied to
+static int unscaled_digits(fhesi_ctx* c, int ks_mode, int nd, int32_t logQ, int32_t decomp_bytes, const u64* src, int32_t nlimbs_in, int64_t count, void** d_dig) {
+  u64* d_parts;
+  FHESI_TRY(unscaled_parts(c, 1, src, 2, nlimbs_in, count, logQ, &d_parts));
+  return key_switch_digits(c, ks_mode, 2, nd, logQ, decomp_bytes, d_parts, count, false, d_dig);
+}
 
 extern "C" int fhesi_ct_automorph_dev(fhesi_ctx* c, int64_t kk, const uint64_t* in, int32_t nparts, int32_t nlimbs_in, int64_t count, uint64_t* out,
                                       int32_t nlimbs_out) {
   CHECK_CTX(c);
   if (nparts < 1 || nlimbs_in < 1 || nlimbs_out < 1) FHESI_FAIL("Ciphertext >>= : bad shape");
   if (!count) return 0;
-  if (kk <= 0 || kk >= c->m || c->zms_idx[kk] < 0) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);     // DoubleCRT.cpp:442-443
+  if (!in_zm_star(c, kk)) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);
   // the coefficient gather gives the integers a(X^k) mod Phi_m themselves; the reference's toPoly centres modulo the chain product: the
   // same thing as long as the sum of two input coefficients (64 nlimbs_in + 1 bits) stays below half of it
-  double chain = 0;
-  for (int i = 0; i < c->L; ++i) chain += std::log2((double)c->q[i]);
-  if (!c->opt.automorph_rows && 64.0 * nlimbs_in + 2 < chain) {        // (fewer output limbs truncate the two's complement value in both forms)
+  if (!c->opt.automorph_rows && 64.0 * nlimbs_in + 2 < chain_bits(c)) {        // (fewer output limbs truncate the two's complement value in both forms)
     const int r = launch_ct_automorph_parts(c, (const u64*)in, nlimbs_in, count * nparts, kk, 0, (u64*)out, nlimbs_out);
     if (r != 2) return r;
   }
@@ -278,31 +298,10 @@ extern "C" int fhesi_ct_automorph_key_switch_dev(fhesi_ctx* c, const fhesi_ksk* 
   FHESI_TRY(key_switch_args(c, k, logQ, decomp_bytes, nlimbs));
   if (nlimbs_in < 1) FHESI_FAIL("Ciphertext >>= : bad shape");
   if (!count) return 0;
-  const i64 n = c->phim;
-  const int ncomp = k->ncomp, nlq = (logQ + 63) / 64;
-  void* d_parts;
-  FHESI_TRY(ws_reserve(c, 2, (size_t)count * ncomp * nlq * n * 8, &d_parts));
-  u64* d_rows;
-  if (kk <= 0 || kk >= c->m || c->zms_idx[kk] < 0) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);     // DoubleCRT.cpp:442-443
-  if (!c->opt.automorph_rows) {
-    // on power-of-two, prime and 2 x prime rings a(X^k) mod Phi_m is a signed gather of the coefficients: no row transform (kernels_ct.hip)
-    const int r = launch_ct_automorph_parts(c, (const u64*)in, nlimbs_in, count * ncomp, kk, logQ, (u64*)d_parts, nlq);
-    if (r == 1) return 1;
-    if (r == 0) {
-      return key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, count, nullptr, out, nlimbs);
-    }
-  }
-  if (kk == 1) {
-    // no automorphism: ApplyKeySwitch on the unscaled ciphertext as it is; ByteDecomp needs the positive residues limb-major
-    FHESI_TRY(automorph_rows(c, 1, in, ncomp, nlimbs_in, count, &d_rows));
-  } else {
-    FHESI_TRY(automorph_rows(c, kk, in, ncomp, nlimbs_in, count, &d_rows));
-  }
-  CrtTables* t;
-  FHESI_TRY(get_crt_tables(c, full_set(c), &t));
-  // toPoly (centred modulo the whole chain), then Reduce(..., positive) of ByteDecompPart (Ciphertext.cpp:94)
-  FHESI_TRY(launch_crt(c, t, d_rows, c->L, nullptr, count * ncomp, 3, 0, logQ, (u64*)d_parts, nlq));
-  return key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, count, d_rows, out, nlimbs);
+  if (!in_zm_star(c, kk)) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);
+  u64* d_parts;      // (k = 1, no automorphism: ApplyKeySwitch on the unscaled ciphertext as it is)
+  FHESI_TRY(unscaled_parts(c, kk, (const u64*)in, k->ncomp, nlimbs_in, count, logQ, &d_parts));
+  return key_switch_tail(c, k, logQ, decomp_bytes, d_parts, count, out, nlimbs);
 }
 
 // --------------------------------------------------------------------------------------------- hoisted rotations
@@ -320,7 +319,7 @@ extern "C" int fhesi_ksk_hoist(const fhesi_ksk* k, int64_t kk, fhesi_ksk** out) 
   CHECK_CTX(c);
   *out = nullptr;
   if (k->ncomp != 2) FHESI_FAIL("ksk_hoist: the matrix has %d source components, a rotation matrix (source key (1, s(X^k))) has 2", k->ncomp);
-  if (kk <= 0 || kk >= c->m || c->zms_idx[kk] < 0) FHESI_FAIL("ksk_hoist: k=%lld is not in Zm*", (long long)kk);
+  if (!in_zm_star(c, kk)) FHESI_FAIL("ksk_hoist: k=%lld is not in Zm*", (long long)kk);
   fhesi_ksk* h;
   FHESI_TRY(fhesi_ksk_create(c, k->ncomp, k->ndigits, &h));
   // DoubleCRT::automorph by k^-1 on every evaluation row [2][ncol][L][phi(m)]: the same gather on every ring and for every prime
@@ -370,7 +369,6 @@ static int rotations_args(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const i
 static int rotations_run(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
                          int32_t nlimbs_in, int64_t count, uint64_t* out, int32_t nlimbs) {
   const i64 n = c->phim;
-  const int nlq = (logQ + 63) / 64;
   const size_t ct_in = (size_t)2 * n * nlimbs_in, ct_out = (size_t)2 * n * nlimbs;
   CrtTables* t_all;
   FHESI_TRY(get_crt_tables(c, full_set(c), &t_all));
@@ -418,21 +416,12 @@ static int rotations_run(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const in
     auto dst = [&](int t) { return (u64*)out + ((size_t)t * count + done) * ct_out; };
     for (int t = 0; t < nk; ++t) if (!hoisted[t]) FHESI_TRY(rotation_close(c, 1, logQ, src, nlimbs_in, cnt, dst(t), nlimbs));
     if (keyed.empty()) continue;
-    // ApplyKeySwitch on the unscaled ciphertext as it is: ByteDecomp needs the positive residues limb-major
-    void *d_parts, *d_dig, *d_pre;
-    FHESI_TRY(ws_reserve(c, 2, (size_t)cnt * 2 * nlq * n * 8, &d_parts));
-    int r = c->opt.automorph_rows ? 2 : launch_ct_automorph_parts(c, src, nlimbs_in, cnt * 2, 1, logQ, (u64*)d_parts, nlq);
-    if (r == 1) return 1;
-    if (r == 2) {
-      u64* d_rows;
-      FHESI_TRY(automorph_rows(c, 1, src, 2, nlimbs_in, cnt, &d_rows));
-      FHESI_TRY(launch_crt(c, t_all, d_rows, c->L, nullptr, cnt * 2, 3, 0, logQ, (u64*)d_parts, nlq));
-    }
-    FHESI_TRY(key_switch_digits(c, ks_mode, 2, nd, logQ, decomp_bytes, (const u64*)d_parts, cnt, false, &d_dig));
+    void *d_dig, *d_pre;
+    FHESI_TRY(unscaled_digits(c, ks_mode, nd, logQ, decomp_bytes, src, nlimbs_in, cnt, &d_dig));
     FHESI_TRY(ws_reserve(c, 4, (size_t)cnt * ct_out * 8, &d_pre));      // one rotation's key-switched ciphertexts, in front of their sigma_k
     if (!multi) {
       for (int t : keyed) {
-        FHESI_TRY(key_switch_finish(c, hoisted[t], ks_mode, logQ, decomp_bytes, d_dig, cnt, nullptr, (uint64_t*)d_pre, nlimbs));
+        FHESI_TRY(key_switch_finish(c, hoisted[t], ks_mode, logQ, decomp_bytes, d_dig, cnt, (uint64_t*)d_pre, nlimbs));
         FHESI_TRY(rotation_close(c, ks[t], logQ, (const u64*)d_pre, nlimbs, cnt, dst(t), nlimbs));
       }
       continue;
@@ -476,41 +465,6 @@ extern "C" int fhesi_ct_rotations_dev(fhesi_ctx* c, const fhesi_ksk* const* hois
   if (ranges_overlap(in, (size_t)count * 2 * c->phim * nlimbs_in * 8, out, (size_t)nk * count * 2 * c->phim * nlimbs * 8)) FHESI_FAIL("ct_rotations: out overlaps in");
   return rotations_run(c, hoisted, ks, nk, logQ, decomp_bytes, in, nlimbs_in, count, out, nlimbs);
 }
-// out[i] = sum_t rot_t(in[i]) (*) w[t]: the rotations of a chunk of ciphertexts into a pool in the workspace (slot 12), then fhesi_ct_plain_sum_dev
-// on the pool -- the composition itself, so its bits
-extern "C" int fhesi_ct_matvec_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, const fhesi_plain* w, int32_t logQ,
-                                   int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
-  CHECK_CTX(c);
-  if (nk < 1) FHESI_FAIL("ct_matvec: %d diagonals", nk);
-  FHESI_TRY(rotations_args(c, hoisted, ks, nk, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  if (!w) FHESI_FAIL("ct_matvec: null prepared plaintext");
-  if (w->ctx != c) FHESI_FAIL("ct_matvec: the prepared plaintext belongs to another context");
-  if (w->nw < nk) FHESI_FAIL("ct_matvec: %d rotations against %lld prepared diagonals", nk, (long long)w->nw);
-  double chain = 0.0;
-  for (int i = 0; i < c->L; ++i) chain += std::log2((double)c->q[i]);
-  const double bits = plain_sum_bits(c->phim, c->pow2, c->phi_two_term, logQ, w->maxabs, nk);
-  if (bits >= chain) FHESI_FAIL("ct_matvec: a sum of %d products needs %.0f bits, the chain holds %.0f", nk, std::ceil(bits), std::floor(chain));
-  if (!count) return 0;
-  if (!in || !out) FHESI_FAIL("ct_matvec: null argument");
-  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
-  if (ranges_overlap(in, (size_t)count * ct_words * 8, out, (size_t)count * ct_words * 8)) FHESI_FAIL("ct_matvec: out overlaps in");
-  // ciphertexts per pass: about 4 GiB of rotated ciphertexts
-  const i64 chunk = std::max<i64>(1, std::min<i64>(count, (i64)(4.0 * 1024 * 1024 * 1024 / ((double)nk * ct_words * 8))));
-  std::vector<int32_t> a_idx((size_t)chunk * nk), b_idx((size_t)chunk * nk), seg((size_t)chunk + 1);
-  for (i64 done = 0; done < count; done += chunk) {
-    const i64 cnt = std::min(chunk, count - done);
-    void* d_pool;
-    FHESI_TRY(ws_reserve(c, 12, (size_t)nk * cnt * ct_words * 8, &d_pool));
-    FHESI_TRY(rotations_run(c, hoisted, ks, nk, logQ, decomp_bytes, in + (size_t)done * ct_words, nlimbs, cnt, (uint64_t*)d_pool, nlimbs));
-    for (i64 i = 0; i < cnt; ++i) {
-      seg[i] = (int32_t)(i * nk);
-      for (int t = 0; t < nk; ++t) { a_idx[i * nk + t] = (int32_t)(t * cnt + i); b_idx[i * nk + t] = t; }
-    }
-    seg[cnt] = (int32_t)(cnt * nk);
-    FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nk * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt, out + (size_t)done * ct_words));
-  }
-  return 0;
-}
 
 // --------------------------------------------------------------------------------------------- baby-step/giant-step matrix-vector products
 // out[i] = Reduce(base[i] + sum_t Ciphertext >>= ks[t] of pre[t][i]), pre[t] at pre + t * term_stride words: ct_rot_sum_kernel where the ring has the signed
@@ -553,7 +507,7 @@ extern "C" int fhesi_ct_rot_sum_dev(fhesi_ctx* c, const int64_t* ks, int32_t nk,
   if (nlimbs < 1 || nlimbs > 32) FHESI_FAIL("ct_rot_sum: ciphertext coefficients of %d limbs are outside the supported 1..32", nlimbs);
   if (logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("ct_rot_sum: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
   for (int t = 0; t < nk; ++t)
-    if (ks[t] <= 0 || ks[t] >= c->m || c->zms_idx[ks[t]] < 0) FHESI_FAIL("ct_rot_sum: k=%lld of term %d is not in Zm*", (long long)ks[t], t);
+    if (!in_zm_star(c, ks[t])) FHESI_FAIL("ct_rot_sum: k=%lld of term %d is not in Zm*", (long long)ks[t], t);
   if (!count) return 0;
   if (!pre || !out) FHESI_FAIL("ct_rot_sum: null argument");
   const size_t ct_bytes = (size_t)2 * c->phim * nlimbs * 8;
@@ -579,64 +533,51 @@ extern "C" int fhesi_matvec_bsgs_plan(int64_t nk, int32_t* baby, int32_t* giant)
 // ApplyKeySwitch(k, src[i]) of count unscaled two-part ciphertexts as they are, no automorphism: what rotations_run computes in front of sigma_k, one matrix at
 // a time (its table built by the caller's key_switch_form, in front of any digit rows)
 static int key_switch_plain_run(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, int32_t logQ, int32_t decomp_bytes, const u64* in, int32_t nlimbs, int64_t count, u64* out) {
-  const i64 n = c->phim;
-  const int nlq = (logQ + 63) / 64, nd = k->ndigits;
-  const size_t ct_words = (size_t)2 * n * nlimbs;
-  CrtTables* t_all;
-  FHESI_TRY(get_crt_tables(c, full_set(c), &t_all));
-  const i64 chunk = std::min<i64>(16384, batch_chunk(c, 2 * nd, ks_mode == KS_MODE_LIMB32, count));
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  const i64 chunk = std::min<i64>(16384, batch_chunk(c, 2 * k->ndigits, ks_mode == KS_MODE_LIMB32, count));
   for (i64 done = 0; done < count; done += chunk) {
     const i64 cnt = std::min(chunk, count - done);
-    const u64* src = in + done * ct_words;
-    void *d_parts, *d_dig;
-    FHESI_TRY(ws_reserve(c, 2, (size_t)cnt * 2 * nlq * n * 8, &d_parts));
-    const int r = c->opt.automorph_rows ? 2 : launch_ct_automorph_parts(c, src, nlimbs, cnt * 2, 1, logQ, (u64*)d_parts, nlq);
-    if (r == 1) return 1;
-    if (r == 2) {
-      u64* d_rows;
-      FHESI_TRY(automorph_rows(c, 1, src, 2, nlimbs, cnt, &d_rows));
-      FHESI_TRY(launch_crt(c, t_all, d_rows, c->L, nullptr, cnt * 2, 3, 0, logQ, (u64*)d_parts, nlq));
-    }
-    FHESI_TRY(key_switch_digits(c, ks_mode, 2, nd, logQ, decomp_bytes, (const u64*)d_parts, cnt, false, &d_dig));
-    FHESI_TRY(key_switch_finish(c, k, ks_mode, logQ, decomp_bytes, d_dig, cnt, nullptr, out + done * ct_words, nlimbs));
+    void* d_dig;
+    FHESI_TRY(unscaled_digits(c, ks_mode, k->ndigits, logQ, decomp_bytes, in + done * ct_words, nlimbs, cnt, &d_dig));
+    FHESI_TRY(key_switch_finish(c, k, ks_mode, logQ, decomp_bytes, d_dig, cnt, out + done * ct_words, nlimbs));
   }
   return 0;
 }
 
-// out[i] = Reduce( sum_g rot_kg[g]( sum_j rot_kb[j](in[i]) (*) w[g B + j] ) )  (include/fhesi_hip.h): per chunk of ciphertexts the baby rotations from one digit
-// set into the pool (slot 12), ONE plaintext sum with G groups per ciphertext (slot 13), one key switch per giant into its slice of slot 14, one rotated sum
-extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted,
-                                        const int64_t* kg, int32_t G, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
-                                        int32_t nlimbs, int64_t count, uint64_t* out) {
-  CHECK_CTX(c);
-  if (B < 1 || G < 1) FHESI_FAIL("ct_matvec_bsgs: %d baby steps and %d giant steps (at least 1 of each)", B, G);
-  if ((i64)nk <= (i64)(G - 1) * B || (i64)nk > (i64)G * B) FHESI_FAIL("ct_matvec_bsgs: %d diagonals outside (%lld, %lld], what %d giant steps of %d baby steps cover", nk, (long long)(G - 1) * B, (long long)G * B, G, B);
-  FHESI_TRY(rotations_args(c, baby_hoisted, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  FHESI_TRY(rotations_args(c, giant_hoisted, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  if (!w) FHESI_FAIL("ct_matvec_bsgs: null prepared plaintext");
-  if (w->ctx != c) FHESI_FAIL("ct_matvec_bsgs: the prepared plaintext belongs to another context");
-  if (w->nw < nk) FHESI_FAIL("ct_matvec_bsgs: %d rotations against %lld prepared diagonals", nk, (long long)w->nw);
-  const int nb = std::min(B, nk);      // (G = 1 with a ragged group: the babies past nk are not run)
-  double chain = 0.0;
-  for (int i = 0; i < c->L; ++i) chain += std::log2((double)c->q[i]);
-  const double bits = plain_sum_bits(c->phim, c->pow2, c->phi_two_term, logQ, w->maxabs, nb);
-  if (bits >= chain) FHESI_FAIL("ct_matvec_bsgs: a sum of %d products needs %.0f bits, the chain holds %.0f", nb, std::ceil(bits), std::floor(chain));
+// What both matrix-vector entries check behind rotations_args: the prepared plaintext, the capacity rule of a sum of `terms` products, the buffers
+static int matvec_args(fhesi_ctx* c, const char* who, const fhesi_plain* w, int32_t nk, int terms, int32_t logQ, const uint64_t* in, int32_t nlimbs, int64_t count, const uint64_t* out) {
+  if (!w) FHESI_FAIL("%s: null prepared plaintext", who);
+  if (w->ctx != c) FHESI_FAIL("%s: the prepared plaintext belongs to another context", who);
+  if (w->nw < nk) FHESI_FAIL("%s: %d rotations against %lld prepared diagonals", who, nk, (long long)w->nw);
+  const double chain = chain_bits(c), bits = plain_sum_bits(c->phim, c->pow2, c->phi_two_term, logQ, w->maxabs, terms);
+  if (bits >= chain) FHESI_FAIL("%s: a sum of %d products needs %.0f bits, the chain holds %.0f", who, terms, std::ceil(bits), std::floor(chain));
   if (!count) return 0;
-  if (!in || !out) FHESI_FAIL("ct_matvec_bsgs: null argument");
+  if (!in || !out) FHESI_FAIL("%s: null argument", who);
+  const size_t bytes = (size_t)count * 2 * c->phim * nlimbs * 8;
+  if (ranges_overlap(in, bytes, out, bytes)) FHESI_FAIL("%s: out overlaps in", who);
+  return 0;
+}
+// out[i] = Reduce( sum_g rot_kg[g]( sum_j rot_kb[j](in[i]) (*) w[g B + j] ) )  (include/fhesi_hip.h): per chunk of ciphertexts the baby rotations from one digit
+// set into the pool (slot 12), ONE plaintext sum with G groups per ciphertext (slot 13), one key switch per giant into its slice of slot 14, one rotated sum.
+// flat (G = 1, no giant): the plaintext sums ARE the result and go straight to out -- fhesi_ct_matvec_dev; no slot 13 or 14, no rotated sum.
+// g_mode: the giants' forms, their tables built by the caller.  Every argument checked by the caller.
+static int matvec_run(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted, const int64_t* kg,
+                      const int* g_mode, int32_t G, bool flat, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs,
+                      int64_t count, uint64_t* out) {
+  const int nb = std::min(B, nk);      // (G = 1 with a ragged group: the babies past nk are not run)
   const size_t ct_words = (size_t)2 * c->phim * nlimbs;
-  if (ranges_overlap(in, (size_t)count * ct_words * 8, out, (size_t)count * ct_words * 8)) FHESI_FAIL("ct_matvec_bsgs: out overlaps in");
-  // the giants' tables before any digit row exists, as rotations_run builds its matrices'
-  std::vector<int> g_mode((size_t)G, -1);
-  for (int g = 0; g < G; ++g) if (giant_hoisted[g]) FHESI_TRY(key_switch_form(c, giant_hoisted[g], logQ, decomp_bytes, &g_mode[g]));
   // ciphertexts per pass: about 4 GiB of rotated ciphertexts, of inner sums and of key-switched sums each
   const i64 chunk = std::max<i64>(1, std::min<i64>(count, (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(nb, G) * ct_words * 8))));
   std::vector<int32_t> a_idx((size_t)chunk * nk), b_idx((size_t)chunk * nk), seg((size_t)chunk * G + 1);
   for (i64 done = 0; done < count; done += chunk) {
     const i64 cnt = std::min(chunk, count - done);
-    void *d_pool, *d_inner, *d_pre;
+    uint64_t* o = out + (size_t)done * ct_words;
+    void *d_pool, *d_inner = o, *d_pre = nullptr;
     FHESI_TRY(ws_reserve(c, 12, (size_t)nb * cnt * ct_words * 8, &d_pool));
-    FHESI_TRY(ws_reserve(c, 13, (size_t)G * cnt * ct_words * 8, &d_inner));
-    FHESI_TRY(ws_reserve(c, 14, (size_t)G * cnt * ct_words * 8, &d_pre));
+    if (!flat) {
+      FHESI_TRY(ws_reserve(c, 13, (size_t)G * cnt * ct_words * 8, &d_inner));
+      FHESI_TRY(ws_reserve(c, 14, (size_t)G * cnt * ct_words * 8, &d_pre));
+    }
     FHESI_TRY(rotations_run(c, baby_hoisted, kb, nb, logQ, decomp_bytes, in + (size_t)done * ct_words, nlimbs, cnt, (uint64_t*)d_pool, nlimbs));
     // group g * cnt + i = sum_j pool[j][i] (*) w[g B + j]
     i64 at = 0;
@@ -647,70 +588,112 @@ extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* ba
       }
     seg[(size_t)G * cnt] = (int32_t)at;
     FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nb * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt * G, (uint64_t*)d_inner));
+    if (flat) continue;
     for (int g = 0; g < G; ++g) {
       const u64* inner = (const u64*)d_inner + (size_t)g * cnt * ct_words;
       u64* pre = (u64*)d_pre + (size_t)g * cnt * ct_words;
       if (!giant_hoisted[g]) HIP_TRY(hipMemcpyAsync(pre, inner, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));      // (k = 1: the sum itself)
       else FHESI_TRY(key_switch_plain_run(c, giant_hoisted[g], g_mode[g], logQ, decomp_bytes, inner, nlimbs, cnt, pre));
     }
-    FHESI_TRY(rot_sum_run(c, kg, G, logQ, nullptr, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, (u64*)out + (size_t)done * ct_words));
+    FHESI_TRY(rot_sum_run(c, kg, G, logQ, nullptr, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, (u64*)o));
   }
   return 0;
 }
+// out[i] = sum_t rot_t(in[i]) (*) w[t]: one giant step that is the identity -- the composition of fhesi_ct_rotations_dev and fhesi_ct_plain_sum_dev itself, so its bits
+extern "C" int fhesi_ct_matvec_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, const fhesi_plain* w, int32_t logQ,
+                                   int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  if (nk < 1) FHESI_FAIL("ct_matvec: %d diagonals", nk);
+  FHESI_TRY(rotations_args(c, hoisted, ks, nk, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(matvec_args(c, "ct_matvec", w, nk, nk, logQ, in, nlimbs, count, out));
+  if (!count) return 0;
+  return matvec_run(c, hoisted, ks, nk, nullptr, nullptr, nullptr, 1, true, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
+}
+extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted,
+                                        const int64_t* kg, int32_t G, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                                        int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  if (B < 1 || G < 1) FHESI_FAIL("ct_matvec_bsgs: %d baby steps and %d giant steps (at least 1 of each)", B, G);
+  if ((i64)nk <= (i64)(G - 1) * B || (i64)nk > (i64)G * B) FHESI_FAIL("ct_matvec_bsgs: %d diagonals outside (%lld, %lld], what %d giant steps of %d baby steps cover", nk, (long long)(G - 1) * B, (long long)G * B, G, B);
+  FHESI_TRY(rotations_args(c, baby_hoisted, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(rotations_args(c, giant_hoisted, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(matvec_args(c, "ct_matvec_bsgs", w, nk, std::min(B, nk), logQ, in, nlimbs, count, out));
+  if (!count) return 0;
+  // the giants' tables before any digit row exists, as rotations_run builds its matrices'
+  std::vector<int> g_mode((size_t)G, -1);
+  for (int g = 0; g < G; ++g) if (giant_hoisted[g]) FHESI_TRY(key_switch_form(c, giant_hoisted[g], logQ, decomp_bytes, &g_mode[g]));
+  return matvec_run(c, baby_hoisted, kb, B, giant_hoisted, kg, g_mode.data(), G, false, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
+}
 
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).
-// Every distinct operand of a chunk is brought to evaluation form ONCE (a matrix entry or a minor typically feeds many products),
-// the products are formed and summed per group in one pass (tensor_sum_kernel), then the groups are key-switched together.
-extern "C" int fhesi_ct_mul_sum_relin_dev(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint64_t p, int32_t decomp_bytes, const uint64_t* pool,
-                                          int32_t nlimbs, const int32_t* a_idx, const int32_t* b_idx, const int32_t* seg, int64_t ngroups, uint64_t* out) {
-  CHECK_CTX(c);
-  FHESI_TRY(key_switch_args(c, k, logQ, decomp_bytes, nlimbs));
-  if (k->ncomp != 3) FHESI_FAIL("ct_mul_sum_relin needs the s^2 -> s matrix (3 source components), got %d", k->ncomp);
-  if (!ngroups) return 0;
-  for (i64 g = 0; g < ngroups; ++g) if (seg[g + 1] <= seg[g]) FHESI_FAIL("ct_mul_sum_relin: group %lld is empty", (long long)g);
+// Every group a single product (a loop of `c *= d; ApplyKeySwitch(c)` recorded by the host mirror, fhesi_engine.h): the operands are
+// gathered into two batches and take the batch pipeline of fhesi_ct_mul_relin_batch_dev -- the tensor products formed in the loader
+// of the inverse transform instead of the sum kernels below (19.6 k -> 22 k multiplications per second at the metric ring with the
+// operands gathered, more with them addressed through the indices)
+static int wave_single_products(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint64_t p, int32_t decomp_bytes, const uint64_t* pool, int32_t nlimbs,
+                                const int32_t* a_idx, const int32_t* b_idx, const int32_t* seg, int64_t ngroups, uint64_t* out) {
+  const i64 ct_words = (i64)2 * c->phim * nlimbs, step = 1024;
+  std::vector<int> ix;
+  for (i64 g0 = 0; g0 < ngroups; g0 += step) {
+    const i64 cnt = std::min<i64>(step, ngroups - g0);
+    const size_t ops_bytes = (size_t)2 * cnt * ct_words * 8;
+    // where the tensor half runs over the 30-bit primes its first kernel takes the operands through the indices (no copy at all);
+    // elsewhere they are gathered into two batches first
+    const bool indexed = tensor32_applies(c, p, nlimbs, logQ);
+    void* d_ops;
+    FHESI_TRY(ws_reserve(c, 12, (indexed ? 0 : ops_bytes) + sizeof(int) * 2 * (size_t)cnt, &d_ops));      // (a slot of its own: the pipeline called below uses most of the others)
+    int* d_ix = (int*)((char*)d_ops + (indexed ? 0 : ops_bytes));
+    ix.resize(2 * cnt);
+    for (i64 g = 0; g < cnt; ++g) { ix[g] = a_idx[seg[g0 + g]]; ix[cnt + g] = b_idx[seg[g0 + g]]; }
+    HIP_TRY(hipMemcpyAsync(d_ix, ix.data(), sizeof(int) * ix.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));             // ix is reused by the next chunk
+    if (indexed) {
+      c->op_idx = d_ix; c->op_idx_n = cnt; c->op_idx_done = 0;
+      const int rc = mul_relin_chunks(c, k, logQ, p, decomp_bytes, (const u64*)pool, (const u64*)pool, out + (size_t)g0 * ct_words, nlimbs, cnt);
+      c->op_idx = nullptr;
+      if (rc) return rc;
+    } else {
+      FHESI_TRY(launch_gather(c, (const u64*)pool, d_ix, 2 * cnt, ct_words, (u64*)d_ops));
+      FHESI_TRY(fhesi_ct_mul_relin_batch_dev(c, k, logQ, p, decomp_bytes, (const u64*)d_ops, (const u64*)d_ops + (size_t)cnt * ct_words, out + (size_t)g0 * ct_words, nlimbs, cnt));
+    }
+  }
+  return 0;
+}
+// One pass of the plan (wave_plan.h; dix: its index words on the device): every distinct operand gathered (slot 7) and brought to evaluation form ONCE
+// (slot 0; the 30-bit path keeps rows of its own) -- a matrix entry or a minor typically feeds many products --, the products formed and summed per
+// group into d_sum (u32 rows on the 30-bit path)
+static int wave_sum_pass(fhesi_ctx* c, const WavePass& P, const int* dix, bool t32, uint64_t p, const uint64_t* pool, int32_t nlimbs, u64* d_sum) {
+  const i64 n = c->phim, ct_words = (i64)2 * n * nlimbs, nu = P.nua + P.nub;
+  const int L = c->L;
+  const int *slot_a = dix + nu, *slot_b = slot_a + P.nt, *gseg = slot_b + P.nt;
+  void *d_ops, *d_rows = nullptr;
+  FHESI_TRY(ws_reserve(c, 7, (size_t)nu * ct_words * 8, &d_ops));
+  if (!t32) FHESI_TRY(ws_reserve(c, 0, (size_t)nu * 2 * L * n * 8, &d_rows));
+  u64* d_a = (u64*)d_ops;
+  u64* d_b = d_a + (size_t)P.nua * ct_words;
+  FHESI_TRY(launch_gather(c, (const u64*)pool, dix, nu, ct_words, d_a));
+  if (t32) return tensor32_sum_pass(c, d_a, P.nua, P.nub, slot_a, slot_b, gseg, P.ng, P.nt, P.accumulate, d_sum);
+  // c1 = DoubleCRT(parts * p), c2 = DoubleCRT(other.parts)   (Ciphertext.cpp:169-176)
+  const u64 lift[2] = {p, p};
+  const std::vector<int> all = full_set(c);
+  u64* ca = (u64*)d_rows;
+  u64* cb = ca + (size_t)P.nua * 2 * L * n;
+  FHESI_TRY(launch_rns_reduce(c, d_a, nlimbs, n, P.nua, 2, lift, ca, L, nullptr));
+  FHESI_TRY(launch_rns_reduce(c, d_b, nlimbs, n, P.nub, 2, nullptr, cb, L, nullptr));
+  FHESI_TRY(row_fwd(c, ca, nu * 2, L, nullptr, all.data()));
+  return launch_tensor_sum(c, ca, cb, slot_a, slot_b, gseg, P.ng, P.accumulate, d_sum, (double)P.nt);
+}
+// The sums of all groups and their key switches.  The passes are planned first and their index words uploaded once (slot 5: alive to the last pass, across the
+// key switches of earlier groups -- nothing on this path reserves it); the sums of a run of groups (slot 4) are key-switched together behind the pass that closes them.
+static int wave_sums(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint64_t p, int32_t decomp_bytes, const uint64_t* pool, int32_t nlimbs,
+                     const int32_t* a_idx, const int32_t* b_idx, const int32_t* seg, int64_t ngroups, uint64_t* out) {
   const i64 n = c->phim;
   const int L = c->L;
   const i64 ct_words = (i64)2 * n * nlimbs, tp_words = (i64)3 * L * n;
-  {
-    // every group a single product (a loop of `c *= d; ApplyKeySwitch(c)` recorded by the host mirror, fhesi_engine.h): the operands are
-    // gathered into two batches and take the batch pipeline of fhesi_ct_mul_relin_batch_dev -- the tensor products formed in the loader
-    // of the inverse transform instead of the sum kernels below (19.6 k -> 22 k multiplications per second at the metric ring with the
-    // operands gathered, more with them addressed through the indices)
-    bool single = c->opt.wave_single != 0;
-    for (i64 g = 0; single && g < ngroups; ++g) single = seg[g + 1] - seg[g] == 1;
-    if (single) {
-      const i64 step = 1024;
-      std::vector<int> ix;
-      for (i64 g0 = 0; g0 < ngroups; g0 += step) {
-        const i64 cnt = std::min<i64>(step, ngroups - g0);
-        const size_t ops_bytes = (size_t)2 * cnt * ct_words * 8;
-        // where the tensor half runs over the 30-bit primes its first kernel takes the operands through the indices (no copy at all);
-        // elsewhere they are gathered into two batches first
-        const bool indexed = tensor32_applies(c, p, nlimbs, logQ);
-        void* d_ops;
-        FHESI_TRY(ws_reserve(c, 12, (indexed ? 0 : ops_bytes) + sizeof(int) * 2 * (size_t)cnt, &d_ops));      // (a slot of its own: the pipeline called below uses most of the others)
-        int* d_ix = (int*)((char*)d_ops + (indexed ? 0 : ops_bytes));
-        ix.resize(2 * cnt);
-        for (i64 g = 0; g < cnt; ++g) { ix[g] = a_idx[seg[g0 + g]]; ix[cnt + g] = b_idx[seg[g0 + g]]; }
-        HIP_TRY(hipMemcpyAsync(d_ix, ix.data(), sizeof(int) * ix.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));             // ix is reused by the next chunk
-        if (indexed) {
-          c->op_idx = d_ix; c->op_idx_n = cnt; c->op_idx_done = 0;
-          const int rc = mul_relin_chunks(c, k, logQ, p, decomp_bytes, (const u64*)pool, (const u64*)pool, out + (size_t)g0 * ct_words, nlimbs, cnt);
-          c->op_idx = nullptr;
-          if (rc) return rc;
-        } else {
-          FHESI_TRY(launch_gather(c, (const u64*)pool, d_ix, 2 * cnt, ct_words, (u64*)d_ops));
-          FHESI_TRY(fhesi_ct_mul_relin_batch_dev(c, k, logQ, p, decomp_bytes, (const u64*)d_ops, (const u64*)d_ops + (size_t)cnt * ct_words, out + (size_t)g0 * ct_words, nlimbs, cnt));
-        }
-      }
-      return 0;
-    }
-  }
-  const std::vector<int> all = full_set(c);
   CrtTables* t_all;
-  FHESI_TRY(get_crt_tables(c, all, &t_all));
-  const i64 chunk = batch_chunk(c, 3 * k->ndigits, ksaux_mode(c, t_all, k->ncomp * k->ndigits, 8 * decomp_bytes, logQ) == KS_MODE_LIMB32);           // groups per key-switch call
+  FHESI_TRY(get_crt_tables(c, full_set(c), &t_all));
+  const bool ks32 = ksaux_mode(c, t_all, k->ncomp * k->ndigits, 8 * decomp_bytes, logQ) == KS_MODE_LIMB32;
+  const i64 chunk = batch_chunk(c, 3 * k->ndigits, ks32);           // groups per key-switch call
   // distinct operands per pass: bound their evaluation-form rows (2 L n words each) to about 4 GiB
   i64 ucap = (i64)(4.0 * 1024 * 1024 * 1024 / ((double)2 * L * n * 8));
   // the sums' integers over primes below 2^30 where that path applies (kernels_tensor32.hip; tProd is not visible from here either)
@@ -723,86 +706,41 @@ extern "C" int fhesi_ct_mul_sum_relin_dev(fhesi_ctx* c, const fhesi_ksk* k, int3
   }
   if (c->opt.wave_operands > 1) ucap = c->opt.wave_operands;
   if (ucap < 2) ucap = 2;
-  const u64 lift[2] = {p, p};
-  std::vector<int> ua, ub, sa, sb, lseg, host_idx;
-  std::map<int, int> ma, mb;
-  // one pass: terms [t0, t1) of the groups [g, g2) (group boundaries in gseg, relative to t0), summed into d_sum[0 .. g2-g)
-  auto pass = [&](i64 t0, i64 t1, const std::vector<int>& gseg, bool accumulate, u64* d_sum) -> int {      // (d_sum: u32 rows on the 30-bit path)
-    ua.clear(); ub.clear(); ma.clear(); mb.clear();
-    sa.resize(t1 - t0); sb.resize(t1 - t0);
-    for (i64 t = t0; t < t1; ++t) {
-      auto ia = ma.find(a_idx[t]); if (ia == ma.end()) { ia = ma.emplace(a_idx[t], (int)ua.size()).first; ua.push_back(a_idx[t]); }
-      auto ib = mb.find(b_idx[t]); if (ib == mb.end()) { ib = mb.emplace(b_idx[t], (int)ub.size()).first; ub.push_back(b_idx[t]); }
-      sa[t - t0] = ia->second; sb[t - t0] = ib->second;
-    }
-    const i64 nua = (i64)ua.size(), nub = (i64)ub.size(), nt = t1 - t0, ng = (i64)gseg.size() - 1;
-    void *d_ops, *d_rows = nullptr, *d_ix;
-    FHESI_TRY(ws_reserve(c, 7, (size_t)(nua + nub) * ct_words * 8, &d_ops));
-    if (!t32) FHESI_TRY(ws_reserve(c, 0, (size_t)(nua + nub) * 2 * L * n * 8, &d_rows));
-    FHESI_TRY(ws_reserve(c, 5, sizeof(int) * (size_t)(nua + nub + 2 * nt + ng + 1), &d_ix));
-    host_idx.clear();
-    host_idx.insert(host_idx.end(), ua.begin(), ua.end());
-    host_idx.insert(host_idx.end(), ub.begin(), ub.end());
-    host_idx.insert(host_idx.end(), sa.begin(), sa.end());
-    host_idx.insert(host_idx.end(), sb.begin(), sb.end());
-    host_idx.insert(host_idx.end(), gseg.begin(), gseg.end());
-    HIP_TRY(hipMemcpyAsync(d_ix, host_idx.data(), sizeof(int) * host_idx.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                 // host_idx is reused by the next pass
-    const int* dix = (const int*)d_ix;
-    u64* d_a = (u64*)d_ops;
-    u64* d_b = d_a + (size_t)nua * ct_words;
-    u64* ca = (u64*)d_rows;
-    u64* cb = ca + (size_t)nua * 2 * L * n;
-    FHESI_TRY(launch_gather(c, (const u64*)pool, dix, nua + nub, ct_words, d_a));
-    if (t32) return tensor32_sum_pass(c, d_a, nua, nub, dix + nua + nub, dix + nua + nub + nt, dix + nua + nub + 2 * nt, ng, nt, accumulate, d_sum);
-    // c1 = DoubleCRT(parts * p), c2 = DoubleCRT(other.parts)   (Ciphertext.cpp:169-176)
-    FHESI_TRY(launch_rns_reduce(c, d_a, nlimbs, n, nua, 2, lift, ca, L, nullptr));
-    FHESI_TRY(launch_rns_reduce(c, d_b, nlimbs, n, nub, 2, nullptr, cb, L, nullptr));
-    FHESI_TRY(row_fwd(c, ca, (nua + nub) * 2, L, nullptr, all.data()));
-    return launch_tensor_sum(c, ca, cb, dix + nua + nub, dix + nua + nub + nt, dix + nua + nub + 2 * nt, ng, accumulate, d_sum, (double)nt);
-  };
-  std::vector<int> gseg;
-  std::set<int> seen_a, seen_b;
-  i64 g = 0;
-  while (g < ngroups) {
-    // groups g..g2-1: at most `chunk` of them and at most `ucap` distinct operands (one group is always taken)
-    seen_a.clear(); seen_b.clear();
-    i64 g2 = g;
-    while (g2 < ngroups && g2 - g < chunk) {
-      std::set<int> na = seen_a, nb = seen_b;
-      for (i64 t = seg[g2]; t < seg[g2 + 1]; ++t) { na.insert(a_idx[t]); nb.insert(b_idx[t]); }
-      if (g2 > g && (i64)(na.size() + nb.size()) > ucap) break;
-      seen_a.swap(na); seen_b.swap(nb);
-      ++g2;
-    }
-    const i64 ng = g2 - g;
-    void* d_sum;
-    FHESI_TRY(ws_reserve(c, 4, t32 ? tensor32_sum_bytes(c, ng) : (size_t)ng * tp_words * 8, &d_sum));
-    if (ng == 1 && (i64)(seen_a.size() + seen_b.size()) > ucap) {
-      // one group with more distinct operands than a pass holds: its terms are summed piecewise into the same accumulator
-      const i64 step = ucap / 2;
-      for (i64 t0 = seg[g]; t0 < seg[g + 1]; t0 += step) {
-        const i64 t1 = std::min<i64>(t0 + step, seg[g + 1]);
-        gseg = {0, (int)(t1 - t0)};
-        FHESI_TRY(pass(t0, t1, gseg, t0 != seg[g], (u64*)d_sum));
-      }
-    } else {
-      gseg.resize(ng + 1);
-      for (i64 i = 0; i <= ng; ++i) gseg[i] = seg[g + i] - seg[g];
-      FHESI_TRY(pass(seg[g], seg[g2], gseg, false, (u64*)d_sum));
-    }
+  // a's and b's are operands alike, counted apart; one group over ucap goes in pieces of ucap / 2 terms
+  const WavePlan plan = wave_plan(a_idx, b_idx, seg, ngroups, chunk, ucap, true);
+  void* d_ix;
+  FHESI_TRY(ws_reserve(c, 5, sizeof(int) * plan.ix.size(), &d_ix));
+  HIP_TRY(hipMemcpyAsync(d_ix, plan.ix.data(), sizeof(int) * plan.ix.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));                 // the one synchronisation: the plan lives on this frame
+  void* d_sum = nullptr;
+  for (const WavePass& P : plan.passes) {
+    // (a piece that accumulates keeps the rows its first piece reserved)
+    if (!P.accumulate) FHESI_TRY(ws_reserve(c, 4, t32 ? tensor32_sum_bytes(c, P.ng) : (size_t)P.ng * tp_words * 8, &d_sum));
+    FHESI_TRY(wave_sum_pass(c, P, (const int*)d_ix + P.off, t32, p, pool, nlimbs, (u64*)d_sum));
+    if (!P.close) continue;
+    uint64_t* o = out + (size_t)P.g * ct_words;
     if (t32) {
       void* d_parts;
-      FHESI_TRY(ws_reserve(c, 2, (size_t)ng * 3 * ((logQ + 63) / 64) * n * 8, &d_parts));
-      const bool wm = c->opt.parts_words && ksaux_mode(c, t_all, k->ncomp * k->ndigits, 8 * decomp_bytes, logQ) == KS_MODE_LIMB32;
-      FHESI_TRY(tensor32_sum_finish(c, d_sum, ng, (u64*)d_parts, wm));
-      FHESI_TRY(key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, ng, nullptr, out + (size_t)g * ct_words, nlimbs, wm));
+      FHESI_TRY(ws_reserve(c, 2, (size_t)P.ng * 3 * ((logQ + 63) / 64) * n * 8, &d_parts));
+      const bool wm = c->opt.parts_words && ks32;
+      FHESI_TRY(tensor32_sum_finish(c, d_sum, P.ng, (u64*)d_parts, wm));
+      FHESI_TRY(key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, P.ng, o, nlimbs, wm));
     } else {
-      FHESI_TRY(fhesi_apply_key_switch_dev(c, k, logQ, decomp_bytes, (const uint64_t*)d_sum, ng, out + (size_t)g * ct_words, nlimbs));
+      FHESI_TRY(fhesi_apply_key_switch_dev(c, k, logQ, decomp_bytes, (const uint64_t*)d_sum, P.ng, o, nlimbs));
     }
-    g = g2;
   }
   return 0;
+}
+extern "C" int fhesi_ct_mul_sum_relin_dev(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint64_t p, int32_t decomp_bytes, const uint64_t* pool,
+                                          int32_t nlimbs, const int32_t* a_idx, const int32_t* b_idx, const int32_t* seg, int64_t ngroups, uint64_t* out) {
+  CHECK_CTX(c);
+  FHESI_TRY(key_switch_args(c, k, logQ, decomp_bytes, nlimbs));
+  if (k->ncomp != 3) FHESI_FAIL("ct_mul_sum_relin needs the s^2 -> s matrix (3 source components), got %d", k->ncomp);
+  if (!ngroups) return 0;
+  for (i64 g = 0; g < ngroups; ++g) if (seg[g + 1] <= seg[g]) FHESI_FAIL("ct_mul_sum_relin: group %lld is empty", (long long)g);
+  bool single = c->opt.wave_single != 0;
+  for (i64 g = 0; single && g < ngroups; ++g) single = seg[g + 1] - seg[g] == 1;
+  return (single ? wave_single_products : wave_sums)(c, k, logQ, p, decomp_bytes, pool, nlimbs, a_idx, b_idx, seg, ngroups, out);
 }
 
 // Ciphertexts per launch of the fused multiplication.  ks32: the key switch really runs over the four 30-bit auxiliary primes (ksaux_mode
@@ -868,11 +806,11 @@ static int mul_relin_chunks(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint
       if (c->op_idx) c->op_idx_done = done;                  // indexed operands: the chunk is a window of the index arrays, the buffer stays put
       const bool wm = ks_mode == KS_MODE_LIMB32 && c->opt.parts_words;      // (the digit loader of the four-prime form reads word rows in whole lines)
       if (!rc) rc = launch_tensor32(c, p, c->op_idx ? a : a + off, c->op_idx ? b : b + off, nlimbs, logQ, cnt, (u64*)d_parts, wm);
-      if (!rc) rc = key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, cnt, nullptr, out + off, nlimbs, wm);
+      if (!rc) rc = key_switch_tail(c, k, logQ, decomp_bytes, (const u64*)d_parts, cnt, out + off, nlimbs, wm);
     } else {
       if (c->op_idx) FHESI_FAIL("ct_mul_relin: indexed operands reached the chain path");      // (only the 30-bit tensor half reads through indices; the caller checks tensor32_applies)
       void* d_tp = nullptr;
-      rc = ws_reserve(c, 5, (size_t)cnt * 3 * L * n * 8, &d_tp);
+      rc = ws_reserve(c, 1, (size_t)cnt * 3 * L * n * 8, &d_tp);
       if (!rc) rc = fhesi_ct_mul_dev(c, p, a + off, b + off, nlimbs, cnt, (uint64_t*)d_tp);
       if (!rc) rc = key_switch_args(c, k, logQ, decomp_bytes, nlimbs);
       if (!rc) rc = apply_key_switch_consume(c, k, logQ, decomp_bytes, (u64*)d_tp, cnt, out + off, nlimbs);      // the chunk's tProd is ours: no copy

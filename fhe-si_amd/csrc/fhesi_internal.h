@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cmath>
 #include <cstdio>
 #include <map>
 #include <string>
@@ -162,9 +163,9 @@ struct fhesi_ctx {
   std::vector<ProfRec> prof;
   const void* prof_fn[16] = {};        // host stub of the kernel the last profiled launch of each class ran (fhesi_prof_kernel_name)
   // grow-only workspace.  Slot owners (a slot may be reused by another owner only when the first one's data is dead):
-  //   0 digit rows / product operands / encrypt rows    1 inverse-transform scratch (tProd copy, dot output, automorph rows)
+  //   0 digit rows / product operands / encrypt rows    1 inverse-transform scratch (tProd of a chunk or its copy, dot output, automorph rows)
   //   2 limb-major parts / small-coefficient staging    3 automorph source rows / encrypt public key
-  //   4 wave sums, per-call constants, noise maxima      5 tProd of a chunk / message staging
+  //   4 wave sums, per-call constants, noise maxima      5 index lists of a sum wave / rows of the 30-bit tensor half / message staging
   //   6 row transforms above 2^14 (two-pass, bit reversal); the per-workgroup clean-up flags of the CRT kernels that decide most coefficients from a
   //     sum and leave the rest to an exact pass (launch_crt_sum, crt32_scale_kernel): written by the first kernel once the inverse transform's use
   //     of the slot is dead, read by the clean-up launched right behind it on the same stream -- per lane, like every slot
@@ -173,8 +174,9 @@ struct fhesi_ctx {
   //   10 auxiliary-prime dot product output (kernels_ksaux.hip)      11 staging of host batches (fhesi_ct_mul_relin_batch)
   //   (the slot layer borrows 8 for its convolution buffer / basis residues, 9 for slot values and 5 for message polynomials -- slots_stage_host,
   //   the stage_msg_* functions in front of encrypt_rows_dev: before the transforms of an encryption start; what follows decrypt_rows_dev:
-  //   after those of a decryption are enqueued; fhesi_ct_plain_sum_dev takes the owners fhesi_ct_mul_sum_relin_dev takes: 7 gathered operands, 0 their
-  //   rows, 4 the sums, 5 the index lists of all passes; the noise entry points own 4 from the CRT of a decryption to their copy-out: the per-block
+  //   after those of a decryption are enqueued; fhesi_ct_plain_sum_dev and the sums of fhesi_ct_mul_sum_relin_dev take the same owners: 7 gathered
+  //   operands, 0 their rows, 4 the sums, 5 the index lists of all passes (wave_plan.h), uploaded once -- in the product wave alive across the key switches of
+  //   earlier groups: no key switch reserves 5, only launch_tensor32, which a sum wave never reaches; the noise entry points own 4 from the CRT of a decryption to their copy-out: the per-block
   //   maxima of launch_decrypt_noise, then the maxima and budgets per ciphertext -- nothing in a decryption touches 4)
   //   (the hoisted rotations, capi_pipeline.hip: 2 the positive residues of a chunk, 0 its digit rows -- alive across all matrices, which is why every table is
   //   built before them --, 10 the dot outputs of the matrices of one launch, 4 one rotation's key-switched ciphertexts in front of their automorphism;
@@ -184,6 +186,9 @@ struct fhesi_ctx {
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
+
+static inline double chain_bits(const fhesi_ctx* c) { double b = 0.0; for (int i = 0; i < c->L; ++i) b += std::log2((double)c->q[i]); return b; }      // log2 of the chain product: what a capacity rule compares with
+static inline bool in_zm_star(const fhesi_ctx* c, i64 k) { return k > 0 && k < c->m && c->zms_idx[k] >= 0; }      // DoubleCRT.cpp:442-443
 
 struct fhesi_dcrt {
   fhesi_ctx* ctx = nullptr;
