@@ -98,6 +98,7 @@ static const OptDesc kOptions[] = {
   {"wave_single", "FHESI_WAVE_SINGLE", offsetof(CtxOptions, wave_single), false},
   {"tensor32", "FHESI_TENSOR32", offsetof(CtxOptions, tensor32), false},
   {"tensor_bits", "FHESI_TENSOR_BITS", offsetof(CtxOptions, tensor_bits), false},
+  {"crt32_mfma", "FHESI_CRT32_MFMA", offsetof(CtxOptions, crt32_mfma), false},
   {"dot32_k4", "FHESI_DOT32_K4", offsetof(CtxOptions, dot32_k4), false},
   {"parts_words", "FHESI_PARTS_WORDS", offsetof(CtxOptions, parts_words), false},
   {"hoist_dot", "FHESI_HOIST_DOT", offsetof(CtxOptions, hoist_dot), false},

@@ -90,7 +90,8 @@ struct CtxOptions {
   int automorph_rows = 0;   // 1: Ciphertext >>= through DoubleCRT::automorph on evaluation rows (the reference's structure) even where the coefficient gather applies
   int tensor32 = 1;         // 1: the fused pipeline's tensor half runs over 30-bit primes where that path applies (fhesi_ct_mul_relin_batch_dev)
   int tensor_bits = 30;     // 30: the tensor half's primes are the largest below 2^30; 29: below 2^29 -- lazy values have room up to 8p, so the row transforms skip 8 of 14 (forward) / 6 of 13 (inverse) range steps, for one or two primes more (36 instead of 35 at the metric ring)
-  int dot32_k4 = 1;         // 1: key switch with 7 or 8 limbs and at least 24 ciphertexts per call runs dot32_kernel4 (keys in LDS, digits and accumulators in registers); 0: dot32_kernel2 (A/B)
+  int crt32_mfma = 1;       // 1: the fast pass of the tensor half's CRT at rows of 2^14, logQ = 512 runs on the int8 matrix cores (crt32_mfma_kernel) in launches of 128 polynomials and more; 2: at any size; 0: crt32_scale_kernel (A/B, and the checker: same F, same flags)
+  int dot32_k4 = 1;        // 1: key switch with 7 or 8 limbs and at least 24 ciphertexts per call runs dot32_kernel4 (keys in LDS, digits and accumulators in registers); 0: dot32_kernel2 (A/B)
   int hoist_dot = 0;        // dot product of the hoisted rotations (fhesi_ct_rotations_dev): 1 = one launch of launch_dot32's choice per matrix on the shared digits; 2 = the multi-matrix kernel (dot32_kernel2m; four-prime form only); 0 = automatic
   int parts_words = 1;      // 1: inside the fused multiplication the scaled-down parts travel as 32-bit word rows (crt32_scale -> digit loader); 0 = 64-bit limb rows (A/B)
 };

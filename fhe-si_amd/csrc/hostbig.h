@@ -74,8 +74,43 @@ inline Big bn_half(const Big& a) {
   for (size_t i = 0; i < a.size(); ++i) r[i] = (a[i] >> 1) | (i + 1 < a.size() ? a[i + 1] << 63 : 0);
   return r;
 }
-// a at exactly n limbs (zero-filled; the caller knows that nothing significant is cut)
+// a at exactly n limbs (zero-filled; the caller knows that nothing significant is cut, or wants the value modulo 2^(64 n))
 inline Big bn_resized(Big a, size_t n) { a.resize(n, 0); return a; }
+// a += b at a's own width: modulo 2^(64 a.size()); limbs of b beyond a's width are ignored
+inline void bn_add(Big& a, const Big& b) {
+  bn_limb c = 0;
+  for (size_t i = 0; i < a.size(); ++i) {
+    const bn_wide s = (bn_wide)a[i] + (i < b.size() ? b[i] : 0) + c;
+    a[i] = (bn_limb)s;
+    c = (bn_limb)(s >> 64);
+  }
+}
+// word l of the radix-2^R form of a (R <= 32; words beyond a are zero)
+inline uint32_t bn_word(const Big& a, int l, int R) {
+  const int bit = R * l, w = bit >> 6, o = bit & 63;
+  bn_limb v = (size_t)w < a.size() ? a[w] >> o : 0;
+  if (o + R > 64 && (size_t)w + 1 < a.size()) v |= a[w + 1] << (64 - o);
+  return (uint32_t)(v & (((bn_limb)1 << R) - 1));
+}
+// sum_l w[l] 2^(R l) over count words below 2^R (R <= 32): the inverse of bn_word
+inline Big bn_from_words(const uint32_t* w, int count, int R) {
+  Big r(((size_t)count * R + 63) / 64 + 1, 0);
+  for (int l = 0; l < count; ++l) {
+    const int bit = R * l, i = bit >> 6, o = bit & 63;
+    r[i] |= (bn_limb)w[l] << o;
+    if (o + R > 64) r[i + 1] |= (bn_limb)w[l] >> (64 - o);
+  }
+  return r;
+}
+// a modulo 2^(8 n) in balanced bytes: out[c] in [-128, 127] with sum_c out[c] 256^c = a (mod 2^(8 n)); n <= 8 a.size()
+inline void bn_balanced_bytes(const Big& a, int n, int8_t* out) {
+  int carry = 0;
+  for (int c = 0; c < n; ++c) {
+    const int b = (int)((a[c >> 3] >> (8 * (c & 7))) & 255) + carry;      // 0 .. 256
+    carry = b >= 128 ? 1 : 0;
+    out[c] = (int8_t)(b - 256 * carry);
+  }
+}
 // first * 2^(64 k) mod q for k < count: the weights of the limbs of a coefficient modulo a prime
 inline Big pow64_table(bn_limb q, int count, bn_limb first = 1) {
   Big r((size_t)count);

@@ -17,8 +17,11 @@
 //                         twiddle (T32Primes, per configuration), so the kernel starts at the multiply-adds.  Only the words from
 //                         28 * 16 = 448 bits upwards are formed -- the dropped part is below 64 * 2^30 * 2^448 = 2^484 and can change
 //                         round(x / 2^512) only when bits 484..511 of x + 2^511 are all ones (2^-27 per coefficient: about one workgroup in
-//                         three launches of 1024 products): those workgroups are flagged and redone with every word (EXACT), the pattern of
-//                         crt_sum_kernel.
+//                         three launches of 1024 products): those workgroups are flagged, listed and redone with every word (EXACT on a small
+//                         grid that walks the list), the pattern of crt_sum_kernel.
+//   crt32_mfma_kernel     the same fast pass at rows of 2^14, logQ = 512 as an int8 matrix product (option crt32_mfma): the window of the constants
+//                         in balanced bytes is operand A, the residues' bytes operand B, fifteen v_mfma_i32_32x32x32_i8 per 32 coefficients and a
+//                         carry pass over nine words per lane -- the same integer, the same limbs, the same flags (crt32_bytes.h).
 // Rows of 2^15 (n = 2^15, the stress shape: 70 primes for logQ = 1024): the head stage of the forward transform is taken inside
 // rns32_reduce_kernel<NL, true> (a thread converts coefficients j and j + 2^14 and stores the two butterfly outputs into the two sub-rows),
 // the tail of the inverse inside crt32_scale_kernel (its first multiplication takes (A + B) or (A - B) with the tail constant folded into
@@ -37,6 +40,7 @@
 #include "fhesi_internal.h"
 #include "lin_fold.h"
 #include "ntt32_core.inc"
+#include "crt32_bytes.h"
 #include <cmath>
 
 // one (lift, limb count, logQ, prime count) configuration: the conversion tables
@@ -49,7 +53,8 @@ struct T32Config {
   Tw32* d_cinv = nullptr;            // [NP][2] (M / p_i)^-1 mod p_i  [times 1/2 | times psi^-brv(1) / 2: the tail of a 2^15-point inverse]   (rows of 2^14: not read, pr.ninv carries it)
   u32* d_inv57 = nullptr;            // [NP] floor(2^57 / p_i)
   u32* d_Mw = nullptr;               // [NP + 1][WT]: M_i in words of R bits; row NP = 2^(R WT) - M
-  ~T32Config() { hipFree(d_rns); hipFree(d_cinv); hipFree(d_inv57); hipFree(d_Mw); }
+  u32* d_bytes = nullptr;            // crt32_mfma_kernel's operand A (crt32_bytes.h): [3][5][64][4]; null where the shape does not qualify
+  ~T32Config() { hipFree(d_rns); hipFree(d_cinv); hipFree(d_inv57); hipFree(d_Mw); hipFree(d_bytes); }
 };
 struct fhesi_tensor32 {
   int S = 0;                         // rows of 2^14 << S
@@ -78,12 +83,7 @@ void tensor32_free(fhesi_ctx* ctx) {
 
 // ---------------------------------------------------------------------------------------------- host big integers (little-endian u64 limbs)
 using hm::Big;
-static u32 big_word(const Big& a, int l, int R) {          // word l of the radix-2^R form
-  const int bit = R * l, w = bit >> 6, o = bit & 63;
-  u64 v = (size_t)w < a.size() ? a[w] >> o : 0;
-  if (o + R > 64 && (size_t)w + 1 < a.size()) v |= a[w + 1] << (64 - o);
-  return (u32)(v & (((u64)1 << R) - 1));
-}
+static u32 big_word(const Big& a, int l, int R) { return hm::bn_word(a, l, R); }          // word l of the radix-2^R form
 
 // the two compiled shapes of crt32_scale_kernel, and the run-time form
 static constexpr int T32_WT_512 = 38, T32_R_512 = 28;        // logQ = 512: words of 28 bits (up to 62 primes), 1064 bits per table row
@@ -104,6 +104,27 @@ __host__ __device__ constexpr int t32_j0(int LQ, int R, int np_max) {
 static_assert(t32_j0(512, T32_R_512, T32_NP_28) == 16 && t32_j0(1024, T32_R_1024, T32_NP_26) == 36, "the compiled windows: words from bit 448 / 936");
 // undecided: bits logQ-28 .. logQ-1 of the rounding limb G (bits logQ-64 .. logQ-1 of F) read 0111...1, i.e. all ones once the rounding bit is added
 __device__ __forceinline__ int t32_undecided(u64 G) { return (G >> (64 - T32_WIN)) == (((u64)1 << (T32_WIN - 1)) - 1) ? 1 : 0; }
+
+// The matrix-core form of the fast pass (crt32_mfma_kernel): rows of 2^14, logQ = 512, the 21 words of 28 bits from bit 448 -- the window
+// crt32_scale_kernel<512, false, 28, 38, 0> forms.  Its depth holds 40 slots of four bytes; the first four depth steps
+// hold primes only, so at least 32 primes, and kappa and the constant need two slots (35 primes below 2^30 and 36 below 2^29 at the metric ring;
+// sums of products take one or two more).
+static constexpr int T32_MFMA_NW = (2 * 512 + T32_R_512 - 1) / T32_R_512 - t32_j0(512, T32_R_512, T32_NP_28);
+static_assert(T32_MFMA_NW == 21 && T32_R_512 * t32_j0(512, T32_R_512, T32_NP_28) + 8 * hm::C32B_COLS == 2 * 512, "72 byte columns from bit 448 reach bit 1024");
+static constexpr size_t T32_MFMA_MIN_WG = 8 * 2048;
+static bool t32_mfma_shape(bool generic, int logQ, int S, int NP) { return !generic && logQ == 512 && S == 0 && NP >= 32 && NP + 2 <= hm::C32B_SLOTS; }
+// The redo list of a fast pass, behind the flags in workspace slot 6: word 0 counts the flagged workgroups, their indices follow from word
+// T32_LIST_HDR.  More than T32_LIST_CAP flagged workgroups (crafted inputs only: about one in three launches of 1024 products flags one) are
+// counted but not listed, and the redo pass then walks the flags instead.
+static constexpr u32 T32_LIST_HDR = 4, T32_LIST_CAP = 4092, T32_REDO_GRID = 256;
+__device__ __forceinline__ void t32_flag(unsigned char* __restrict__ flags, u32* __restrict__ list, u32 wg, int any) {
+  flags[wg] = any ? 1 : 0;
+  if (any) {
+    const u32 at = atomicAdd(list, 1u);
+    if (at < T32_LIST_CAP) list[T32_LIST_HDR + at] = wg;
+  }
+}
+__global__ void t32_list_clear_kernel(u32* __restrict__ list) { if (threadIdx.x == 0) list[0] = 0; }
 
 struct T32Plan { int NP = 0; bool generic = false; };
 // The number of primes the tensor half needs (0: this shape does not run through it).
@@ -352,6 +373,14 @@ static int t32_config(fhesi_ctx* ctx, u64 lift, int nlimbs, int logQ, i64 gmax, 
     delete c;
     FHESI_FAIL("tensor32: table upload failed");
   }
+  if (t32_mfma_shape(pl.generic, logQ, S, NP)) {
+    // the same window of the same table rows as balanced bytes (crt32_bytes.h): the matrix-core form of the fast pass
+    const hm::Crt32Bytes bt = hm::crt32_bytes_build(Mw.data(), NP, WT, R, t32_j0(512, T32_R_512, T32_NP_28), T32_MFMA_NW);
+    if (!up((void**)&c->d_bytes, bt.aop.data(), bt.aop.size() * 4)) {
+      delete c;
+      FHESI_FAIL("tensor32: table upload failed");
+    }
+  }
   x->cfgs.push_back(c);
   *out = c;
   return 0;
@@ -546,10 +575,10 @@ __global__ void __launch_bounds__(256) tensor_sum32_kernel(const u32* __restrict
 // S = 0: the rows are y_i = x (M / p_i)^-1 mod p_i already (T32_ROWS_CRT, below p: the inverse transform's closing constants), cinv is not read.
 // S = 1: the rows are the two sub-inverses of 2^15-point rows; coefficient j < 2^14 is (A_j + B_j) / 2, coefficient j + 2^14 is
 // (A_j - B_j) psi^-brv(1) / 2 -- the constants are folded into the CRT constant of the first multiplication.
+// crt32_scale_block: the 128 coefficients from 128 bx of polynomial poly, one per thread; returns the thread's undecided bit (fast pass).
 template <int LQ, bool EXACT, int R, int WT, int S>
-__global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict__ rows, i64 n, int NP, T32Primes pr, const Tw32* __restrict__ cinv,
-                                                           const u32* __restrict__ inv57, const u32* __restrict__ Mw, u64* __restrict__ out,
-                                                           unsigned char* __restrict__ flags, int wm /* 1: out as 32-bit WORD rows [npolys][LQ/32][n] (what the 32-bit digit loader reads whole lines of) */) {
+__device__ __forceinline__ int crt32_scale_block(const u32* __restrict__ rows, i64 n, int NP, const T32Primes& pr, const Tw32* __restrict__ cinv,
+                                                 const u32* __restrict__ inv57, const u32* __restrict__ Mw, u64* __restrict__ out, int wm, i64 poly, u32 bx) {
   static_assert((LQ & 63) == 0, "logQ a multiple of 64");
   constexpr int WU = (2 * LQ + R - 1) / R;            // words that reach below bit 2 logQ
   constexpr int NPMAX = R == 28 ? T32_NP_28 : T32_NP_26;
@@ -560,10 +589,7 @@ __global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict_
   static_assert(EXACT || ((u64)(NPMAX + 1) << 30) <= ((u64)1 << (LQ - T32_WIN - R * J0)), "dropped words stay below bit logQ - 28");
   static_assert(EXACT || ((u64)(NPMAX + 1) << 30) > ((u64)1 << (LQ - T32_WIN - R * (J0 + 1) < 0 ? 0 : LQ - T32_WIN - R * (J0 + 1))), "... and J0 is the largest such");
   static_assert(R * J0 <= LQ - 64, "the rounding limb is formed");
-  const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-  if (EXACT && !flags[wg]) return;
-  const i64 poly = blockIdx.y;
-  const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  const i64 j = (i64)bx * blockDim.x + threadIdx.x;
   const int hi = S ? (int)(j >> A32_LOGN) : 0;        // (uniform per workgroup)
   const u32* __restrict__ src = rows + poly * NP * n + (S ? (j & (A32_N - 1)) : j);
   u64 acc[NW];
@@ -617,9 +643,184 @@ __global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict_
     if (wm) { o32[(i64)(2 * i) * n] = (u32)v; o32[(i64)(2 * i + 1) * n] = (u32)(v >> 32); }
     else o[(i64)i * n] = v;
   }
-  if (!EXACT) {
+  return undecided;
+}
+// The fast pass (EXACT = false): grid (n / 128, npolys), one block per workgroup; a workgroup with an undecided coefficient sets its flag and
+// appends itself to the redo list (t32_flag).  The redo pass (EXACT = true): T32_REDO_GRID workgroups walk that list -- or, had it overflowed,
+// the flags of all npolys n / 128 blocks -- and form every word of the flagged blocks again.  (Until the list the redo pass was launched over
+// the fast pass's grid, 393 216 workgroups per 1024 products that read one flag byte each: 0.09 ms of a 30.4 ms step.)
+template <int LQ, bool EXACT, int R, int WT, int S>
+__global__ void __launch_bounds__(128) crt32_scale_kernel(const u32* __restrict__ rows, i64 n, int NP, T32Primes pr, const Tw32* __restrict__ cinv,
+                                                           const u32* __restrict__ inv57, const u32* __restrict__ Mw, u64* __restrict__ out,
+                                                           unsigned char* __restrict__ flags, u32* __restrict__ list, u32 npolys,
+                                                           int wm /* 1: out as 32-bit WORD rows [npolys][LQ/32][n] (what the 32-bit digit loader reads whole lines of) */) {
+  if constexpr (!EXACT) {
+    const u32 wg = blockIdx.y * gridDim.x + blockIdx.x;
+    const int undecided = crt32_scale_block<LQ, false, R, WT, S>(rows, n, NP, pr, cinv, inv57, Mw, out, wm, blockIdx.y, blockIdx.x);
     const int any = __syncthreads_or(undecided);
-    if (threadIdx.x == 0) flags[wg] = any ? 1 : 0;
+    if (threadIdx.x == 0) t32_flag(flags, list, wg, any);
+  } else {
+    const u32 gx = (u32)(n / 128), total = gx * npolys, cnt = list[0];
+    if (cnt <= T32_LIST_CAP) {
+      for (u32 k = blockIdx.x; k < cnt; k += gridDim.x) {
+        const u32 wg = list[T32_LIST_HDR + k];
+        crt32_scale_block<LQ, true, R, WT, S>(rows, n, NP, pr, cinv, inv57, Mw, out, wm, wg / gx, wg % gx);
+      }
+    } else {
+      for (u32 wg = blockIdx.x; wg < total; wg += gridDim.x)
+        if (flags[wg]) crt32_scale_block<LQ, true, R, WT, S>(rows, n, NP, pr, cinv, inv57, Mw, out, wm, wg / gx, wg % gx);
+    }
+  }
+}
+
+// The fast pass of crt32_scale_kernel<512, false, 28, 38, 0> on the int8 matrix cores (option crt32_mfma; tables and arithmetic: crt32_bytes.h).
+// Per coefficient the window F = sum_i y_i C_i + kappa C_kappa is a product of the residues' bytes with a constant matrix, 160 deep and 72 byte
+// columns wide: operand A holds the constants (rows = byte columns), operand B the residues (column = coefficient), fifteen
+// v_mfma_i32_32x32x32_i8 per 32 coefficients -- three row tiles by five depth steps -- instead of 770 64-bit multiply-adds per coefficient.
+//   * A wave takes 32 coefficients.  Lane l of half h = l / 32 loads, for coefficient l % 32, the residue words of primes 8 ks + 4 h + (0 .. 3)
+//     per depth step ks: each load instruction reads 128 contiguous bytes of two rows.  y ^ 0x80808080 are the signed bytes yb - 128; the
+//     constant slot NP + 1 (operand bytes 1, 0, 0, 0) makes up for the offset and for the bias the accumulators start at (crt32_bytes.h).
+//   * kappa is crt32_scale_kernel's value, bit for bit: the same sum of floors umulhi(y_i, inv57_i) over the primes (a u32 sum in any order),
+//     twenty per lane and one exchange between the half waves.  It then takes slot NP of the depth, a "residue" like the others.
+//   * The rows are mapped so that lanes 0-31 end with columns 0 .. 35 (bits 448 .. 735) of their coefficient in 36 accumulator registers and
+//     lanes 32-63 with columns 36 .. 71 (bits 736 .. 1023).  Every column sum is a positive number below 2^23, so two columns join in 32 bits,
+//     two such pairs in a (word, carry) pair, and one add-with-carry per word runs the carries through a lane's nine words.  The low half
+//     holds the rounding limb G (words 0, 1: bits 448 .. 511), decides `undecided` exactly as t32_undecided does, and hands its carry -- with
+//     the rounding carry, which runs through only when its seven output words are all ones -- to the high half: one more exchange and one
+//     more run of add-with-carry.  Each half stores whole 128-byte pieces of its 7 / 9 output word rows.
+//   * The same integer F mod 2^576 as the VALU kernel (the balanced bytes represent 256^a C_i exactly), so the same limbs, the same rounding and
+//     the same flags: the EXACT pass behind it is the unchanged one.
+// A workgroup is four waves = the 128 coefficients one flag stands for, and walks nblk consecutive blocks with the 60 registers of A loaded once.
+typedef int t32_v16i __attribute__((ext_vector_type(16)));
+typedef int t32_v4i __attribute__((ext_vector_type(4)));
+template <int LQ>
+__global__ void __launch_bounds__(256, 2) crt32_mfma_kernel(const u32* __restrict__ rows, int NP, const u32* __restrict__ inv57, const u32* __restrict__ bytes,
+                                                             u32* __restrict__ out32, unsigned char* __restrict__ flags, u32* __restrict__ list, u32 nwg, u32 nblk, int wm) {
+  static_assert(LQ == 512, "the compiled window: 72 byte columns from bit 448");
+  constexpr u32 n = A32_N;
+  constexpr int KS = hm::C32B_KSTEPS, NT = hm::C32B_TILES, NWD = hm::C32B_HALF / 4;      // 9 words per lane
+  const int lane = threadIdx.x & 63, h = lane >> 5;
+  const u32 jw = (threadIdx.x >> 6) * 32 + (lane & 31);          // coefficient within the block
+  t32_v4i A[NT * KS];
+  {
+    const t32_v4i* __restrict__ ap = reinterpret_cast<const t32_v4i*>(bytes);
+#pragma unroll
+    for (int i = 0; i < NT * KS; ++i) A[i] = ap[i * 64 + lane];
+  }
+  t32_v16i bias;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) bias[r] = hm::C32B_BIAS;
+  asm volatile("" : "+v"(bias));                                  // (sixteen registers for the whole loop, not sixteen moves per tile)
+  u32 iv[KS][4];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { const int s = ks * 8 + h * 4 + t; iv[ks][t] = s < NP ? inv57[s] : 0u; }
+  // lane offsets of the loads: the half wave's share of the row index goes into the offset, the rest is wave-uniform.  The last depth step holds
+  // the slots from 32: beyond the primes a lane reads row NP - 1 (a valid address) and drops the value.
+  // (buffer loads and stores: a descriptor per block -- the polynomial's rows from the block's first coefficient, range-checked -- with the row as
+  // the scalar offset and ONE 32-bit register per lane; as pointers the compiler forms a 64-bit address per row in vector registers)
+  const u32 loff = ((u32)h * (4 * n) + jw) * 4;
+  u32 loff4[4];
+  bool prime4[4], kappa4[4], const4[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int s = 32 + h * 4 + t;
+    prime4[t] = s < NP; kappa4[t] = s == NP; const4[t] = s == NP + 1;
+    loff4[t] = ((u32)(s < NP ? s : NP - 1) * n + jw) * 4;
+  }
+  // the residues of block wg: twenty loads per lane, all in flight together
+  u32 y[KS][4];
+  auto load_block = [&](u32 wg) {
+    const i64 poly = wg / (n / 128);
+    const u32 j0 = (wg % (n / 128)) * 128;
+    const __amdgpu_buffer_rsrc_t src = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32*>(rows + poly * NP * n + j0), 0, (int)(((u32)NP * n - j0) * 4), 0x00020000);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)                                // (NP >= 32: the first four steps hold primes only)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) y[ks][t] = __builtin_amdgcn_raw_buffer_load_b32(src, loff, (ks * 8 + t) * n * 4, 0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) y[4][t] = __builtin_amdgcn_raw_buffer_load_b32(src, loff4[t], 0, 0);
+  };
+  // the workgroup's flag: one LDS word per block, three in rotation, so that one barrier per block is enough -- word (b + 2) % 3 is cleared by
+  // thread 0 behind barrier b (it last read it behind barrier b - 1) and written by the waves of block b + 2, which thread 0 lets through
+  // barrier b + 1 only after that.  (The barrier is a bare s_barrier behind the LDS write: nothing here waits for the block's stores.)
+  __shared__ u32 s_any[3];
+  if (threadIdx.x < 3) s_any[threadIdx.x] = 0;
+  __syncthreads();
+  const u32 wg0 = blockIdx.x * nblk;
+  const u32 nb = wg0 < nwg ? (nwg - wg0 < nblk ? nwg - wg0 : nblk) : 0u;
+  if (nb) load_block(wg0);
+  for (u32 b = 0; b < nb; ++b) {
+    const u32 wg = wg0 + b;
+    const i64 poly = wg / (n / 128);
+    const u32 j0 = (wg % (n / 128)) * 128;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) y[4][t] = prime4[t] ? y[4][t] : 0u;
+    u32 fsum = 0;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) fsum += __umulhi(y[ks][t], iv[ks][t]);      // (y / p) 2^25, low by less than one unit; 0 beyond the primes
+    fsum += (u32)__shfl_xor((int)fsum, 32);
+    const u32 kappa = (fsum + (1u << 24)) >> 25;
+    t32_v4i B[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) B[ks][t] = (int)(y[ks][t] ^ 0x80808080u);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) B[4][t] = const4[t] ? 1 : (kappa4[t] ? (int)(kappa ^ 0x80808080u) : B[4][t]);
+    if (b + 1 < nb) load_block(wg + 1);                  // (the next block's residues travel while this one is worked on: y is dead from here)
+    t32_v16i acc[NT];
+#pragma unroll
+    for (int tl = 0; tl < NT; ++tl) {
+      acc[tl] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[tl * KS], B[0], bias, 0, 0, 0);
+#pragma unroll
+      for (int ks = 1; ks < KS; ++ks) acc[tl] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[tl * KS + ks], B[ks], acc[tl], 0, 0, 0);
+    }
+    // word w = columns 4 w .. 4 w + 3 of this half: T[w] + 2^32 H[w] with H below 2^16; then W[w] = T[w] + H[w - 1] + carry
+    u32 W[NWD];
+    u32 Hp = 0, cy = 0;
+#pragma unroll
+    for (int w = 0; w < NWD; ++w) {
+      const int q = 4 * w;
+      const u32 lo = (u32)acc[q >> 4][q & 15] + ((u32)acc[(q + 1) >> 4][(q + 1) & 15] << 8);          // below 2^23 * 257 < 2^32
+      const u32 hi2 = (u32)acc[(q + 2) >> 4][(q + 2) & 15] + ((u32)acc[(q + 3) >> 4][(q + 3) & 15] << 8);
+      const u64 v = (u64)lo + ((u64)hi2 << 16);
+      W[w] = __builtin_addc((u32)v, Hp, cy, &cy);
+      Hp = (u32)(v >> 32);
+    }
+    const u64 G = ((u64)W[1] << 32) | W[0];              // bits 448 .. 511 (the low half's; the high half's value is not used)
+    const int undecided = h ? 0 : t32_undecided(G);
+    const u32 rnd = h ? 0u : W[1] >> 31;                  // round half up: + bit 511
+    const u32 ones = W[2] & W[3] & W[4] & W[5] & W[6] & W[7] & W[8];
+    const u32 cout = Hp + cy + ((rnd && ones == 0xffffffffu) ? 1u : 0u);
+    const u32 cswap = (u32)__shfl_xor((int)cout, 32);    // (every lane takes part: an exchange inside `h ? ... : 0` would run with the low half switched off and read nothing from it)
+    const u32 cin = h ? cswap : 0u;
+    cy = 0;
+#pragma unroll
+    for (int w = 0; w < NWD; ++w) W[w] = __builtin_addc(W[w], w == 0 ? cin : (w == 2 ? rnd : 0u), cy, &cy);
+    // output word ow of the coefficient: the low half's words 2 .. 8 are 0 .. 6, the high half's 0 .. 8 are 7 .. 15
+    if (wm) {
+      const __amdgpu_buffer_rsrc_t o = __builtin_amdgcn_make_buffer_rsrc(out32 + poly * (LQ / 32) * n + j0, 0, (int)(((LQ / 32) * n - j0) * 4), 0x00020000);
+      const u32 soff = ((u32)h * (9 * n) + jw) * 4;
+#pragma unroll
+      for (int w = 2; w < NWD; ++w) __builtin_amdgcn_raw_buffer_store_b32(W[w], o, soff, (w - 2) * n * 4, 0);
+      if (h) { __builtin_amdgcn_raw_buffer_store_b32(W[0], o, jw * 4, 7 * n * 4, 0); __builtin_amdgcn_raw_buffer_store_b32(W[1], o, jw * 4, 8 * n * 4, 0); }
+    } else {
+#pragma unroll
+      for (int w = 0; w < NWD; ++w) {
+        const int ow = h ? 7 + w : w - 2;
+        if (ow >= 0) out32[((poly * (LQ / 64) + (ow >> 1)) * n + j0 + jw) * 2 + (ow & 1)] = W[w];
+      }
+    }
+    if (undecided) atomicOr(&s_any[b % 3], 1u);                  // (LDS atomics: the words are read and cleared the same way, behind the barrier)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (threadIdx.x == 0) {
+      t32_flag(flags, list, wg, (int)atomicOr(&s_any[b % 3], 0u));
+      atomicAnd(&s_any[(b + 2) % 3], 0u);
+    }
   }
 }
 
@@ -833,13 +1034,31 @@ static int t32_launch_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i6
   const i64 n = (i64)A32_N << S;
   const dim3 grid((unsigned)(n / 128), (unsigned)npolys);
   void* d_fl;
-  FHESI_TRY(ws_reserve(ctx, 6, (size_t)grid.x * grid.y, &d_fl));          // (per lane, like every workspace slot)
+  // flags, then the redo list (t32_flag): per lane, like every workspace slot, so two lanes keep separate flags and separate lists
+  const size_t nwg = (size_t)grid.x * grid.y, fl_bytes = (nwg + 15) & ~(size_t)15;
+  if (nwg > 0x7fffffff) FHESI_FAIL("tensor32: too many rows per launch");
+  FHESI_TRY(ws_reserve(ctx, 6, fl_bytes + (size_t)(T32_LIST_HDR + T32_LIST_CAP) * 4, &d_fl));
   unsigned char* fl = (unsigned char*)d_fl;
-  PROF_KERNEL(ctx, PROF_CRT, (crt32_scale_kernel<LQ, false, R, WT, S>));
-  crt32_scale_kernel<LQ, false, R, WT, S><<<grid, 128, 0, ctx->stream>>>(d_t, n, c->NP, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, wm ? 1 : 0);
+  u32* list = reinterpret_cast<u32*>(fl + fl_bytes);
+  t32_list_clear_kernel<<<1, 64, 0, ctx->stream>>>(list);          // (a kernel, not a memset: nothing here may stop the stream)
+  // The matrix-core form pays 60 KB of operand loads per workgroup before its first coefficient, so a workgroup walks up to 32 blocks -- as many
+  // as leave 2048 workgroups -- and launches below T32_MFMA_MIN_WG blocks (128 polynomials: 43 products) keep the VALU kernel, whose
+  // workgroups start at once.  crt32_mfma = 2 takes the matrix cores at any size (tests, A/B).
+  bool mfma = false;
+  if constexpr (LQ == 512 && S == 0) mfma = c->d_bytes != nullptr && (ctx->opt.crt32_mfma >= 2 || (ctx->opt.crt32_mfma == 1 && nwg >= T32_MFMA_MIN_WG));
+  if (mfma) {
+    if constexpr (LQ == 512 && S == 0) {
+      const u32 nblk = nwg >= 32 * 2048 ? 32u : (nwg >= 2 * 2048 ? (u32)(nwg / 2048) : 1u);
+      PROF_KERNEL(ctx, PROF_CRT, (crt32_mfma_kernel<LQ>));
+      crt32_mfma_kernel<LQ><<<(unsigned)((nwg + nblk - 1) / nblk), 256, 0, ctx->stream>>>(d_t, c->NP, c->d_inv57, c->d_bytes, reinterpret_cast<u32*>(d_parts), fl, list, (u32)nwg, nblk, wm ? 1 : 0);
+    }
+  } else {
+    PROF_KERNEL(ctx, PROF_CRT, (crt32_scale_kernel<LQ, false, R, WT, S>));
+    crt32_scale_kernel<LQ, false, R, WT, S><<<grid, 128, 0, ctx->stream>>>(d_t, n, c->NP, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, list, (u32)npolys, wm ? 1 : 0);
+  }
   HIP_TRY(hipGetLastError());
   if (!ctx->opt.crt_skip_cleanup) {
-    crt32_scale_kernel<LQ, true, R, WT, S><<<grid, 128, 0, ctx->stream>>>(d_t, n, c->NP, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, wm ? 1 : 0);
+    crt32_scale_kernel<LQ, true, R, WT, S><<<T32_REDO_GRID, 128, 0, ctx->stream>>>(d_t, n, c->NP, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, list, (u32)npolys, wm ? 1 : 0);
     HIP_TRY(hipGetLastError());
   }
   return 0;
