@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "fhesi_ct_noise_batch", "fhesi_decrypt_noise_batch", "fhesi_ct_noise_int_batch",
     "fhesi_ksk_hoist", "fhesi_ct_rotations_dev", "fhesi_ct_matvec_dev",
     "fhesi_ct_rot_sum_dev", "fhesi_matvec_bsgs_plan", "fhesi_ct_matvec_bsgs_dev",
+    "fhesi_linear_plan", "fhesi_linear_create", "fhesi_linear_create_dev", "fhesi_linear_free", "fhesi_linear_info", "fhesi_linear_diagonals",
+    "fhesi_ct_rot_fold_dev", "fhesi_ct_linear_dev",
 ]
 ROT_SUM_MAX_TERMS = 16   # FHESI_ROT_SUM_MAX_TERMS: the terms one launch of the rotated-sum kernel takes (more terms chain launches)
 ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
@@ -86,6 +88,7 @@ def build_library(force: bool = False) -> str:
 
 _lib = None
 _vp, _i32, _i64, _u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
+_byref = C.byref         # (for functions whose parameters are named R and C, as the layers are)
 
 
 def _load():
@@ -246,6 +249,14 @@ def _load():
         "fhesi_ct_rot_sum_dev": [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp],
         "fhesi_matvec_bsgs_plan": [_i64, _vp, _vp],
         "fhesi_ct_matvec_bsgs_dev": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_linear_plan": [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_linear_create": [_vp, _vp, _i64, _i64, _vp, _i32, _vp],
+        "fhesi_linear_create_dev": [_vp, _vp, _i64, _i64, _vp, _i32, _vp],
+        "fhesi_linear_free": [_vp],
+        "fhesi_linear_info": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_linear_diagonals": [_vp, _vp, _i64, _i64, _i32, _vp],
+        "fhesi_ct_rot_fold_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_ct_linear_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -598,6 +609,13 @@ class Context:
         hg, kc = self._hoisted_args(giant_hoisted, kg)
         _ck(_load().fhesi_ct_matvec_bsgs_dev(self.h, hb, _p(ka), len(ka), hg, _p(kc), len(kc), nk, plain.h, logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
 
+    # ---- folds (fhesi_ct_rot_fold_dev): y <- y + rot_k(y) over a list of k, SumBatchedData on hoisted matrices
+    def ct_rot_fold_dev(self, hoisted, ks, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """y_0 = Reduce(src), y_{s+1} = Reduce(y_s + rot_ks[s](y_s)), out = the last y: per step the words of ct_rotations_dev with one matrix followed
+        by ct_add_dev.  hoisted[s]: the hoisted matrix of ks[s], or None with ks[s] = 1.  out may be src."""
+        hs, ka = self._hoisted_args(hoisted, ks)
+        _ck(_load().fhesi_ct_rot_fold_dev(self.h, hs, _p(ka) if len(ka) else None, len(ka), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+
     def release_host_staging(self):
         """hand back the pinned + device staging ring the host-buffer calls keep between uses"""
         _ck(_load().fhesi_host_stage_release(self.h))
@@ -608,6 +626,17 @@ def matvec_bsgs_plan(nk: int) -> tuple:
     b, g = _i32(0), _i32(0)
     _ck(_load().fhesi_matvec_bsgs_plan(int(nk), C.byref(b), C.byref(g)))
     return b.value, g.value
+
+
+def linear_plan(cols: int, R: int, C: int, baby: int = 0) -> dict:
+    """The plan of an R x C layer on rows of `cols` slots (fhesi_linear_plan): T = min(R, C) diagonals in G giant steps of B baby steps (baby = 0:
+    the B of matvec_bsgs_plan(T)), nfold = log2(C / R) folds for R < C, and the rotation amounts in the order Linear.apply takes their matrices --
+    babies 1 .. B - 1, giants B .. (G - 1) B, folds C/2 .. R.  Raises FhesiError naming the condition on a refused shape.  Touches no device."""
+    T, B, G, nfold = _i32(0), _i32(0), _i32(0), _i32(0)
+    _ck(_load().fhesi_linear_plan(int(cols), int(R), int(C), int(baby), _byref(T), _byref(B), _byref(G), _byref(nfold), None))
+    amounts = np.zeros(B.value - 1 + G.value - 1 + nfold.value, dtype=np.int64)
+    _ck(_load().fhesi_linear_plan(int(cols), int(R), int(C), int(baby), None, None, None, None, _p(amounts) if len(amounts) else None))
+    return {"T": T.value, "B": B.value, "G": G.value, "nfold": nfold.value, "amounts": [int(a) for a in amounts]}
 
 
 def plain_sum_bits(m: int, logQ: int, maxabs: int, terms: int) -> float:
@@ -631,6 +660,39 @@ class Plain:
     def close(self):
         if getattr(self, "h", None):
             _load().fhesi_plain_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Linear:
+    """One R x C layer y = M x + b on a slot space (fhesi_linear): its T = min(R, C) prepared diagonals, its replicated bias and its plan, resident in
+    HBM; made by SlotSpace.linear.  .amounts lists the rotation amounts whose hoisted matrices apply() takes: babies, giants, folds."""
+
+    def __init__(self, space: "SlotSpace", h):
+        self.space, self.ctx, self.h = space, space.ctx, h
+        R, Cc, T, B, G, nfold, bias = _i64(0), _i64(0), _i32(0), _i32(0), _i32(0), _i32(0), _i32(0)
+        _ck(_load().fhesi_linear_info(self.h, _byref(R), _byref(Cc), _byref(T), _byref(B), _byref(G), _byref(nfold), _byref(bias), None))
+        self.R, self.C, self.T, self.B, self.G, self.nfold, self.has_bias = R.value, Cc.value, T.value, B.value, G.value, nfold.value, bool(bias.value)
+        a = np.zeros(self.B - 1 + self.G - 1 + self.nfold, dtype=np.int64)
+        _ck(_load().fhesi_linear_info(self.h, None, None, None, None, None, None, None, _p(a) if len(a) else None))
+        self.amounts = [int(x) for x in a]
+
+    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[i] = the layer of src[i] (fhesi_ct_linear_dev): src holds x replicated with period C in every row (SlotSpace.replicate), out holds
+        M x + b with period R.  hoisted_by_amount: a mapping amount -> hoisted matrix of SlotSpace.rotation_k(amount) covering .amounts, or the
+        list of matrices in the order of .amounts.  The words of SlotSpace.matvec_bsgs, SlotSpace.fold and SlotSpace.ct_add_slots_dev in that order."""
+        hs = [hoisted_by_amount[a] for a in self.amounts] if hasattr(hoisted_by_amount, "keys") else list(hoisted_by_amount)
+        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
+        _ck(_load().fhesi_ct_linear_dev(self.ctx.h, self.h, arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+
+    def close(self):
+        if getattr(self, "h", None):
+            _load().fhesi_linear_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -807,6 +869,69 @@ class SlotSpace:
         """Ciphertext += Plaintext(vals) on unscaled ciphertexts; vals [nv][nvals] slot values, nv = 1 (one constant for all) or count."""
         vals = np.ascontiguousarray(np.atleast_2d(vals), dtype=np.int64)
         _ck(_load().fhesi_ct_add_slots_dev(self.ctx.h, self.h, logQ, ct.ptr, nparts, nlimbs, count, _p(vals), vals.shape[1], int(only_usable), vals.shape[0]))
+
+    # ---- dense linear layers: y = M x + b for a matrix given as a matrix (fhesi_linear_*): the diagonals are made on the device
+    def fold(self, hoisted, amounts, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """y <- y + rotate(y, a) for a in amounts ("swap" included), out = the last y (Context.ct_rot_fold_dev with k = rotation_k(a)); out may be src.
+        Over cols/2 .. 1 and "swap" it leaves the sum of all slots in every slot."""
+        self.ctx.ct_rot_fold_dev(hoisted, [self.rotation_k(a) for a in amounts], logQ, src, nlimbs, count, out, decomp_bytes)
+
+    def replicate(self, x, C: int) -> np.ndarray:
+        """x [..][rows][C] (or [..][C] on a one-row space) -> slot values [..][total]: row r holds x_r with period C, the input layout of a layer with
+        C columns.  C must divide the row.  Host only."""
+        rows, cols = max(self.rows, 1), self.total // max(self.rows, 1)
+        if C < 1 or cols % C:
+            raise ValueError(f"replicate: period {C} does not divide the row of {cols} slots")
+        x = np.asarray(x)
+        lead = x.shape[:-2] if rows == 2 else x.shape[:-1]
+        if x.shape[len(lead):] not in ((rows, C), (C,) if rows == 1 else None):
+            raise ValueError(f"replicate: values of shape {x.shape}, a plaintext takes [{rows}][{C}]")
+        v = x.reshape(lead + (rows, C))
+        return np.ascontiguousarray(np.tile(v, cols // C).reshape(lead + (self.total,)))
+
+    @staticmethod
+    def _device_words(a, what: str):
+        """a tensor in HBM (anything with data_ptr(), shape, and int64 elements: a torch tensor) -> (address, shape)"""
+        if not hasattr(a, "data_ptr") or "int64" not in str(getattr(a, "dtype", "")) or not a.is_contiguous():
+            raise ValueError(f"linear: device=True takes {what} as a contiguous int64 tensor in HBM")
+        return _vp(a.data_ptr()), tuple(a.shape)
+
+    def linear(self, M, bias=None, baby: int = 0, device: bool = False) -> Linear:
+        """The layer y = M x + b for M [R][C], bias [R] or None, any int64 (reduced modulo p on the device).  device=True: M and bias are int64 tensors
+        in HBM (torch tensors), read where they are.  baby: the baby step, 0 for the planner's.  Admitted shapes: linear_plan."""
+        h = _vp()
+        if device:
+            mp, shape = self._device_words(M, "the matrix")
+            if len(shape) != 2:
+                raise ValueError("linear: the matrix is [R][C]")
+            bp = None
+            if bias is not None:
+                bp, bshape = self._device_words(bias, "the bias")
+                if bshape != (shape[0],):
+                    raise ValueError(f"linear: a bias of shape {bshape} for {shape[0]} rows")
+            _ck(_load().fhesi_linear_create_dev(self.h, mp, shape[0], shape[1], bp, int(baby), _byref(h)))
+            return Linear(self, h)
+        M = np.ascontiguousarray(M, dtype=np.int64)
+        if M.ndim != 2:
+            raise ValueError("linear: the matrix is [R][C]")
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(bias, dtype=np.int64)
+            if b.shape != (M.shape[0],):
+                raise ValueError(f"linear: a bias of shape {b.shape} for {M.shape[0]} rows")
+        _ck(_load().fhesi_linear_create(self.h, _p(M), M.shape[0], M.shape[1], _p(b) if b is not None else None, int(baby), _byref(h)))
+        return Linear(self, h)
+
+    def linear_diagonals(self, M, baby: int = 0) -> np.ndarray:
+        """The prepared slot vectors of the layer M [R][C]: [T][total], row g B + j the diagonal g B + j rotated back by g B (fhesi_linear_diagonals) --
+        what SlotSpace.linear embeds, downloaded."""
+        M = np.ascontiguousarray(M, dtype=np.int64)
+        if M.ndim != 2:
+            raise ValueError("linear_diagonals: the matrix is [R][C]")
+        plan = linear_plan(self.total // max(self.rows, 1), M.shape[0], M.shape[1], baby)
+        vals = np.zeros((plan["T"], self.total), dtype=np.int64)
+        _ck(_load().fhesi_linear_diagonals(self.h, _p(M), M.shape[0], M.shape[1], int(baby), _p(vals)))
+        return vals
 
 
 def slots_basis_plan(m: int, bits: int, prime_bits: int, generator: int) -> dict:
@@ -1005,6 +1130,16 @@ class SlotBasis:
         words = 2 * self.ctx.phim * nlimbs * 8
         for c in range(self.k):
             self.channel(c).matvec_bsgs(baby, giant, B, plains[c], logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
+
+    def linear(self, M, bias=None, baby: int = 0) -> list:
+        """SlotSpace.linear per channel: the k handles of the layer M [R][C], bias [R] (integers of any size), channel c holding them modulo primes[c]."""
+        return [self.channel(c).linear(self._residues(M, c), None if bias is None else self._residues(bias, c)[0], baby) for c in range(self.k)]
+
+    def linear_apply(self, layers, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """Linear.apply per channel (one key set serves every channel): src, out [k][count] logical ciphertexts, layers from SlotBasis.linear."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            layers[c].apply(hoisted_by_amount, logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
 
     def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nlimbs: int, count: int, vals):
         """Ciphertext += integers, per channel: ct [k][count] two-part ciphertexts, vals [nv][nvals] integers, nv = 1 or count."""

@@ -560,6 +560,106 @@ extern "C" int fhesi_ct_add_slots_dev(fhesi_ctx* c, fhesi_slots* s, int32_t logQ
   return 0;
 }
 
+// --------------------------------------------------------------------------------------------- dense linear layers
+// fhesi_linear (include/fhesi_hip.h).  The stage next to stage_msg_slots: the T prepared slot vectors w_t of an R x C layer [T][phi(m)] in the values
+// slot (workspace 9), written by linear_diag_kernel from the matrix where it is -- a host matrix is uploaded into the same slot, behind them.  Checks
+// its own arguments and plans the layer; nothing here synchronises.
+struct LinearPlan { int32_t T = 0, B = 0, G = 0, nfold = 0; std::vector<int64_t> amounts; };
+static int stage_linear_vals(fhesi_slots* s, const int64_t* M, bool on_dev, i64 R, i64 C, int32_t baby, const char* what, LinearPlan* plan, i64** d_vals) {
+  if (!s) FHESI_FAIL("%s: null plaintext space", what);
+  fhesi_ctx* c = s->ctx;
+  CHECK_CTX(c);
+  if (!M) FHESI_FAIL("%s: null matrix", what);
+  const i64 total = s->S.phim;
+  FHESI_TRY(fhesi_linear_plan(total / s->S.rows, R, C, baby, &plan->T, &plan->B, &plan->G, &plan->nfold, nullptr));
+  if (plan->T > 65535) FHESI_FAIL("%s: %d diagonals per handle, 1 .. 65535 are taken", what, plan->T);
+  plan->amounts.resize((size_t)(plan->B - 1 + plan->G - 1 + plan->nfold));
+  FHESI_TRY(fhesi_linear_plan(total / s->S.rows, R, C, baby, nullptr, nullptr, nullptr, nullptr, plan->amounts.data()));
+  const size_t nvals = (size_t)plan->T * total;
+  FHESI_TRY(ws_i64(c, 9, (nvals + (on_dev ? 0 : (size_t)R * C)) * 8, d_vals));
+  const i64* d_M = M;
+  if (!on_dev) {
+    HIP_TRY(hipMemcpyAsync(*d_vals + nvals, M, (size_t)R * C * 8, hipMemcpyHostToDevice, c->stream));
+    d_M = *d_vals + nvals;
+  }
+  return launch_linear_diag(c, s->S, d_M, R, C, plan->T, plan->B, *d_vals);
+}
+// b[i mod R] in every row: the diagonal of the R x 1 layer whose only column is the bias.  Before stage_linear_vals, which takes the values slot over.
+static int linear_bias_vals(fhesi_slots* s, const int64_t* bias, bool on_dev, i64 R, i64* d_bias) {
+  fhesi_ctx* c = s->ctx;
+  const i64* d_b = bias;
+  if (!on_dev) {
+    i64* up;
+    FHESI_TRY(upload_vals(c, bias, (size_t)R * 8, &up));
+    d_b = up;
+  }
+  return launch_linear_diag(c, s->S, d_b, R, 1, 1, 1, d_bias);
+}
+static int linear_create(fhesi_slots* s, const int64_t* M, const int64_t* bias, bool on_dev, i64 R, i64 C, int32_t baby, fhesi_linear** out) {
+  if (!out) FHESI_FAIL("linear_create: null output pointer");
+  *out = nullptr;
+  if (!s) FHESI_FAIL("linear_create: null plaintext space");
+  fhesi_ctx* c = s->ctx;
+  CHECK_CTX(c);
+  if (!M) FHESI_FAIL("linear_create: null matrix");
+  FHESI_TRY(fhesi_linear_plan(s->S.phim / s->S.rows, R, C, baby, nullptr, nullptr, nullptr, nullptr, nullptr));      // the shape, before anything is launched
+  i64* d_bias = nullptr;
+  if (bias) {
+    if (hipMalloc(&d_bias, (size_t)s->S.phim * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("linear_create: hipMalloc of %zu bytes failed", (size_t)s->S.phim * 8); }
+    if (const int rc = linear_bias_vals(s, bias, on_dev, R, d_bias)) { hipFree(d_bias); return rc; }
+  }
+  LinearPlan plan;
+  i64 *d_vals = nullptr, *d_msg = nullptr;
+  fhesi_plain* w = nullptr;
+  int rc = stage_linear_vals(s, M, on_dev, R, C, baby, "linear_create", &plan, &d_vals);
+  if (!rc) rc = msg_staging(c, plan.T, &d_msg);
+  if (!rc) rc = slots_embed_rows(s, d_vals, s->S.phim, false, plan.T, d_msg);
+  if (!rc) rc = plain_rows_dev(c, d_msg, plan.T, s->S.p - 1, s->S.p, &w);      // synchronises: a host matrix and bias are the caller's again
+  if (rc) { hipStreamSynchronize(c->stream); hipFree(d_bias); return rc; }
+  fhesi_linear* lin = new fhesi_linear();
+  lin->ctx = c; lin->slots = s; lin->R = R; lin->C = C;
+  lin->T = plan.T; lin->B = plan.B; lin->G = plan.G; lin->nfold = plan.nfold;
+  lin->amounts.assign(plan.amounts.begin(), plan.amounts.end());
+  lin->w = w; lin->d_bias = d_bias;
+  *out = lin;
+  return 0;
+}
+extern "C" int fhesi_linear_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, const int64_t* bias_host, int32_t baby, fhesi_linear** out) {
+  return linear_create(s, M_host, bias_host, false, R, C, baby, out);
+}
+extern "C" int fhesi_linear_create_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t C, const int64_t* bias_dev, int32_t baby, fhesi_linear** out) {
+  return linear_create(s, M_dev, bias_dev, true, R, C, baby, out);
+}
+extern "C" int fhesi_linear_free(fhesi_linear* lin) {
+  if (!lin) return 0;
+  fhesi_plain_free(lin->w);      // (synchronises; the one live handle the layer counts as)
+  hipFree(lin->d_bias);
+  delete lin;
+  return 0;
+}
+extern "C" int fhesi_linear_info(const fhesi_linear* lin, int64_t* R, int64_t* C, int32_t* T, int32_t* B, int32_t* G, int32_t* nfold, int32_t* has_bias, int64_t* amounts) {
+  if (!lin) FHESI_FAIL("null linear layer");
+  if (R) *R = lin->R;
+  if (C) *C = lin->C;
+  if (T) *T = lin->T;
+  if (B) *B = lin->B;
+  if (G) *G = lin->G;
+  if (nfold) *nfold = lin->nfold;
+  if (has_bias) *has_bias = lin->d_bias ? 1 : 0;
+  if (amounts) std::copy(lin->amounts.begin(), lin->amounts.end(), amounts);
+  return 0;
+}
+extern "C" int fhesi_linear_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int32_t baby, int64_t* vals_host) {
+  if (!vals_host) FHESI_FAIL("linear_diagonals: null output");
+  LinearPlan plan;
+  i64* d_vals = nullptr;
+  FHESI_TRY(stage_linear_vals(s, M_host, false, R, C, baby, "linear_diagonals", &plan, &d_vals));
+  fhesi_ctx* c = s->ctx;
+  HIP_TRY(hipMemcpyAsync(vals_host, d_vals, (size_t)plan.T * s->S.phim * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order
 static int keyswitch_init_impl(fhesi_ksk* k, const fhesi_dcrt* const* src, int32_t nsrc, const fhesi_dcrt* dst_t, int32_t logQ, int32_t decomp_bytes,
                                const uint64_t* a_host, int32_t nlimbs, const int64_t* err_host, bool seeded, u64 seed, u64 pub_seed, u64 first) {

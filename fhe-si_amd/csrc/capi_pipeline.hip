@@ -625,6 +625,123 @@ extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* ba
   return matvec_run(c, baby_hoisted, kb, B, giant_hoisted, kg, g_mode.data(), G, false, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
 }
 
+// --------------------------------------------------------------------------------------------- folds and dense linear layers
+// y[i] <- Reduce(y[i] + rot_ks[s](y[i])) for s = 0 .. nk-1, in place (include/fhesi_hip.h): per chunk of ciphertexts and step one key switch of y as it is
+// into workspace slot 14 (a copy where the step has no matrix: k = 1), then the rotated sum with base = out = y.  mode: the matrices' forms, their tables
+// built by the caller in front of any digit row.  Every argument checked by the caller.
+static int rot_fold_run(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, const int* mode, int32_t logQ, int32_t decomp_bytes, u64* y,
+                        int32_t nlimbs, int64_t count) {
+  if (!nk) return 0;
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  const i64 chunk = std::max<i64>(1, std::min<i64>(count, (i64)(4.0 * 1024 * 1024 * 1024 / ((double)ct_words * 8))));      // about 4 GiB of key-switched ciphertexts
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    u64* o = y + (size_t)done * ct_words;
+    void* d_pre;
+    FHESI_TRY(ws_reserve(c, 14, (size_t)cnt * ct_words * 8, &d_pre));
+    for (int s = 0; s < nk; ++s) {
+      if (!hoisted[s]) HIP_TRY(hipMemcpyAsync(d_pre, o, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));
+      else FHESI_TRY(key_switch_plain_run(c, hoisted[s], mode[s], logQ, decomp_bytes, o, nlimbs, cnt, (u64*)d_pre));
+      FHESI_TRY(rot_sum_run(c, ks + s, 1, logQ, o, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, o));
+    }
+  }
+  return 0;
+}
+static int key_switch_forms(fhesi_ctx* c, const fhesi_ksk* const* hoisted, int32_t nk, int32_t logQ, int32_t decomp_bytes, std::vector<int>* mode) {
+  mode->assign((size_t)nk, -1);
+  for (int t = 0; t < nk; ++t) if (hoisted[t]) FHESI_TRY(key_switch_form(c, hoisted[t], logQ, decomp_bytes, &(*mode)[t]));
+  return 0;
+}
+extern "C" int fhesi_ct_rot_fold_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                                     int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  FHESI_TRY(rotations_args(c, hoisted, ks, nk, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  if (!count) return 0;
+  if (!in || !out) FHESI_FAIL("ct_rot_fold: null argument");
+  const size_t bytes = (size_t)count * 2 * c->phim * nlimbs * 8;
+  if (in != out && ranges_overlap(in, bytes, out, bytes)) FHESI_FAIL("ct_rot_fold: out overlaps in without being in");
+  std::vector<int> mode;
+  FHESI_TRY(key_switch_forms(c, hoisted, nk, logQ, decomp_bytes, &mode));
+  // y_0 = Reduce(in): the copy, times one
+  if (in != out) HIP_TRY(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
+  FHESI_TRY(launch_ct_mul_long(c, (u64*)out, count * 2 * c->phim, nlimbs, logQ, 1));
+  return rot_fold_run(c, hoisted, ks, nk, mode.data(), logQ, decomp_bytes, (u64*)out, nlimbs, count);
+}
+
+// host only.  The amounts in the order fhesi_ct_linear_dev takes their matrices: babies, giants, folds
+extern "C" int fhesi_linear_plan(int64_t cols, int64_t R, int64_t C, int32_t baby, int32_t* T_out, int32_t* B_out, int32_t* G_out, int32_t* nfold_out, int64_t* amounts) {
+  if (cols < 1 || cols > ((i64)1 << 20)) FHESI_FAIL("linear_plan: a row of %lld slots outside [1, 2^20]", (long long)cols);
+  if (R < 1 || C < 1) FHESI_FAIL("linear_plan: a %lld x %lld matrix (both sizes at least 1)", (long long)R, (long long)C);
+  const i64 D = std::max(R, C), T = std::min(R, C);
+  if (D > cols) FHESI_FAIL("linear_plan: max(R, C) = %lld exceeds the row of %lld slots", (long long)D, (long long)cols);
+  if (cols % D) FHESI_FAIL("linear_plan: max(R, C) = %lld does not divide the row of %lld slots", (long long)D, (long long)cols);
+  if (D % T) FHESI_FAIL("linear_plan: min(R, C) = %lld does not divide max(R, C) = %lld", (long long)T, (long long)D);
+  int32_t nfold = 0;
+  if (R < C) {
+    const i64 q = C / R;
+    if (q & (q - 1)) FHESI_FAIL("linear_plan: C / R = %lld is not a power of two", (long long)q);
+    while (((i64)1 << nfold) < q) ++nfold;
+  }
+  if (baby < 0) FHESI_FAIL("linear_plan: %d baby steps", baby);
+  int32_t B = (int32_t)std::min<i64>(baby, T), G = 0;
+  if (!baby) FHESI_TRY(fhesi_matvec_bsgs_plan(T, &B, &G));
+  G = (int32_t)((T + B - 1) / B);
+  if (T_out) *T_out = (int32_t)T;
+  if (B_out) *B_out = B;
+  if (G_out) *G_out = G;
+  if (nfold_out) *nfold_out = nfold;
+  if (amounts) {
+    for (int j = 1; j < B; ++j) *amounts++ = j;
+    for (int g = 1; g < G; ++g) *amounts++ = (i64)g * B;
+    for (i64 a = C / 2; R < C && a >= R; a /= 2) *amounts++ = a;
+  }
+  return 0;
+}
+
+// out[i] = M in[i] + b on the slots (include/fhesi_hip.h): matvec_run with the layer's diagonals, the folds in place on out, the bias -- embedded into the
+// message staging slot once the sums' index lists in it are dead -- through launch_ct_add_const.  The words of fhesi_ct_matvec_bsgs_dev,
+// fhesi_ct_rot_fold_dev and fhesi_ct_add_slots_dev in that order.
+extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                                   int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  if (!lin) FHESI_FAIL("ct_linear: null linear layer");
+  if (lin->ctx != c) FHESI_FAIL("ct_linear: the linear layer belongs to another context");
+  const int B = lin->B, G = lin->G, nf = lin->nfold;
+  if (nh != B - 1 + G - 1 + nf) FHESI_FAIL("ct_linear: %d matrices, the layer takes %d (%d baby, %d giant and %d fold rotations)", nh, B - 1 + G - 1 + nf, B - 1, G - 1, nf);
+  if (nh && !hoisted) FHESI_FAIL("ct_linear: null argument");
+  // the identity in front of the babies and of the giants; k = g^amount mod m
+  std::vector<const fhesi_ksk*> hs((size_t)nh + 2, nullptr);
+  std::vector<int64_t> ks((size_t)nh + 2, 1);
+  for (int t = 0; t < nh; ++t) {
+    const size_t at = (size_t)t + (t < B - 1 ? 1 : 2);
+    hs[at] = hoisted[t];
+    ks[at] = (int64_t)hm::powmod(lin->slots->S.g, (u64)lin->amounts[(size_t)t], (u64)c->m);
+  }
+  const fhesi_ksk* const* hb = hs.data(), * const* hg = hb + B, * const* hf = hg + G;
+  const int64_t *kb = ks.data(), *kg = kb + B, *kf = kg + G;
+  FHESI_TRY(rotations_args(c, hb, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(rotations_args(c, hg, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(rotations_args(c, hf, kf, nf, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(matvec_args(c, "ct_linear", lin->w, lin->T, std::min(B, lin->T), logQ, in, nlimbs, count, out));
+  if (!count) return 0;
+  // every table before any digit row exists, as rotations_run builds its matrices'
+  std::vector<int> g_mode, f_mode;
+  FHESI_TRY(key_switch_forms(c, hg, G, logQ, decomp_bytes, &g_mode));
+  FHESI_TRY(key_switch_forms(c, hf, nf, logQ, decomp_bytes, &f_mode));
+  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, g_mode.data(), G, false, lin->T, lin->w, logQ, decomp_bytes, in, nlimbs, count, out));
+  FHESI_TRY(rot_fold_run(c, hf, kf, nf, f_mode.data(), logQ, decomp_bytes, (u64*)out, nlimbs, count));
+  if (!lin->d_bias) return 0;
+  const size_t n = (size_t)c->phim;
+  void* d_msg;
+  FHESI_TRY(ws_reserve(c, 5, n * 8, &d_msg));
+  FHESI_TRY(slots_embed_rows(lin->slots, lin->d_bias, c->phim, false, 1, (i64*)d_msg));
+  for (i64 done = 0; done < count; done += 65535) {
+    const i64 cnt = std::min<i64>(65535, count - done);
+    FHESI_TRY(launch_ct_add_const(c, (u64*)out + (size_t)done * 2 * n * nlimbs, (const i64*)d_msg, 1, 2, nlimbs, logQ, lin->slots->S.p, cnt));
+  }
+  return 0;
+}
+
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).
 // Every group a single product (a loop of `c *= d; ApplyKeySwitch(c)` recorded by the host mirror, fhesi_engine.h): the operands are
 // gathered into two batches and take the batch pipeline of fhesi_ct_mul_relin_batch_dev -- the tensor products formed in the loader

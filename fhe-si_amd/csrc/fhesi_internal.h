@@ -183,7 +183,9 @@ struct fhesi_ctx {
   //   built before them --, 10 the dot outputs of the matrices of one launch, 4 one rotation's key-switched ciphertexts in front of their automorphism;
   //   fhesi_ct_matvec_dev keeps the rotated ciphertexts of a chunk in 12 until fhesi_ct_plain_sum_dev has read them; fhesi_ct_matvec_bsgs_dev keeps the baby
   //   rotations there too, the inner sums of a chunk in 13 and the giants' key-switched ciphertexts in 14 -- neither the plaintext sum nor a key switch touches
-  //   those --, and the composed form of the rotated sum keeps one rotated term in 15)
+  //   those --, and the composed form of the rotated sum keeps one rotated term in 15; a linear layer's constructor writes its slot vectors -- and a host
+  //   matrix behind them -- into 9 and embeds them into 5 like any slot-valued stage; fhesi_ct_rot_fold_dev keeps a step's key-switched ciphertexts in 14, as
+  //   the giants do, and fhesi_ct_linear_dev embeds its bias into 5 behind the last fold, when the sums' index lists there are dead)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -414,6 +416,20 @@ double plain_sum_bits(i64 n, bool pow2, bool two_term, int logQ, u64 maxabs, i64
 constexpr int kPlainSumFold = 64;      // terms an accumulator of plain_sum_kernel takes between folds (derivation at the kernel)
 int launch_plain_sum(fhesi_ctx* ctx, const u64* d_ca /* [nu][2][L][n] */, const u64* d_w /* [nw][L][n] */, const int* d_slot_a, const int* d_slot_w, const int* d_seg,
                      i64 ngroups, bool accumulate, u64* d_out /* [ngroups][2][L][n] */, double nterms);
+
+// --------------------------------------------------------------------------------- dense linear layers (capi_ct.hip, capi_pipeline.hip, kernels_slots.hip)
+// One R x C layer on a slot space (include/fhesi_hip.h): the T = min(R, C) prepared diagonals, the replicated bias, the plan
+struct fhesi_linear {
+  fhesi_ctx* ctx = nullptr;
+  fhesi_slots* slots = nullptr;        // the space the layer was made on, borrowed: embeds the bias in front of its addition
+  i64 R = 0, C = 0;
+  int T = 0, B = 0, G = 0, nfold = 0;
+  std::vector<i64> amounts;            // babies 1 .. B - 1, giants B .. (G - 1) B, folds C/2 .. R: the order of the apply call's matrices
+  fhesi_plain* w = nullptr;            // w_t = rot_{-gB}(e_t), t = g B + j
+  i64* d_bias = nullptr;               // [phim] slot values b[i mod R] in [0, p), every row alike; null without a bias
+};
+// d_out[t][s] = w_t at slot s = (row, i), reduced into [0, p): t < T slot vectors of S.phim values, M [R][C] int64 in HBM (linear_diag_kernel, kernels_slots.hip)
+int launch_linear_diag(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_M, i64 R, i64 C, int T, int B, i64* d_out /* [T][phim] */);
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

@@ -547,6 +547,53 @@ int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* ctx, const fhesi_ksk* const* baby_hoiste
                              const int64_t* kg, int32_t G, int32_t nk, const fhesi_plain* w /* nw >= nk, term t = g*B + j */, int32_t logQ,
                              int32_t decomp_bytes, const uint64_t* in_dev, int32_t nlimbs, int64_t count, uint64_t* out_dev);
 
+/* ---- dense linear layers on packed slots: y = M x + b for an R x C matrix given as a matrix (capi_ct.hip, capi_pipeline.hip, linear_diag_kernel in
+ * kernels_slots.hip).  The space has rows (1 or 2) rows of cols slots, rot_t moves every row t slots to the left.  D = max(R, C),
+ * T = min(R, C).  ADMITTED: R, C >= 1, T | D, D | cols, and for R < C the ratio C / R a power of two.
+ *   input      slot (r, i) = x_r[i mod C]: a vector of length C per row, replicated with period C
+ *   diagonals  e_t[i] = M[(i mod D) mod R][((i mod D) + t) mod C], t < T, alike in every row, period D
+ *   prepared   w_t = rot_{-gB}(e_t) for t = g B + j, j < B:  w_t[i] = e_t[(i - g B) mod D]
+ *   product    y = sum_g rot_{gB}( sum_j w_{gB+j} (*) rot_j(x) )                                    (fhesi_ct_matvec_bsgs_dev)
+ *   folds      only for R < C: for a = C/2, C/4, .., R:  y <- y + rot_a(y)                          (fhesi_ct_rot_fold_dev)
+ *   bias       y <- y + (b[i mod R])                                                                (fhesi_ct_add_slots_dev)
+ *   result     slot (r, i) = (M x_r + b)[i mod R], period R: the replicated input of a following layer with C' = R.
+ * R diagonals where the matrix padded to a D x D square takes D: B + G - 2 + log2(C / R) key switches instead of about 2 sqrt(D).
+ *
+ * fhesi_linear_plan (host only): T, B (baby = 0: what fhesi_matvec_bsgs_plan(T) picks; otherwise min(baby, T)), G = ceil(T / B), nfold = log2(C / R) for
+ *   R < C and 0 otherwise, and -- amounts != NULL -- the B - 1 + G - 1 + nfold rotation amounts in the order every call below takes their matrices:
+ *   the babies 1 .. B - 1, the giants B, 2B, .., (G - 1) B, the folds C/2 .. R.  An amount two lists share is listed once per use.  Any output may be
+ *   NULL.  REFUSED with the condition named: a size below 1, D above cols, D not dividing cols, T not dividing D, C / R not a power of two, baby < 0.
+ * fhesi_linear_create / _create_dev: the handle of one layer on the space s -- M [R][C] row-major and bias [R] (or NULL) any int64, reduced into [0, p)
+ *   on the device; _dev takes both in HBM, where they stay (the call synchronises).  linear_diag_kernel writes the T slot vectors w_t, the embedding and
+ *   the transforms of fhesi_plain_create_slots follow: the handle's plaintext IS fhesi_plain_create_slots(w, only_usable = 0).  The handle owns that
+ *   plaintext, the replicated bias as slot values and the plan; it counts as a live handle of the context and borrows s, which must outlive it.
+ *   T <= 65535 as for any fhesi_plain.  fhesi_linear_info: shape, plan, whether it has a bias, the amounts (any pointer may be NULL).
+ * fhesi_linear_diagonals: the same stage without a handle -- vals_host [T][phi(m)] receives the slot vectors w_t.
+ * fhesi_ct_rot_fold_dev: y_0 = Reduce(in), y_{s+1} = Reduce(y_s + rot_ks[s](y_s)), out = y_nk -- SumBatchedData on hoisted matrices.  rot_k exactly what
+ *   fhesi_ct_rotations_dev gives for (hoisted[s], ks[s]).  DEFINED as, and word for word equal to, per step fhesi_ct_rotations_dev with nk = 1 followed
+ *   by fhesi_ct_add_dev.  Per step and chunk of ciphertexts one key switch into the workspace and one rotated sum with base y_s.  out_dev may be in_dev
+ *   (the same address; any other overlap is refused).  REFUSED as fhesi_ct_rotations_dev refuses.
+ * fhesi_ct_linear_dev: out[i] = the layer of in[i].  hoisted [nh]: the matrices of the amounts in fhesi_linear_info's order (k = g^amount mod m), NULL
+ *   only where that k is 1.  DEFINED as, and word for word equal to, fhesi_ct_matvec_bsgs_dev with the handle's plaintext, fhesi_ct_rot_fold_dev over
+ *   the fold amounts, fhesi_ct_add_slots_dev with the replicated bias.  The capacity rule of fhesi_ct_plain_sum_dev is checked with min(B, T) terms
+ *   before anything is launched.  REFUSED on the host with the condition named, the context usable afterwards: nh other than the plan's count; a
+ *   matrix not hoisted or hoisted for another k; a handle or a matrix of another context; out overlapping in; what fhesi_ct_matvec_bsgs_dev refuses. */
+typedef struct fhesi_linear fhesi_linear; /* one R x C layer on a slot space: its prepared diagonals, its replicated bias and its plan */
+int fhesi_linear_plan(int64_t cols, int64_t R, int64_t C, int32_t baby /* 0: the planner's */, int32_t* T, int32_t* B, int32_t* G, int32_t* nfold,
+                      int64_t* amounts /* [B - 1 + G - 1 + nfold] or NULL */);
+int fhesi_linear_create(fhesi_slots* s, const int64_t* M_host /* [R][C] */, int64_t R, int64_t C, const int64_t* bias_host /* [R] or NULL */, int32_t baby,
+                        fhesi_linear** out);
+int fhesi_linear_create_dev(fhesi_slots* s, const int64_t* M_dev /* [R][C] */, int64_t R, int64_t C, const int64_t* bias_dev /* [R] or NULL */, int32_t baby,
+                            fhesi_linear** out);
+int fhesi_linear_free(fhesi_linear* lin);
+int fhesi_linear_info(const fhesi_linear* lin, int64_t* R, int64_t* C, int32_t* T, int32_t* B, int32_t* G, int32_t* nfold, int32_t* has_bias,
+                      int64_t* amounts /* [B - 1 + G - 1 + nfold] or NULL */);
+int fhesi_linear_diagonals(fhesi_slots* s, const int64_t* M_host /* [R][C] */, int64_t R, int64_t C, int32_t baby, int64_t* vals_host /* [T][phi(m)] */);
+int fhesi_ct_rot_fold_dev(fhesi_ctx* ctx, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int32_t logQ, int32_t decomp_bytes,
+                          const uint64_t* in_dev /* [count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count, uint64_t* out_dev);
+int fhesi_ct_linear_dev(fhesi_ctx* ctx, const fhesi_linear* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
+                        const uint64_t* in_dev /* [count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count, uint64_t* out_dev);
+
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
  * fhesi_comm_init_all: one process, one host thread per GPU -- ncclCommInitAll over `devices`, comms_out[r] is rank r's handle.
