@@ -291,14 +291,10 @@ static inline bool prof_timed_class(int cls) { return (cls >= 0 && cls < PROF_NC
 
 // --------------------------------------------------------------------------------- host number theory (hostmath.cpp)
 namespace hm {
-u64 mulmod(u64 a, u64 b, u64 q);
-u64 powmod(u64 a, u64 e, u64 q);
-u64 invmod(u64 a, u64 q);              // q prime
-bool is_prime(u64 n);
+// (mulmod, powmod, invmod, is_prime, brv: defined inline in hostbig.h)
 i64 prime_power_ring(i64 m, int* k);   // q when m = q^k or 2 q^k (q an odd prime, k >= 1), else 0
 u64 shoup(u64 w, u64 q);
 u64 shoup63(u64 w, u64 q);             // floor(w 2^63 / q)
-u64 brv(u64 x, int bits);
 int ilog2_ceil(i64 n);
 std::vector<int> zms_idx(i64 m, i64* phim);
 std::vector<i64> cyclotomic(i64 m);

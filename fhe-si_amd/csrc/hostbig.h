@@ -10,6 +10,45 @@ typedef uint64_t bn_limb;
 typedef unsigned __int128 bn_wide;
 typedef std::vector<bn_limb> Big;
 
+// ---- word-sized number theory: the one definition (fhesi_internal.h and hostmath.cpp take it from here)
+inline bn_limb mulmod(bn_limb a, bn_limb b, bn_limb q) { return (bn_limb)(((bn_wide)a * b) % q); }
+inline bn_limb powmod(bn_limb a, bn_limb e, bn_limb q) {
+  bn_limb r = 1 % q;
+  a %= q;
+  for (; e; e >>= 1) {
+    if (e & 1) r = mulmod(r, a, q);
+    a = mulmod(a, a, q);
+  }
+  return r;
+}
+inline bn_limb invmod(bn_limb a, bn_limb q) { return powmod(a % q, q - 2, q); }      // q prime
+inline bool is_prime(bn_limb n) {
+  static const bn_limb bases[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};   // deterministic below 3.3e24
+  if (n < 2) return false;
+  for (bn_limb p : bases)
+    if (n % p == 0) return n == p;
+  bn_limb d = n - 1;
+  int s = 0;
+  while (!(d & 1)) { d >>= 1; ++s; }
+  for (bn_limb a : bases) {
+    bn_limb x = powmod(a, d, n);
+    if (x == 1 || x == n - 1) continue;
+    bool composite = true;
+    for (int r = 1; r < s && composite; ++r) {
+      x = mulmod(x, x, n);
+      if (x == n - 1) composite = false;
+    }
+    if (composite) return false;
+  }
+  return true;
+}
+// the low `bits` bits of x in reverse order
+inline bn_limb brv(bn_limb x, int bits) {
+  bn_limb r = 0;
+  for (int i = 0; i < bits; ++i) { r = (r << 1) | (x & 1); x >>= 1; }
+  return r;
+}
+
 // a * b, trimmed to its significant limbs (at least one)
 inline Big bn_mul_small(const Big& a, bn_limb b) {
   Big r(a.size() + 1, 0);

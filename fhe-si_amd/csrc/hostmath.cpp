@@ -18,40 +18,7 @@ extern "C" const char* fhesi_last_error(void) { return g_err; }
 
 namespace hm {
 
-u64 mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
-
-u64 powmod(u64 a, u64 e, u64 q) {
-  u64 r = 1 % q;
-  a %= q;
-  for (; e; e >>= 1) {
-    if (e & 1) r = mulmod(r, a, q);
-    a = mulmod(a, a, q);
-  }
-  return r;
-}
-
-u64 invmod(u64 a, u64 q) { return powmod(a % q, q - 2, q); }
-
-bool is_prime(u64 n) {
-  static const u64 bases[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};   // deterministic below 3.3e24
-  if (n < 2) return false;
-  for (u64 p : bases)
-    if (n % p == 0) return n == p;
-  u64 d = n - 1;
-  int s = 0;
-  while (!(d & 1)) { d >>= 1; ++s; }
-  for (u64 a : bases) {
-    u64 x = powmod(a, d, n);
-    if (x == 1 || x == n - 1) continue;
-    bool composite = true;
-    for (int r = 1; r < s && composite; ++r) {
-      x = mulmod(x, x, n);
-      if (x == n - 1) composite = false;
-    }
-    if (composite) return false;
-  }
-  return true;
-}
+// (mulmod, powmod, invmod, is_prime, brv: hostbig.h)
 
 // m = q^k or 2 q^k with q an odd prime, k >= 1: the rings whose Phi_m is Phi_q(+-X^s), s = q^(k-1) (PAlgebra.cpp:40-56 builds Phi_m for any m;
 // these are the ones whose remainder is a three-term fold).  Returns q (0: m is not of that form) and k.
@@ -71,12 +38,6 @@ i64 prime_power_ring(i64 m, int* k) {
 
 u64 shoup(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
 u64 shoup63(u64 w, u64 q) { return (u64)(((u128)w << 63) / q); }
-
-u64 brv(u64 x, int bits) {
-  u64 r = 0;
-  for (int i = 0; i < bits; ++i) { r = (r << 1) | (x & 1); x >>= 1; }
-  return r;
-}
 
 int ilog2_ceil(i64 n) {
   int k = 0;

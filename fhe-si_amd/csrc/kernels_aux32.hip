@@ -8,7 +8,8 @@
 // written for this one size.  Evaluation order is whatever the forward transform produces (no bit reversal anywhere): the dot
 // product is element-wise and the inverse transform is the exact mirror.
 //
-//   p_a = the four largest primes below 2^30 with p = 1 mod 2n  (aux32_init; roots and tables per context, on first use)
+//   p_a = the four largest primes below 2^30 with p = 1 mod 2n  (aux32_init, on first use; roots and transform tables: hm::ring32_build,
+//         ring32_tables.h -- the builder the tensor half uses too; Aux32Primes / Aux32Head are derived here from its per-prime values)
 //   ntt32_fwd_kernel3<DIGITS>  (ntt32_core.inc) 32 values per thread, 512 threads per row of 2^14: 5 stages in registers, LDS exchange, 5
 //                              stages, exchange, 4 stages; rows of 2^15 = head stage + two sub-transforms
 //   ntt32_inv_kernel3          the mirror (Gentleman-Sande), 1/n folded into a final multiplication
@@ -56,66 +57,36 @@ i64 aux32_row_len(const fhesi_ctx* ctx) {
 static int aux32_init(fhesi_ctx* ctx) {
   if (ctx->aux32) return 0;
   if (!aux32_applies(ctx)) FHESI_FAIL("aux32: only for n = 2^14, 2^15 and for rings m = prime or 2 * prime with 2 phi(m) - 1 <= 2^20");
-  fhesi_aux32* x = new fhesi_aux32();
   const i64 n = aux32_row_len(ctx);                // 2^14, or 2^15 .. 2^20 = 2^S sub-transforms per row
   int S = 0;
   while (((i64)A32_N << S) < n) ++S;
-  if (S > 6) { delete x; FHESI_FAIL("aux32: rows of 2^%d", A32_LOGN + S); }
+  if (S > 6) FHESI_FAIL("aux32: rows of 2^%d", A32_LOGN + S);
   const int lg = A32_LOGN + S, NS = 1 << S;
-  x->S = S;
   // the four largest primes below 2^30 that are 1 mod 2n
-  int found = 0;
-  for (u64 k = ((u64)1 << (29 - lg)) - 1; k > 0 && found < 4; --k) {
+  std::vector<u32> primes;
+  for (u64 k = ((u64)1 << (29 - lg)) - 1; k > 0 && primes.size() < 4; --k) {
     const u64 cand = (k << (lg + 1)) + 1;
-    if (cand < ((u64)1 << 30) && hm::is_prime(cand)) x->pr.p[found++] = (u32)cand;
+    if (cand < ((u64)1 << 30) && hm::is_prime(cand)) primes.push_back((u32)cand);
   }
-  if (found < 4) { delete x; FHESI_FAIL("aux32: no primes"); }
-  const size_t per_prime = (size_t)A32_N << S;
-  std::vector<Tw32> hf(4 * per_prime, Tw32{0, 0}), hi(4 * per_prime, Tw32{0, 0}), ff((size_t)n), fi((size_t)n), ht(4 * A32_HT, Tw32{0, 0});
-  const int HSN = A32_HSN(S);
-  std::vector<Tw32> hs(S >= 3 ? (size_t)4 * 2 * HSN : 0, Tw32{0, 0});      // S >= 3: head / tail twiddles of the stand-alone passes (ntt32_core.inc)
+  if (primes.size() < 4) FHESI_FAIL("aux32: no primes");
+  for (u32 p : primes)
+    if (p > ((u64)1 << 30) - ((u64)1 << 15) + 1) FHESI_FAIL("aux32: prime above 2^30 - 2^15 + 1");     // the bound dot32_kernel2's accumulation relies on
+  hm::Ring32Tables t;                              // every table the transforms read (ring32_tables.h); the constants below are this user's own
+  if (!hm::ring32_build(primes, S, t)) FHESI_FAIL("aux32: no 2n-th root");
+  fhesi_aux32* x = new fhesi_aux32();
+  x->S = S;
   for (int a = 0; a < 4; ++a) {
-    const u64 p = x->pr.p[a];
-    u64 psi = 0;
-    for (u64 gq = 2; gq < 1000 && !psi; ++gq) {
-      const u64 cand = hm::powmod(gq, (p - 1) / (2 * (u64)n), p);
-      if (hm::powmod(cand, (u64)n, p) == p - 1) psi = cand;
-    }
-    if (!psi) { delete x; FHESI_FAIL("aux32: no 2n-th root"); }
-    const u64 ipsi = hm::invmod(psi, p);
-    auto tw = [&](u64 w) { return Tw32{(u32)w, (u32)((w << 32) / p)}; };
-    a32_bitrev_powers(p, psi, lg, ff); a32_bitrev_powers(p, ipsi, lg, fi);       // the full table of the n-point transform: psi^brv(idx)
-    auto fwd_form = [](Tw32 t) { return Tw32{0u - t.w, t.wp}; };      // what a32_ct takes: (-w mod 2^32, floor(w 2^32 / p))
-    if (!S) {
-      std::transform(ff.begin(), ff.end(), hf.begin() + (size_t)a * per_prime, fwd_form);
-      std::copy(fi.begin(), fi.end(), hi.begin() + (size_t)a * per_prime);
-    } else {
-      // sub-block h runs stage s >= S of the row on its groups i = h 2^(s-S) + i':  own index m' + i' (m' = 2^(s-S))  <->  (m' << S) + h m' + i'
-      for (int h = 0; h < NS; ++h)
-        for (u64 mp = 1; mp < (u64)A32_N; mp <<= 1)
-          for (u64 ip = 0; ip < mp; ++ip) {
-            hf[((size_t)a * NS + h) * A32_N + mp + ip] = fwd_form(ff[(mp << S) + h * mp + ip]);
-            hi[((size_t)a * NS + h) * A32_N + mp + ip] = fi[(mp << S) + h * mp + ip];
-          }
+    const u64 p = primes[a];
+    const hm::Ring32Prime& q = t.k.pp[a];
+    x->pr.p[a] = (u32)p;
+    if (S) {
       const u64 inv2 = (p + 1) / 2;
-      x->hd.head[a] = ff[1];
-      x->hd.tail_sum[a] = tw(inv2);
-      x->hd.tail_dif[a] = tw(hm::mulmod(fi[1].w, inv2, p));
-      if (S == 2) {
-        x->hd.head1[a][0] = ff[2]; x->hd.head1[a][1] = ff[3];
-        Tw32* c = &ht[(size_t)a * A32_HT];
-        c[0] = ff[1]; c[1] = ff[2]; c[2] = ff[3];
-        c[4] = tw(inv2); c[5] = tw(hm::mulmod(fi[2].w, inv2, p)); c[6] = tw(hm::mulmod(fi[3].w, inv2, p)); c[7] = tw(hm::mulmod(fi[1].w, inv2, p));
-      }
-      if (S >= 3) {
-        Tw32* f = &hs[(size_t)a * 2 * HSN];
-        Tw32* b = f + HSN;
-        for (int idx = 1; idx < NS; ++idx) { f[idx] = ff[idx]; b[idx] = fi[idx]; }
-        const u64 c = hm::invmod((u64)NS % p, p), cm = hm::mulmod(c, ((u64)1 << 32) % p, p);      // 2^-S and 2^-S 2^32
-        b[NS] = tw(c); b[NS + 1] = tw(hm::mulmod(fi[1].w, c, p)); b[NS + 2] = tw(cm); b[NS + 3] = tw(hm::mulmod(fi[1].w, cm, p));
-      }
+      x->hd.head[a] = q.head;
+      x->hd.tail_sum[a] = hm::tw32(inv2, p);
+      x->hd.tail_dif[a] = hm::tw32(hm::mulmod(q.tail.w, inv2, p), p);
+      if (S == 2) { x->hd.head1[a][0] = q.head1[0]; x->hd.head1[a][1] = q.head1[1]; }
     }
-    const u64 ninv = hm::invmod(A32_N % p, p);     // of the 2^14-point (sub-)transform; the tail of a 2^15-point row carries the other 1/2
+    const u64 ninv = q.ninv;                       // of the 2^14-point (sub-)transform; the tail of a 2^15-point row carries the other 1/2
     x->pr.ninv[a] = (u32)ninv;
     x->pr.ninv_p[a] = (u32)((ninv << 32) / p);
     x->pr.pinv64[a] = ~(u64)0 / p;
@@ -124,36 +95,20 @@ static int aux32_init(fhesi_ctx* ctx) {
     { u32 inv = 1; for (int it = 0; it < 5; ++it) inv *= 2u - (u32)p * inv; x->pr.mont[a] = 0u - inv; }      // Newton: p^-1 mod 2^32
     const u64 nm = hm::mulmod(ninv, ((u64)1 << 32) % p, p);
     x->pr.ninv_m[a] = (u32)nm; x->pr.ninv_m_p[a] = (u32)((nm << 32) / p);
-    // the inverse transform's last stage carries the final scaling (ntt32_inv_kernel3): table entries 0 and 1 of every (prime, sub-block) become
-    // 1/n and w / n, w = that sub-block's distance-16 twiddle; the Montgomery pair (2^32 / n, w 2^32 / n) travels with the primes
-    for (int h = 0; h < NS; ++h) {
-      Tw32* t0 = &hi[((size_t)a * NS + h) * A32_N];
-      const u64 w1 = t0[1].w, wn = hm::mulmod(w1, ninv, p), wm = hm::mulmod(w1, nm, p);
-      t0[0] = tw(ninv); t0[1] = tw(wn);
-      if (h < 4) { x->pr.ninv_mw[a][h] = (u32)wm; x->pr.ninv_mw_p[a][h] = (u32)((wm << 32) / p); }      // (S >= 3 runs the plain inverse: the 2^32 sits in the tail pass)
+    // the Montgomery pair of the inverse's last stage (ntt32_inv_kernel3, MONT): (2^32 / n, w 2^32 / n), w = the sub-block's last twiddle
+    // (S >= 3 runs the plain inverse: the 2^32 sits in the tail pass)
+    for (int h = 0; h < 4; ++h) {
+      const u64 wm = hm::mulmod(t.k.last[(size_t)a * NS + (h < NS ? h : 0)], nm, p);
+      x->pr.ninv_mw[a][h] = (u32)wm; x->pr.ninv_mw_p[a][h] = (u32)((wm << 32) / p);
     }
-    for (int h = NS; h < 4; ++h) { x->pr.ninv_mw[a][h] = x->pr.ninv_mw[a][0]; x->pr.ninv_mw_p[a][h] = x->pr.ninv_mw_p[a][0]; }
-    if (p > ((u64)1 << 30) - ((u64)1 << 15) + 1) { delete x; FHESI_FAIL("aux32: prime above 2^30 - 2^15 + 1"); }     // the bound dot32_kernel2's accumulation relies on
   }
-  a32_permute_phase_c(hf); a32_permute_phase_c(hi);      // (the last four stages' twiddles in the order the waves load them: A32_TWC)
-  if (hipMalloc(&x->d_fwd, hf.size() * sizeof(Tw32)) != hipSuccess || hipMalloc(&x->d_inv, hi.size() * sizeof(Tw32)) != hipSuccess) { delete x; FHESI_FAIL("aux32: hipMalloc failed"); }
-  HIP_TRY(hipMemcpy(x->d_fwd, hf.data(), hf.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(x->d_inv, hi.data(), hi.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-  if (S >= 2) {
-    if (hipMalloc(&x->d_ht, ht.size() * sizeof(Tw32)) != hipSuccess || hipMalloc(&x->d_p, 4 * sizeof(u32)) != hipSuccess) { delete x; FHESI_FAIL("aux32: hipMalloc failed"); }
-    HIP_TRY(hipMemcpy(x->d_ht, ht.data(), ht.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(x->d_p, x->pr.p, 4 * sizeof(u32), hipMemcpyHostToDevice));
-  }
-  if (S >= 3) {
-    if (hipMalloc(&x->d_hs, hs.size() * sizeof(Tw32)) != hipSuccess) { delete x; FHESI_FAIL("aux32: hipMalloc failed"); }
-    HIP_TRY(hipMemcpy(x->d_hs, hs.data(), hs.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-  }
+  if (x->tab.upload(t)) { delete x; return 1; }    // (installed only when complete)
   ctx->aux32 = x;
   return 0;
 }
 void aux32_free(fhesi_ctx* ctx) {
   if (!ctx->aux32) return;
-  hipFree(ctx->aux32->d_fwd); hipFree(ctx->aux32->d_inv); hipFree(ctx->aux32->d_ht); hipFree(ctx->aux32->d_p); hipFree(ctx->aux32->d_hs);
+  ctx->aux32->tab.release();
   delete ctx->aux32;
   ctx->aux32 = nullptr;
 }
@@ -164,7 +119,7 @@ int launch_ntt32_fwd(fhesi_ctx* ctx, u32* d_rows, i64 count, int nslots, int a0)
   if (!count) return 0;
   const fhesi_aux32* x = ctx->aux32;
   const int S = x->S;
-  if (S >= 2) { if (!launch_ntt32_head_pass(ctx->stream, S, d_rows, count * nslots, nslots, a0, x->d_p, x->d_ht, x->d_hs)) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S); }
+  if (S >= 2) { if (!launch_ntt32_head_pass(ctx->stream, S, d_rows, count * nslots, nslots, a0, x->tab)) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S); }
   else if (S) ntt32_head_kernel<<<dim3(16, (unsigned)(count * nslots)), 256, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->hd);
   if (S) HIP_TRY(hipGetLastError());
   if (count > 0x7fffffff || (nslots << S) > 65535) FHESI_FAIL("ntt32: too many rows per launch");
@@ -172,7 +127,7 @@ int launch_ntt32_fwd(fhesi_ctx* ctx, u32* d_rows, i64 count, int nslots, int a0)
   if (!a32_with_S<0, 6>(S, [&](auto s) {
     constexpr int SS = decltype(s)::value;
     PROF_KERNEL(ctx, PROF_NTT_FWD, ntt32_fwd_kernel3<false, SS>);
-    ntt32_fwd_kernel3<false, SS><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_fwd, Dig32Src{}, x->hd);
+    ntt32_fwd_kernel3<false, SS><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->tab.d_fwd, Dig32Src{}, x->hd);
   })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -187,12 +142,12 @@ int launch_ntt32_inv(fhesi_ctx* ctx, u32* d_rows, i64 count, int nslots, int a0,
   if (count > 0x7fffffff || (nslots << S) > 65535) FHESI_FAIL("ntt32: too many rows per launch");
   const dim3 grid((unsigned)count, (unsigned)(nslots << S));
   // (S >= 3: the plain inverse; the 2^32 of a Montgomery-form row is a constant of the tail pass)
-  if (mont && S < 3) { PROF_KERNEL(ctx, PROF_NTT_INV, ntt32_inv_kernel3<true>); ntt32_inv_kernel3<true><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_inv, S, nullptr); }
-  else { PROF_KERNEL(ctx, PROF_NTT_INV, ntt32_inv_kernel3<false>); ntt32_inv_kernel3<false><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->d_inv, S, nullptr); }
+  if (mont && S < 3) { PROF_KERNEL(ctx, PROF_NTT_INV, ntt32_inv_kernel3<true>); ntt32_inv_kernel3<true><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->tab.d_inv, S, nullptr); }
+  else { PROF_KERNEL(ctx, PROF_NTT_INV, ntt32_inv_kernel3<false>); ntt32_inv_kernel3<false><<<grid, A32_T, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->tab.d_inv, S, nullptr); }
   HIP_TRY(hipGetLastError());
   if (S >= 2 && !tail) FHESI_FAIL("ntt32: rows of 2^16 and longer have no consumer that takes their tail stages");
   if (S && tail) {
-    if (S >= 2) { if (!launch_ntt32_tail_pass(ctx->stream, S, d_rows, count * nslots, nslots, a0, x->d_p, x->d_ht, x->d_hs, mont ? 1 : 0)) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S); }
+    if (S >= 2) { if (!launch_ntt32_tail_pass(ctx->stream, S, d_rows, count * nslots, nslots, a0, x->tab, mont ? 1 : 0)) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S); }
     else ntt32_tail_kernel<<<dim3(16, (unsigned)(count * nslots)), 256, 0, ctx->stream>>>(d_rows, count, nslots, a0, x->pr, x->hd);
     HIP_TRY(hipGetLastError());
   }
@@ -226,8 +181,8 @@ int launch_ntt32_fwd_digits(fhesi_ctx* ctx, const u64* d_parts, int nl, int digi
     const dim3 hg(A32_N / 256, (unsigned)units);
     if (!a32_with_S<3, 6>(S, [&](auto s) {
       constexpr int SS = decltype(s)::value;
-      if (wm) dig32_headS_kernel<SS, true><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->d_hs);
-      else dig32_headS_kernel<SS, false><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->d_hs);
+      if (wm) dig32_headS_kernel<SS, true><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->tab.d_hs);
+      else dig32_headS_kernel<SS, false><<<hg, 256, 0, ctx->stream>>>(src, d_plain, x->pr, x->tab.d_hs);
     })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
     HIP_TRY(hipGetLastError());
     // the sub-transforms read those rows and store the tiled layout the dot product reads (ntt32_fwd_kernel3<DIGITS, S >= 3>: row source)
@@ -238,7 +193,7 @@ int launch_ntt32_fwd_digits(fhesi_ctx* ctx, const u64* d_parts, int nl, int digi
     if (!a32_with_S<3, 6>(S, [&](auto s) {
       constexpr int SS = decltype(s)::value;
       PROF_KERNEL(ctx, PROF_NTT_FWD_DIGITS_MAIN, (ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false>));
-      ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false><<<(unsigned)blocks3, A32_T, 0, ctx->stream>>>(d_out, units, 4, 0, x->pr, x->d_fwd, rs, x->hd);
+      ntt32_fwd_kernel3<true, SS, true, Aux32Primes, true, false><<<(unsigned)blocks3, A32_T, 0, ctx->stream>>>(d_out, units, 4, 0, x->pr, x->tab.d_fwd, rs, x->hd);
     })) FHESI_FAIL("ntt32: no kernel for rows of 2^%d", A32_LOGN + S);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -253,7 +208,7 @@ int launch_ntt32_fwd_digits(fhesi_ctx* ctx, const u64* d_parts, int nl, int digi
     auto go = [&](auto pp, auto ww) {
       constexpr bool PP = decltype(pp)::value, WW = decltype(ww)::value;
       PROF_KERNEL(ctx, PROF_NTT_FWD_DIGITS_MAIN, (ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW>));
-      ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW><<<(unsigned)blocks, A32_T, 0, ctx->stream>>>(d_out, npolys * nd, 4, 0, x->pr, x->d_fwd, src, x->hd);
+      ntt32_fwd_kernel3<true, SS, PP, Aux32Primes, true, WW><<<(unsigned)blocks, A32_T, 0, ctx->stream>>>(d_out, npolys * nd, 4, 0, x->pr, x->tab.d_fwd, src, x->hd);
     };
     auto go_w = [&](auto pp) { if (wm) go(pp, std::true_type{}); else go(pp, std::false_type{}); };
     if constexpr (SS == 2) go_w(std::true_type{});      // (rows of 2^16 are always padded: no other form is built)

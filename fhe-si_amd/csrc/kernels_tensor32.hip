@@ -37,6 +37,8 @@
 // (ntt32_headS_kernel / ntt32_tailS_kernel, ntt32_core.inc); the CRT kernel then folds from whole rows.
 // fhesi_ct_mul_dev keeps the reference chain (its rows ARE visible).  Option tensor32 = 0 keeps the chain in the fused pipeline too; option
 // tensor_bits = 29 takes the primes below 2^29 (fewer range steps in the row transforms, one or two primes more: measured a tie).
+// Host tables: ring32_tables.h builds them all -- hm::ring32_build the transform tables (t32_ring; the key switch's four primes go through the
+// same builder), hm::conv32_build the conversion tables of a configuration (t32_config) -- and tests/test_ring32_tables.py checks them on the CPU.
 #include "fhesi_internal.h"
 #include "lin_fold.h"
 #include "ntt32_core.inc"
@@ -59,15 +61,11 @@ struct T32Config {
 struct fhesi_tensor32 {
   int S = 0;                         // rows of 2^14 << S
   int bits = 30;                     // 30: the largest primes below 2^30; 29: below 2^29 (option tensor_bits: one or two primes more, 6 of 14 / 7 of 13 range steps per row transform)
-  std::vector<u32> primes;           // the primes with transform tables, largest first
-  std::vector<Tw32> head, tail;      // per prime: psi^brv(1), psi^-brv(1)   (S = 1)
-  std::vector<Tw32> head1;           // per prime: psi^brv(2), psi^brv(3)    (S = 2: the second head stage)
-  std::vector<u32> last;             // per prime: the twiddle of the inverse's last stage (S = 0: what entry 1 of d_inv held before the 1/n went in)
-  Tw32* d_fwd = nullptr;             // [primes][2^S][2^14]
-  Tw32* d_inv = nullptr;
-  Tw32* d_ht = nullptr;              // S = 2: [primes][A32_HT] constants of the stand-alone tail pass (ntt32_tail2_kernel)
-  u32* d_p = nullptr;                // S >= 2: the primes
-  Tw32* d_hs = nullptr;              // S >= 3: [primes][2][A32_HSN(S)] head / tail twiddles of the stand-alone passes (ntt32_headS_kernel / ntt32_tailS_kernel)
+  // what the device tables were built for, committed after them (t32_ring): k.primes, largest first, and per prime the values the configurations
+  // derive their constants from -- head (psi^brv(1): S = 1), head1 (psi^brv(2), psi^brv(3): S = 2), tail (psi^-brv(1)), last (S = 0: the twiddle of
+  // the inverse's last stage before the 1/n went in)
+  hm::Ring32Consts k;
+  Ring32Dev tab;                     // [primes][2^S][2^14] forward and inverse tables, and the constants of the stand-alone passes (S >= 2)
   std::vector<T32Config*> cfgs;
   T32Config* cur = nullptr;          // the configuration of the running sum (tensor32_sum_begin)
 };
@@ -76,14 +74,10 @@ void tensor32_free(fhesi_ctx* ctx) {
   fhesi_tensor32* x = ctx->tensor32;
   if (!x) return;
   for (T32Config* c : x->cfgs) delete c;
-  hipFree(x->d_fwd); hipFree(x->d_inv); hipFree(x->d_ht); hipFree(x->d_p); hipFree(x->d_hs);
+  x->tab.release();
   delete x;
   ctx->tensor32 = nullptr;
 }
-
-// ---------------------------------------------------------------------------------------------- host big integers (little-endian u64 limbs)
-using hm::Big;
-static u32 big_word(const Big& a, int l, int R) { return hm::bn_word(a, l, R); }          // word l of the radix-2^R form
 
 // the two compiled shapes of crt32_scale_kernel, and the run-time form
 static constexpr int T32_WT_512 = 38, T32_R_512 = 28;        // logQ = 512: words of 28 bits (up to 62 primes), 1064 bits per table row
@@ -207,85 +201,14 @@ static int t32_ring(fhesi_ctx* ctx, const std::vector<u32>& primes) {
     x = nullptr;
   }
   if (!x) { x = new fhesi_tensor32(); x->S = (ctx->lin_q ? ctx->lin_lg : ctx->logn) - A32_LOGN; x->bits = pb; ctx->tensor32 = x; }
-  if (x->primes.size() >= primes.size()) return 0;
+  if (x->k.primes.size() >= primes.size()) return 0;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (ctx->lane_stream) HIP_TRY(hipStreamSynchronize(ctx->lane_stream));
-  const int S = x->S, lg = A32_LOGN + S, NP = (int)primes.size(), NS = 1 << S;
-  if (S < 0 || S > 6) FHESI_FAIL("tensor32: rows of 2^%d", lg);
-  const int HSN = A32_HSN(S);
-  std::vector<Tw32> hs(S >= 3 ? (size_t)NP * 2 * HSN : 0, Tw32{0, 0});
-  const i64 n = (i64)A32_N << S;
-  const size_t per_prime = (size_t)A32_N << S;
-  std::vector<Tw32> hf((size_t)NP * per_prime, Tw32{0, 0}), hi((size_t)NP * per_prime, Tw32{0, 0}), ff((size_t)n), fi((size_t)n), ht((size_t)NP * A32_HT, Tw32{0, 0});
-  x->head.assign(NP, Tw32{0, 0}); x->tail.assign(NP, Tw32{0, 0}); x->head1.assign((size_t)NP * 2, Tw32{0, 0}); x->last.assign(NP, 0);
-  for (int a = 0; a < NP; ++a) {
-    const u64 p = primes[a];
-    u64 psi = 0;
-    for (u64 gq = 2; gq < 1000 && !psi; ++gq) {
-      const u64 cand = hm::powmod(gq, (p - 1) / (2 * (u64)n), p);
-      if (hm::powmod(cand, (u64)n, p) == p - 1) psi = cand;
-    }
-    if (!psi) FHESI_FAIL("tensor32: no 2n-th root");
-    const u64 ipsi = hm::invmod(psi, p);
-    auto tw = [&](u64 w) { return Tw32{(u32)w, (u32)((w << 32) / p)}; };
-    auto fwd_form = [](Tw32 t) { return Tw32{0u - t.w, t.wp}; };      // what a32_ct<NEGW> takes: (-w mod 2^32, floor(w 2^32 / p)), as aux32_init
-    a32_bitrev_powers(p, psi, lg, ff); a32_bitrev_powers(p, ipsi, lg, fi);       // the full table of the n-point transform: psi^brv(idx)
-    if (!S) {
-      std::transform(ff.begin(), ff.end(), hf.begin() + (size_t)a * per_prime, fwd_form);
-      std::copy(fi.begin(), fi.end(), hi.begin() + (size_t)a * per_prime);
-      x->last[a] = fi[1].w;
-    } else {
-      // sub-block h runs stage s >= 1 of the row on its groups i = h 2^(s-1) + i':  own index m' + i' (m' = 2^(s-1))  <->  2 m' + h m' + i'  (as aux32_init)
-      for (int h = 0; h < NS; ++h)
-        for (u64 mp = 1; mp < (u64)A32_N; mp <<= 1)
-          for (u64 ip = 0; ip < mp; ++ip) {
-            hf[((size_t)a * NS + h) * A32_N + mp + ip] = fwd_form(ff[(mp << S) + h * mp + ip]);
-            hi[((size_t)a * NS + h) * A32_N + mp + ip] = fi[(mp << S) + h * mp + ip];
-          }
-      x->head[a] = ff[1]; x->tail[a] = fi[1];
-      if (S == 2) {
-        x->head1[(size_t)a * 2] = ff[2]; x->head1[(size_t)a * 2 + 1] = ff[3];
-        const u64 inv2 = (p + 1) / 2;
-        Tw32* c = &ht[(size_t)a * A32_HT];
-        c[0] = ff[1]; c[1] = ff[2]; c[2] = ff[3];
-        c[4] = tw(inv2); c[5] = tw(hm::mulmod(fi[2].w, inv2, p)); c[6] = tw(hm::mulmod(fi[3].w, inv2, p)); c[7] = tw(hm::mulmod(fi[1].w, inv2, p));
-      }
-      if (S >= 3) {          // (as aux32_init)
-        Tw32* f = &hs[(size_t)a * 2 * HSN];
-        Tw32* b = f + HSN;
-        for (int idx = 1; idx < NS; ++idx) { f[idx] = ff[idx]; b[idx] = fi[idx]; }
-        const u64 c = hm::invmod((u64)NS % p, p), cm = hm::mulmod(c, ((u64)1 << 32) % p, p);
-        b[NS] = tw(c); b[NS + 1] = tw(hm::mulmod(fi[1].w, c, p)); b[NS + 2] = tw(cm); b[NS + 3] = tw(hm::mulmod(fi[1].w, cm, p));
-      }
-    }
-  }
-  // the inverse transform's last stage carries the final scaling (ntt32_inv_kernel3): entries 0 and 1 of every (prime, sub-block) table
-  // become 1/n and w / n, w = that sub-block's distance-16 twiddle (n = 2^14: the sub-transform's length).  (Rows of 2^14 do not read the pair:
-  // t32_config puts (M / p_i)^-1 / n and w (M / p_i)^-1 / n into T32Primes -- M depends on the configuration, this table does not.)
-  for (size_t a = 0; a < primes.size(); ++a) {
-    const u64 p = primes[a], ninv = hm::invmod((u64)A32_N % p, p);
-    for (int h = 0; h < NS; ++h) {
-      Tw32* t0 = &hi[(a * NS + h) * A32_N];
-      const u64 wn = hm::mulmod(t0[1].w, ninv, p);
-      t0[0] = Tw32{(u32)ninv, (u32)((ninv << 32) / p)}; t0[1] = Tw32{(u32)wn, (u32)((wn << 32) / p)};
-    }
-  }
-  hipFree(x->d_fwd); hipFree(x->d_inv); hipFree(x->d_ht); hipFree(x->d_p); hipFree(x->d_hs);
-  x->d_fwd = x->d_inv = x->d_ht = x->d_hs = nullptr; x->d_p = nullptr;
-  if (S >= 2) {
-    if (hipMalloc(&x->d_ht, ht.size() * sizeof(Tw32)) != hipSuccess || hipMalloc(&x->d_p, (size_t)NP * sizeof(u32)) != hipSuccess) FHESI_FAIL("tensor32: hipMalloc failed");
-    HIP_TRY(hipMemcpy(x->d_ht, ht.data(), ht.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(x->d_p, primes.data(), (size_t)NP * sizeof(u32), hipMemcpyHostToDevice));
-  }
-  if (S >= 3) {
-    if (hipMalloc(&x->d_hs, hs.size() * sizeof(Tw32)) != hipSuccess) FHESI_FAIL("tensor32: hipMalloc failed");
-    HIP_TRY(hipMemcpy(x->d_hs, hs.data(), hs.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-  }
-  a32_permute_phase_c(hf); a32_permute_phase_c(hi);      // (the last four stages' twiddles in the order the waves load them: A32_TWC)
-  if (hipMalloc(&x->d_fwd, hf.size() * sizeof(Tw32)) != hipSuccess || hipMalloc(&x->d_inv, hi.size() * sizeof(Tw32)) != hipSuccess) FHESI_FAIL("tensor32: hipMalloc failed");
-  HIP_TRY(hipMemcpy(x->d_fwd, hf.data(), hf.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(x->d_inv, hi.data(), hi.size() * sizeof(Tw32), hipMemcpyHostToDevice));
-  x->primes = primes;
+  if (x->S < 0 || x->S > 6) FHESI_FAIL("tensor32: rows of 2^%d", A32_LOGN + x->S);
+  hm::Ring32Tables t;                    // (ring32_tables.h: the builder the key switch's four primes go through as well)
+  if (!hm::ring32_build(primes, x->S, t)) FHESI_FAIL("tensor32: no 2n-th root");
+  FHESI_TRY(x->tab.upload(t));           // (a failure leaves the old tables AND the old prime list in force)
+  x->k = std::move(t.k);
   return 0;
 }
 
@@ -300,87 +223,20 @@ static int t32_config(fhesi_ctx* ctx, u64 lift, int nlimbs, int logQ, i64 gmax, 
   const int NP = pl.NP, S = x->S;
   double have = 0;
   for (int a = 0; a < NP; ++a) have += std::log2((double)primes[a]);
+  const int R = pl.generic ? 28 : (logQ == 512 ? T32_R_512 : T32_R_1024);
+  const int WT = pl.generic ? (int)((have + 8) / 28) + 2 : (logQ == 512 ? T32_WT_512 : T32_WT_1024);
+  const hm::Conv32Tables h = hm::conv32_build(x->k, NP, lift, nlimbs, R, WT);      // (ring32_tables.h)
   T32Config* c = new T32Config();
-  c->lift = lift; c->nl = nlimbs; c->logQ = logQ; c->NP = NP; c->generic = pl.generic;
-  c->R = pl.generic ? 28 : (logQ == 512 ? T32_R_512 : T32_R_1024);
-  c->WT = pl.generic ? (int)((have + 8) / 28) + 2 : (logQ == 512 ? T32_WT_512 : T32_WT_1024);
-  const int R = c->R, WT = c->WT, stride = (2 * nlimbs + 8 + 7) & ~7;          // (rows of whole 32-byte lines: the kernel reads them with scalar loads)
-  std::vector<u32> rns((size_t)2 * NP * stride);
+  c->lift = lift; c->nl = nlimbs; c->logQ = logQ; c->NP = NP; c->generic = pl.generic; c->R = R; c->WT = WT;
   for (int a = 0; a < NP; ++a) {
-    const u64 p = primes[a];
-    const u64 ninv = hm::invmod((u64)A32_N % p, p);     // of the 2^14-point (sub-)transform; the tail carries the other 1/2
-    c->pr.p[a] = (u32)p;
-    c->pr.ninv[a] = (u32)ninv;                          // (S = 0: times (M / p_i)^-1 below, once M is known)
-    c->pr.ninv_p[a] = (u32)((ninv << 32) / p);
-    c->pr.mu61[a] = (u32)(((u64)1 << (32 + t32_shift((u32)p))) / p);
-    for (int cls = 0; cls < 2; ++cls) {
-      u32* e = &rns[((size_t)cls * NP + a) * stride];
-      const u64 b32 = ((u64)1 << 32) % p;
-      u64 cur = cls == 0 ? lift % p : 1;
-      for (int k = 0; k < 2 * nlimbs; ++k) { e[k] = (u32)cur; cur = hm::mulmod(cur, b32, p); }
-      e[2 * nlimbs] = (u32)((p - cur) % p);          // two's complement: value = unsigned - 2^(64 nl)
-      e[2 * nlimbs + 1] = (u32)b32;
-      e[2 * nlimbs + 2] = c->pr.mu61[a];
-      e[2 * nlimbs + 3] = (u32)p;
-      // head stage of a 2^15-point row: psi^brv(1); padded rows of 2^16: the second head stage's psi^brv(2), psi^brv(3) (the first is a duplication)
-      e[2 * nlimbs + 4] = S == 2 ? x->head1[(size_t)a * 2].w : (S ? x->head[a].w : 0);
-      e[2 * nlimbs + 5] = S == 2 ? x->head1[(size_t)a * 2].wp : (S ? x->head[a].wp : 0);
-      e[2 * nlimbs + 6] = S == 2 ? x->head1[(size_t)a * 2 + 1].w : 0;
-      e[2 * nlimbs + 7] = S == 2 ? x->head1[(size_t)a * 2 + 1].wp : 0;
-    }
+    const Tw32 cn = h.closing[2 * a], cw = h.closing[2 * a + 1];
+    c->pr.p[a] = primes[a]; c->pr.mu61[a] = h.mu61[a]; c->pr.ninv[a] = cn.w; c->pr.ninv_p[a] = cn.wp; c->pr.ninv_w[a] = cw.w; c->pr.ninv_w_p[a] = cw.wp;
   }
-  // CRT tables
   c->pr.closing = S ? T32_ROWS_PLAIN : T32_ROWS_CRT;
-  Big M{1};
-  for (int a = 0; a < NP; ++a) M = hm::bn_mul_small(M, primes[a]);
-  std::vector<Tw32> cinv((size_t)NP * 2);
-  std::vector<u32> inv57(NP), Mw((size_t)(NP + 1) * WT + 64);        // (padded: the generic kernel multiplies a fixed number of words per row, whatever the window)
-  for (int a = 0; a < NP; ++a) {
-    Big Mi{1};
-    for (int b = 0; b < NP; ++b) if (b != a) Mi = hm::bn_mul_small(Mi, primes[b]);
-    const u64 p = primes[a];
-    const u64 ci = hm::invmod(hm::bn_mod_small(Mi, p), p);
-    auto tw = [&](u64 w) { return Tw32{(u32)w, (u32)((w << 32) / p)}; };
-    if (!S) {
-      // rows of 2^14: the product by ci is the inverse transform's own closing multiplication (ntt32_inv_kernel3, last stage: (X + Y) c and
-      // (X - Y)(w c) with c = ci / n), so its rows are y_i = x ci mod p_i, below p, and the CRT kernels multiply by nothing
-      const u64 cn = hm::mulmod(ci, c->pr.ninv[a], p), cw = hm::mulmod(cn, x->last[a], p);
-      c->pr.ninv[a] = (u32)cn; c->pr.ninv_p[a] = (u32)((cn << 32) / p);
-      c->pr.ninv_w[a] = (u32)cw; c->pr.ninv_w_p[a] = (u32)((cw << 32) / p);
-    }
-    if (S != 1) cinv[(size_t)a * 2] = cinv[(size_t)a * 2 + 1] = tw(ci);      // (rows of 2^16: the tail stages are a pass of their own, ntt32_tail2_kernel)
-    else {
-      const u64 inv2 = (p + 1) / 2;
-      cinv[(size_t)a * 2] = tw(hm::mulmod(ci, inv2, p));
-      cinv[(size_t)a * 2 + 1] = tw(hm::mulmod(ci, hm::mulmod(x->tail[a].w, inv2, p), p));
-    }
-    inv57[a] = (u32)(((u64)1 << 57) / p);
-    for (int l = 0; l < WT; ++l) Mw[(size_t)a * WT + l] = big_word(Mi, l, R);
-  }
-  {
-    // 2^(R WT) - M: two's complement of M over enough limbs, read through the same word extraction (masked to R WT bits)
-    Big N(M);
-    N.resize((R * WT + 63) / 64 + 1, 0);
-    u64 carry = 1;
-    for (auto& w : N) { const u64 v = ~w + carry; carry = (carry && v == 0) ? 1 : 0; w = v; }
-    for (int l = 0; l < WT; ++l) Mw[(size_t)NP * WT + l] = big_word(N, l, R);
-  }
-  auto up = [&](void** d, const void* h, size_t bytes) -> bool {
-    return hipMalloc(d, bytes) == hipSuccess && hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  if (!up((void**)&c->d_rns, rns.data(), rns.size() * 4) || !up((void**)&c->d_cinv, cinv.data(), cinv.size() * sizeof(Tw32)) ||
-      !up((void**)&c->d_inv57, inv57.data(), inv57.size() * 4) || !up((void**)&c->d_Mw, Mw.data(), Mw.size() * 4)) {
-    delete c;
-    FHESI_FAIL("tensor32: table upload failed");
-  }
-  if (t32_mfma_shape(pl.generic, logQ, S, NP)) {
-    // the same window of the same table rows as balanced bytes (crt32_bytes.h): the matrix-core form of the fast pass
-    const hm::Crt32Bytes bt = hm::crt32_bytes_build(Mw.data(), NP, WT, R, t32_j0(512, T32_R_512, T32_NP_28), T32_MFMA_NW);
-    if (!up((void**)&c->d_bytes, bt.aop.data(), bt.aop.size() * 4)) {
-      delete c;
-      FHESI_FAIL("tensor32: table upload failed");
-    }
-  }
+  bool ok = a32_upload(&c->d_rns, h.rns) && a32_upload(&c->d_cinv, h.cinv) && a32_upload(&c->d_inv57, h.inv57) && a32_upload(&c->d_Mw, h.Mw);
+  // the same window of the same table rows as balanced bytes (crt32_bytes.h): the matrix-core form of the fast pass
+  if (ok && t32_mfma_shape(pl.generic, logQ, S, NP)) ok = a32_upload(&c->d_bytes, hm::crt32_bytes_build(h.Mw.data(), NP, WT, R, t32_j0(512, T32_R_512, T32_NP_28), T32_MFMA_NW).aop);
+  if (!ok) { delete c; FHESI_FAIL("tensor32: table upload failed"); }
   x->cfgs.push_back(c);
   *out = c;
   return 0;
@@ -1006,6 +862,11 @@ static int t32_rns(fhesi_ctx* ctx, const T32Config* c, const u64* d_a, const u64
 #undef T32_RNS
   FHESI_FAIL("tensor32: %d limbs", c->nl);
 }
+// f(std::integral_constant<int, PB>) for the size of the context's primes, 29 or 30 bits; f reads it as decltype(pb)::value (a32_with_S's pattern)
+template <class F>
+static inline void t32_with_bits(const fhesi_tensor32* x, F&& f) {
+  if (x->bits == 29) f(std::integral_constant<int, 29>{}); else f(std::integral_constant<int, 30>{});
+}
 static int t32_fwd(fhesi_ctx* ctx, const T32Config* c, u32* d_r, i64 npolys) {
   const fhesi_tensor32* x = ctx->tensor32;
   ProfScope prof(ctx, PROF_NTT_FWD, (double)(npolys * c->NP));
@@ -1013,18 +874,30 @@ static int t32_fwd(fhesi_ctx* ctx, const T32Config* c, u32* d_r, i64 npolys) {
   const dim3 grid((unsigned)npolys, (unsigned)(c->NP << x->S));
   // head stages of the plain rows as a pass of their own (rows of 2^16 take them in rns32_reduce)
   if (x->S >= 3) {
-    if (!launch_ntt32_head_pass(ctx->stream, x->S, d_r, npolys * c->NP, c->NP, 0, x->d_p, x->d_ht, x->d_hs)) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
+    if (!launch_ntt32_head_pass(ctx->stream, x->S, d_r, npolys * c->NP, c->NP, 0, x->tab)) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
     HIP_TRY(hipGetLastError());
   }
   if (!a32_with_S<0, 6>(x->S, [&](auto s) {
     constexpr int SS = decltype(s)::value;
-    auto go = [&](auto pb) {
+    t32_with_bits(x, [&](auto pb) {
       constexpr int PB = decltype(pb)::value;
       PROF_KERNEL(ctx, PROF_NTT_FWD, (ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB>));
-      ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB><<<grid, A32_T, 0, ctx->stream>>>(d_r, npolys, c->NP, 0, c->pr, x->d_fwd, Dig32Src{}, Aux32Head{});
-    };
-    if (x->bits == 29) go(std::integral_constant<int, 29>{}); else go(std::integral_constant<int, 30>{});
+      ntt32_fwd_kernel3<false, SS, false, T32Primes, true, false, PB><<<grid, A32_T, 0, ctx->stream>>>(d_r, npolys, c->NP, 0, c->pr, x->tab.d_fwd, Dig32Src{}, Aux32Head{});
+    });
   })) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// the inverse transforms of nrows rows, in place; TENSOR: the rows are formed in the loader, as the tensor products of src's forward rows
+template <bool TENSOR>
+static int t32_inv(fhesi_ctx* ctx, const T32Config* c, u32* rows, i64 nrows, dim3 grid, const u32* src) {
+  const fhesi_tensor32* x = ctx->tensor32;
+  ProfScope prof(ctx, PROF_NTT_INV, (double)(nrows * c->NP));
+  t32_with_bits(x, [&](auto pb) {
+    constexpr int PB = decltype(pb)::value;
+    PROF_KERNEL(ctx, PROF_NTT_INV, (ntt32_inv_kernel3<false, TENSOR, T32Primes, PB>));
+    ntt32_inv_kernel3<false, TENSOR, T32Primes, PB><<<grid, A32_T, 0, ctx->stream>>>(rows, nrows, c->NP, 0, c->pr, x->tab.d_inv, x->S, src);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1091,31 +964,33 @@ static int t32_crt(fhesi_ctx* ctx, const T32Config* c, const u32* d_t, i64 npoly
   unsigned char* fl = (unsigned char*)d_fl;
   const int fold = !ctx->lin_q ? 0 : (ctx->lin_prime ? 2 : 1);
   const i64 off = ctx->lin_q ? lin_fold_pack(ctx->lin_q, ctx->lin_s, false) : 0;      // (the kind of fold is the template argument)
-  // (S, FOLD) compile-time; the first pass over 16 or 24 words, whichever holds the window
-#define T32_GEN_GO(NWM, SS, FF) do { \
-    PROF_KERNEL(ctx, PROF_CRT, (crt32_scale_generic_kernel<NWM, false, SS, FF>)); \
-    crt32_scale_generic_kernel<NWM, false, SS, FF><<<grid, 128, 0, ctx->stream>>>(d_t, nrow, n_out, off, c->NP, logQ, J0, NW, c->WT, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, wm ? 1 : 0); \
-    HIP_TRY(hipGetLastError()); \
-    if (!ctx->opt.crt_skip_cleanup) { \
-      crt32_scale_generic_kernel<T32_GEN_NWX, true, SS, FF><<<grid, 128, 0, ctx->stream>>>(d_t, nrow, n_out, off, c->NP, logQ, 0, WU, c->WT, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, wm ? 1 : 0); \
-      HIP_TRY(hipGetLastError()); \
-    } } while (0)
   if (S >= 2) {      // rows of 2^16 and longer: the tail stages as a pass of their own over the sub-inverses (in place), then the fold from whole rows
     const fhesi_tensor32* x = ctx->tensor32;
-    if (!launch_ntt32_tail_pass(ctx->stream, S, const_cast<u32*>(d_t), npolys * c->NP, c->NP, 0, x->d_p, x->d_ht, x->d_hs, 0)) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
+    if (!launch_ntt32_tail_pass(ctx->stream, S, const_cast<u32*>(d_t), npolys * c->NP, c->NP, 0, x->tab, 0)) FHESI_FAIL("tensor32: no kernel for rows of 2^%d", A32_LOGN + x->S);
     HIP_TRY(hipGetLastError());
   }
   // (A compiled form of this kernel for the reference drivers' own shapes -- logQ, word window and limb positions as constants, the words in
   // registers from the multiply-adds to the limbs -- was measured in round 6 and removed: crt class 8.80-8.85 ms per 1024 multiplications at
   // m = 32602 with this run-time form, 8.92-8.99 with the compiled one (profiles/r06_ab_crt_compiled.txt).  The kernel's time is its loads -- two
   // sub-rows at three folded positions per prime -- and its multiply-adds, twice the metric ring's for rows twice as long, not its indexing.)
-#define T32_GEN_SF(NWM) do { \
-    if (S != 1) { if (fold == 0) T32_GEN_GO(NWM, 0, 0); else if (fold == 1) T32_GEN_GO(NWM, 0, 1); else T32_GEN_GO(NWM, 0, 2); } \
-    else { if (fold == 0) T32_GEN_GO(NWM, 1, 0); else if (fold == 1) T32_GEN_GO(NWM, 1, 1); else T32_GEN_GO(NWM, 1, 2); } } while (0)
-  if (NW <= 16) T32_GEN_SF(16); else T32_GEN_SF(T32_GEN_NW);
-#undef T32_GEN_SF
-#undef T32_GEN_GO
-  return 0;
+  // (S == 1, FOLD) compile-time; the first pass over 16 or 24 words, whichever holds the window
+  int rc = 0;
+  auto go = [&](auto nwm, auto ss, auto ff) -> int {
+    constexpr int NWM = decltype(nwm)::value, SS = decltype(ss)::value, FF = decltype(ff)::value;
+    PROF_KERNEL(ctx, PROF_CRT, (crt32_scale_generic_kernel<NWM, false, SS, FF>));
+    crt32_scale_generic_kernel<NWM, false, SS, FF><<<grid, 128, 0, ctx->stream>>>(d_t, nrow, n_out, off, c->NP, logQ, J0, NW, c->WT, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, wm ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    if (!ctx->opt.crt_skip_cleanup) {
+      crt32_scale_generic_kernel<T32_GEN_NWX, true, SS, FF><<<grid, 128, 0, ctx->stream>>>(d_t, nrow, n_out, off, c->NP, logQ, 0, WU, c->WT, c->pr, c->d_cinv, c->d_inv57, c->d_Mw, d_parts, fl, wm ? 1 : 0);
+      HIP_TRY(hipGetLastError());
+    }
+    return 0;
+  };
+  auto go_sf = [&](auto nwm) {      // (a32_with_S: a run-time value of a small range as a compile-time constant)
+    a32_with_S<0, 1>(S == 1 ? 1 : 0, [&](auto ss) { a32_with_S<0, 2>(fold, [&](auto ff) { rc = go(nwm, ss, ff); }); });
+  };
+  if (NW <= 16) go_sf(std::integral_constant<int, 16>{}); else go_sf(std::integral_constant<int, T32_GEN_NW>{});
+  return rc;
 }
 
 // ---- pairs (fhesi_ct_mul_relin_batch_dev): a, b [count][2][phi(m)][nlimbs] -> d_parts [count * 3][ceil(logQ/64)][phi(m)]: the scaled-down tProd as ByteDecomp takes it
@@ -1131,18 +1006,8 @@ int launch_tensor32(fhesi_ctx* ctx, u64 p, const u64* d_a, const u64* d_b, int n
   FHESI_TRY(ws_reserve(ctx, 1, (size_t)count * 3 * NP * nrow * 4, &d_t));
   FHESI_TRY(t32_rns(ctx, c, d_a, d_b, count * 4, 0, true, (u32*)d_r));
   FHESI_TRY(t32_fwd(ctx, c, (u32*)d_r, count * 4));
-  {
-    ProfScope prof(ctx, PROF_NTT_INV, (double)(count * 3 * NP));
-    const dim3 grid((unsigned)(count >= 8 ? ((count + 7) / 8) * 24 : count * 3), (unsigned)(NP << S));      // (groups of 8 ciphertexts x 3 rows, or the rows themselves: see the kernel)
-    if (x->bits == 29) {
-      PROF_KERNEL(ctx, PROF_NTT_INV, (ntt32_inv_kernel3<false, true, T32Primes, 29>));
-      ntt32_inv_kernel3<false, true, T32Primes, 29><<<grid, A32_T, 0, ctx->stream>>>((u32*)d_t, count * 3, NP, 0, c->pr, x->d_inv, S, (const u32*)d_r);
-    } else {
-      PROF_KERNEL(ctx, PROF_NTT_INV, (ntt32_inv_kernel3<false, true, T32Primes>));
-      ntt32_inv_kernel3<false, true, T32Primes><<<grid, A32_T, 0, ctx->stream>>>((u32*)d_t, count * 3, NP, 0, c->pr, x->d_inv, S, (const u32*)d_r);
-    }
-    HIP_TRY(hipGetLastError());
-  }
+  const dim3 grid((unsigned)(count >= 8 ? ((count + 7) / 8) * 24 : count * 3), (unsigned)(NP << S));      // (groups of 8 ciphertexts x 3 rows, or the rows themselves: see the kernel)
+  FHESI_TRY(t32_inv<true>(ctx, c, (u32*)d_t, count * 3, grid, (const u32*)d_r));
   return t32_crt(ctx, c, (const u32*)d_t, count * 3, c->pr.closing, d_parts, parts_wm);
 }
 
@@ -1177,18 +1042,7 @@ int tensor32_sum_pass(fhesi_ctx* ctx, const u64* d_ops, i64 nua, i64 nub, const 
 }
 int tensor32_sum_finish(fhesi_ctx* ctx, void* d_sum, i64 ng, u64* d_parts, bool parts_wm) {
   const T32Config* c = ctx->tensor32->cur;
-  const fhesi_tensor32* x = ctx->tensor32;
-  {
-    ProfScope prof(ctx, PROF_NTT_INV, (double)(ng * 3 * c->NP));
-    const dim3 grid((unsigned)(ng * 3), (unsigned)(c->NP << x->S));
-    if (x->bits == 29) {
-      PROF_KERNEL(ctx, PROF_NTT_INV, (ntt32_inv_kernel3<false, false, T32Primes, 29>));
-      ntt32_inv_kernel3<false, false, T32Primes, 29><<<grid, A32_T, 0, ctx->stream>>>((u32*)d_sum, ng * 3, c->NP, 0, c->pr, x->d_inv, x->S, nullptr);
-    } else {
-      PROF_KERNEL(ctx, PROF_NTT_INV, (ntt32_inv_kernel3<false, false, T32Primes>));
-      ntt32_inv_kernel3<false, false, T32Primes><<<grid, A32_T, 0, ctx->stream>>>((u32*)d_sum, ng * 3, c->NP, 0, c->pr, x->d_inv, x->S, nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-  }
+  const dim3 grid((unsigned)(ng * 3), (unsigned)(c->NP << ctx->tensor32->S));
+  FHESI_TRY(t32_inv<false>(ctx, c, (u32*)d_sum, ng * 3, grid, nullptr));
   return t32_crt(ctx, c, (const u32*)d_sum, ng * 3, c->pr.closing, d_parts, parts_wm);
 }

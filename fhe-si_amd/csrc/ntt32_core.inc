@@ -2,11 +2,14 @@
 // below 4p): the third-form forward / inverse kernels and their helpers, shared by the key switch through four auxiliary primes
 // (kernels_aux32.hip) and the tensor half of the fused multiplication through ~35 of them (kernels_tensor32.hip).
 // Included inside a translation unit after fhesi_internal.h; everything is static / templated.
+// Tw32, A32_LOGN, A32_N, A32_HT, A32_HSN, t32_shift and every host table these kernels read -- a32_bitrev_powers, a32_permute_phase_c,
+// hm::ring32_build -- live in ring32_tables.h (host-only, tested on the CPU); Ring32Dev below owns their device copies for both users.
 #pragma once
 #include <algorithm>
 #include <type_traits>
 
-struct Tw32 { u32 w, wp; };          // constant and floor(w 2^32 / p)
+#include "ring32_tables.h"
+
 struct Aux32Primes { u32 p[4]; u32 ninv[4], ninv_p[4]; u64 pinv64[4] /* floor((2^64 - 1) / p) */, r64[4] /* 2^64 mod p */, r48[4] /* 2^48 mod p */;
                      u32 mont[4] /* -p^-1 mod 2^32 */, ninv_m[4], ninv_m_p[4] /* n^-1 2^32 mod p and its quotient: undoes the 2^-32 of dot32_kernel2's Montgomery step */;
                      u32 ninv_mw[4][4], ninv_mw_p[4][4] /* ... times the last inverse stage's twiddle, per sub-block (ntt32_inv_kernel3, MONT) */; };
@@ -20,8 +23,6 @@ struct Aux32Head { Tw32 head[4], tail_sum[4], tail_dif[4];         // psi^brv(1)
 // table entries (2^t << S) + h 2^t + i.  The head and the tail of plain rows are passes of their own at this size (ntt32_head2_kernel,
 // ntt32_tail2_kernel: kernels_aux32.hip); the digit loader and rns32_reduce take the head in their loaders (the upper half of a padded
 // polynomial is zero, so the first head stage is a duplication and the second the x +- w y of the 2^15-point rows).
-// constants per prime for those passes: [0..2] head w0, w1a, w1b;  [4..7] tail 1/2, w1a^-1 / 2, w1b^-1 / 2, w0^-1 / 2
-static constexpr int A32_HT = 8;
 // the primes of the tensor half (kernels_tensor32.hip): up to 72 of them, passed by value like the four above
 static constexpr int T32_MAXP = 76;
 // mu61: floor(2^(32 + sh) / p) with sh = 29 for primes of 30 bits, sh = 28 for primes of 29 bits (t32_shift): the quotient estimate of a value
@@ -31,19 +32,42 @@ static constexpr int T32_MAXP = 76;
 // the inverse already multiplied by the CRT constant of their prime (which depends on the number of primes: per configuration, not per ring)
 struct T32Primes { u32 p[T32_MAXP], ninv[T32_MAXP], ninv_p[T32_MAXP], mu61[T32_MAXP], ninv_w[T32_MAXP], ninv_w_p[T32_MAXP]; u32 closing; };
 static constexpr u32 T32_ROWS_PLAIN = 0, T32_ROWS_CRT = 1;      // what a row of the tensor half's inverse holds: x / n, or x (M / p_i)^-1 / n
-__host__ __device__ __forceinline__ u32 t32_shift(u32 p) { return (p >> 29) ? 29u : 28u; }
+// a host vector into a fresh device buffer; false (and *d null or to be freed by its owner) when either step fails
+template <class T, class V>
+static inline bool a32_upload(T** d, const V& v) {
+  const size_t bytes = v.size() * sizeof(v[0]);
+  return hipMalloc((void**)d, bytes) == hipSuccess && hipMemcpy(*d, v.data(), bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+// The device copies of one hm::Ring32Tables, owned once for both users.  upload() fills fresh buffers and swaps them in only when every step has
+// succeeded (then it frees the old ones); on failure it frees what it allocated and the old tables stay in force.
+struct Ring32Dev {
+  Tw32* d_fwd = nullptr;               // [primes][2^S][2^14]  psi^brv(idx), idx = m + i (stage with m groups, group i), per sub-block
+  Tw32* d_inv = nullptr;               // [primes][2^S][2^14]  the inverses
+  Tw32* d_ht = nullptr;                // S >= 2: [primes][A32_HT] head / tail constants of the stand-alone passes of S = 2
+  u32* d_p = nullptr;                  // S >= 2: the primes
+  Tw32* d_hs = nullptr;                // S >= 3: [primes][2][A32_HSN(S)] head / tail twiddles of ntt32_headS_kernel / ntt32_tailS_kernel
+  void release() { hipFree(d_fwd); hipFree(d_inv); hipFree(d_ht); hipFree(d_p); hipFree(d_hs); *this = Ring32Dev(); }
+  int upload(const hm::Ring32Tables& t) {
+    Ring32Dev n;
+    const int S = t.k.S;
+    if (!(a32_upload(&n.d_fwd, t.fwd) && a32_upload(&n.d_inv, t.inv) && (S < 2 || (a32_upload(&n.d_ht, t.ht) && a32_upload(&n.d_p, t.k.primes))) &&
+          (S < 3 || a32_upload(&n.d_hs, t.hs)))) {
+      n.release();
+      FHESI_FAIL("30-bit rows: uploading the transform tables of %d primes failed", (int)t.k.primes.size());
+    }
+    release();
+    *this = n;
+    return 0;
+  }
+};
 struct fhesi_aux32 {
   Aux32Primes pr;
   Aux32Head hd;
   int S = 0;                           // log2 of the sub-transforms per row (0: rows of 2^14 elements, 1: rows of 2^15, 2: rows of 2^16, 3 .. 6: the simple path up to rows of 2^20)
-  Tw32* d_fwd = nullptr;               // [4][2^S][2^14]  psi^brv(idx), idx = m + i (stage with m groups, group i), per sub-block
-  Tw32* d_inv = nullptr;               // [4][2^S][2^14]  the inverses
-  Tw32* d_ht = nullptr;                // S = 2: [4][A32_HT] head / tail constants of the stand-alone passes
-  u32* d_p = nullptr;                  // S >= 2: the four primes
-  Tw32* d_hs = nullptr;                // S >= 3: [4][2][A32_HSN(S)] head / tail twiddles of ntt32_headS_kernel / ntt32_tailS_kernel
+  Ring32Dev tab;                       // the four primes' tables
 };
 
-static constexpr int A32_LOGN = 14, A32_N = 1 << A32_LOGN, A32_T = 512, A32_P = 592;      // LDS stride of a 512-element sub-problem (padded)
+static constexpr int A32_T = 512, A32_P = 592;      // LDS stride of a 512-element sub-problem (padded)
 __device__ __forceinline__ u32 a32_f(u32 t_id) { return t_id + ((t_id >> 5) << 2); }       // position inside a sub-problem (4 pad words per 32)
 __device__ __forceinline__ u32 mul_lazy32(u32 y, Tw32 t, u32 p) { return y * t.w - __umulhi(y, t.wp) * p; }     // y any 32-bit value -> [0, 2p)
 __device__ __forceinline__ int a32_bfly_k(int b, int h) { return ((b / h) * 2 * h) + (b % h); }
@@ -167,9 +191,7 @@ static __global__ void __launch_bounds__(256) ntt32_tail2_kernel(u32* __restrict
 // allowed, FHEContext.cpp:89, and every reference driver uses m = p - 1): the SIMPLE path -- head and tail stages as passes of their own over
 // materialised rows, 2^S sub-transforms of 2^14 points in between (the fused loaders stop at S = 2).  The first S stages of the row transform pair
 // elements 2^14 or more apart: for a fixed position e < 2^14 they are an S-stage network over the 2^S values v[h] = row[h 2^14 + e], entirely
-// inside one thread.  hs: per prime [2][A32_HSN(S)] -- direction 0: psi^brv(idx) (stage s, group i: idx = 2^s + i); direction 1: psi^-brv(idx)
-// and, at the end, the constants of the last inverse stage: 2^-S, psi^-brv(1) 2^-S, and both times 2^32 (rows that carry dot32's factor 2^-32).
-__host__ __device__ constexpr int A32_HSN(int S) { return (1 << S) + 4; }
+// inside one thread.  hs: per prime [2][A32_HSN(S)] (ring32_tables.h).
 template <int S>
 __device__ __forceinline__ void a32_head_net(u32 (&v)[1 << S], const Tw32* __restrict__ tw, u32 p) {
   const u32 twop = 2 * p;
@@ -261,18 +283,18 @@ static inline bool a32_row_launches(u32* rows, i64 nrows, int nslots, int S, F&&
   return true;
 }
 // The head stages of rows of 2^16 and longer (S >= 2) as a pass of their own, in place: row r belongs to prime a0 + r % nslots, nrows is a
-// multiple of nslots.  d_ht: the constants of S = 2 (ntt32_head2_kernel / ntt32_tail2_kernel), d_hs: the twiddles of S >= 3.  false: no such pass for this S
-static inline bool launch_ntt32_head_pass(hipStream_t stream, int S, u32* rows, i64 nrows, int nslots, int a0, const u32* d_p, const Tw32* d_ht, const Tw32* d_hs) {
+// multiple of nslots.  t.d_ht: the constants of S = 2 (ntt32_head2_kernel / ntt32_tail2_kernel), t.d_hs: the twiddles of S >= 3.  false: no such pass for this S
+static inline bool launch_ntt32_head_pass(hipStream_t stream, int S, u32* rows, i64 nrows, int nslots, int a0, const Ring32Dev& t) {
   return a32_row_launches(rows, nrows, nslots, S, [&](u32* rp, unsigned ny) {
-    if (S == 2) { ntt32_head2_kernel<<<dim3(16, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_ht); return true; }
-    return a32_with_S<3, 6>(S, [&](auto s) { ntt32_headS_kernel<decltype(s)::value><<<dim3(A32_N / 256, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_hs); });
+    if (S == 2) { ntt32_head2_kernel<<<dim3(16, ny), 256, 0, stream>>>(rp, nslots, a0, t.d_p, t.d_ht); return true; }
+    return a32_with_S<3, 6>(S, [&](auto s) { ntt32_headS_kernel<decltype(s)::value><<<dim3(A32_N / 256, ny), 256, 0, stream>>>(rp, nslots, a0, t.d_p, t.d_hs); });
   });
 }
 // ... and the tail stages of the inverse over the sub-inverses; mont: the rows carry dot32's factor 2^-32, undone here (S >= 3; at S = 2 the sub-inverses undo it)
-static inline bool launch_ntt32_tail_pass(hipStream_t stream, int S, u32* rows, i64 nrows, int nslots, int a0, const u32* d_p, const Tw32* d_ht, const Tw32* d_hs, int mont) {
+static inline bool launch_ntt32_tail_pass(hipStream_t stream, int S, u32* rows, i64 nrows, int nslots, int a0, const Ring32Dev& t, int mont) {
   return a32_row_launches(rows, nrows, nslots, S, [&](u32* rp, unsigned ny) {
-    if (S == 2) { ntt32_tail2_kernel<<<dim3(16, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_ht); return true; }
-    return a32_with_S<3, 6>(S, [&](auto s) { ntt32_tailS_kernel<decltype(s)::value><<<dim3(A32_N / 256, ny), 256, 0, stream>>>(rp, nslots, a0, d_p, d_hs, mont); });
+    if (S == 2) { ntt32_tail2_kernel<<<dim3(16, ny), 256, 0, stream>>>(rp, nslots, a0, t.d_p, t.d_ht); return true; }
+    return a32_with_S<3, 6>(S, [&](auto s) { ntt32_tailS_kernel<decltype(s)::value><<<dim3(A32_N / 256, ny), 256, 0, stream>>>(rp, nslots, a0, t.d_p, t.d_hs, mont); });
   });
 }
 
@@ -344,29 +366,8 @@ static constexpr int A32_HR = 16;                   // rows of the half buffer
 // The per-lane twiddles of the last four stages (table entries 1024 .. 16383) are stored in the ORDER THE WAVES LOAD THEM.  At
 // stage v (groups of 16 >> v ... distance 8 >> v) thread t needs the 2^(v+1) consecutive entries from (1024 << v) + (t << (v + 1)): in the natural
 // order a 16-byte load instruction of a wave touches 8 << v different 128-byte lines (64 at the last stage), 680 line requests per wave and
-// transform where 120 carry the same bytes.  The builders (a32_permute_phase_c, host side) transpose every wave's block so that load q of
+// transform where 120 carry the same bytes.  The builder (a32_permute_phase_c, ring32_tables.h) transposes every wave's block so that load q of
 // stage v reads 64 lanes x 16 contiguous bytes:  pair (t, q) of stage v  ->  position ((t >> 6) * 2^v + q) * 64 + (t & 63)  of that stage's region.
-// host side: every block of 2^14 entries (one per prime and sub-block) has its regions [1024 << v, 2048 << v), v = 0 .. 3, re-ordered
-// host side: out[idx] = psi^brv(idx) (with its Shoup word) for idx < 2^lg -- running powers in natural order scattered to their bit-reversed
-// slots, two 64-bit divisions per entry (p < 2^30).  (A power per entry cost 2.7 s on the first call of a ring with rows of 2^20.)
-static inline void a32_bitrev_powers(u64 p, u64 psi, int lg, std::vector<Tw32>& out) {
-  const u64 n = (u64)1 << lg;
-  u64 w = 1;
-  for (u64 e = 0; e < n; ++e) { out[hm::brv(e, lg)] = Tw32{(u32)w, (u32)((w << 32) / p)}; w = w * psi % p; }
-}
-static inline void a32_permute_phase_c(std::vector<Tw32>& t) {
-  std::vector<Tw32> tmp;
-  for (size_t base = 0; base + ((size_t)1 << 14) <= t.size(); base += (size_t)1 << 14)
-    for (int v = 0; v < 4; ++v) {
-      const size_t off = base + ((size_t)1024 << v), nq = (size_t)1 << v;      // nq 16-byte pairs per thread
-      tmp.assign(t.begin() + off, t.begin() + off + ((size_t)1024 << v));
-      for (size_t tid = 0; tid < 512; ++tid)
-        for (size_t q = 0; q < nq; ++q) {
-          const size_t src = tid * nq + q, dst = ((tid >> 6) * nq + q) * 64 + (tid & 63);
-          t[off + 2 * dst] = tmp[2 * src]; t[off + 2 * dst + 1] = tmp[2 * src + 1];
-        }
-    }
-}
 static constexpr int A32_TBL = 992;
 __device__ __forceinline__ u32 a32_tbl_pos(u32 e) {      // entry e (0 .. 991) of the phase-B table -> its LDS slot
   return e;

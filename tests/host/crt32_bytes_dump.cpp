@@ -1,5 +1,5 @@
 // crt32_bytes_dump.cpp -- TEST HARNESS (no GPU, no library): the operand tables of crt32_mfma_kernel as the library's own host routine builds them
-// (fhe-si_amd/csrc/crt32_bytes.h over hostbig.h), for the primes given on the command line; tests/test_crt32_mfma_model.py compares them with
+// (fhe-si_amd/csrc/crt32_bytes.h over the table rows of ring32_tables.h), for the primes given on the command line; tests/test_crt32_mfma_model.py compares them with
 // Python's integers and runs its model of the kernel on them.  Built by that test with -fsanitize=address,undefined.
 //   crt32_bytes_dump <prime> <prime> ...      (28-bit words, 38 per row, window of 21 words from word 16: the compiled shape)
 // Output: "d <slot> <a> <72 bytes>" for every slot and byte plane, then "aop <tile> <kstep> <lane> <4 words, hex>".
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../fhe-si_amd/csrc/crt32_bytes.h"
+#include "../../fhe-si_amd/csrc/ring32_tables.h"
 
 int main(int argc, char** argv) {
   const int R = 28, WT = 38, J0 = 16, NW = 21;
@@ -16,22 +17,9 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; ++i) primes.push_back(std::strtoull(argv[i], nullptr, 0));
   const int NP = (int)primes.size();
   if (NP < 32 || NP + 2 > hm::C32B_SLOTS) { std::fprintf(stderr, "32 .. 38 primes\n"); return 2; }
-  // the table rows as t32_config cuts them: M / p_i, and 2^(R WT) - M behind them
-  std::vector<uint32_t> Mw((size_t)(NP + 1) * WT);
-  hm::Big M{1};
-  for (int a = 0; a < NP; ++a) M = hm::bn_mul_small(M, primes[a]);
-  for (int a = 0; a < NP; ++a) {
-    hm::Big Mi{1};
-    for (int b = 0; b < NP; ++b) if (b != a) Mi = hm::bn_mul_small(Mi, primes[b]);
-    for (int l = 0; l < WT; ++l) Mw[(size_t)a * WT + l] = hm::bn_word(Mi, l, R);
-  }
-  {
-    hm::Big N(M);
-    N.resize((R * WT + 63) / 64 + 1, 0);
-    uint64_t carry = 1;
-    for (auto& w : N) { const uint64_t v = ~w + carry; carry = (carry && v == 0) ? 1 : 0; w = v; }
-    for (int l = 0; l < WT; ++l) Mw[(size_t)NP * WT + l] = hm::bn_word(N, l, R);
-  }
+  // the table rows from the library's own builder (ring32_tables.h, what t32_config uploads): M / p_i, and 2^(R WT) - M behind them
+  const std::vector<uint32_t> p32(primes.begin(), primes.end());
+  const std::vector<uint32_t> Mw = hm::crt32_mw(p32.data(), NP, R, WT);
   const hm::Crt32Bytes t = hm::crt32_bytes_build(Mw.data(), NP, WT, R, J0, NW);
   for (int s = 0; s < hm::C32B_SLOTS; ++s)
     for (int a = 0; a < 4; ++a) {

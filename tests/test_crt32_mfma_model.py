@@ -1,5 +1,6 @@
 """CPU: the arithmetic of crt32_mfma_kernel (fhe-si_amd/csrc/kernels_tensor32.hip) -- the fast pass of the tensor half's CRT as an int8 matrix
-product -- on the operand tables the library's own host routine builds (fhe-si_amd/csrc/crt32_bytes.h, printed by the stand-alone program
+product -- on the operand tables the library's own host routines build (fhe-si_amd/csrc/crt32_bytes.h over the table rows of hm::crt32_mw,
+fhe-si_amd/csrc/ring32_tables.h: the rows t32_config uploads, not a restatement of them; printed by the stand-alone program
 tests/host/crt32_bytes_dump.cpp, built here with -fsanitize=address,undefined), against Python's integers and against the model of
 crt32_scale_kernel<512, false, 28, 38, 0> in tests/test_crt32_fold_model.py.
 
