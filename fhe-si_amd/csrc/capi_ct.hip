@@ -58,7 +58,7 @@ extern "C" int fhesi_ct_mul_poly_dev(fhesi_ctx* c, int32_t logQ, uint64_t* ct, i
   FHESI_TRY(launch_rns_reduce(c, (const u64*)ct, nlimbs, n, count, nparts, nullptr, (u64*)d_rows, L, nullptr));
   FHESI_TRY(row_fwd(c, (u64*)d_rows, count * nparts, L, nullptr, all.data()));
   if (npoly == 1) {
-    for (i64 done = 0; done < count * nparts; done += 65535) FHESI_TRY(launch_rows_mul_bcast(c, (u64*)d_rows + (size_t)done * L * n, (const u64*)d_rows + (size_t)done * L * n, (const u64*)d_prow, std::min<i64>(65535, count * nparts - done)));
+    FHESI_TRY(grid_chunks(count * nparts, [&](i64 done, i64 cnt) { return launch_rows_mul_bcast(c, (u64*)d_rows + (size_t)done * L * n, (const u64*)d_rows + (size_t)done * L * n, (const u64*)d_prow, cnt); }));
   } else {
     for (i64 ci = 0; ci < count; ++ci) FHESI_TRY(launch_rows_mul_bcast(c, (u64*)d_rows + (size_t)ci * nparts * L * n, (const u64*)d_rows + (size_t)ci * nparts * L * n, (const u64*)d_prow + (size_t)ci * L * n, nparts));
   }
@@ -552,10 +552,9 @@ extern "C" int fhesi_ct_add_slots_dev(fhesi_ctx* c, fhesi_slots* s, int32_t logQ
   i64* d_msg = nullptr;
   FHESI_TRY(stage_msg_slots(c, s, vals_host, nvals, only_usable != 0, nv, &d_msg, "Ciphertext += slots"));
   const size_t n = (size_t)c->phim;
-  for (i64 done = 0; done < count; done += 65535) {
-    const i64 cnt = std::min<i64>(65535, count - done);
-    FHESI_TRY(launch_ct_add_const(c, (u64*)ct + (size_t)done * nparts * n * nlimbs, d_msg + (nv == 1 ? 0 : (size_t)done * n), nv == 1 ? 1 : (int)cnt, nparts, nlimbs, logQ, s->S.p, cnt));
-  }
+  FHESI_TRY(grid_chunks(count, [&](i64 done, i64 cnt) {
+    return launch_ct_add_const(c, (u64*)ct + (size_t)done * nparts * n * nlimbs, d_msg + (nv == 1 ? 0 : (size_t)done * n), nv == 1 ? 1 : (int)cnt, nparts, nlimbs, logQ, s->S.p, cnt);
+  }));
   HIP_TRY(hipStreamSynchronize(c->stream));        // vals_host may be released on return
   return 0;
 }

@@ -308,11 +308,6 @@ extern "C" int fhesi_ct_automorph_key_switch_dev(fhesi_ctx* c, const fhesi_ksk* 
 // sigma_k is a ring map, so  sum_j sigma_k(D_j(c)) W_k[j] = sigma_k( sum_j D_j(c) W'_k[j] )  with W'_k = sigma_k^-1(W_k), every column, both rows
 // (DESIGN.md 9a): the digits of the UNTOUCHED ciphertext are decomposed and transformed once and serve every rotation; a rotation is one dot
 // product with its derived matrix, one inverse, one recombination and the signed gather of two polynomials.
-static i64 inv_mod_m(i64 k, i64 m) {            // k in Z_m^* (checked by the caller)
-  i64 a = k % m, b = m, x0 = 1, x1 = 0;
-  while (b) { const i64 q = a / b; i64 t = a - q * b; a = b; b = t; t = x0 - q * x1; x0 = x1; x1 = t; }
-  return ((x0 % m) + m) % m;
-}
 extern "C" int fhesi_ksk_hoist(const fhesi_ksk* k, int64_t kk, fhesi_ksk** out) {
   if (!k || !out) FHESI_FAIL("ksk_hoist: null argument");
   fhesi_ctx* c = k->ctx;
@@ -323,7 +318,7 @@ extern "C" int fhesi_ksk_hoist(const fhesi_ksk* k, int64_t kk, fhesi_ksk** out) 
   fhesi_ksk* h;
   FHESI_TRY(fhesi_ksk_create(c, k->ncomp, k->ndigits, &h));
   // DoubleCRT::automorph by k^-1 on every evaluation row [2][ncol][L][phi(m)]: the same gather on every ring and for every prime
-  const i64 nrows = (i64)2 * k->ncomp * k->ndigits * c->L, kinv = inv_mod_m(kk, c->m), step = 32768;
+  const i64 nrows = (i64)2 * k->ncomp * k->ndigits * c->L, kinv = hm::inv_mod(kk, c->m), step = 32768;      // (k in Z_m^*: checked above)
   int rc = 0;
   for (i64 r0 = 0; r0 < nrows && !rc; r0 += step) rc = launch_automorph(c, h->d_rows + r0 * c->phim, k->d_rows + r0 * c->phim, std::min(step, nrows - r0), kinv);
   if (rc) { fhesi_ksk_free(h); return rc; }
@@ -735,11 +730,7 @@ extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const 
   void* d_msg;
   FHESI_TRY(ws_reserve(c, 5, n * 8, &d_msg));
   FHESI_TRY(slots_embed_rows(lin->slots, lin->d_bias, c->phim, false, 1, (i64*)d_msg));
-  for (i64 done = 0; done < count; done += 65535) {
-    const i64 cnt = std::min<i64>(65535, count - done);
-    FHESI_TRY(launch_ct_add_const(c, (u64*)out + (size_t)done * 2 * n * nlimbs, (const i64*)d_msg, 1, 2, nlimbs, logQ, lin->slots->S.p, cnt));
-  }
-  return 0;
+  return grid_chunks(count, [&](i64 done, i64 cnt) { return launch_ct_add_const(c, (u64*)out + (size_t)done * 2 * n * nlimbs, (const i64*)d_msg, 1, 2, nlimbs, logQ, lin->slots->S.p, cnt); });
 }
 
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).

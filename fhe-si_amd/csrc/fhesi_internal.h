@@ -8,12 +8,12 @@
 #include <string>
 #include <atomic>
 #include <vector>
+#include <algorithm>
+#include <type_traits>
 #include "hostbig.h"
+#include "ct_wide.h"                     // u64, i64, u128; reduce_limb and the multi-limb steps of kernels_ct.hip
 
-typedef uint64_t u64;
-typedef int64_t i64;
 typedef unsigned int u32;
-typedef unsigned __int128 u128;
 
 // --------------------------------------------------------------------------------- error plumbing
 void fhesi_set_error(const char* fmt, ...);
@@ -22,6 +22,30 @@ void fhesi_set_error(const char* fmt, ...);
 #define FHESI_OP_SET_ 4
 #define FHESI_WS_SLOTS 16
 #define FHESI_TRY(expr) do { int r__ = (expr); if (r__) return r__; } while (0)
+
+// --------------------------------------------------------------------------------- launch helpers
+// The kernels over multi-limb registers are compiled per limb class: f(std::integral_constant<int, C>{}) for the first C >= n of the ascending
+// list; the last class takes whatever is left (the launchers refuse what exceeds it).  One call, one argument list per launcher.
+template <int C, int... Rest, class F> static inline void with_limb_class(int n, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, C>{});
+  else if (n <= C) f(std::integral_constant<int, C>{});
+  else with_limb_class<Rest...>(n, f);
+}
+// A batch index on grid.y / grid.z: f(done, cnt) over count in launches of at most 65535 (f returns nothing, or an error code that ends the loop)
+constexpr long long kGridRows = 65535;
+template <class F> static inline int grid_chunks(long long count, F&& f) {
+  for (long long done = 0; done < count; done += kGridRows) {
+    const long long cnt = std::min(kGridRows, count - done);
+    if constexpr (std::is_void_v<decltype(f(done, cnt))>) f(done, cnt);
+    else FHESI_TRY(f(done, cnt));
+  }
+  return 0;
+}
+// ... or refused where a caller's chunks are smaller by construction: "<who>: more than 65535 <rows>"
+static inline int grid_y_ok(const char* who, const char* rows, long long count) {
+  if (count > kGridRows) FHESI_FAIL("%s: more than %lld %s", who, kGridRows, rows);
+  return 0;
+}
 
 // --------------------------------------------------------------------------------- per-prime device constants
 // One entry per chain prime (role of the reference's Cmodulus object, CModulus.h:42-61).
@@ -523,14 +547,7 @@ __device__ __forceinline__ u64 d_shoup(u64 y, u64 w, u64 wp, u64 q) {
   u64 r = d_shoup_lazy(y, w, wp, q);
   return r >= q ? r - q : r;
 }
-// Reduce (Util.cpp:3-26) of limb i of a value modulo 2^logQ: sign-extend from bit logQ-1 (sbit = that bit: the centred residue) or clear
-// everything from bit logQ upwards (sbit = 0: the positive residue).  The one limb rule of every run-time store loop.
-__device__ __forceinline__ u64 reduce_limb(u64 val, int i, int logQ, u64 sbit) {
-  const int bits_left = logQ - 64 * i;
-  if (bits_left <= 0) return sbit ? ~0ull : 0ull;
-  if (bits_left < 64) { const u64 mask = (1ull << bits_left) - 1; return sbit ? (val | ~mask) : (val & mask); }
-  return val;
-}
+// (reduce_limb, the limb rule of every run-time store loop: ct_wide.h)
 __device__ __forceinline__ u64 d_addmod(u64 a, u64 b, u64 q) { u64 s = a + b; return s >= q ? s - q : s; }
 __device__ __forceinline__ u64 d_submod(u64 a, u64 b, u64 q) { return a >= b ? a - b : a + q - b; }
 

@@ -22,6 +22,12 @@ inline bn_limb powmod(bn_limb a, bn_limb e, bn_limb q) {
   return r;
 }
 inline bn_limb invmod(bn_limb a, bn_limb q) { return powmod(a % q, q - 2, q); }      // q prime
+// k^-1 modulo any m >= 1 (extended Euclid; k of either sign), in [0, m); 0 when gcd(k, m) != 1
+inline int64_t inv_mod(int64_t k, int64_t m) {
+  int64_t a = ((k % m) + m) % m, b = m, x0 = 1, x1 = 0;
+  while (b) { const int64_t q = a / b; int64_t t = a - q * b; a = b; b = t; t = x0 - q * x1; x0 = x1; x1 = t; }
+  return a == 1 ? ((x0 % m) + m) % m : 0;
+}
 inline bool is_prime(bn_limb n) {
   static const bn_limb bases[] = {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37};   // deterministic below 3.3e24
   if (n < 2) return false;

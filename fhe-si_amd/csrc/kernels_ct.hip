@@ -5,29 +5,15 @@
 // ciphertexts (tProd) are residue rows [count][3][L][phi(m)].  All kernels are streaming (HBM-bound) integer work.
 #include "fhesi_internal.h"
 
-// (Reduce, Util.cpp:3-26, of one limb: reduce_limb in fhesi_internal.h)
+// (the multi-limb steps -- sum with carry, multiply by a word, negation, the centred store of Reduce, Util.cpp:3-26 -- are ct_wide.h's)
 // Ciphertext::operator+= for unscaled ciphertexts (Ciphertext.cpp:123-134): parts[i] += other.parts[i]; ReduceCoefficients
 template <int MAXNL>
 __global__ void __launch_bounds__(256) ct_add_kernel(u64* __restrict__ dst, const u64* __restrict__ src, i64 ncoeffs, int nl, int logQ) {
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= ncoeffs) return;
   u64 x[MAXNL];
-  u64 carry = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) {
-      const u64 a = dst[j * nl + i], b = src[j * nl + i];
-      const u64 s = a + b, s2 = s + carry;
-      carry = (s < a) | (s2 < s);
-      x[i] = s2;
-    }
-  u64 sb = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i == (logQ - 1) >> 6) sb = (x[i] >> ((logQ - 1) & 63)) & 1;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) dst[j * nl + i] = reduce_limb(x[i], i, logQ, sb);
+  ctw_sum(x, nl, 0, [=](int i) { return dst[j * nl + i]; }, [=](int i) { return src[j * nl + i]; });
+  ctw_store_centred(x, nl, logQ, dst + j * nl);
 }
 
 // CiphertextPart::operator*=(long) (Ciphertext.cpp:21-27): coefficient * l, Reduce.  Two's complement product mod 2^(64 nl)
@@ -37,39 +23,20 @@ __global__ void __launch_bounds__(256) ct_mul_long_kernel(u64* __restrict__ ct, 
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= ncoeffs) return;
   u64 x[MAXNL];
-  u64 carry = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) {
-      const u64 a = ct[j * nl + i];
-      const u64 lo = a * mag, hi = d_mulhi(a, mag);
-      const u64 s = lo + carry;
-      carry = hi + (s < lo);
-      x[i] = s;
-    }
-  if (negate) {
-    u64 c = 1;
-#pragma unroll
-    for (int i = 0; i < MAXNL; ++i)
-      if (i < nl) { const u64 v = ~x[i] + c; c = (c && v == 0); x[i] = v; }
-  }
-  u64 sb = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i == (logQ - 1) >> 6) sb = (x[i] >> ((logQ - 1) & 63)) & 1;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) ct[j * nl + i] = reduce_limb(x[i], i, logQ, sb);
+  ctw_muladd(x, nl, CtwNone{}, [=](int i) { return ct[j * nl + i]; }, mag);
+  if (negate) ctw_neg(x, nl);
+  ctw_store_centred(x, nl, logQ, ct + j * nl);
 }
 
+static int limbs_ok(const char* who, int nl) {
+  if (nl > 32) FHESI_FAIL("%s of %d limbs exceed the supported 32", who, nl);
+  return 0;
+}
 int launch_ct_add(fhesi_ctx* ctx, u64* d_dst, const u64* d_src, i64 ncoeffs, int nl, int logQ) {
   if (!ncoeffs) return 0;
-  if (nl > 32) FHESI_FAIL("ciphertext coefficients of %d limbs exceed the supported 32", nl);
+  FHESI_TRY(limbs_ok("ciphertext coefficients", nl));
   const unsigned grid = (unsigned)((ncoeffs + 255) / 256);
-  if (nl <= 2) ct_add_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_dst, d_src, ncoeffs, nl, logQ);
-  else if (nl <= 8) ct_add_kernel<8><<<grid, 256, 0, ctx->stream>>>(d_dst, d_src, ncoeffs, nl, logQ);
-  else if (nl <= 16) ct_add_kernel<16><<<grid, 256, 0, ctx->stream>>>(d_dst, d_src, ncoeffs, nl, logQ);
-  else ct_add_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_dst, d_src, ncoeffs, nl, logQ);
+  with_limb_class<2, 8, 16, 32>(nl, [&](auto C) { ct_add_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(d_dst, d_src, ncoeffs, nl, logQ); });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -128,41 +95,49 @@ __global__ void __launch_bounds__(256) ct_automorph_parts_kernel(const u64* __re
   const u64* __restrict__ a1 = in + (poly * n + j1) * nl_in;
   const u64* __restrict__ a2 = in + (poly * n + j2) * nl_in;
   const u64 ext1 = (a1[nl_in - 1] >> 63) ? ~0ull : 0ull, ext2 = (a2[nl_in - 1] >> 63) ? ~0ull : 0ull;
-  u64 carry = (s1 < 0 ? 1 : 0) + (s2 < 0 ? 1 : 0);                  // the +1 of every two's complement negation
+  u64 carry = ctw_neg_carry(s1, s2);
   u64* __restrict__ o = logQ ? out + poly * nlq * n + i : out + (poly * n + i) * nlq;
   for (int w = 0; w < nlq; ++w) {
-    u64 x1 = w < nl_in ? a1[w] : ext1, x2 = w < nl_in ? a2[w] : ext2;
-    x1 = s1 == 0 ? 0 : (s1 < 0 ? ~x1 : x1);
-    x2 = s2 == 0 ? 0 : (s2 < 0 ? ~x2 : x2);
+    const u64 x1 = ctw_signed(w < nl_in ? a1[w] : ext1, s1), x2 = ctw_signed(w < nl_in ? a2[w] : ext2, s2);
     const u128 sum = (u128)x1 + x2 + carry;
     u64 v = (u64)sum;
     carry = (u64)(sum >> 64);
     if (logQ) {
       const int bits_left = logQ - 64 * w;
-      if (bits_left < 64) v &= ((u64)1 << bits_left) - 1;
+      if (bits_left < 64) v &= ((u64)1 << bits_left) - 1;      // (reduce_limb's rule, spelled out: through it the kernel timed above the parent, profiles/ct_wide_refactor_ab.txt)
       o[(i64)w * n] = v;
     } else o[w] = v;
   }
+}
+// which signed gather the ring has: mode 0 power of two, 1 m = 2 q^k, 2 m = q^k, st = the stride q^(k-1); false: none
+static bool ring_gather(const fhesi_ctx* ctx, int* mode, i64* st) {
+  const i64 m = ctx->m;
+  *st = 1;
+  if (ctx->pow2) { *mode = 0; return true; }
+  const i64 qq = hm::prime_power_ring(m, nullptr);
+  if (!qq) return false;
+  *mode = (m & 1) ? 2 : 1;
+  *st = ((m & 1) ? m : m / 2) / qq;
+  return true;
+}
+// (k mod m, k^-1 mod m) of an automorphism, both in [0, m)
+static int gather_key(const fhesi_ctx* ctx, i64 k, i64* kk, i64* kinv) {
+  *kk = ((k % ctx->m) + ctx->m) % ctx->m;
+  *kinv = hm::inv_mod(k, ctx->m);
+  if (!*kinv) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)k);
+  return 0;
 }
 // 0 = launched; 2 = this ring / exponent is not covered (the caller keeps the evaluation-form path)
 int launch_ct_automorph_parts(fhesi_ctx* ctx, const u64* d_in, int nl_in, i64 npolys, i64 kk, int logQ, u64* d_parts, int nlq) {
   const i64 m = ctx->m, n = ctx->phim;
   int mode;
-  i64 st = 1;                         // the stride q^(k-1) of m = q^k, 2 q^k
-  if (ctx->pow2) mode = 0;
-  else if (const i64 qq = hm::prime_power_ring(m, nullptr)) { mode = (m & 1) ? 2 : 1; st = ((m & 1) ? m : m / 2) / qq; }
-  else return 2;
+  i64 st, kinv;
+  if (!ring_gather(ctx, &mode, &st)) return 2;
   if (!npolys) return 0;
-  // k^-1 mod m (k in Z_m^*: checked by the caller)
-  i64 kinv = 0;
-  {
-    i64 a = kk % m, b = m, x0 = 1, x1 = 0;
-    while (b) { const i64 qq = a / b; i64 t = a - qq * b; a = b; b = t; t = x0 - qq * x1; x0 = x1; x1 = t; }
-    if (a != 1) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)kk);
-    kinv = ((x0 % m) + m) % m;
-  }
+  FHESI_TRY(grid_y_ok("automorph", "polynomials per call", npolys));
+  FHESI_TRY(gather_key(ctx, kk, &kk, &kinv));
   dim3 grid((unsigned)((n + 255) / 256), (unsigned)npolys);
-  ct_automorph_parts_kernel<<<grid, 256, 0, ctx->stream>>>(d_in, n, nl_in, m, kk % m, kinv, mode, st, logQ, d_parts, nlq);
+  ct_automorph_parts_kernel<<<grid, 256, 0, ctx->stream>>>(d_in, n, nl_in, m, kk, kinv, mode, st, logQ, d_parts, nlq);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -190,54 +165,37 @@ __global__ void __launch_bounds__(256) ct_rot_sum_kernel(const RotSumKeys keys, 
     automorph_sources(i, n, m, keys.k[t], keys.kinv[t], mode, st, j1, s1, j2, s2);
     const u64* __restrict__ a1 = pre + t * term_stride + (poly * n + j1) * nl;
     const u64* __restrict__ a2 = pre + t * term_stride + (poly * n + j2) * nl;
-    const u64 f1 = s1 < 0 ? ~0ull : 0ull, f2 = s2 < 0 ? ~0ull : 0ull;      // a negated term: ~a + 1
-    const u64 k1 = s1 ? ~0ull : 0ull, k2 = s2 ? ~0ull : 0ull;              // an absent term: 0
-    u64 carry = (s1 < 0 ? 1 : 0) + (s2 < 0 ? 1 : 0);
+    u64 carry = ctw_neg_carry(s1, s2);
 #pragma unroll
     for (int w = 0; w < MAXNL; ++w)
       if (w < nl) {
-        const u64 x1 = (a1[w] ^ f1) & k1, x2 = (a2[w] ^ f2) & k2;
-        const u128 sum = (u128)x[w] + x1 + x2 + carry;
+        const u128 sum = (u128)x[w] + ctw_signed(a1[w], s1) + ctw_signed(a2[w], s2) + carry;
         x[w] = (u64)sum;
         carry = (u64)(sum >> 64);
       }
   }
-  u64 sb = 0;
-#pragma unroll
-  for (int w = 0; w < MAXNL; ++w)
-    if (w == (logQ - 1) >> 6) sb = (x[w] >> ((logQ - 1) & 63)) & 1;
-#pragma unroll
-  for (int w = 0; w < MAXNL; ++w)
-    if (w < nl) out[at + w] = reduce_limb(x[w], w, logQ, sb);
+  ctw_store_centred(x, nl, logQ, out + at);
 }
 // 0 = launched (nk > kRotSumMax terms: a chain of launches with base = out); 2 = this ring is not covered (the caller runs the composition).
-// ks in Z_m^* and nl in 1..32 holding logQ: checked by the caller; npolys <= 65535.
+// ks in Z_m^* and nl >= 1 holding logQ: checked by the caller.
 int launch_ct_rot_sum(fhesi_ctx* ctx, const i64* ks, int nk, int logQ, const u64* d_base, const u64* d_pre, i64 term_stride, i64 npolys, int nl, u64* d_out) {
   const i64 m = ctx->m, n = ctx->phim;
   int mode;
-  i64 st = 1;
-  if (ctx->pow2) mode = 0;
-  else if (const i64 qq = hm::prime_power_ring(m, nullptr)) { mode = (m & 1) ? 2 : 1; st = ((m & 1) ? m : m / 2) / qq; }
-  else return 2;
+  i64 st;
+  if (!ring_gather(ctx, &mode, &st)) return 2;
   if (!npolys || nk < 1) return 0;
   if (nl < 1 || nl > 32) FHESI_FAIL("ciphertext coefficients of %d limbs exceed the supported 32", nl);
+  FHESI_TRY(grid_y_ok("ct_rot_sum", "polynomials per call", npolys));
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)npolys);
   for (int t0 = 0; t0 < nk; t0 += kRotSumMax) {
     const int nt = nk - t0 < kRotSumMax ? nk - t0 : kRotSumMax;
     RotSumKeys keys{};
-    for (int t = 0; t < nt; ++t) {
-      i64 a = ks[t0 + t] % m, b = m, x0 = 1, x1 = 0;
-      while (b) { const i64 qq = a / b; i64 r = a - qq * b; a = b; b = r; r = x0 - qq * x1; x0 = x1; x1 = r; }
-      if (a != 1) FHESI_FAIL("automorph: k=%lld is not in Zm*", (long long)ks[t0 + t]);
-      keys.k[t] = ks[t0 + t] % m;
-      keys.kinv[t] = ((x0 % m) + m) % m;
-    }
+    for (int t = 0; t < nt; ++t) FHESI_TRY(gather_key(ctx, ks[t0 + t], &keys.k[t], &keys.kinv[t]));
     const u64* base = t0 ? d_out : d_base;
     const u64* pre = d_pre + (i64)t0 * term_stride;
-    if (nl <= 2) ct_rot_sum_kernel<2><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
-    else if (nl <= 8) ct_rot_sum_kernel<8><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
-    else if (nl <= 16) ct_rot_sum_kernel<16><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
-    else ct_rot_sum_kernel<32><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
+    with_limb_class<2, 8, 16, 32>(nl, [&](auto C) {
+      ct_rot_sum_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(keys, nt, base, pre, term_stride, n, nl, m, mode, st, logQ, d_out);
+    });
     HIP_TRY(hipGetLastError());
   }
   return 0;
@@ -245,78 +203,40 @@ int launch_ct_rot_sum(fhesi_ctx* ctx, const i64* ks, int nk, int logQ, const u64
 
 int launch_ct_mul_long(fhesi_ctx* ctx, u64* d_ct, i64 ncoeffs, int nl, int logQ, i64 l) {
   if (!ncoeffs) return 0;
-  if (nl > 32) FHESI_FAIL("ciphertext coefficients of %d limbs exceed the supported 32", nl);
+  FHESI_TRY(limbs_ok("ciphertext coefficients", nl));
   const u64 mag = l < 0 ? (u64)(-(l + 1)) + 1 : (u64)l;
   const int neg = l < 0;
   const unsigned grid = (unsigned)((ncoeffs + 255) / 256);
-  if (nl <= 2) ct_mul_long_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_ct, ncoeffs, nl, logQ, mag, neg);
-  else if (nl <= 8) ct_mul_long_kernel<8><<<grid, 256, 0, ctx->stream>>>(d_ct, ncoeffs, nl, logQ, mag, neg);
-  else if (nl <= 16) ct_mul_long_kernel<16><<<grid, 256, 0, ctx->stream>>>(d_ct, ncoeffs, nl, logQ, mag, neg);
-  else ct_mul_long_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_ct, ncoeffs, nl, logQ, mag, neg);
+  with_limb_class<2, 8, 16, 32>(nl, [&](auto C) { ct_mul_long_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(d_ct, ncoeffs, nl, logQ, mag, neg); });
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
 // ---- Ciphertext::operator+=(const ZZX&) on unscaled ciphertexts (Ciphertext.cpp:147-156): scaledConstant_j = (other_j << logQ) / p
-// with NTL's floor division, parts[0] += scaledConstant, ReduceCoefficients.  poly: [npoly][n] machine-word coefficients (npoly = 1:
-// one constant for the whole batch).  Only the quotient modulo 2^logQ matters; it is formed limb by limb from the top by 128 / 64-bit
-// long division of |other_j| 2^logQ, and a negative constant takes -(q + [remainder != 0]) (floor, not truncation).
+// with NTL's floor division (ctw_floor_quotient), parts[0] += scaledConstant, ReduceCoefficients.  poly: [npoly][n] machine-word coefficients (npoly = 1:
+// one constant for the whole batch).  Only the quotient modulo 2^logQ matters.
 template <int MAXNL>
 __global__ void __launch_bounds__(256) ct_add_const_kernel(u64* __restrict__ ct, const i64* __restrict__ poly, int npoly, i64 n, int nparts, int nl, int logQ,
                                                            u64 p) {
   const i64 c = blockIdx.y;
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const i64 cv = poly[(npoly == 1 ? 0 : c) * n + j];
-  const u64 mag = cv < 0 ? (u64)(-(cv + 1)) + 1 : (u64)cv;
-  // |cv| 2^logQ occupies limbs sh .. sh + 1 (sh = logQ / 64), shifted by logQ % 64 bits
-  const int sh = logQ >> 6, bs = logQ & 63;
-  const u64 lo = bs ? mag << bs : mag, hi = bs ? mag >> (64 - bs) : 0;
   u64 q[MAXNL];
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i) q[i] = 0;
-  u64 rem = 0;
-  for (int i = sh + 1; i >= 0; --i) {
-    const u64 limb = i == sh + 1 ? hi : (i == sh ? lo : 0);
-    const u128 cur = ((u128)rem << 64) | limb;
-    const u64 ql = (u64)(cur / p);
-    rem = (u64)(cur % p);
-#pragma unroll
-    for (int t = 0; t < MAXNL; ++t) if (t == i) q[t] = ql;       // (limbs at or above nl only matter modulo 2^logQ: dropped)
-  }
-  if (cv < 0) {
-    // -(q + (rem != 0)) in two's complement
-    u64 carry = rem != 0;
-#pragma unroll
-    for (int t = 0; t < MAXNL; ++t) { const u64 v = q[t] + carry; carry = v < carry; q[t] = v; }
-    u64 cneg = 1;
-#pragma unroll
-    for (int t = 0; t < MAXNL; ++t) { const u64 v = ~q[t] + cneg; cneg = (cneg && v == 0); q[t] = v; }
-  }
+  ctw_floor_quotient(q, poly[(npoly == 1 ? 0 : c) * n + j], logQ, p);
   u64* x0 = ct + ((c * nparts) * n + j) * nl;                     // part 0 of ciphertext c
   u64 x[MAXNL];
-  u64 carry = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) { const u64 a = x0[i], s1 = a + q[i], s2 = s1 + carry; carry = (s1 < a) | (s2 < s1); x[i] = s2; }
-  u64 sb = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i == (logQ - 1) >> 6) sb = (x[i] >> ((logQ - 1) & 63)) & 1;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) x0[i] = reduce_limb(x[i], i, logQ, sb);
+  ctw_sum(x, nl, 0, [=](int i) { return x0[i]; }, [&](int i) { return q[i]; });
+  ctw_store_centred(x, nl, logQ, x0);
 }
 int launch_ct_add_const(fhesi_ctx* ctx, u64* d_ct, const i64* d_poly, int npoly, int nparts, int nl, int logQ, u64 p, i64 count) {
   if (!count) return 0;
-  if (nl > 32) FHESI_FAIL("ciphertext coefficients of %d limbs exceed the supported 32", nl);
-  if (count > 65535) FHESI_FAIL("Ciphertext += ZZX: more than 65535 ciphertexts per call");
+  FHESI_TRY(limbs_ok("ciphertext coefficients", nl));
+  FHESI_TRY(grid_y_ok("Ciphertext += ZZX", "ciphertexts per call", count));
   const dim3 grid((unsigned)((ctx->phim + 255) / 256), (unsigned)count);
-  // (the quotient needs limbs 0 .. logQ / 64 + 1 <= nl + 1: the instantiation one step above nl holds them)
-  if (nl < 2) ct_add_const_kernel<4><<<grid, 256, 0, ctx->stream>>>(d_ct, d_poly, npoly, ctx->phim, nparts, nl, logQ, p);
-  else if (nl < 7) ct_add_const_kernel<8><<<grid, 256, 0, ctx->stream>>>(d_ct, d_poly, npoly, ctx->phim, nparts, nl, logQ, p);
-  else if (nl < 15) ct_add_const_kernel<16><<<grid, 256, 0, ctx->stream>>>(d_ct, d_poly, npoly, ctx->phim, nparts, nl, logQ, p);
-  else ct_add_const_kernel<34><<<grid, 256, 0, ctx->stream>>>(d_ct, d_poly, npoly, ctx->phim, nparts, nl, logQ, p);
+  // (the quotient needs limbs 0 .. logQ / 64 + 1 <= nl + 1: the class of nl + 2 holds them)
+  with_limb_class<4, 8, 16, 34>(nl + 2, [&](auto C) {
+    ct_add_const_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(d_ct, d_poly, npoly, ctx->phim, nparts, nl, logQ, p);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -331,10 +251,7 @@ int launch_gather(fhesi_ctx* ctx, const u64* d_pool, const int* d_idx, i64 count
   if (!count || !words) return 0;
   unsigned gx = (unsigned)((words + 255) / 256);
   if (gx > 256) gx = 256;
-  for (i64 done = 0; done < count; done += 65535) {
-    const i64 cnt = count - done < 65535 ? count - done : 65535;
-    gather_kernel<<<dim3(gx, (unsigned)cnt), 256, 0, ctx->stream>>>(d_pool, d_idx + done, d_out + done * words, words);
-  }
+  grid_chunks(count, [&](i64 done, i64 cnt) { gather_kernel<<<dim3(gx, (unsigned)cnt), 256, 0, ctx->stream>>>(d_pool, d_idx + done, d_out + done * words, words); });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -360,11 +277,10 @@ int launch_segment_sum(fhesi_ctx* ctx, const u64* d_in, const int* d_seg, i64 ng
   if (!ngroups) return 0;
   unsigned gx = (unsigned)((ctx->phim + 255) / 256);
   if (gx > 64) gx = 64;
-  for (i64 done = 0; done < ngroups; done += 65535) {
-    const i64 cnt = ngroups - done < 65535 ? ngroups - done : 65535;
+  grid_chunks(ngroups, [&](i64 done, i64 cnt) {
     segment_sum_kernel<<<dim3(gx, (unsigned)(ncomp * ctx->L), (unsigned)cnt), 256, 0, ctx->stream>>>(
         d_in, d_seg + done, d_out + done * ncomp * ctx->L * ctx->phim, ncomp * ctx->L, ctx->phim, ctx->d_pc, ctx->L);
-  }
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -390,12 +306,10 @@ int launch_encrypt_combine(fhesi_ctx* ctx, const u64* d_rows, const u64* d_pk, i
   if (!count) return 0;
   unsigned gx = (unsigned)((ctx->phim + 255) / 256);
   if (gx > 64) gx = 64;
-  for (i64 done = 0; done < count; done += 65535) {
-    const i64 cnt = count - done < 65535 ? count - done : 65535;
+  grid_chunks(count, [&](i64 done, i64 cnt) {
     encrypt_combine_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_rows + done * 3 * ctx->L * ctx->phim, d_pk,
-                                                                                               d_out + done * 2 * ctx->L * ctx->phim,
-                                                                                              ctx->L, ctx->phim, ctx->d_pc);
-  }
+                                                                                               d_out + done * 2 * ctx->L * ctx->phim, ctx->L, ctx->phim, ctx->d_pc);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -408,38 +322,17 @@ __global__ void __launch_bounds__(256) add_scaled_msg_kernel(u64* __restrict__ c
   const i64 c = blockIdx.y;
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const u64 mv = (u64)msg[c * n + j];
   u64* x = ct + ((c * 2) * n + j) * nl;
   u64 v[MAXNL];
-  u64 mc = 0, ac = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) {
-      const u64 dl = delta[i];
-      const u64 lo = dl * mv, hi = d_mulhi(dl, mv);
-      const u64 pr = lo + mc;
-      mc = hi + (pr < lo);
-      const u64 a = x[i], s = a + pr, s2 = s + ac;
-      ac = (s < a) | (s2 < s);
-      v[i] = s2;
-    }
-  u64 sb = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i == (logQ - 1) >> 6) sb = (v[i] >> ((logQ - 1) & 63)) & 1;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) x[i] = reduce_limb(v[i], i, logQ, sb);
+  ctw_muladd(v, nl, [=](int i) { return x[i]; }, [=](int i) { return delta[i]; }, (u64)msg[c * n + j]);
+  ctw_store_centred(v, nl, logQ, x);
 }
 int launch_add_scaled_msg(fhesi_ctx* ctx, u64* d_ct, const i64* d_msg, const u64* d_delta, i64 count, int nl, int logQ) {
   if (!count) return 0;
-  if (nl > 32) FHESI_FAIL("ciphertext coefficients of %d limbs exceed the supported 32", nl);
+  FHESI_TRY(limbs_ok("ciphertext coefficients", nl));
+  FHESI_TRY(grid_y_ok("Encrypt", "plaintexts per call", count));
   const dim3 grid((unsigned)((ctx->phim + 255) / 256), (unsigned)count);
-  if (count > 65535) FHESI_FAIL("Encrypt: more than 65535 plaintexts per call");
-  if (nl <= 2) add_scaled_msg_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_ct, d_msg, d_delta, ctx->phim, nl, logQ);
-  else if (nl <= 8) add_scaled_msg_kernel<8><<<grid, 256, 0, ctx->stream>>>(d_ct, d_msg, d_delta, ctx->phim, nl, logQ);
-  else if (nl <= 16) add_scaled_msg_kernel<16><<<grid, 256, 0, ctx->stream>>>(d_ct, d_msg, d_delta, ctx->phim, nl, logQ);
-  else add_scaled_msg_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_ct, d_msg, d_delta, ctx->phim, nl, logQ);
+  with_limb_class<2, 8, 16, 32>(nl, [&](auto C) { add_scaled_msg_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(d_ct, d_msg, d_delta, ctx->phim, nl, logQ); });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -457,107 +350,35 @@ int launch_decrypt_dot(fhesi_ctx* ctx, const u64* d_rows, const u64* d_t, i64 co
   if (!count) return 0;
   unsigned gx = (unsigned)((ctx->phim + 255) / 256);
   if (gx > 64) gx = 64;
-  for (i64 done = 0; done < count; done += 65535) {
-    const i64 cnt = count - done < 65535 ? count - done : 65535;
+  grid_chunks(count, [&](i64 done, i64 cnt) {
     decrypt_dot_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_rows + done * 2 * ctx->L * ctx->phim, d_t,
-                                                                                           d_out + done * ctx->L * ctx->phim, ctx->L,
-                                                                                          ctx->phim, ctx->d_pc);
-  }
+                                                                                           d_out + done * ctx->L * ctx->phim, ctx->L, ctx->phim, ctx->d_pc);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// ---- the rounding of Decrypt (FHE-SI.cpp:110-116): m = floor((2 p z + q) / (2 q)) mod p, q = 2^logQ.
-// Writing z = zh * 2q + zl with zl = z mod 2q in [0, 2q) gives floor(...) = 2 p zh + floor((2 p zl + q) / 2q), and the first
-// term vanishes modulo p: only the low logQ+1 bits of z matter, and the quotient is at most 2p.
+// ---- the rounding of Decrypt (FHE-SI.cpp:110-116): m = floor((2 p z + q) / (2 q)) mod p, q = 2^logQ (round_product, round_quotient: ct_wide.h).
 // z: [npolys][n][nw] two's complement truncated to nw = ceil((logQ+1)/64) limbs; out: [npolys][n]
-// limbs 0 .. nw-1 of 2 p zl + q in P, limb nw in `carry`
-template <int MAXNL>
-__device__ __forceinline__ void round_product(const u64* __restrict__ z, i64 j, int nw, int logQ, u64 p, u64 (&P)[MAXNL + 1], u64& carry) {
-  const int top_bits = logQ + 1 - 64 * (nw - 1);                  // bits of zl in its top limb (1..64)
-  const u64 twop = 2 * p;
-  carry = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i) {
-    P[i] = 0;
-    if (i < nw) {
-      u64 xi = z[j * nw + i];
-      if (i == nw - 1 && top_bits < 64) xi &= (1ull << top_bits) - 1;
-      const u64 lo = xi * twop, hi = d_mulhi(xi, twop);
-      const u64 s = lo + carry;
-      carry = hi + (s < lo);
-      P[i] = s;
-    }
-  }
-  // limb nw of the product is `carry`; add q = 2^logQ with carry propagation
-  const int wq = logQ >> 6;
-  u64 add = 1ull << (logQ & 63);
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nw && i >= wq) { const u64 s = P[i] + add; add = s < add; P[i] = s; }
-  carry += add;
-}
-// bits from logQ+1 upward: at most 2p, fits one word
-template <int MAXNL>
-__device__ __forceinline__ u64 round_quotient(const u64 (&P)[MAXNL + 1], u64 carry, int nw, int logQ) {
-  const int ws = (logQ + 1) >> 6, bs = (logQ + 1) & 63;
-  u64 lo = 0, hi = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i) {
-    if (i == ws) lo = (i < nw) ? P[i] : carry;
-    if (i == ws + 1) hi = (i < nw) ? P[i] : (i == nw ? carry : 0);
-  }
-  if (ws == MAXNL) lo = carry;
-  if (ws + 1 == MAXNL) hi = (nw == MAXNL) ? carry : hi;
-  return bs ? ((lo >> bs) | (hi << (64 - bs))) : lo;
-}
 template <int MAXNL>
 __global__ void __launch_bounds__(256) decrypt_round_kernel(const u64* __restrict__ z, i64 total, int nw, int logQ, u64 p, i64* __restrict__ out) {
   const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= total) return;
-  u64 P[MAXNL + 1];
+  u64 P[MAXNL];
   u64 carry;
-  round_product<MAXNL>(z, j, nw, logQ, p, P, carry);
-  out[j] = (i64)(round_quotient<MAXNL>(P, carry, nw, logQ) % p);
+  round_product(z, j, nw, logQ, p, P, carry);
+  out[j] = (i64)(round_quotient(P, carry, nw, logQ) % p);
 }
 int launch_decrypt_round(fhesi_ctx* ctx, const u64* d_z, i64 total, int nw, int logQ, u64 p, i64* d_out) {
   if (!total) return 0;
   if (nw > 32) FHESI_FAIL("Decrypt: logQ=%d exceeds the supported 2047 bits", logQ);
   const unsigned grid = (unsigned)((total + 255) / 256);
-  if (nw <= 2) decrypt_round_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
-  else if (nw <= 9) decrypt_round_kernel<9><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
-  else if (nw <= 17) decrypt_round_kernel<17><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
-  else decrypt_round_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out);
+  with_limb_class<2, 9, 17, 32>(nw, [&](auto C) { decrypt_round_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(d_z, total, nw, logQ, p, d_out); });
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// ---- the noise of a ciphertext, from the same product: P = (2 p z + q) mod 2q is the remainder the rounding above throws away, r = P - q in
-// [-q, q) the decryption residual (invariant noise v = r / 2q in [-1/2, 1/2)).  |r| takes logQ+1 bits, nw limbs as z does: bit logQ of P set
-// means r >= 0 and |r| is P with that bit cleared; otherwise |r| = q - P, which is q at the half-way point P = 0.
-// The residual equals the true noise only while the true noise is below 1/2: past that the message has already rounded to a neighbour and the
-// residual measured is the distance to THAT message, so a budget of 0 reads "at or within one bit of failure", never "failed by this much".
-template <int MAXNL>
-__device__ __forceinline__ void round_residual(const u64 (&P)[MAXNL + 1], int nw, int logQ, u64 (&a)[MAXNL]) {
-  const int wq = logQ >> 6;                                       // (= nw - 1: the limb of bit logQ is the top limb)
-  const u64 qbit = 1ull << (logQ & 63), top_mask = (qbit << 1) - 1;
-  u64 nonneg = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i == wq) nonneg = P[i] & qbit;
-  u64 borrow = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i) {
-    a[i] = 0;
-    if (i < nw) {
-      const u64 x = i == wq ? P[i] & top_mask : P[i];             // limb i of P mod 2q
-      const u64 qi = i == wq ? qbit : 0;
-      const u64 d = qi - x, d2 = d - borrow;
-      borrow = (qi < x) | (d < borrow);
-      a[i] = nonneg ? (i == wq ? x & ~qbit : x) : d2;
-    }
-  }
-}
+// ---- the noise of a ciphertext, from the same product: the maximum over the coefficients of |r|, r = (2 p z + q) mod 2q - q (round_residual, ct_wide.h).
 // Exact maximum of the block's nw-limb values without a multi-limb shuffle: the limbs are walked from the top, each round takes the 64-bit
 // maximum over the threads still level with the maximum so far (wave64 shuffles, then LDS across the waves), and the threads below it drop out.
 // Ties are harmless: tied threads hold the same limbs.  Thread 0 writes the nw limbs to `out`; every thread returns the maximum's bit length.
@@ -592,14 +413,13 @@ __global__ void __launch_bounds__(256) decrypt_noise_kernel(const u64* __restric
   const i64 c = blockIdx.y;
   const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
   u64 a[MAXNL];
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i) a[i] = 0;
+  ctw_zero(a);
   if (j < n) {
-    u64 P[MAXNL + 1];
+    u64 P[MAXNL];
     u64 carry;
-    round_product<MAXNL>(z, c * n + j, nw, logQ, p, P, carry);
-    if (msg) msg[c * n + j] = (i64)(round_quotient<MAXNL>(P, carry, nw, logQ) % p);
-    round_residual<MAXNL>(P, nw, logQ, a);
+    round_product(z, c * n + j, nw, logQ, p, P, carry);
+    if (msg) msg[c * n + j] = (i64)(round_quotient(P, carry, nw, logQ) % p);
+    round_residual(P, nw, logQ, a);
   }
   block_limb_max<MAXNL, 4>(a, nw, part + (c * gridDim.x + blockIdx.x) * nw);
 }
@@ -610,8 +430,7 @@ __global__ void __launch_bounds__(64) noise_budget_kernel(const u64* __restrict_
                                                           int* __restrict__ budget) {
   const i64 c = blockIdx.x;
   u64 a[MAXNL];
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i) a[i] = 0;
+  ctw_zero(a);
   for (int g = threadIdx.x; g < np; g += 64) {
     const u64* x = part + (c * np + g) * nw;
     u64 v[MAXNL];
@@ -633,20 +452,13 @@ __global__ void __launch_bounds__(64) noise_budget_kernel(const u64* __restrict_
 int launch_decrypt_noise(fhesi_ctx* ctx, const u64* d_z, i64 count, int nw, int logQ, u64 p, i64* d_msg, u64* d_part, u64* d_maxres, int* d_budget) {
   if (!count) return 0;
   if (nw > 32) FHESI_FAIL("Decrypt: logQ=%d exceeds the supported 2047 bits", logQ);
-  if (count > 65535) FHESI_FAIL("Decrypt: more than 65535 ciphertexts per launch");
+  FHESI_TRY(grid_y_ok("Decrypt", "ciphertexts per launch", count));
   const i64 n = ctx->phim, np = noise_blocks(ctx);
-  {
-    const dim3 grid((unsigned)np, (unsigned)count);
-    if (nw <= 2) decrypt_noise_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
-    else if (nw <= 9) decrypt_noise_kernel<9><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
-    else if (nw <= 17) decrypt_noise_kernel<17><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
-    else decrypt_noise_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
-  }
-  const unsigned grid = (unsigned)count;
-  if (nw <= 2) noise_budget_kernel<2><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
-  else if (nw <= 9) noise_budget_kernel<9><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
-  else if (nw <= 17) noise_budget_kernel<17><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
-  else noise_budget_kernel<32><<<grid, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
+  with_limb_class<2, 9, 17, 32>(nw, [&](auto C) {
+    constexpr int N = decltype(C)::value;
+    decrypt_noise_kernel<N><<<dim3((unsigned)np, (unsigned)count), 256, 0, ctx->stream>>>(d_z, n, nw, logQ, p, d_msg, d_part);
+    noise_budget_kernel<N><<<(unsigned)count, 64, 0, ctx->stream>>>(d_part, (int)np, nw, logQ, d_maxres, d_budget);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -665,7 +477,7 @@ __global__ void __launch_bounds__(256) rows_mul_bcast_kernel(u64* __restrict__ d
 }
 int launch_rows_mul_bcast(fhesi_ctx* ctx, u64* d_dst, const u64* d_a, const u64* d_t, i64 ncols) {
   if (!ncols) return 0;
-  if (ncols > 65535) FHESI_FAIL("KeySwitchSI::Init: more than 65535 columns");
+  FHESI_TRY(grid_y_ok("KeySwitchSI::Init", "columns", ncols));
   unsigned gx = (unsigned)((ctx->phim + 255) / 256);
   if (gx > 64) gx = 64;
   rows_mul_bcast_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)ncols), 256, 0, ctx->stream>>>(d_dst, d_a, d_t, ctx->L, ctx->phim, ctx->d_pc);
@@ -688,38 +500,23 @@ __global__ void __launch_bounds__(256) keygen_combine_kernel(const u64* __restri
   const u64* sx = scoef + (comp * n + j) * ws;
   const i64 e = err[col * n + j];
   const u64 bsign = (bx[wb - 1] >> 63) ? ~0ull : 0, ssign = (sx[ws - 1] >> 63) ? ~0ull : 0, esign = e < 0 ? ~0ull : 0;
+  // limb k of the sign-extended s; limb i of (s << sh) is made of its limbs i - wsh and i - wsh - 1
+  auto slimb = [=](int k) -> u64 { return k < 0 ? 0 : (k < ws ? sx[k] : ssign); };
   u64 v[MAXNL];
-  u64 carry = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) {
-      const u64 b = i < wb ? bx[i] : bsign;
-      const u64 ev = i == 0 ? (u64)e : esign;
-      // limb i of (s << sh): limbs i - wsh and i - wsh - 1 of the sign-extended s
-      auto slimb = [&](int k) -> u64 { return k < 0 ? 0 : (k < ws ? sx[k] : ssign); };
-      const u64 hi = slimb(i - wsh), lo = slimb(i - wsh - 1);
-      const u64 sv = bsh ? ((hi << bsh) | (lo >> (64 - bsh))) : hi;
-      const u128 t = (u128)b + ev + sv + carry;
-      v[i] = (u64)t; carry = (u64)(t >> 64);
-    }
-  u64 sb = 0;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i == (logQ - 1) >> 6) sb = (v[i] >> ((logQ - 1) & 63)) & 1;
-  u64* o = out + (col * n + j) * nl;
-#pragma unroll
-  for (int i = 0; i < MAXNL; ++i)
-    if (i < nl) o[i] = reduce_limb(v[i], i, logQ, sb);
+  ctw_sum(v, nl, 0, [=](int i) { return i < wb ? bx[i] : bsign; }, [=](int i) { return i == 0 ? (u64)e : esign; }, [=](int i) {
+    const u64 hi = slimb(i - wsh), lo = slimb(i - wsh - 1);
+    return bsh ? ((hi << bsh) | (lo >> (64 - bsh))) : hi;
+  });
+  ctw_store_centred(v, nl, logQ, out + (col * n + j) * nl);
 }
 int launch_keygen_combine(fhesi_ctx* ctx, const u64* d_bcoef, int wb, const u64* d_scoef, int ws, const i64* d_err, i64 ncols, int nd, int digit_bits, int nl,
                           int logQ, u64* d_out) {
   if (!ncols) return 0;
-  if (nl > 32) FHESI_FAIL("KeySwitchSI::Init: coefficients of %d limbs exceed the supported 32", nl);
+  FHESI_TRY(limbs_ok("KeySwitchSI::Init: coefficients", nl));
   const dim3 grid((unsigned)((ctx->phim + 255) / 256), (unsigned)ncols);
-  if (nl <= 2) keygen_combine_kernel<2><<<grid, 256, 0, ctx->stream>>>(d_bcoef, wb, d_scoef, ws, d_err, ctx->phim, nd, digit_bits, nl, logQ, d_out);
-  else if (nl <= 8) keygen_combine_kernel<8><<<grid, 256, 0, ctx->stream>>>(d_bcoef, wb, d_scoef, ws, d_err, ctx->phim, nd, digit_bits, nl, logQ, d_out);
-  else if (nl <= 16) keygen_combine_kernel<16><<<grid, 256, 0, ctx->stream>>>(d_bcoef, wb, d_scoef, ws, d_err, ctx->phim, nd, digit_bits, nl, logQ, d_out);
-  else keygen_combine_kernel<32><<<grid, 256, 0, ctx->stream>>>(d_bcoef, wb, d_scoef, ws, d_err, ctx->phim, nd, digit_bits, nl, logQ, d_out);
+  with_limb_class<2, 8, 16, 32>(nl, [&](auto C) {
+    keygen_combine_kernel<decltype(C)::value><<<grid, 256, 0, ctx->stream>>>(d_bcoef, wb, d_scoef, ws, d_err, ctx->phim, nd, digit_bits, nl, logQ, d_out);
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -328,12 +328,11 @@ int launch_tensor_sum(fhesi_ctx* ctx, const u64* d_ca, const u64* d_cb, const in
   for (int l = 0; l < ctx->L; ++l) if (ctx->pc[l].bar_k > 61) FHESI_FAIL("tensor_sum: %u-bit residues overflow the 128-bit accumulator", ctx->pc[l].bar_k);
   ProfScope prof(ctx, PROF_TENSOR, nproducts);
   PROF_KERNEL(ctx, PROF_TENSOR, tensor_sum_kernel);
-  for (i64 done = 0; done < ngroups; done += 65535) {
-    const i64 cnt = ngroups - done < 65535 ? ngroups - done : 65535;
+  grid_chunks(ngroups, [&](i64 done, i64 cnt) {
     dim3 grid(grid_x_for(ctx->phim), (unsigned)ctx->L, (unsigned)cnt);
     tensor_sum_kernel<<<grid, 256, 0, ctx->stream>>>(d_ca, d_cb, d_slot_a, d_slot_b, d_seg + done, accumulate ? 1 : 0, d_out + done * 3 * ctx->L * ctx->phim, ctx->phim, ctx->L,
                                                      ctx->d_pc);
-  }
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }

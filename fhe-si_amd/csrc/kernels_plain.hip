@@ -51,11 +51,10 @@ int launch_plain_sum(fhesi_ctx* ctx, const u64* d_ca, const u64* d_w, const int*
   PROF_KERNEL(ctx, PROF_PLAIN_SUM, plain_sum_kernel);
   const i64 b = (ctx->phim / 2 + 255) / 256;
   const unsigned gx = (unsigned)(b < 1 ? 1 : (b > 64 ? 64 : b));
-  for (i64 done = 0; done < ngroups; done += 65535) {
-    const i64 cnt = ngroups - done < 65535 ? ngroups - done : 65535;
+  grid_chunks(ngroups, [&](i64 done, i64 cnt) {
     plain_sum_kernel<<<dim3(gx, (unsigned)ctx->L, (unsigned)cnt), 256, 0, ctx->stream>>>(d_ca, d_w, d_slot_a, d_slot_w, d_seg + done, accumulate ? 1 : 0,
                                                                                         d_out + done * 2 * ctx->L * ctx->phim, ctx->phim, ctx->L, ctx->d_pc);
-  }
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }

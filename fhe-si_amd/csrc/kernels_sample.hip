@@ -63,21 +63,19 @@ __global__ void __launch_bounds__(256) sample_gaussian_kernel(i64* __restrict__ 
 // (the object index sits in gridDim.y: launches of at most 65535 objects, the index and the pointers advanced per launch)
 int launch_sample_encrypt(fhesi_ctx* ctx, i64* d_rnd, i64 count, u64 seed, u64 first) {
   const i64 n = ctx->phim;
-  for (i64 done = 0; done < count; done += 65535) {
-    const i64 cnt = std::min<i64>(65535, count - done);
+  return grid_chunks(count, [&](i64 done, i64 cnt) {
     sample_encrypt_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)cnt), 256, 0, ctx->stream>>>(d_rnd + done * 3 * n, n, seed, first + (u64)done);
     HIP_TRY(hipGetLastError());
-  }
-  return 0;
+    return 0;
+  });
 }
 int launch_sample_keygen(fhesi_ctx* ctx, u64* d_a, i64* d_err, i64 ncol, int nl, int logQ, u64 seed, u64 pub_seed, u64 first) {
   const i64 n = ctx->phim;
-  for (i64 done = 0; done < ncol; done += 65535) {
-    const i64 cnt = std::min<i64>(65535, ncol - done);
+  return grid_chunks(ncol, [&](i64 done, i64 cnt) {
     sample_keygen_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)cnt), 256, 0, ctx->stream>>>(d_a + done * n * nl, d_err + done * n, n, nl, logQ, seed, pub_seed, first + (u64)done);
     HIP_TRY(hipGetLastError());
-  }
-  return 0;
+    return 0;
+  });
 }
 int launch_sample_poly(fhesi_ctx* ctx, i64* d_poly, int kind, i64 param, u64 seed, u64 obj) {
   if (kind == 0) {

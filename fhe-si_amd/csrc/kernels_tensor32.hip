@@ -1032,11 +1032,10 @@ int tensor32_sum_pass(fhesi_ctx* ctx, const u64* d_ops, i64 nua, i64 nub, const 
   const u32* rb = ra + (size_t)nua * 2 * c->NP * nrow;
   ProfScope prof(ctx, PROF_TENSOR, (double)nterms);
   PROF_KERNEL(ctx, PROF_TENSOR, tensor_sum32_kernel);
-  for (i64 done = 0; done < ng; done += 65535) {
-    const i64 cnt = ng - done < 65535 ? ng - done : 65535;
+  grid_chunks(ng, [&](i64 done, i64 cnt) {
     dim3 grid((unsigned)(nrow / 256), (unsigned)c->NP, (unsigned)cnt);
     tensor_sum32_kernel<<<grid, 256, 0, ctx->stream>>>(ra, rb, d_slot_a, d_slot_b, d_seg + done, accumulate ? 1 : 0, (u32*)d_sum + (size_t)done * 3 * c->NP * nrow, nrow, c->NP, c->pr);
-  }
+  });
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -2,7 +2,7 @@
 // file, one operation per line; the results go to standard output, one line each, for tests/test_hostbig.py to compare with Python's
 // integers.  Built with -fsanitize=address,undefined.
 //   operand: <limbs>:<hex>, the value on exactly that many limbs (two's complement where the operation is signed)
-//   mul_small A b | mod_small A q | mod A q | bitlen A | shl A s | sub A B | ge A B | half A | pow64 q count first
+//   mul_small A b | mod_small A q | mod A q | bitlen A | shl A s | sub A B | ge A B | half A | pow64 q count first | inv_mod k m
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +49,7 @@ int main(int argc, char** argv) {
     else if (op == "ge") std::printf("%d\n", hm::bn_ge(parse(a), parse(b)) ? 1 : 0);
     else if (op == "half") print(hm::bn_half(parse(a)));
     else if (op == "pow64") print(hm::pow64_table(word(a), (int)word(b), word(c)));
+    else if (op == "inv_mod") std::printf("%lld\n", (long long)hm::inv_mod((int64_t)std::strtoll(a.c_str(), nullptr, 0), (int64_t)word(b)));
     else { std::fprintf(stderr, "unknown operation: %s\n", line.c_str()); return 2; }
   }
   return 0;

@@ -1,7 +1,9 @@
 """CPU (no GPU): the host's big-integer helpers (fhe-si_amd/csrc/hostbig.h: the one set every table builder of the library uses) as a
 stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer (tests/host/test_hostbig.cpp), against Python's integers.  Operands:
 1, 2 and 45 limbs; 0, 1, 2^64 - 1, 2^(64k) - 1; the most negative two's complement value for bn_mod; shifts by 0, 63, 64 and 65; the products
-and (P - 1) / 2 of the first 2, 18 and 45 chain primes below 2^60 (the context's rule: primes 1 mod 2m descending from 2^60, m = 32)."""
+and (P - 1) / 2 of the first 2, 18 and 45 chain primes below 2^60 (the context's rule: primes 1 mod 2m descending from 2^60, m = 32).  inv_mod (the extended Euclid for any modulus, 0 off the units): every k of
+a prime, a prime power, twice a prime power and a power of two, and k = 1, m - 1 and neighbours at m near 2^20."""
+import math
 import os
 import subprocess
 
@@ -71,6 +73,12 @@ def cases():
         out.append((f"sub {operand(prod << 3, n)} {operand(prod, n)}", limbs_hex(7 * prod, n)))
         out.append((f"ge {operand(prod, n)} {operand(prod, n - 1)}", "1"))
         out.append((f"ge {operand((prod - 1) // 2, n)} {operand(prod, n)}", "0"))
+    for m in (1, 2, 23, 27, 25, 18, 250, 32, 1024):
+        for k in range(-2, m + 3):
+            out.append((f"inv_mod {k} {m}", str(pow(k, -1, m) if math.gcd(k, m) == 1 and m > 1 else 0)))
+    for m in ((1 << 20) - 3, 1 << 20, 1042441, 2 * 3 ** 12, (1 << 20) + 7):      # (1042441 = 1021^2)
+        for k in (1, 2, 3, 1021, m - 2, m - 1, m // 2, m // 2 + 1, 5 * m + 1):
+            out.append((f"inv_mod {k} {m}", str(pow(k, -1, m) if math.gcd(k, m) == 1 else 0)))
     return out
 
 
@@ -86,4 +94,4 @@ def test_host_big_integers_under_sanitizers(tmp_path):
     assert len(got) == len(cs)
     wrong = [(line, want, have) for (line, want), have in zip(cs, got) if want != have]
     assert not wrong, wrong[:5]
-    assert {line.split()[0] for line, _ in cs} == {"mul_small", "mod_small", "mod", "bitlen", "shl", "sub", "ge", "half", "pow64"}
+    assert {line.split()[0] for line, _ in cs} == {"mul_small", "mod_small", "mod", "bitlen", "shl", "sub", "ge", "half", "pow64", "inv_mod"}
