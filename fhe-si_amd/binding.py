@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "fhesi_ct_rot_sum_dev", "fhesi_matvec_bsgs_plan", "fhesi_ct_matvec_bsgs_dev",
     "fhesi_linear_plan", "fhesi_linear_create", "fhesi_linear_create_dev", "fhesi_linear_free", "fhesi_linear_info", "fhesi_linear_diagonals",
     "fhesi_ct_rot_fold_dev", "fhesi_ct_linear_dev",
+    "fhesi_linear_grid_plan", "fhesi_linear_grid_create", "fhesi_linear_grid_create_dev", "fhesi_linear_grid_free", "fhesi_linear_grid_info",
+    "fhesi_linear_grid_diagonals", "fhesi_ct_linear_grid_dev",
 ]
 ROT_SUM_MAX_TERMS = 16   # FHESI_ROT_SUM_MAX_TERMS: the terms one launch of the rotated-sum kernel takes (more terms chain launches)
 ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
@@ -257,6 +259,13 @@ def _load():
         "fhesi_linear_diagonals": [_vp, _vp, _i64, _i64, _i32, _vp],
         "fhesi_ct_rot_fold_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
         "fhesi_ct_linear_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_linear_grid_plan": [_i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_linear_grid_create": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i32, _vp],
+        "fhesi_linear_grid_create_dev": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _i32, _vp],
+        "fhesi_linear_grid_free": [_vp],
+        "fhesi_linear_grid_info": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_linear_grid_diagonals": [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
+        "fhesi_ct_linear_grid_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -639,6 +648,20 @@ def linear_plan(cols: int, R: int, C: int, baby: int = 0) -> dict:
     return {"T": T.value, "B": B.value, "G": G.value, "nfold": nfold.value, "amounts": [int(a) for a in amounts]}
 
 
+def linear_grid_plan(cols: int, R: int, C: int, Rb: int, Cb: int, baby: int = 0) -> dict:
+    """The plan of an R x C matrix as a grid of Rb x Cb blocks on rows of `cols` slots (fhesi_linear_grid_plan): nI x nJ blocks, the block's T and
+    nfold, B (baby = 0: the B that minimises nJ (B - 1) + nI (G - 1), of equal costs the larger), G, and the amounts in linear_plan's order.
+    "key_switches" is nJ (B - 1) + nI (G - 1) + nI nfold, what LinearGrid.apply runs per item.  Raises FhesiError naming the condition on a refused
+    shape.  Touches no device."""
+    nI, nJ, T, B, G, nfold = (_i32(0) for _ in range(6))
+    args = (int(cols), int(R), int(C), int(Rb), int(Cb), int(baby))
+    _ck(_load().fhesi_linear_grid_plan(*args, _byref(nI), _byref(nJ), _byref(T), _byref(B), _byref(G), _byref(nfold), None))
+    amounts = np.zeros(B.value - 1 + G.value - 1 + nfold.value, dtype=np.int64)
+    _ck(_load().fhesi_linear_grid_plan(*args, None, None, None, None, None, None, _p(amounts) if len(amounts) else None))
+    return {"nI": nI.value, "nJ": nJ.value, "T": T.value, "B": B.value, "G": G.value, "nfold": nfold.value, "amounts": [int(a) for a in amounts],
+            "key_switches": nJ.value * (B.value - 1) + nI.value * (G.value - 1) + nI.value * nfold.value}
+
+
 def plain_sum_bits(m: int, logQ: int, maxabs: int, terms: int) -> float:
     """Bits the chain product must exceed for a sum of `terms` ciphertext x plaintext products on the ring m: log2 of twice
     terms * growth * phi(m) * 2^(logQ-1) * maxabs, growth = 1 (m a power of two), 2 (m = q^k, 2 q^k) or phi(m).  Touches no device."""
@@ -693,6 +716,44 @@ class Linear:
     def close(self):
         if getattr(self, "h", None):
             _load().fhesi_linear_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LinearGrid:
+    """An R x C matrix larger than a row of slots as a grid of nI x nJ blocks of Rb x Cb (fhesi_linear_grid): the prepared diagonals of every block,
+    the replicated biases and the plan, resident in HBM; made by SlotSpace.linear_grid.  .amounts lists the rotation amounts whose hoisted matrices
+    apply() takes -- babies, giants, the block's folds; .key_switches is what apply() runs per item."""
+
+    def __init__(self, space: "SlotSpace", h):
+        self.space, self.ctx, self.h = space, space.ctx, h
+        R, Cc, Rb, Cb = _i64(0), _i64(0), _i64(0), _i64(0)
+        nI, nJ, T, B, G, nfold, bias = (_i32(0) for _ in range(7))
+        _ck(_load().fhesi_linear_grid_info(self.h, _byref(R), _byref(Cc), _byref(Rb), _byref(Cb), _byref(nI), _byref(nJ), _byref(T), _byref(B), _byref(G),
+                                           _byref(nfold), _byref(bias), None))
+        self.R, self.C, self.Rb, self.Cb, self.nI, self.nJ = R.value, Cc.value, Rb.value, Cb.value, nI.value, nJ.value
+        self.T, self.B, self.G, self.nfold, self.has_bias = T.value, B.value, G.value, nfold.value, bool(bias.value)
+        a = np.zeros(self.B - 1 + self.G - 1 + self.nfold, dtype=np.int64)
+        _ck(_load().fhesi_linear_grid_info(self.h, None, None, None, None, None, None, None, None, None, None, None, _p(a) if len(a) else None))
+        self.amounts = [int(x) for x in a]
+        self.key_switches = self.nJ * (self.B - 1) + self.nI * (self.G - 1) + self.nI * self.nfold
+
+    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[I][i] = block row I of the product for item i (fhesi_ct_linear_grid_dev): src [nJ][count] holds SlotSpace.replicate_blocks(x, Cb)
+        encrypted, out [nI][count] holds (M x + b)[I Rb ..] with period Rb.  hoisted_by_amount as Linear.apply takes it.  The babies of an input
+        block serve every output block; the giants and folds of an output block run once, behind the sum over the input blocks."""
+        hs = [hoisted_by_amount[a] for a in self.amounts] if hasattr(hoisted_by_amount, "keys") else list(hoisted_by_amount)
+        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
+        _ck(_load().fhesi_ct_linear_grid_dev(self.ctx.h, self.h, arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+
+    def close(self):
+        if getattr(self, "h", None):
+            _load().fhesi_linear_grid_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -932,6 +993,71 @@ class SlotSpace:
         vals = np.zeros((plan["T"], self.total), dtype=np.int64)
         _ck(_load().fhesi_linear_diagonals(self.h, _p(M), M.shape[0], M.shape[1], int(baby), _p(vals)))
         return vals
+
+    # ---- matrices larger than a row of slots: a grid of blocks (fhesi_linear_grid_*)
+    def _grid_block(self, R: int, C: int, block):
+        cols = self.total // max(self.rows, 1)
+        return (min(R, cols), min(C, cols)) if block is None else (int(block[0]), int(block[1]))
+
+    def linear_grid(self, M, bias=None, block=None, baby: int = 0, device: bool = False) -> LinearGrid:
+        """The product y = M x + b for M [R][C] as a grid of blocks [Rb][Cb] = block (default (min(R, cols), min(C, cols))): R a multiple of Rb, C of
+        Cb -- pad with zeros --, the block a shape linear_plan admits.  M, bias, device and baby as SlotSpace.linear takes them."""
+        h = _vp()
+        if device:
+            mp, shape = self._device_words(M, "the matrix")
+            if len(shape) != 2:
+                raise ValueError("linear_grid: the matrix is [R][C]")
+            bp = None
+            if bias is not None:
+                bp, bshape = self._device_words(bias, "the bias")
+                if bshape != (shape[0],):
+                    raise ValueError(f"linear_grid: a bias of shape {bshape} for {shape[0]} rows")
+            Rb, Cb = self._grid_block(shape[0], shape[1], block)
+            _ck(_load().fhesi_linear_grid_create_dev(self.h, mp, shape[0], shape[1], Rb, Cb, bp, int(baby), _byref(h)))
+            return LinearGrid(self, h)
+        M = np.ascontiguousarray(M, dtype=np.int64)
+        if M.ndim != 2:
+            raise ValueError("linear_grid: the matrix is [R][C]")
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(bias, dtype=np.int64)
+            if b.shape != (M.shape[0],):
+                raise ValueError(f"linear_grid: a bias of shape {b.shape} for {M.shape[0]} rows")
+        Rb, Cb = self._grid_block(M.shape[0], M.shape[1], block)
+        _ck(_load().fhesi_linear_grid_create(self.h, _p(M), M.shape[0], M.shape[1], Rb, Cb, _p(b) if b is not None else None, int(baby), _byref(h)))
+        return LinearGrid(self, h)
+
+    def linear_grid_diagonals(self, M, block=None, baby: int = 0) -> np.ndarray:
+        """The prepared slot vectors of the grid: [nI][nJ][T][total], entry (I, J) what linear_diagonals gives for the block M[I Rb .., J Cb ..] with
+        the grid's B (fhesi_linear_grid_diagonals) -- what SlotSpace.linear_grid embeds, downloaded."""
+        M = np.ascontiguousarray(M, dtype=np.int64)
+        if M.ndim != 2:
+            raise ValueError("linear_grid_diagonals: the matrix is [R][C]")
+        Rb, Cb = self._grid_block(M.shape[0], M.shape[1], block)
+        plan = linear_grid_plan(self.total // max(self.rows, 1), M.shape[0], M.shape[1], Rb, Cb, baby)
+        vals = np.zeros((plan["nI"], plan["nJ"], plan["T"], self.total), dtype=np.int64)
+        _ck(_load().fhesi_linear_grid_diagonals(self.h, _p(M), M.shape[0], M.shape[1], Rb, Cb, int(baby), _p(vals)))
+        return vals
+
+    def replicate_blocks(self, x, Cb: int) -> np.ndarray:
+        """x [count][rows][C] (or [count][C] on a one-row space), C = nJ Cb -> slot values [nJ][count][total]: plaintext (J, i) holds x_i[J Cb ..
+        (J + 1) Cb) with period Cb in every row, the input layout of LinearGrid.apply.  Host only."""
+        x = np.asarray(x)
+        C = x.shape[-1]
+        if Cb < 1 or C % Cb:
+            raise ValueError(f"replicate_blocks: {C} values per row are not a multiple of the block's {Cb} columns")
+        return np.ascontiguousarray(np.stack([self.replicate(x[..., J * Cb:(J + 1) * Cb], Cb) for J in range(C // Cb)]))
+
+    def collect_blocks(self, y, Rb: int) -> np.ndarray:
+        """The inverse on the output side: decrypted slot values y [nI][count][total], block I with period Rb -> [count][rows][nI Rb] (the rows axis
+        dropped on a one-row space): the first period of every row, the blocks side by side.  Host only."""
+        y = np.asarray(y)
+        rows, cols = max(self.rows, 1), self.total // max(self.rows, 1)
+        if Rb < 1 or cols % Rb or y.ndim != 3 or y.shape[-1] != self.total:
+            raise ValueError(f"collect_blocks: values of shape {y.shape} with period {Rb} on rows of {cols} slots")
+        first = y.reshape(y.shape[0], y.shape[1], rows, cols)[..., :Rb]                 # [nI][count][rows][Rb]
+        out = np.moveaxis(first, 0, 2).reshape(y.shape[1], rows, y.shape[0] * Rb)       # [count][rows][nI][Rb] -> [count][rows][R]
+        return np.ascontiguousarray(out if self.rows == 2 else out[:, 0, :])
 
 
 def slots_basis_plan(m: int, bits: int, prime_bits: int, generator: int) -> dict:

@@ -405,20 +405,34 @@ extern "C" int fhesi_ct_noise_int_batch(fhesi_ctx* c, fhesi_slots_basis* b, cons
 // fhesi_plain (include/fhesi_hip.h): the one core behind both constructors.  d_msg [nw][phi(m)] int64 message polynomials in HBM (a stage above
 // left them in workspace slot 5) -> DoubleCRT rows over all primes, owned by the handle.  Synchronises: the array the stage uploaded from is the
 // caller's again on return.
-static int plain_rows_dev(fhesi_ctx* c, const i64* d_msg, i64 nw, u64 maxabs, u64 p, fhesi_plain** out) {
-  const i64 n = c->phim;
-  const int L = c->L;
-  const std::vector<int> all = full_set(c);
+// In two halves, for a stage that makes its message polynomials in chunks (a grid of linear blocks): the handle with its rows allocated and nothing in
+// them -- not yet a live handle of the context --, and the rows [row0, row0 + nrows) from d_msg [nrows][phi(m)], enqueued.
+static int plain_alloc(fhesi_ctx* c, i64 nw, u64 maxabs, u64 p, fhesi_plain** out) {
   fhesi_plain* w = new fhesi_plain();
   w->ctx = c; w->nw = nw; w->maxabs = maxabs; w->p = p;
-  if (hipMalloc(&w->d_rows, (size_t)nw * L * n * 8) != hipSuccess) { (void)hipGetLastError(); delete w; FHESI_FAIL("prepared plaintext: hipMalloc of %zu bytes failed", (size_t)nw * L * n * 8); }
-  int rc = launch_rns_reduce(c, (const u64*)d_msg, 1, n, nw, 1, nullptr, w->d_rows, L, nullptr);      // one signed limb per coefficient
-  if (!rc) rc = row_fwd(c, w->d_rows, nw, L, nullptr, all.data());
+  const size_t bytes = (size_t)nw * c->L * c->phim * 8;
+  if (hipMalloc(&w->d_rows, bytes) != hipSuccess) { (void)hipGetLastError(); delete w; FHESI_FAIL("prepared plaintext: hipMalloc of %zu bytes failed", bytes); }
+  *out = w;
+  return 0;
+}
+static int plain_rows_fill(fhesi_ctx* c, fhesi_plain* w, i64 row0, const i64* d_msg, i64 nrows) {
+  const std::vector<int> all = full_set(c);
+  u64* rows = w->d_rows + (size_t)row0 * c->L * c->phim;
+  FHESI_TRY(launch_rns_reduce(c, (const u64*)d_msg, 1, c->phim, nrows, 1, nullptr, rows, c->L, nullptr));      // one signed limb per coefficient
+  return row_fwd(c, rows, nrows, c->L, nullptr, all.data());
+}
+// closes what the two halves began: waits for the transforms and counts the handle, or releases it (rc: how the fills went)
+static int plain_rows_close(fhesi_ctx* c, fhesi_plain* w, int rc, fhesi_plain** out) {
   if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) { fhesi_set_error("prepared plaintext: the transforms failed"); rc = 1; }
-  if (rc) { hipFree(w->d_rows); delete w; return rc; }
+  if (rc) { hipStreamSynchronize(c->stream); hipFree(w->d_rows); delete w; return rc; }
   ++c->live_handles;
   *out = w;
   return 0;
+}
+static int plain_rows_dev(fhesi_ctx* c, const i64* d_msg, i64 nw, u64 maxabs, u64 p, fhesi_plain** out) {
+  fhesi_plain* w;
+  FHESI_TRY(plain_alloc(c, nw, maxabs, p, &w));
+  return plain_rows_close(c, w, plain_rows_fill(c, w, 0, d_msg, nw), out);
 }
 extern "C" int fhesi_plain_create_slots(fhesi_slots* s, const int64_t* vals_host, int64_t nvals, int32_t only_usable, int64_t nw, fhesi_plain** out) {
   if (!out) FHESI_FAIL("prepared plaintext: null output pointer");
@@ -563,76 +577,130 @@ extern "C" int fhesi_ct_add_slots_dev(fhesi_ctx* c, fhesi_slots* s, int32_t logQ
 // fhesi_linear (include/fhesi_hip.h).  The stage next to stage_msg_slots: the T prepared slot vectors w_t of an R x C layer [T][phi(m)] in the values
 // slot (workspace 9), written by linear_diag_kernel from the matrix where it is -- a host matrix is uploaded into the same slot, behind them.  Checks
 // its own arguments and plans the layer; nothing here synchronises.
-struct LinearPlan { int32_t T = 0, B = 0, G = 0, nfold = 0; std::vector<int64_t> amounts; };
-static int stage_linear_vals(fhesi_slots* s, const int64_t* M, bool on_dev, i64 R, i64 C, int32_t baby, const char* what, LinearPlan* plan, i64** d_vals) {
+// A layer is the grid of one block (Rb = R, Cb = C): everything below is written for the grid.  The blocks are staged in chunks of whole blocks, so the
+// values slot holds a chunk and never the grid.
+struct LinearPlan { int32_t nI = 0, nJ = 0, T = 0, B = 0, G = 0, nfold = 0; std::vector<int64_t> amounts; };
+struct LinearStage {
+  LinearPlan plan;
+  i64 per = 0;                 // blocks per chunk
+  i64* d_vals = nullptr;       // [per][T][phi(m)] in workspace slot 9, a host matrix behind them
+  const i64* d_M = nullptr;    // the matrix in HBM
+  i64 ld = 0;
+};
+constexpr size_t kLinearChunkBytes = (size_t)256 << 20;      // slot values of one chunk of blocks (a single block may take more)
+static int linear_stage_open(fhesi_slots* s, const int64_t* M, bool on_dev, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what, LinearStage* st) {
   if (!s) FHESI_FAIL("%s: null plaintext space", what);
   fhesi_ctx* c = s->ctx;
   CHECK_CTX(c);
   if (!M) FHESI_FAIL("%s: null matrix", what);
-  const i64 total = s->S.phim;
-  FHESI_TRY(fhesi_linear_plan(total / s->S.rows, R, C, baby, &plan->T, &plan->B, &plan->G, &plan->nfold, nullptr));
-  if (plan->T > 65535) FHESI_FAIL("%s: %d diagonals per handle, 1 .. 65535 are taken", what, plan->T);
-  plan->amounts.resize((size_t)(plan->B - 1 + plan->G - 1 + plan->nfold));
-  FHESI_TRY(fhesi_linear_plan(total / s->S.rows, R, C, baby, nullptr, nullptr, nullptr, nullptr, plan->amounts.data()));
-  const size_t nvals = (size_t)plan->T * total;
-  FHESI_TRY(ws_i64(c, 9, (nvals + (on_dev ? 0 : (size_t)R * C)) * 8, d_vals));
-  const i64* d_M = M;
+  LinearPlan& plan = st->plan;
+  const i64 total = s->S.phim, cols = total / s->S.rows;
+  FHESI_TRY(fhesi_linear_grid_plan(cols, R, C, Rb, Cb, baby, &plan.nI, &plan.nJ, &plan.T, &plan.B, &plan.G, &plan.nfold, nullptr));
+  plan.amounts.resize((size_t)(plan.B - 1 + plan.G - 1 + plan.nfold));
+  FHESI_TRY(fhesi_linear_grid_plan(cols, R, C, Rb, Cb, baby, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plan.amounts.data()));
+  const size_t block_vals = (size_t)plan.T * total;
+  st->per = std::max<i64>(1, std::min<i64>((i64)plan.nI * plan.nJ, (i64)(kLinearChunkBytes / (block_vals * 8))));
+  const size_t nvals = (size_t)st->per * block_vals;
+  FHESI_TRY(ws_i64(c, 9, (nvals + (on_dev ? 0 : (size_t)R * C)) * 8, &st->d_vals));
+  st->d_M = M; st->ld = C;
   if (!on_dev) {
-    HIP_TRY(hipMemcpyAsync(*d_vals + nvals, M, (size_t)R * C * 8, hipMemcpyHostToDevice, c->stream));
-    d_M = *d_vals + nvals;
+    HIP_TRY(hipMemcpyAsync(st->d_vals + nvals, M, (size_t)R * C * 8, hipMemcpyHostToDevice, c->stream));
+    st->d_M = st->d_vals + nvals;
   }
-  return launch_linear_diag(c, s->S, d_M, R, C, plan->T, plan->B, *d_vals);
+  return 0;
 }
-// b[i mod R] in every row: the diagonal of the R x 1 layer whose only column is the bias.  Before stage_linear_vals, which takes the values slot over.
-static int linear_bias_vals(fhesi_slots* s, const int64_t* bias, bool on_dev, i64 R, i64* d_bias) {
+// the slot vectors of the blocks [first, first + nb), nb <= per, into d_vals
+static int linear_stage_blocks(fhesi_slots* s, const LinearStage& st, i64 Rb, i64 Cb, i64 first, i64 nb) {
+  return launch_linear_diag(s->ctx, s->S, st.d_M, st.ld, st.plan.nJ, (int)first, (int)nb, Rb, Cb, st.plan.T, st.plan.B, st.d_vals);
+}
+// b[I Rb + i mod Rb] in every row, I < nI: per output block the diagonal of the Rb x 1 block whose only column is its part of the bias -- a grid of nI x 1
+// such blocks with leading dimension 1.  Before linear_stage_open, which takes the values slot over.
+static int linear_bias_vals(fhesi_slots* s, const int64_t* bias, bool on_dev, i64 Rb, int nI, i64* d_bias) {
   fhesi_ctx* c = s->ctx;
   const i64* d_b = bias;
   if (!on_dev) {
     i64* up;
-    FHESI_TRY(upload_vals(c, bias, (size_t)R * 8, &up));
+    FHESI_TRY(upload_vals(c, bias, (size_t)nI * Rb * 8, &up));
     d_b = up;
   }
-  return launch_linear_diag(c, s->S, d_b, R, 1, 1, 1, d_bias);
+  return launch_linear_diag(c, s->S, d_b, 1, 1, 0, nI, Rb, 1, 1, 1, d_bias);
 }
-static int linear_create(fhesi_slots* s, const int64_t* M, const int64_t* bias, bool on_dev, i64 R, i64 C, int32_t baby, fhesi_linear** out) {
-  if (!out) FHESI_FAIL("linear_create: null output pointer");
-  *out = nullptr;
-  if (!s) FHESI_FAIL("linear_create: null plaintext space");
+static int linear_create(fhesi_slots* s, const int64_t* M, const int64_t* bias, bool on_dev, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what,
+                         fhesi_linear_grid* lin) {
+  if (!s) FHESI_FAIL("%s: null plaintext space", what);
   fhesi_ctx* c = s->ctx;
   CHECK_CTX(c);
-  if (!M) FHESI_FAIL("linear_create: null matrix");
-  FHESI_TRY(fhesi_linear_plan(s->S.phim / s->S.rows, R, C, baby, nullptr, nullptr, nullptr, nullptr, nullptr));      // the shape, before anything is launched
+  if (!M) FHESI_FAIL("%s: null matrix", what);
+  int32_t nI = 0;
+  FHESI_TRY(fhesi_linear_grid_plan(s->S.phim / s->S.rows, R, C, Rb, Cb, baby, &nI, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));      // the shape, before anything is launched
+  const size_t n = (size_t)s->S.phim;
   i64* d_bias = nullptr;
   if (bias) {
-    if (hipMalloc(&d_bias, (size_t)s->S.phim * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("linear_create: hipMalloc of %zu bytes failed", (size_t)s->S.phim * 8); }
-    if (const int rc = linear_bias_vals(s, bias, on_dev, R, d_bias)) { hipFree(d_bias); return rc; }
+    if (hipMalloc(&d_bias, (size_t)nI * n * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("%s: hipMalloc of %zu bytes failed", what, (size_t)nI * n * 8); }
+    if (const int rc = linear_bias_vals(s, bias, on_dev, Rb, nI, d_bias)) { hipFree(d_bias); return rc; }
   }
-  LinearPlan plan;
-  i64 *d_vals = nullptr, *d_msg = nullptr;
-  fhesi_plain* w = nullptr;
-  int rc = stage_linear_vals(s, M, on_dev, R, C, baby, "linear_create", &plan, &d_vals);
-  if (!rc) rc = msg_staging(c, plan.T, &d_msg);
-  if (!rc) rc = slots_embed_rows(s, d_vals, s->S.phim, false, plan.T, d_msg);
-  if (!rc) rc = plain_rows_dev(c, d_msg, plan.T, s->S.p - 1, s->S.p, &w);      // synchronises: a host matrix and bias are the caller's again
+  LinearStage st;
+  i64* d_msg = nullptr;
+  fhesi_plain *w = nullptr, *made = nullptr;
+  int rc = linear_stage_open(s, M, on_dev, R, C, Rb, Cb, baby, what, &st);
+  const LinearPlan& plan = st.plan;
+  const i64 nblocks = (i64)plan.nI * plan.nJ;
+  if (!rc) rc = msg_staging(c, st.per * plan.T, &d_msg);
+  if (!rc) rc = plain_alloc(c, nblocks * plan.T, s->S.p - 1, s->S.p, &w);      // the embedding leaves coefficients in [0, p)
   if (rc) { hipStreamSynchronize(c->stream); hipFree(d_bias); return rc; }
-  fhesi_linear* lin = new fhesi_linear();
-  lin->ctx = c; lin->slots = s; lin->R = R; lin->C = C;
-  lin->T = plan.T; lin->B = plan.B; lin->G = plan.G; lin->nfold = plan.nfold;
+  for (i64 first = 0; first < nblocks && !rc; first += st.per) {
+    const i64 nb = std::min(st.per, nblocks - first);
+    rc = linear_stage_blocks(s, st, Rb, Cb, first, nb);
+    if (!rc) rc = slots_embed_rows(s, st.d_vals, s->S.phim, false, nb * plan.T, d_msg);
+    if (!rc) rc = plain_rows_fill(c, w, first * plan.T, d_msg, nb * plan.T);
+  }
+  rc = plain_rows_close(c, w, rc, &made);      // synchronises: a host matrix and bias are the caller's again
+  if (rc) { hipFree(d_bias); return rc; }
+  lin->ctx = c; lin->slots = s; lin->R = R; lin->C = C; lin->Rb = Rb; lin->Cb = Cb;
+  lin->nI = plan.nI; lin->nJ = plan.nJ; lin->T = plan.T; lin->B = plan.B; lin->G = plan.G; lin->nfold = plan.nfold;
   lin->amounts.assign(plan.amounts.begin(), plan.amounts.end());
-  lin->w = w; lin->d_bias = d_bias;
+  lin->w = made; lin->d_bias = d_bias;
+  return 0;
+}
+template <class H>
+static int linear_create_handle(fhesi_slots* s, const int64_t* M, const int64_t* bias, bool on_dev, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what, H** out) {
+  if (!out) FHESI_FAIL("%s: null output pointer", what);
+  *out = nullptr;
+  H* lin = new H();
+  if (const int rc = linear_create(s, M, bias, on_dev, R, C, Rb, Cb, baby, what, lin)) { delete lin; return rc; }
   *out = lin;
   return 0;
 }
+static int linear_free(fhesi_linear_grid* lin) {
+  fhesi_plain_free(lin->w);      // (synchronises; the one live handle the grid counts as)
+  hipFree(lin->d_bias);
+  return 0;
+}
+// the same stage without a handle: vals_host [nI][nJ][T][phi(m)], chunk by chunk
+static int linear_diagonals(fhesi_slots* s, const int64_t* M_host, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what, int64_t* vals_host) {
+  if (!vals_host) FHESI_FAIL("%s: null output", what);
+  LinearStage st;
+  FHESI_TRY(linear_stage_open(s, M_host, false, R, C, Rb, Cb, baby, what, &st));
+  fhesi_ctx* c = s->ctx;
+  const i64 nblocks = (i64)st.plan.nI * st.plan.nJ;
+  const size_t block_vals = (size_t)st.plan.T * s->S.phim;
+  for (i64 first = 0; first < nblocks; first += st.per) {
+    const i64 nb = std::min(st.per, nblocks - first);
+    FHESI_TRY(linear_stage_blocks(s, st, Rb, Cb, first, nb));
+    HIP_TRY(hipMemcpyAsync(vals_host + (size_t)first * block_vals, st.d_vals, (size_t)nb * block_vals * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
 extern "C" int fhesi_linear_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, const int64_t* bias_host, int32_t baby, fhesi_linear** out) {
-  return linear_create(s, M_host, bias_host, false, R, C, baby, out);
+  return linear_create_handle(s, M_host, bias_host, false, R, C, R, C, baby, "linear_create", out);
 }
 extern "C" int fhesi_linear_create_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t C, const int64_t* bias_dev, int32_t baby, fhesi_linear** out) {
-  return linear_create(s, M_dev, bias_dev, true, R, C, baby, out);
+  return linear_create_handle(s, M_dev, bias_dev, true, R, C, R, C, baby, "linear_create", out);
 }
 extern "C" int fhesi_linear_free(fhesi_linear* lin) {
   if (!lin) return 0;
-  fhesi_plain_free(lin->w);      // (synchronises; the one live handle the layer counts as)
-  hipFree(lin->d_bias);
+  linear_free(lin);
   delete lin;
   return 0;
 }
@@ -649,14 +717,41 @@ extern "C" int fhesi_linear_info(const fhesi_linear* lin, int64_t* R, int64_t* C
   return 0;
 }
 extern "C" int fhesi_linear_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int32_t baby, int64_t* vals_host) {
-  if (!vals_host) FHESI_FAIL("linear_diagonals: null output");
-  LinearPlan plan;
-  i64* d_vals = nullptr;
-  FHESI_TRY(stage_linear_vals(s, M_host, false, R, C, baby, "linear_diagonals", &plan, &d_vals));
-  fhesi_ctx* c = s->ctx;
-  HIP_TRY(hipMemcpyAsync(vals_host, d_vals, (size_t)plan.T * s->S.phim * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  return linear_diagonals(s, M_host, R, C, R, C, baby, "linear_diagonals", vals_host);
+}
+extern "C" int fhesi_linear_grid_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int64_t Rb, int64_t Cb, const int64_t* bias_host, int32_t baby,
+                                        fhesi_linear_grid** out) {
+  return linear_create_handle(s, M_host, bias_host, false, R, C, Rb, Cb, baby, "linear_grid_create", out);
+}
+extern "C" int fhesi_linear_grid_create_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t C, int64_t Rb, int64_t Cb, const int64_t* bias_dev, int32_t baby,
+                                            fhesi_linear_grid** out) {
+  return linear_create_handle(s, M_dev, bias_dev, true, R, C, Rb, Cb, baby, "linear_grid_create", out);
+}
+extern "C" int fhesi_linear_grid_free(fhesi_linear_grid* lin) {
+  if (!lin) return 0;
+  linear_free(lin);
+  delete lin;
   return 0;
+}
+extern "C" int fhesi_linear_grid_info(const fhesi_linear_grid* lin, int64_t* R, int64_t* C, int64_t* Rb, int64_t* Cb, int32_t* nI, int32_t* nJ, int32_t* T, int32_t* B, int32_t* G,
+                                      int32_t* nfold, int32_t* has_bias, int64_t* amounts) {
+  if (!lin) FHESI_FAIL("null linear grid");
+  if (R) *R = lin->R;
+  if (C) *C = lin->C;
+  if (Rb) *Rb = lin->Rb;
+  if (Cb) *Cb = lin->Cb;
+  if (nI) *nI = lin->nI;
+  if (nJ) *nJ = lin->nJ;
+  if (T) *T = lin->T;
+  if (B) *B = lin->B;
+  if (G) *G = lin->G;
+  if (nfold) *nfold = lin->nfold;
+  if (has_bias) *has_bias = lin->d_bias ? 1 : 0;
+  if (amounts) std::copy(lin->amounts.begin(), lin->amounts.end(), amounts);
+  return 0;
+}
+extern "C" int fhesi_linear_grid_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int64_t* vals_host) {
+  return linear_diagonals(s, M_host, R, C, Rb, Cb, baby, "linear_grid_diagonals", vals_host);
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

@@ -539,58 +539,71 @@ static int key_switch_plain_run(fhesi_ctx* c, const fhesi_ksk* k, int ks_mode, i
   return 0;
 }
 
-// What both matrix-vector entries check behind rotations_args: the prepared plaintext, the capacity rule of a sum of `terms` products, the buffers
-static int matvec_args(fhesi_ctx* c, const char* who, const fhesi_plain* w, int32_t nk, int terms, int32_t logQ, const uint64_t* in, int32_t nlimbs, int64_t count, const uint64_t* out) {
+// What every matrix-vector entry checks behind rotations_args: the prepared plaintext -- nk diagonals for each of nI x nJ blocks --, the capacity rule of
+// a sum of `terms` products, the buffers: in [nJ][count], out [nI][count]
+static int matvec_args(fhesi_ctx* c, const char* who, const fhesi_plain* w, int nI, int nJ, int32_t nk, int terms, int32_t logQ, const uint64_t* in, int32_t nlimbs,
+                       int64_t count, const uint64_t* out) {
   if (!w) FHESI_FAIL("%s: null prepared plaintext", who);
   if (w->ctx != c) FHESI_FAIL("%s: the prepared plaintext belongs to another context", who);
-  if (w->nw < nk) FHESI_FAIL("%s: %d rotations against %lld prepared diagonals", who, nk, (long long)w->nw);
+  if (w->nw < (i64)nI * nJ * nk) FHESI_FAIL("%s: %lld rotations against %lld prepared diagonals", who, (long long)nI * nJ * nk, (long long)w->nw);
   const double chain = chain_bits(c), bits = plain_sum_bits(c->phim, c->pow2, c->phi_two_term, logQ, w->maxabs, terms);
   if (bits >= chain) FHESI_FAIL("%s: a sum of %d products needs %.0f bits, the chain holds %.0f", who, terms, std::ceil(bits), std::floor(chain));
   if (!count) return 0;
   if (!in || !out) FHESI_FAIL("%s: null argument", who);
   const size_t bytes = (size_t)count * 2 * c->phim * nlimbs * 8;
-  if (ranges_overlap(in, bytes, out, bytes)) FHESI_FAIL("%s: out overlaps in", who);
+  if (ranges_overlap(in, nJ * bytes, out, nI * bytes)) FHESI_FAIL("%s: out overlaps in", who);
   return 0;
 }
 // out[i] = Reduce( sum_g rot_kg[g]( sum_j rot_kb[j](in[i]) (*) w[g B + j] ) )  (include/fhesi_hip.h): per chunk of ciphertexts the baby rotations from one digit
 // set into the pool (slot 12), ONE plaintext sum with G groups per ciphertext (slot 13), one key switch per giant into its slice of slot 14, one rotated sum.
 // flat (G = 1, no giant): the plaintext sums ARE the result and go straight to out -- fhesi_ct_matvec_dev; no slot 13 or 14, no rotated sum.
 // g_mode: the giants' forms, their tables built by the caller.  Every argument checked by the caller.
+// The grid of nI x nJ blocks (fhesi_ct_linear_grid_dev) runs the same schedule with two of its three factors shared: in [nJ][count], out [nI][count], w row
+// (I nJ + J) nk + t.  The babies of input block J, from one digit set, serve every output block -- pool [nJ][nb][cnt]; the ONE plaintext sum has the
+// groups (I, g, i) with the terms (J, j), so the sum over J is taken where sums are exact and free; the giants of output block I run once, behind it.  Slot 14
+// holds the G key-switched sums of one output block at a time.  One block (nI = nJ = 1) is the schedule above, launch for launch.
 static int matvec_run(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted, const int64_t* kg,
-                      const int* g_mode, int32_t G, bool flat, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs,
-                      int64_t count, uint64_t* out) {
+                      const int* g_mode, int32_t G, bool flat, int nI, int nJ, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                      int32_t nlimbs, int64_t count, uint64_t* out) {
   const int nb = std::min(B, nk);      // (G = 1 with a ragged group: the babies past nk are not run)
   const size_t ct_words = (size_t)2 * c->phim * nlimbs;
-  // ciphertexts per pass: about 4 GiB of rotated ciphertexts, of inner sums and of key-switched sums each
-  const i64 chunk = std::max<i64>(1, std::min<i64>(count, (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(nb, G) * ct_words * 8))));
-  std::vector<int32_t> a_idx((size_t)chunk * nk), b_idx((size_t)chunk * nk), seg((size_t)chunk * G + 1);
+  const i64 nterms = (i64)nI * nJ * nk;      // terms of one ciphertext's sums
+  // ciphertexts per pass: about 4 GiB of rotated ciphertexts, of inner sums and of key-switched sums each; and index lists that 32 bits hold
+  const i64 chunk = std::max<i64>(1, std::min<i64>(std::min<i64>(count, ((i64)1 << 31) / (nterms + 1) - 1),
+                                                  (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(nJ * nb, nI * G) * ct_words * 8))));
+  std::vector<int32_t> a_idx((size_t)chunk * nterms), b_idx((size_t)chunk * nterms), seg((size_t)chunk * nI * G + 1);
   for (i64 done = 0; done < count; done += chunk) {
     const i64 cnt = std::min(chunk, count - done);
-    uint64_t* o = out + (size_t)done * ct_words;
-    void *d_pool, *d_inner = o, *d_pre = nullptr;
-    FHESI_TRY(ws_reserve(c, 12, (size_t)nb * cnt * ct_words * 8, &d_pool));
+    void *d_pool, *d_inner = out + (size_t)done * ct_words, *d_pre = nullptr;
+    FHESI_TRY(ws_reserve(c, 12, (size_t)nJ * nb * cnt * ct_words * 8, &d_pool));
     if (!flat) {
-      FHESI_TRY(ws_reserve(c, 13, (size_t)G * cnt * ct_words * 8, &d_inner));
+      FHESI_TRY(ws_reserve(c, 13, (size_t)nI * G * cnt * ct_words * 8, &d_inner));
       FHESI_TRY(ws_reserve(c, 14, (size_t)G * cnt * ct_words * 8, &d_pre));
     }
-    FHESI_TRY(rotations_run(c, baby_hoisted, kb, nb, logQ, decomp_bytes, in + (size_t)done * ct_words, nlimbs, cnt, (uint64_t*)d_pool, nlimbs));
-    // group g * cnt + i = sum_j pool[j][i] (*) w[g B + j]
+    for (int J = 0; J < nJ; ++J)
+      FHESI_TRY(rotations_run(c, baby_hoisted, kb, nb, logQ, decomp_bytes, in + ((size_t)J * count + done) * ct_words, nlimbs, cnt,
+                              (uint64_t*)d_pool + (size_t)J * nb * cnt * ct_words, nlimbs));
+    // group (I G + g) cnt + i = sum_J sum_j pool[J][j][i] (*) w[(I nJ + J) nk + g B + j]
     i64 at = 0;
-    for (int g = 0; g < G; ++g)
-      for (i64 i = 0; i < cnt; ++i) {
-        seg[(size_t)g * cnt + i] = (int32_t)at;
-        for (int j = 0; j < B && g * B + j < nk; ++j, ++at) { a_idx[at] = (int32_t)(j * cnt + i); b_idx[at] = g * B + j; }
-      }
-    seg[(size_t)G * cnt] = (int32_t)at;
-    FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nb * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt * G, (uint64_t*)d_inner));
+    for (int I = 0; I < nI; ++I)
+      for (int g = 0; g < G; ++g)
+        for (i64 i = 0; i < cnt; ++i) {
+          seg[((size_t)I * G + g) * cnt + i] = (int32_t)at;
+          for (int J = 0; J < nJ; ++J)
+            for (int j = 0; j < B && g * B + j < nk; ++j, ++at) { a_idx[at] = (int32_t)(((i64)J * nb + j) * cnt + i); b_idx[at] = (I * nJ + J) * nk + g * B + j; }
+        }
+    seg[(size_t)nI * G * cnt] = (int32_t)at;
+    FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nJ * nb * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt * nI * G, (uint64_t*)d_inner));
     if (flat) continue;
-    for (int g = 0; g < G; ++g) {
-      const u64* inner = (const u64*)d_inner + (size_t)g * cnt * ct_words;
-      u64* pre = (u64*)d_pre + (size_t)g * cnt * ct_words;
-      if (!giant_hoisted[g]) HIP_TRY(hipMemcpyAsync(pre, inner, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));      // (k = 1: the sum itself)
-      else FHESI_TRY(key_switch_plain_run(c, giant_hoisted[g], g_mode[g], logQ, decomp_bytes, inner, nlimbs, cnt, pre));
+    for (int I = 0; I < nI; ++I) {
+      for (int g = 0; g < G; ++g) {
+        const u64* inner = (const u64*)d_inner + ((size_t)I * G + g) * cnt * ct_words;
+        u64* pre = (u64*)d_pre + (size_t)g * cnt * ct_words;
+        if (!giant_hoisted[g]) HIP_TRY(hipMemcpyAsync(pre, inner, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));      // (k = 1: the sum itself)
+        else FHESI_TRY(key_switch_plain_run(c, giant_hoisted[g], g_mode[g], logQ, decomp_bytes, inner, nlimbs, cnt, pre));
+      }
+      FHESI_TRY(rot_sum_run(c, kg, G, logQ, nullptr, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, out + ((size_t)I * count + done) * ct_words));
     }
-    FHESI_TRY(rot_sum_run(c, kg, G, logQ, nullptr, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, (u64*)o));
   }
   return 0;
 }
@@ -600,9 +613,9 @@ extern "C" int fhesi_ct_matvec_dev(fhesi_ctx* c, const fhesi_ksk* const* hoisted
   CHECK_CTX(c);
   if (nk < 1) FHESI_FAIL("ct_matvec: %d diagonals", nk);
   FHESI_TRY(rotations_args(c, hoisted, ks, nk, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  FHESI_TRY(matvec_args(c, "ct_matvec", w, nk, nk, logQ, in, nlimbs, count, out));
+  FHESI_TRY(matvec_args(c, "ct_matvec", w, 1, 1, nk, nk, logQ, in, nlimbs, count, out));
   if (!count) return 0;
-  return matvec_run(c, hoisted, ks, nk, nullptr, nullptr, nullptr, 1, true, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
+  return matvec_run(c, hoisted, ks, nk, nullptr, nullptr, nullptr, 1, true, 1, 1, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
 }
 extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const int64_t* kb, int32_t B, const fhesi_ksk* const* giant_hoisted,
                                         const int64_t* kg, int32_t G, int32_t nk, const fhesi_plain* w, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
@@ -612,12 +625,12 @@ extern "C" int fhesi_ct_matvec_bsgs_dev(fhesi_ctx* c, const fhesi_ksk* const* ba
   if ((i64)nk <= (i64)(G - 1) * B || (i64)nk > (i64)G * B) FHESI_FAIL("ct_matvec_bsgs: %d diagonals outside (%lld, %lld], what %d giant steps of %d baby steps cover", nk, (long long)(G - 1) * B, (long long)G * B, G, B);
   FHESI_TRY(rotations_args(c, baby_hoisted, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
   FHESI_TRY(rotations_args(c, giant_hoisted, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  FHESI_TRY(matvec_args(c, "ct_matvec_bsgs", w, nk, std::min(B, nk), logQ, in, nlimbs, count, out));
+  FHESI_TRY(matvec_args(c, "ct_matvec_bsgs", w, 1, 1, nk, std::min(B, nk), logQ, in, nlimbs, count, out));
   if (!count) return 0;
   // the giants' tables before any digit row exists, as rotations_run builds its matrices'
   std::vector<int> g_mode((size_t)G, -1);
   for (int g = 0; g < G; ++g) if (giant_hoisted[g]) FHESI_TRY(key_switch_form(c, giant_hoisted[g], logQ, decomp_bytes, &g_mode[g]));
-  return matvec_run(c, baby_hoisted, kb, B, giant_hoisted, kg, g_mode.data(), G, false, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
+  return matvec_run(c, baby_hoisted, kb, B, giant_hoisted, kg, g_mode.data(), G, false, 1, 1, nk, w, logQ, decomp_bytes, in, nlimbs, count, out);
 }
 
 // --------------------------------------------------------------------------------------------- folds and dense linear layers
@@ -693,17 +706,47 @@ extern "C" int fhesi_linear_plan(int64_t cols, int64_t R, int64_t C, int32_t bab
   return 0;
 }
 
-// out[i] = M in[i] + b on the slots (include/fhesi_hip.h): matvec_run with the layer's diagonals, the folds in place on out, the bias -- embedded into the
-// message staging slot once the sums' index lists in it are dead -- through launch_ct_add_const.  The words of fhesi_ct_matvec_bsgs_dev,
-// fhesi_ct_rot_fold_dev and fhesi_ct_add_slots_dev in that order.
-extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
-                                   int32_t nlimbs, int64_t count, uint64_t* out) {
+// host only.  The grid of nI x nJ blocks of Rb x Cb: the block's plan with the B that suits the shared schedule -- the babies run once per input block, the
+// giants once per output block, so B minimises nJ (B - 1) + nI (G - 1); of equal costs the larger B.  One block: what fhesi_linear_plan picks.
+extern "C" int fhesi_linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int32_t* nI_out, int32_t* nJ_out, int32_t* T_out, int32_t* B_out,
+                                      int32_t* G_out, int32_t* nfold_out, int64_t* amounts) {
+  int32_t T = 0, B = 0, G = 0, nfold = 0;
+  FHESI_TRY(fhesi_linear_plan(cols, Rb, Cb, baby, &T, &B, &G, &nfold, nullptr));      // the block's shape, in the planner's own words
+  if (R < 1 || C < 1) FHESI_FAIL("linear_grid_plan: a %lld x %lld matrix (both sizes at least 1)", (long long)R, (long long)C);
+  if (R % Rb) FHESI_FAIL("linear_grid_plan: R = %lld is not a multiple of the block's %lld rows (pad the matrix with zero rows)", (long long)R, (long long)Rb);
+  if (C % Cb) FHESI_FAIL("linear_grid_plan: C = %lld is not a multiple of the block's %lld columns (pad the matrix with zero columns)", (long long)C, (long long)Cb);
+  const i64 nI = R / Rb, nJ = C / Cb;
+  if (nI * nJ > 65535 || nI * nJ * T > 65535) FHESI_FAIL("linear_grid_plan: %lld x %lld blocks of %d diagonals per handle, 1 .. 65535 diagonals are taken", (long long)nI, (long long)nJ, T);
+  if (!baby) {
+    i64 cost = -1;
+    for (i64 b = 1; b <= T; ++b) {
+      const i64 s = nJ * (b - 1) + nI * ((T + b - 1) / b - 1);
+      if (cost < 0 || s <= cost) { cost = s; B = (int32_t)b; }
+    }
+    G = (T + B - 1) / B;
+  }
+  if (nI_out) *nI_out = (int32_t)nI;
+  if (nJ_out) *nJ_out = (int32_t)nJ;
+  if (T_out) *T_out = T;
+  if (B_out) *B_out = B;
+  if (G_out) *G_out = G;
+  if (nfold_out) *nfold_out = nfold;
+  if (amounts) FHESI_TRY(fhesi_linear_plan(cols, Rb, Cb, B, nullptr, nullptr, nullptr, nullptr, amounts));      // (baby = B > 0: min(B, T) = B)
+  return 0;
+}
+
+// out[I][i] = sum_J M_IJ in[J][i] + b_I on the slots (include/fhesi_hip.h): matvec_run over the grid's diagonals, the folds in place on out -- nI count
+// ciphertexts in a row --, the biases -- embedded into the message staging slot once the sums' index lists in it are dead -- through launch_ct_add_const.
+// One block: the words of fhesi_ct_matvec_bsgs_dev, fhesi_ct_rot_fold_dev and fhesi_ct_add_slots_dev in that order.  who: the entry point, for its refusals.
+static int linear_run(fhesi_ctx* c, const char* who, const char* what, const fhesi_linear_grid* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ,
+                      int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
   CHECK_CTX(c);
-  if (!lin) FHESI_FAIL("ct_linear: null linear layer");
-  if (lin->ctx != c) FHESI_FAIL("ct_linear: the linear layer belongs to another context");
-  const int B = lin->B, G = lin->G, nf = lin->nfold;
-  if (nh != B - 1 + G - 1 + nf) FHESI_FAIL("ct_linear: %d matrices, the layer takes %d (%d baby, %d giant and %d fold rotations)", nh, B - 1 + G - 1 + nf, B - 1, G - 1, nf);
-  if (nh && !hoisted) FHESI_FAIL("ct_linear: null argument");
+  if (!lin) FHESI_FAIL("%s: null %s", who, what);
+  if (lin->ctx != c) FHESI_FAIL("%s: the %s belongs to another context", who, what);
+  const int B = lin->B, G = lin->G, nf = lin->nfold, nI = lin->nI, nJ = lin->nJ;
+  if (nh != B - 1 + G - 1 + nf) FHESI_FAIL("%s: %d matrices, the layer takes %d (%d baby, %d giant and %d fold rotations)", who, nh, B - 1 + G - 1 + nf, B - 1, G - 1, nf);
+  if (nh && !hoisted) FHESI_FAIL("%s: null argument", who);
+  if ((double)std::max(nI, nJ) * (double)count > 2147483647.0) FHESI_FAIL("%s: %lld ciphertexts per block exceed what the grid of %d x %d blocks can index", who, (long long)count, nI, nJ);
   // the identity in front of the babies and of the giants; k = g^amount mod m
   std::vector<const fhesi_ksk*> hs((size_t)nh + 2, nullptr);
   std::vector<int64_t> ks((size_t)nh + 2, 1);
@@ -717,20 +760,32 @@ extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const 
   FHESI_TRY(rotations_args(c, hb, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
   FHESI_TRY(rotations_args(c, hg, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
   FHESI_TRY(rotations_args(c, hf, kf, nf, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  FHESI_TRY(matvec_args(c, "ct_linear", lin->w, lin->T, std::min(B, lin->T), logQ, in, nlimbs, count, out));
+  FHESI_TRY(matvec_args(c, who, lin->w, nI, nJ, lin->T, nJ * std::min(B, lin->T), logQ, in, nlimbs, count, out));
   if (!count) return 0;
   // every table before any digit row exists, as rotations_run builds its matrices'
   std::vector<int> g_mode, f_mode;
   FHESI_TRY(key_switch_forms(c, hg, G, logQ, decomp_bytes, &g_mode));
   FHESI_TRY(key_switch_forms(c, hf, nf, logQ, decomp_bytes, &f_mode));
-  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, g_mode.data(), G, false, lin->T, lin->w, logQ, decomp_bytes, in, nlimbs, count, out));
-  FHESI_TRY(rot_fold_run(c, hf, kf, nf, f_mode.data(), logQ, decomp_bytes, (u64*)out, nlimbs, count));
+  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, g_mode.data(), G, false, nI, nJ, lin->T, lin->w, logQ, decomp_bytes, in, nlimbs, count, out));
+  FHESI_TRY(rot_fold_run(c, hf, kf, nf, f_mode.data(), logQ, decomp_bytes, (u64*)out, nlimbs, (i64)nI * count));
   if (!lin->d_bias) return 0;
   const size_t n = (size_t)c->phim;
   void* d_msg;
-  FHESI_TRY(ws_reserve(c, 5, n * 8, &d_msg));
-  FHESI_TRY(slots_embed_rows(lin->slots, lin->d_bias, c->phim, false, 1, (i64*)d_msg));
-  return grid_chunks(count, [&](i64 done, i64 cnt) { return launch_ct_add_const(c, (u64*)out + (size_t)done * 2 * n * nlimbs, (const i64*)d_msg, 1, 2, nlimbs, logQ, lin->slots->S.p, cnt); });
+  FHESI_TRY(ws_reserve(c, 5, (size_t)nI * n * 8, &d_msg));
+  FHESI_TRY(slots_embed_rows(lin->slots, lin->d_bias, c->phim, false, nI, (i64*)d_msg));
+  for (int I = 0; I < nI; ++I)
+    FHESI_TRY(grid_chunks(count, [&](i64 done, i64 cnt) {
+      return launch_ct_add_const(c, (u64*)out + ((size_t)I * count + done) * 2 * n * nlimbs, (const i64*)d_msg + (size_t)I * n, 1, 2, nlimbs, logQ, lin->slots->S.p, cnt);
+    }));
+  return 0;
+}
+extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                                   int32_t nlimbs, int64_t count, uint64_t* out) {
+  return linear_run(c, "ct_linear", "linear layer", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
+}
+extern "C" int fhesi_ct_linear_grid_dev(fhesi_ctx* c, const fhesi_linear_grid* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
+                                        const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
+  return linear_run(c, "ct_linear_grid", "linear grid", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
 }
 
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).

@@ -209,7 +209,9 @@ struct fhesi_ctx {
   //   rotations there too, the inner sums of a chunk in 13 and the giants' key-switched ciphertexts in 14 -- neither the plaintext sum nor a key switch touches
   //   those --, and the composed form of the rotated sum keeps one rotated term in 15; a linear layer's constructor writes its slot vectors -- and a host
   //   matrix behind them -- into 9 and embeds them into 5 like any slot-valued stage; fhesi_ct_rot_fold_dev keeps a step's key-switched ciphertexts in 14, as
-  //   the giants do, and fhesi_ct_linear_dev embeds its bias into 5 behind the last fold, when the sums' index lists there are dead)
+  //   the giants do, and fhesi_ct_linear_dev embeds its bias into 5 behind the last fold, when the sums' index lists there are dead; a grid of blocks,
+  //   fhesi_linear_grid_*, keeps the same owners: 9 and 5 hold one chunk of blocks at creation, 12 the babies of every input block of a chunk of
+  //   ciphertexts, 13 the inner sums of every output block, 14 the key-switched sums of ONE output block at a time, 5 the nI embedded biases)
   void* ws[FHESI_WS_SLOTS] = {};
   size_t ws_bytes[FHESI_WS_SLOTS] = {};
 };
@@ -438,18 +440,24 @@ int launch_plain_sum(fhesi_ctx* ctx, const u64* d_ca /* [nu][2][L][n] */, const 
                      i64 ngroups, bool accumulate, u64* d_out /* [ngroups][2][L][n] */, double nterms);
 
 // --------------------------------------------------------------------------------- dense linear layers (capi_ct.hip, capi_pipeline.hip, kernels_slots.hip)
-// One R x C layer on a slot space (include/fhesi_hip.h): the T = min(R, C) prepared diagonals, the replicated bias, the plan
-struct fhesi_linear {
+// An R x C matrix, R = nI Rb, C = nJ Cb, as a grid of Rb x Cb blocks on a slot space (include/fhesi_hip.h): the nI nJ T prepared diagonals of the blocks,
+// T = min(Rb, Cb), in ONE prepared plaintext, the replicated biases of the nI output blocks, the plan every block shares
+struct fhesi_linear_grid {
   fhesi_ctx* ctx = nullptr;
-  fhesi_slots* slots = nullptr;        // the space the layer was made on, borrowed: embeds the bias in front of its addition
-  i64 R = 0, C = 0;
-  int T = 0, B = 0, G = 0, nfold = 0;
-  std::vector<i64> amounts;            // babies 1 .. B - 1, giants B .. (G - 1) B, folds C/2 .. R: the order of the apply call's matrices
-  fhesi_plain* w = nullptr;            // w_t = rot_{-gB}(e_t), t = g B + j
-  i64* d_bias = nullptr;               // [phim] slot values b[i mod R] in [0, p), every row alike; null without a bias
+  fhesi_slots* slots = nullptr;        // the space the grid was made on, borrowed: embeds the bias in front of its addition
+  i64 R = 0, C = 0, Rb = 0, Cb = 0;
+  int nI = 0, nJ = 0, T = 0, B = 0, G = 0, nfold = 0;
+  std::vector<i64> amounts;            // babies 1 .. B - 1, giants B .. (G - 1) B, folds Cb/2 .. Rb: the order of the apply call's matrices
+  fhesi_plain* w = nullptr;            // row (I nJ + J) T + t: w_t = rot_{-gB}(e_t) of block (I, J), t = g B + j
+  i64* d_bias = nullptr;               // [nI][phim] slot values b[I Rb + i mod Rb] in [0, p), every row alike; null without a bias
 };
-// d_out[t][s] = w_t at slot s = (row, i), reduced into [0, p): t < T slot vectors of S.phim values, M [R][C] int64 in HBM (linear_diag_kernel, kernels_slots.hip)
-int launch_linear_diag(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_M, i64 R, i64 C, int T, int B, i64* d_out /* [T][phim] */);
+// One R x C layer (include/fhesi_hip.h): the grid of one block, Rb = R, Cb = C
+struct fhesi_linear : fhesi_linear_grid {};
+// d_out[(b - first) T + t][s] = w_t of block b = I nJ + J at slot s = (row, i), reduced into [0, p): the blocks first .. first + nblocks - 1 of the row-major
+// matrix d_M of leading dimension ld, block (I, J) at d_M + I R ld + J C; t < T slot vectors of S.phim values each (linear_diag_kernel, kernels_slots.hip).
+// One layer: ld = C, nJ = 1, first = 0, nblocks = 1.
+int launch_linear_diag(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_M, i64 ld, int nJ, int first, int nblocks, i64 R, i64 C, int T, int B,
+                       i64* d_out /* [nblocks][T][phim] */);
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

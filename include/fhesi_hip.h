@@ -594,6 +594,51 @@ int fhesi_ct_rot_fold_dev(fhesi_ctx* ctx, const fhesi_ksk* const* hoisted, const
 int fhesi_ct_linear_dev(fhesi_ctx* ctx, const fhesi_linear* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
                         const uint64_t* in_dev /* [count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count, uint64_t* out_dev);
 
+/* ---- dense layers larger than a row of slots: an R x C matrix as a grid of nI x nJ blocks of Rb x Cb, R = nI Rb, C = nJ Cb (capi_ct.hip,
+ * capi_pipeline.hip, linear_diag_kernel in kernels_slots.hip).  The block shape is one fhesi_linear_plan(cols, Rb, Cb, .) admits;
+ * T = min(Rb, Cb), D = max(Rb, Cb), nfold and the folds are the block's.  Rotations are ring maps and plaintext sums are exact, so
+ *   input      nJ ciphertexts per item, ciphertext J: slot (r, i) = x_r[J Cb + (i mod Cb)]
+ *   diagonals  of block (I, J): those of fhesi_linear_create on the sub-matrix M[I Rb .., J Cb ..] with the grid's B,
+ *              e_t[i] = M[I Rb + (i mod D) mod Rb][J Cb + ((i mod D) + t) mod Cb],  w^{IJ}_t = rot_{-gB}(e_t), t = g B + j
+ *   output     y_I = fold( sum_{g<G} rot_{gB}( sum_{J<nJ} sum_{j<B, gB+j<T} w^{IJ}_{gB+j} (*) rot_j(x_J) ) ) + b_I
+ *   result     slot (r, i) of y_I = (M x_r + b)[I Rb + (i mod Rb)]
+ * the baby rotations of input block J serve every output block and the giants and folds of output block I run behind the sum over J:
+ * nJ (B - 1) + nI (G - 1) + nI nfold key switches where one fhesi_linear per block takes nI nJ (B + G - 2 + nfold).
+ *
+ * fhesi_linear_grid_plan (host only): nI, nJ, the block's T and nfold, B (baby = 0: the B in 1 .. T that minimises nJ (B - 1) + nI (ceil(T / B) - 1),
+ *   of equal costs the larger; otherwise min(baby, T)), G = ceil(T / B), and the amounts in fhesi_linear_plan's order: babies 1 .. B - 1, giants
+ *   B .. (G - 1) B, the block's folds Cb/2 .. Rb.  A 1 x 1 grid plans as fhesi_linear_plan does.  Any output may be NULL.  REFUSED with the condition
+ *   named: a block shape fhesi_linear_plan refuses (in its words); R not a multiple of Rb or C not a multiple of Cb (the caller pads with zeros);
+ *   more than 65535 diagonals nI nJ T per handle.
+ * fhesi_linear_grid_create / _create_dev: M [R][C] row-major and bias [R] (or NULL) any int64, on the host or in HBM as for fhesi_linear_create.  The
+ *   handle owns ONE prepared plaintext of nI nJ T diagonals, row (I nJ + J) T + t, the replicated biases [nI][phi(m)] and the plan; the diagonals
+ *   are written, embedded and transformed in chunks of whole blocks, so the workspace holds a chunk and never the grid.  It counts as a live handle
+ *   of the context and borrows s.  fhesi_linear_grid_info: shapes, plan, whether it has a bias, the amounts (any pointer may be NULL).
+ * fhesi_linear_grid_diagonals: the same stage without a handle -- vals_host [nI][nJ][T][phi(m)] receives the slot vectors.
+ * fhesi_ct_linear_grid_dev: in_dev [nJ][count], out_dev [nI][count] two-part ciphertexts; hoisted [nh] as fhesi_ct_linear_dev takes them.  DEFINED
+ *   as, and word for word equal to: fhesi_ct_rotations_dev per input block (identity first) into one pool [nJ][min(B, T)][count]; ONE
+ *   fhesi_ct_plain_sum_dev with the groups (I, g, i) and the terms (J, j); per output block fhesi_ct_rotations_dev of each inner sum by its giant
+ *   and fhesi_ct_add_dev; fhesi_ct_rot_fold_dev; fhesi_ct_add_slots_dev with the block's replicated bias.  A 1 x 1 grid returns the words of
+ *   fhesi_ct_linear_dev.  The capacity rule of fhesi_ct_plain_sum_dev is checked with nJ min(B, T) terms before anything is launched; pool, inner
+ *   sums and key-switched sums live in the workspace, in chunks of ciphertexts.  REFUSED as fhesi_ct_linear_dev refuses.
+ * NOT HERE: a form of the C++ mirror; a form over a slot basis (a caller runs one grid per channel); Cb / Rb other than a power of two inside a
+ *   block; mixing the two rows of a two-row space. */
+typedef struct fhesi_linear_grid fhesi_linear_grid; /* a grid of blocks on a slot space: its prepared diagonals, its replicated biases and its plan */
+int fhesi_linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby /* 0: the planner's */, int32_t* nI, int32_t* nJ, int32_t* T,
+                           int32_t* B, int32_t* G, int32_t* nfold, int64_t* amounts /* [B - 1 + G - 1 + nfold] or NULL */);
+int fhesi_linear_grid_create(fhesi_slots* s, const int64_t* M_host /* [R][C] */, int64_t R, int64_t C, int64_t Rb, int64_t Cb,
+                             const int64_t* bias_host /* [R] or NULL */, int32_t baby, fhesi_linear_grid** out);
+int fhesi_linear_grid_create_dev(fhesi_slots* s, const int64_t* M_dev /* [R][C] */, int64_t R, int64_t C, int64_t Rb, int64_t Cb,
+                                 const int64_t* bias_dev /* [R] or NULL */, int32_t baby, fhesi_linear_grid** out);
+int fhesi_linear_grid_free(fhesi_linear_grid* grid);
+int fhesi_linear_grid_info(const fhesi_linear_grid* grid, int64_t* R, int64_t* C, int64_t* Rb, int64_t* Cb, int32_t* nI, int32_t* nJ, int32_t* T, int32_t* B,
+                           int32_t* G, int32_t* nfold, int32_t* has_bias, int64_t* amounts /* [B - 1 + G - 1 + nfold] or NULL */);
+int fhesi_linear_grid_diagonals(fhesi_slots* s, const int64_t* M_host /* [R][C] */, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby,
+                                int64_t* vals_host /* [nI][nJ][T][phi(m)] */);
+int fhesi_ct_linear_grid_dev(fhesi_ctx* ctx, const fhesi_linear_grid* grid, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
+                             const uint64_t* in_dev /* [nJ][count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count,
+                             uint64_t* out_dev /* [nI][count][2][phi(m)][nlimbs] */);
+
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
  * fhesi_comm_init_all: one process, one host thread per GPU -- ncclCommInitAll over `devices`, comms_out[r] is rank r's handle.
