@@ -110,6 +110,10 @@ def test_ops_scalar_automorph(m):
 
 
 def test_index_sets_add_remove_scrt():
+    """Index sets on one small ring (m = 128: the generic LDS rows, 60-bit primes): from_poly over [0, 2], addPrimes / removePrimes
+    (DoubleCRT.cpp:142-156), the errors of mismatching sets and contexts, SingleCRT <-> DoubleCRT over the whole chain.  The same calls over proper
+    sets on every other class of row transform -- tile, two-pass and global-stage rows, the Bluestein forms -- and on primes of different sizes:
+    test_gpu_index_sets.py."""
     m = 128
     ctx, orc, primes = make(m, logQ=150)
     L, n = len(primes), ctx.phim
