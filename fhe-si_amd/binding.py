@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "fhesi_ct_rot_fold_dev", "fhesi_ct_linear_dev",
     "fhesi_linear_grid_plan", "fhesi_linear_grid_create", "fhesi_linear_grid_create_dev", "fhesi_linear_grid_free", "fhesi_linear_grid_info",
     "fhesi_linear_grid_diagonals", "fhesi_ct_linear_grid_dev",
+    "fhesi_ct_lin_comb_dev", "fhesi_poly_eval_plan", "fhesi_ct_poly_eval_dev",
 ]
 ROT_SUM_MAX_TERMS = 16   # FHESI_ROT_SUM_MAX_TERMS: the terms one launch of the rotated-sum kernel takes (more terms chain launches)
 ABI_VERSION = 9          # FHESI_ABI_VERSION of the include/fhesi_hip.h this table was written against (checked in _load)
@@ -266,6 +267,9 @@ def _load():
         "fhesi_linear_grid_info": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "fhesi_linear_grid_diagonals": [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
         "fhesi_ct_linear_grid_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_ct_lin_comb_dev": [_vp, _i32, _u64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+        "fhesi_poly_eval_plan": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_ct_poly_eval_dev": [_vp, _vp, _i32, _u64, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -625,6 +629,27 @@ class Context:
         hs, ka = self._hoisted_args(hoisted, ks)
         _ck(_load().fhesi_ct_rot_fold_dev(self.h, hs, _p(ka) if len(ka) else None, len(ka), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
 
+    # ---- polynomial activations: scalar linear combinations and y = f(x) slot by slot (fhesi_ct_lin_comb_dev, fhesi_ct_poly_eval_dev)
+    def ct_lin_comb_dev(self, logQ: int, p: int, pool, npool: int, nlimbs: int, a_idx, coef, seg, konst, out: DevBuf):
+        """out[g] = Reduce(sum_{t in [seg[g], seg[g+1])} coef[t] pool[a_idx[t]] + konst[g]) on unscaled two-part ciphertexts: the words of a copy,
+        ct_mul_long_dev and ct_add_dev per term and ct_add_const_dev with (konst[g], 0, .., 0).  coef, konst: any int64; konst None: no constants.
+        The arguments are checked by the library (FhesiError names what it refuses)."""
+        ia, sg = np.ascontiguousarray(a_idx, dtype=np.int32), np.ascontiguousarray(seg, dtype=np.int32)
+        cf = np.ascontiguousarray(coef, dtype=np.int64)
+        kn = None if konst is None else np.ascontiguousarray(konst, dtype=np.int64)
+        if len(ia) != len(cf) or (kn is not None and len(kn) != len(sg) - 1):
+            raise ValueError("ct_lin_comb_dev: one coefficient per term and one constant per group")
+        _ck(_load().fhesi_ct_lin_comb_dev(self.h, logQ, p, pool.ptr if pool is not None else None, npool, nlimbs, _p(ia) if len(ia) else None,
+                                          _p(cf) if len(cf) else None, _p(sg), _p(kn) if kn is not None else None, len(sg) - 1, out.ptr))
+
+    def ct_poly_eval_dev(self, ksk: "KeySwitchMatrix", logQ: int, p: int, coef, src: DevBuf, nlimbs: int, count: int, out: DevBuf, baby: int = 0, decomp_bytes: int = 3):
+        """out[i] = f(src[i]) slot by slot, f = sum_k coef[k] X^k (any int64, reduced modulo p): Paterson-Stockmeyer with `baby` baby powers (0: the
+        planner's, poly_eval_plan) -- word for word the composition of ct_mul_sum_relin_dev and ct_lin_comb_dev that tests/poly_model.py states."""
+        cf = np.ascontiguousarray(coef, dtype=np.int64)
+        if cf.ndim != 1 or len(cf) < 2:
+            raise ValueError("ct_poly_eval_dev: coef is [degree + 1], degree >= 1")
+        _ck(_load().fhesi_ct_poly_eval_dev(self.h, ksk.h, logQ, p, decomp_bytes, _p(cf), len(cf) - 1, int(baby), src.ptr, nlimbs, count, out.ptr))
+
     def release_host_staging(self):
         """hand back the pinned + device staging ring the host-buffer calls keep between uses"""
         _ck(_load().fhesi_host_stage_release(self.h))
@@ -635,6 +660,15 @@ def matvec_bsgs_plan(nk: int) -> tuple:
     b, g = _i32(0), _i32(0)
     _ck(_load().fhesi_matvec_bsgs_plan(int(nk), C.byref(b), C.byref(g)))
     return b.value, g.value
+
+
+def poly_eval_plan(degree: int, baby: int = 0) -> dict:
+    """The Paterson-Stockmeyer plan of a dense polynomial of degree 1 .. 4096 (fhesi_poly_eval_plan): B baby powers (baby = 0: the B of least key
+    switches, of equal ones the smaller depth, then the larger B), G = degree // B + 1 groups, the products, the key switches and the multiplicative
+    depth of Context.ct_poly_eval_dev.  Raises FhesiError naming the condition on a refused shape.  Touches no device."""
+    v = [_i32(0) for _ in range(5)]
+    _ck(_load().fhesi_poly_eval_plan(int(degree), int(baby), *(_byref(x) for x in v)))
+    return dict(zip(("B", "G", "nprod", "nks", "depth"), (x.value for x in v)))
 
 
 def linear_plan(cols: int, R: int, C: int, baby: int = 0) -> dict:
@@ -930,6 +964,11 @@ class SlotSpace:
         """Ciphertext += Plaintext(vals) on unscaled ciphertexts; vals [nv][nvals] slot values, nv = 1 (one constant for all) or count."""
         vals = np.ascontiguousarray(np.atleast_2d(vals), dtype=np.int64)
         _ck(_load().fhesi_ct_add_slots_dev(self.ctx.h, self.h, logQ, ct.ptr, nparts, nlimbs, count, _p(vals), vals.shape[1], int(only_usable), vals.shape[0]))
+
+    def poly_eval(self, ksk: "KeySwitchMatrix", coef, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, baby: int = 0, decomp_bytes: int = 3):
+        """out[i] = f(src[i]) slot by slot modulo p, f = sum_k coef[k] X^k: the activation between two layers (Context.ct_poly_eval_dev with this
+        space's p).  ksk: the s^2 -> s matrix."""
+        self.ctx.ct_poly_eval_dev(ksk, logQ, self.p, coef, src, nlimbs, count, out, baby, decomp_bytes)
 
     # ---- dense linear layers: y = M x + b for a matrix given as a matrix (fhesi_linear_*): the diagonals are made on the device
     def fold(self, hoisted, amounts, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
@@ -1266,6 +1305,14 @@ class SlotBasis:
         words = 2 * self.ctx.phim * nlimbs * 8
         for c in range(self.k):
             layers[c].apply(hoisted_by_amount, logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
+
+    def poly_eval(self, ksk: "KeySwitchMatrix", coef, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, baby: int = 0, decomp_bytes: int = 3):
+        """SlotSpace.poly_eval per channel (one key set serves every channel): src, out [k][count] logical ciphertexts; coef Python integers of any
+        size, channel c taking them modulo primes[c].  Exact while |f(v)| stays below half the product of the primes."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            cf = [int(v) % self.primes[c] for v in coef]
+            self.channel(c).poly_eval(ksk, cf, logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), baby, decomp_bytes)
 
     def ct_add_slots_dev(self, logQ: int, ct: DevBuf, nlimbs: int, count: int, vals):
         """Ciphertext += integers, per channel: ct [k][count] two-part ciphertexts, vals [nv][nvals] integers, nv = 1 or count."""

@@ -1,6 +1,7 @@
 // capi_ct.hip -- ciphertext algebra between multiplications, Encrypt / Decrypt batches, prepared plaintext operands, key generation (include/fhesi_hip.h)
 #include "capi_common.h"
 #include "wave_plan.h"
+#include "poly_plan.h"
 
 // ---- coefficient-domain ciphertext algebra on device batches (kernels_ct.hip)
 extern "C" int fhesi_ct_add_dev(fhesi_ctx* c, int32_t logQ, uint64_t* dst, const uint64_t* src, int32_t nparts, int32_t nlimbs, int64_t count) {
@@ -554,6 +555,45 @@ extern "C" int fhesi_ct_plain_sum_dev(fhesi_ctx* c, const fhesi_plain* w, int32_
     FHESI_TRY(launch_crt(c, t_all, (const u64*)d_sum, L, nullptr, P.ng * 2, 2, 0, logQ, (u64*)out + (size_t)P.g * ct_words, nlimbs));
   }
   return 0;
+}
+// out[g] = Reduce_logQ(sum_{t in [seg[g], seg[g+1])} coef[t] pool[a_idx[t]] + konst[g]) on unscaled two-part ciphertexts (include/fhesi_hip.h): one launch of
+// ct_lin_comb_kernel per 65535 polynomials, whatever the number of terms.  The lists (lin_comb_lists, poly_plan.h) are uploaded once, in front of the first
+// launch, into workspace slot 5: [magnitudes][constants][pool indices][bounds].
+extern "C" int fhesi_ct_lin_comb_dev(fhesi_ctx* c, int32_t logQ, uint64_t p, const uint64_t* pool, int64_t npool, int32_t nlimbs, const int32_t* a_idx,
+                                     const int64_t* coef, const int32_t* seg, const int64_t* konst, int64_t ngroups, uint64_t* out) {
+  CHECK_CTX(c);
+  if (nlimbs < 1 || nlimbs > 32) FHESI_FAIL("ct_lin_comb: ciphertext coefficients of %d limbs are outside the supported 1..32", nlimbs);
+  if (logQ < 1 || nlimbs * 64 < logQ) FHESI_FAIL("ct_lin_comb: coefficients of %d limbs cannot hold logQ=%d bits", nlimbs, logQ);
+  if (p < 2) FHESI_FAIL("ct_lin_comb: plaintext modulus %llu", (unsigned long long)p);
+  if (ngroups < 0 || npool < 0) FHESI_FAIL("ct_lin_comb: negative count");
+  if (!ngroups) return 0;
+  if (!seg || !out) FHESI_FAIL("ct_lin_comb: null argument");
+  if (seg[0] != 0) FHESI_FAIL("ct_lin_comb: seg must start at 0, got %d", seg[0]);
+  for (i64 g = 0; g < ngroups; ++g)
+    if (seg[g + 1] < seg[g]) FHESI_FAIL("ct_lin_comb: seg is not non-decreasing at group %lld (%d after %d)", (long long)g, seg[g + 1], seg[g]);
+  const i64 nterms = seg[ngroups];
+  if (nterms && (!a_idx || !coef || !pool)) FHESI_FAIL("ct_lin_comb: null argument");
+  for (i64 t = 0; t < nterms; ++t)
+    if (a_idx[t] < 0 || a_idx[t] >= npool) FHESI_FAIL("ct_lin_comb: ciphertext index %d of term %lld out of range (pool of %lld)", a_idx[t], (long long)t, (long long)npool);
+  const size_t ct_bytes = (size_t)2 * c->phim * nlimbs * 8;
+  {
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)ngroups * ct_bytes, p0 = (uintptr_t)pool, p1 = p0 + (size_t)npool * ct_bytes;
+    if (pool && npool && o0 < p1 && p0 < o1) FHESI_FAIL("ct_lin_comb: out overlaps pool");
+  }
+  const LinCombLists L = lin_comb_lists(a_idx, coef, seg, ngroups);
+  const size_t nt = L.idx.size(), ng = (size_t)ngroups, nk = konst ? ng : 0;
+  void* d;
+  FHESI_TRY(ws_reserve(c, 5, (nt + nk) * 8 + (nt + 3 * ng) * 4, &d));
+  u64* d_mag = (u64*)d;
+  i64* d_konst = (i64*)(d_mag + nt);
+  int* d_idx = (int*)(d_konst + nk);
+  int* d_bounds = d_idx + nt;
+  if (nt) HIP_TRY(hipMemcpyAsync(d_mag, L.mag.data(), nt * 8, hipMemcpyHostToDevice, c->stream));
+  if (nk) HIP_TRY(hipMemcpyAsync(d_konst, konst, nk * 8, hipMemcpyHostToDevice, c->stream));
+  if (nt) HIP_TRY(hipMemcpyAsync(d_idx, L.idx.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_bounds, L.bounds.data(), 3 * ng * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));                 // the one synchronisation: the lists live on this frame, konst is the caller's again on return
+  return launch_ct_lin_comb(c, (const u64*)pool, d_idx, d_mag, d_bounds, nk ? d_konst : nullptr, ngroups, nlimbs, logQ, p, (u64*)out);
 }
 // Ciphertext::operator+=(const ZZX&) unscaled (Ciphertext.cpp:147-156) with the constant given as slot values: the embed stage, then the kernel
 // behind fhesi_ct_add_const_dev on the message polynomials where they are

@@ -2,6 +2,7 @@
 #include "capi_common.h"
 #include "copy_pool.h"
 #include "wave_plan.h"
+#include "poly_plan.h"
 
 // --------------------------------------------------------------------------------------------- key-switch matrix
 extern "C" int fhesi_ksk_create(fhesi_ctx* c, int32_t ncomp, int32_t ndigits, fhesi_ksk** out) {
@@ -904,6 +905,94 @@ extern "C" int fhesi_ct_mul_sum_relin_dev(fhesi_ctx* c, const fhesi_ksk* k, int3
   bool single = c->opt.wave_single != 0;
   for (i64 g = 0; single && g < ngroups; ++g) single = seg[g + 1] - seg[g] == 1;
   return (single ? wave_single_products : wave_sums)(c, k, logQ, p, decomp_bytes, pool, nlimbs, a_idx, b_idx, seg, ngroups, out);
+}
+
+// --------------------------------------------------------------------------------------------- polynomial activations
+// host only: the plan of a dense polynomial (poly_plan.h; tests/poly_model.py states it)
+extern "C" int fhesi_poly_eval_plan(int32_t degree, int32_t baby, int32_t* B, int32_t* G, int32_t* nprod, int32_t* nks, int32_t* depth) {
+  if (degree < 1 || degree > kPolyMaxDegree) FHESI_FAIL("poly_eval_plan: degree %d outside 1 .. %d", degree, kPolyMaxDegree);
+  if (baby < 0 || baby > degree) FHESI_FAIL("poly_eval_plan: %d baby powers outside 0 .. %d (0 = choose)", baby, degree);
+  const PolyCounts pc = poly_plan(degree, baby);
+  if (B) *B = pc.B;
+  if (G) *G = pc.G;
+  if (nprod) *nprod = pc.nprod;
+  if (nks) *nks = pc.nks;
+  if (depth) *depth = pc.depth;
+  return 0;
+}
+// out[i] = f(in[i]) slot by slot (include/fhesi_hip.h): the schedule of poly_plan.h through the public entry points, per chunk of ciphertexts.  One workspace
+// slot (13: nothing fhesi_ct_mul_sum_relin_dev or fhesi_ct_lin_comb_dev calls reserves it) holds the entries of a chunk, entry e of item i at e cnt + i: the
+// powers (the input copied to entry 0), the inner sums, W -- one buffer, because the outer sum's operands and the closing combination's are each ONE pool.
+// A level of powers is one wave of single products written into the pool it reads (its destinations are entries no product of the level reads); all inner
+// sums one scalar combination (pool: the powers; out: the entries behind them); W one wave of one group per item; y one scalar combination into out.
+// Every argument checked and the schedule built by the caller.
+static int poly_eval_run(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint64_t p, int32_t decomp_bytes, const PolySchedule& s, const uint64_t* in, int32_t nlimbs,
+                         int64_t count, uint64_t* out) {
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  const int ninner = (int)s.inner.size();
+  // ciphertexts per chunk: about 4 GiB of powers and of sums each (option "wave_operands": at most that many entries, for tests); index lists that 32 bits hold
+  i64 chunk = (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(s.npowers, ninner + 1) * ct_words * 8));
+  if (c->opt.wave_operands > 0) chunk = std::min<i64>(chunk, c->opt.wave_operands / s.nentries);
+  chunk = std::max<i64>(1, std::min<i64>(std::min<i64>(chunk, count), ((i64)1 << 30) / ((i64)s.nentries * (s.B + 1))));
+  void* d_pool_v;
+  FHESI_TRY(ws_reserve(c, 13, (size_t)s.nentries * chunk * ct_words * 8, &d_pool_v));
+  u64* d_pool = (u64*)d_pool_v;
+  std::vector<int32_t> a_idx, b_idx, seg;
+  std::vector<int64_t> coef, konst;
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    auto at = [&](int entry, i64 i) { return (int32_t)((i64)entry * cnt + i); };
+    HIP_TRY(hipMemcpyAsync(d_pool, in + (size_t)done * ct_words, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));      // x^1: the input as it is
+    for (const std::vector<PolyProduct>& level : s.levels) {
+      a_idx.clear(); b_idx.clear(); seg.assign(1, 0);
+      for (const PolyProduct& pr : level)
+        for (i64 i = 0; i < cnt; ++i) { a_idx.push_back(at(pr.a, i)); b_idx.push_back(at(pr.b, i)); seg.push_back((int32_t)a_idx.size()); }
+      FHESI_TRY(fhesi_ct_mul_sum_relin_dev(c, k, logQ, p, decomp_bytes, d_pool, nlimbs, a_idx.data(), b_idx.data(), seg.data(), (int64_t)level.size() * cnt,
+                                           d_pool + (size_t)level[0].dst * cnt * ct_words));
+    }
+    if (ninner) {
+      a_idx.clear(); coef.clear(); konst.clear(); seg.assign(1, 0);
+      for (const PolyInner& u : s.inner)
+        for (i64 i = 0; i < cnt; ++i) {
+          for (const PolyTerm& t : u.terms) { a_idx.push_back(at(t.entry, i)); coef.push_back(t.c); }
+          seg.push_back((int32_t)a_idx.size());
+          konst.push_back(u.konst);
+        }
+      FHESI_TRY(fhesi_ct_lin_comb_dev(c, logQ, p, d_pool, (int64_t)s.npowers * cnt, nlimbs, a_idx.data(), coef.data(), seg.data(), konst.data(), (int64_t)ninner * cnt,
+                                      d_pool + (size_t)s.npowers * cnt * ct_words));
+      a_idx.clear(); b_idx.clear(); seg.assign(1, 0);
+      for (i64 i = 0; i < cnt; ++i) {
+        for (int u = 0; u < ninner; ++u) { a_idx.push_back(at(s.npowers + u, i)); b_idx.push_back(at(s.power_entry(s.inner[u].g * s.B), i)); }
+        seg.push_back((int32_t)a_idx.size());
+      }
+      FHESI_TRY(fhesi_ct_mul_sum_relin_dev(c, k, logQ, p, decomp_bytes, d_pool, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt, d_pool + (size_t)s.w_entry * cnt * ct_words));
+    }
+    a_idx.clear(); coef.clear(); konst.assign((size_t)cnt, s.final_konst); seg.assign(1, 0);
+    for (i64 i = 0; i < cnt; ++i) {
+      for (const PolyTerm& t : s.final_terms) { a_idx.push_back(at(t.entry, i)); coef.push_back(t.c); }
+      seg.push_back((int32_t)a_idx.size());
+    }
+    FHESI_TRY(fhesi_ct_lin_comb_dev(c, logQ, p, d_pool, (int64_t)s.nentries * cnt, nlimbs, a_idx.data(), coef.data(), seg.data(), konst.data(), cnt, out + (size_t)done * ct_words));
+  }
+  return 0;
+}
+extern "C" int fhesi_ct_poly_eval_dev(fhesi_ctx* c, const fhesi_ksk* k, int32_t logQ, uint64_t p, int32_t decomp_bytes, const int64_t* coef, int32_t degree, int32_t baby,
+                                      const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
+  CHECK_CTX(c);
+  FHESI_TRY(key_switch_args(c, k, logQ, decomp_bytes, nlimbs));
+  if (k->ncomp != 3) FHESI_FAIL("ct_poly_eval needs the s^2 -> s matrix (3 source components), got %d", k->ncomp);
+  if (nlimbs < 1 || nlimbs > 32) FHESI_FAIL("ct_poly_eval: ciphertext coefficients of %d limbs are outside the supported 1..32", nlimbs);
+  if (logQ < 1) FHESI_FAIL("ct_poly_eval: logQ=%d", logQ);
+  if (p < 2 || p >= (1ull << 62)) FHESI_FAIL("ct_poly_eval: plaintext modulus %llu outside [2, 2^62)", (unsigned long long)p);
+  if (degree < 1 || degree > kPolyMaxDegree) FHESI_FAIL("ct_poly_eval: degree %d outside 1 .. %d", degree, kPolyMaxDegree);
+  if (baby < 0 || baby > degree) FHESI_FAIL("ct_poly_eval: %d baby powers outside 0 .. %d (0 = choose)", baby, degree);
+  if (count < 0) FHESI_FAIL("ct_poly_eval: negative count");
+  if (!coef) FHESI_FAIL("ct_poly_eval: null coefficients");
+  if (!count) return 0;
+  if (!in || !out) FHESI_FAIL("ct_poly_eval: null argument");
+  const size_t bytes = (size_t)count * 2 * c->phim * nlimbs * 8;
+  if (ranges_overlap(in, bytes, out, bytes)) FHESI_FAIL("ct_poly_eval: out overlaps in");
+  return poly_eval_run(c, k, logQ, p, decomp_bytes, poly_schedule(coef, degree, p, poly_plan(degree, baby).B), in, nlimbs, count, out);
 }
 
 // Ciphertexts per launch of the fused multiplication.  ks32: the key switch really runs over the four 30-bit auxiliary primes (ksaux_mode

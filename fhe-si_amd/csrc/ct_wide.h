@@ -90,7 +90,8 @@ template <int MAXNL> CTW_FN void ctw_store_centred(const u64 (&x)[MAXNL], int nl
 
 // ---- Ciphertext += ZZX (Ciphertext.cpp:147-156): q = floor(cv 2^logQ / p) modulo 2^(64 MAXNL), NTL's floor division.  |cv| 2^logQ occupies
 // limbs sh, sh + 1 (sh = logQ / 64; MAXNL >= sh + 2 holds them), divided limb by limb from the top by 128 / 64-bit long division; a negative
-// constant takes -(q + [remainder != 0]) (floor, not truncation).
+// constant takes -(q + [remainder != 0]) (floor, not truncation).  A smaller MAXNL gives the same quotient modulo 2^(64 MAXNL): the limbs above leave the shift
+// below, the remainders they hand down are the same (ctw_lin_comb, which needs the quotient modulo 2^logQ only; tests/host/ct_lin_comb_check.cpp).
 template <int MAXNL> CTW_FN void ctw_floor_quotient(u64 (&q)[MAXNL], i64 cv, int logQ, u64 p) {
   const u64 mag = cv < 0 ? (u64)(-(cv + 1)) + 1 : (u64)cv;
   const int sh = logQ >> 6, bs = logQ & 63;
@@ -109,6 +110,22 @@ template <int MAXNL> CTW_FN void ctw_floor_quotient(u64 (&q)[MAXNL], i64 cv, int
   if (cv < 0) {
     ctw_sum(q, MAXNL, rem != 0, [&](int i) { return q[i]; });
     ctw_neg(q, MAXNL);
+  }
+}
+
+// ---- a scalar linear combination with a constant (ct_lin_comb_kernel): x[0..nl) = -sum_{t in [t0, ts)} mag[t] a_t + sum_{t in [ts, t1)} mag[t] a_t
+// (+ floor(cv 2^logQ / p) when with_const) modulo 2^(64 nl) -- exact modulo 2^logQ, which divides it.  The terms of negative coefficient come first: their sum is
+// negated ONCE, where the positive ones begin.  src(t) is the limb source of a_t; mag is read at t only.  The quotient is taken modulo 2^(64 MAXNL) (limbs
+// from MAXNL upwards leave ctw_floor_quotient's shift), of which the low nl limbs count.
+template <int MAXNL, class S> CTW_FN void ctw_lin_comb(u64 (&x)[MAXNL], int nl, const u64* mag, int t0, int ts, int t1, S src, bool with_const, i64 cv, int logQ, u64 p) {
+  ctw_zero(x);
+  for (int t = t0; t < ts; ++t) ctw_muladd(x, nl, [&](int i) { return x[i]; }, src(t), mag[t]);
+  if (ts > t0) ctw_neg(x, nl);
+  for (int t = ts; t < t1; ++t) ctw_muladd(x, nl, [&](int i) { return x[i]; }, src(t), mag[t]);
+  if (with_const) {
+    u64 q[MAXNL];
+    ctw_floor_quotient(q, cv, logQ, p);
+    ctw_sum(x, nl, 0, [&](int i) { return x[i]; }, [&](int i) { return q[i]; });
   }
 }
 

@@ -498,6 +498,8 @@ int launch_sample_encrypt(fhesi_ctx* ctx, i64* d_rnd /* [count][3][n] */, i64 co
 int launch_sample_keygen(fhesi_ctx* ctx, u64* d_a, i64* d_err, i64 ncol, int nl, int logQ, u64 seed, u64 pub_seed, u64 first);
 int launch_sample_poly(fhesi_ctx* ctx, i64* d_poly /* [n] */, int kind /* 0 sampleHWt(param), 1 sampleGaussian */, i64 param, u64 seed, u64 obj);
 int launch_ct_add_const(fhesi_ctx* ctx, u64* d_ct /* [count][nparts][n][nl] */, const i64* d_poly /* [npoly][n] */, int npoly, int nparts, int nl, int logQ, u64 p, i64 count);
+int launch_ct_lin_comb(fhesi_ctx* ctx, const u64* d_pool /* [npool][2][n][nl] */, const int* d_idx, const u64* d_mag, const int* d_bounds /* [ngroups][3] */,
+                       const i64* d_konst /* [ngroups] or null */, i64 ngroups, int nl, int logQ, u64 p, u64* d_out /* [ngroups][2][n][nl] */);
 int launch_ct_automorph_parts(fhesi_ctx* ctx, const u64* d_in /* [npolys][n][nl_in] */, int nl_in, i64 npolys, i64 kk, int logQ, u64* d_parts /* [npolys][nlq][n] */, int nlq);   // 2: ring not covered
 constexpr int kRotSumMax = 16;      // terms of one ct_rot_sum_kernel launch: their (k, k^-1) pairs travel in the argument segment (FHESI_ROT_SUM_MAX_TERMS)
 int launch_ct_rot_sum(fhesi_ctx* ctx, const i64* ks, int nk, int logQ, const u64* d_base /* [npolys][n][nl] or null; may be d_out */, const u64* d_pre /* term t at + t * term_stride */,

@@ -241,6 +241,42 @@ int launch_ct_add_const(fhesi_ctx* ctx, u64* d_ct, const i64* d_poly, int npoly,
   return 0;
 }
 
+// ---- scalar linear combinations with a constant, out[g] = Reduce_logQ(sum_t coef[t] pool[idx[t]] + konst[g]) (fhesi_ct_lin_comb_dev, include/fhesi_hip.h): what
+// the composition -- a copy, Ciphertext *= long and Ciphertext += per term, Ciphertext += ZZX -- makes in three passes per term, in one read per term and one
+// write.  A thread owns one coefficient of one polynomial of one group and sums in registers (ctw_lin_comb).  The lists are the host's (lin_comb_lists,
+// poly_plan.h), in device memory and read at block-uniform addresses: idx, mag per term, the negative coefficients of a group first; bounds[3 g ..] = first
+// term, first positive term, end; konst [ngroups] or null.  The constant goes to coefficient 0 of part 0.  poly0: the first polynomial (2 g + part) of this launch.
+template <int MAXNL>
+__global__ void __launch_bounds__(256) ct_lin_comb_kernel(const u64* __restrict__ pool, const int* __restrict__ idx, const u64* __restrict__ mag,
+                                                          const int* __restrict__ bounds, const i64* __restrict__ konst, i64 poly0, i64 n, int nl, int logQ, u64 p,
+                                                          u64* __restrict__ out) {
+  const i64 poly = poly0 + blockIdx.y, g = poly >> 1, part = poly & 1;
+  const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int t0 = bounds[3 * g], ts = bounds[3 * g + 1], t1 = bounds[3 * g + 2];
+  const i64 cv = konst ? konst[g] : 0;
+  u64 x[MAXNL];
+  ctw_lin_comb(x, nl, mag, t0, ts, t1, [=](int t) {
+    const u64* __restrict__ a = pool + (((i64)idx[t] * 2 + part) * n + j) * nl;
+    return [=](int i) { return a[i]; };
+  }, cv != 0 && part == 0 && j == 0, cv, logQ, p);
+  ctw_store_centred(x, nl, logQ, out + (poly * n + j) * nl);
+}
+// idx < the pool's size, nl in 1..32 holding logQ, out apart from pool: checked by the caller
+int launch_ct_lin_comb(fhesi_ctx* ctx, const u64* d_pool, const int* d_idx, const u64* d_mag, const int* d_bounds, const i64* d_konst, i64 ngroups, int nl, int logQ,
+                       u64 p, u64* d_out) {
+  if (!ngroups) return 0;
+  FHESI_TRY(limbs_ok("ciphertext coefficients", nl));
+  const unsigned gx = (unsigned)((ctx->phim + 255) / 256);
+  grid_chunks(ngroups * 2, [&](i64 done, i64 cnt) {
+    with_limb_class<2, 8, 16, 32>(nl, [&](auto C) {
+      ct_lin_comb_kernel<decltype(C)::value><<<dim3(gx, (unsigned)cnt), 256, 0, ctx->stream>>>(d_pool, d_idx, d_mag, d_bounds, d_konst, done, ctx->phim, nl, logQ, p, d_out);
+    });
+  });
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---- gather: out[i] = pool[idx[i]], `words` u64 per element (operands of one wave of Matrix products)
 __global__ void __launch_bounds__(256) gather_kernel(const u64* __restrict__ pool, const int* __restrict__ idx, u64* __restrict__ out, i64 words) {
   const u64* __restrict__ s = pool + (i64)idx[blockIdx.y] * words;

@@ -639,6 +639,41 @@ int fhesi_ct_linear_grid_dev(fhesi_ctx* ctx, const fhesi_linear_grid* grid, cons
                              const uint64_t* in_dev /* [nJ][count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count,
                              uint64_t* out_dev /* [nI][count][2][phi(m)][nlimbs] */);
 
+/* ---- polynomial activations on packed slots: y = f(x) = sum_{k <= d} c_k x^k slot by slot, the non-linear step between two linear layers (DESIGN.md 9a;
+ * tests/poly_model.py is the normative statement of the plan and of the schedule).
+ * fhesi_ct_lin_comb_dev: for every group g,  out[g] = Reduce_logQ( sum_{t in [seg[g], seg[g+1])} coef[t] * pool[a_idx[t]] + konst[g] ) on unscaled two-part
+ *   ciphertexts; the constant enters by the rule of Ciphertext += ZZX (Ciphertext.cpp:147-156): floor((konst[g] << logQ) / p) is added to coefficient 0 of
+ *   part 0.  DEFINED as, and bit for bit equal to: a copy of each operand, fhesi_ct_mul_long_dev(coef[t]), fhesi_ct_add_dev per term, fhesi_ct_add_const_dev
+ *   with the polynomial (konst[g], 0, .., 0) -- all exact modulo 2^logQ, so the order of the terms cannot matter.  One kernel launch reads every term once and
+ *   writes once; there is no bound on the terms of a group.  An empty group gives the trivial ciphertext of its constant (the zero ciphertext for konst NULL or
+ *   konst[g] = 0).  coef and konst: any int64.  The host arrays are read before the call returns.
+ *   REFUSED before any launch, the condition named, the context usable: out overlapping pool; an index outside the pool; seg not starting at 0 or
+ *   decreasing; nlimbs outside 1 .. 32 or not holding logQ; p < 2; a null argument where terms exist.
+ * fhesi_poly_eval_plan (host only): the Paterson-Stockmeyer plan of a DENSE polynomial of degree 1 .. 4096 with B baby powers x^1 .. x^B and the giants
+ *   x^(gB), g = 2 .. G - 1, G = floor(degree / B) + 1.  nks key switches = (B - 1) + max(G - 2, 0) + [a group g >= 1 has terms], nprod products = the same
+ *   powers + one per such group, depth = ceil(log2 B) + ceil(log2 max(G - 1, 1)) + [a group g >= 1 has terms].  baby = 0 picks the B of least nks, of
+ *   equal nks the smaller depth, of equal depth the larger B (degree 15: B = 4, G = 4, 6 key switches and depth 5 where Horner takes 14 and 14).  Any
+ *   output pointer may be NULL.
+ * fhesi_ct_poly_eval_dev: out[i] = f(in[i]), f given by coef[0 .. degree] (any int64; reduced modulo p, scalar factors by their centred representative in
+ *   (-p/2, p/2], constants by the one in [0, p)).  DEFINED as, and word for word equal to, this composition of the entry points above:
+ *   powers x^j = MulRelin(x^ceil(j/2), x^floor(j/2)) for j = 2 .. B and x^(gB) = MulRelin(x^(ceil(g/2) B), x^(floor(g/2) B)) for g = 2 .. G - 1, every level
+ *   ceil(log2 .) ONE fhesi_ct_mul_sum_relin_dev of single-term groups over all items (all powers, whatever the zero pattern of the coefficients);
+ *   u_g = lin_comb(c_(gB+j) x^j, 1 <= j < B, non-zero terms only; konst c_(gB)) for every g >= 1 that has such a term, all of them ONE fhesi_ct_lin_comb_dev;
+ *   W = ONE fhesi_ct_mul_sum_relin_dev with one group per item holding the pairs (u_g, x^(gB)) in ascending g: one key switch whatever G is;
+ *   y = lin_comb(group 0's terms in ascending j, then (c_(gB), x^(gB)) of the groups g >= 1 that are a non-zero constant alone, then (1, W); konst c_0).
+ *   Everything between in and out lives in the workspace, in chunks of ciphertexts.  REFUSED before any launch: what fhesi_ct_mul_sum_relin_dev refuses
+ *   (a matrix of another context, of another digit count or without 3 source components, a decompSize outside 1 .. 7, nlimbs not holding logQ); a degree
+ *   outside 1 .. 4096; baby outside 0 .. degree; p outside [2, 2^62); out overlapping in; null arguments.
+ * NOT HERE: per-slot coefficients (a prepared plaintext per power); several polynomials of one input sharing its powers; pruning the powers a zero pattern
+ *   leaves unused; a form of the C++ mirror; a C-ABI form over a slot basis (the Python binding runs one call per channel). */
+int fhesi_ct_lin_comb_dev(fhesi_ctx* ctx, int32_t logQ, uint64_t p, const uint64_t* pool_dev /* [npool][2][phi(m)][nlimbs] */, int64_t npool, int32_t nlimbs,
+                          const int32_t* a_idx, const int64_t* coef /* per term */, const int32_t* seg /* [ngroups + 1] */, const int64_t* konst /* [ngroups] or NULL */,
+                          int64_t ngroups, uint64_t* out_dev /* [ngroups][2][phi(m)][nlimbs] */);
+int fhesi_poly_eval_plan(int32_t degree, int32_t baby /* 0 = choose */, int32_t* B, int32_t* G, int32_t* nprod, int32_t* nks, int32_t* depth);
+int fhesi_ct_poly_eval_dev(fhesi_ctx* ctx, const fhesi_ksk* k /* s^2 -> s, 3 source components */, int32_t logQ, uint64_t p, int32_t decomp_bytes,
+                           const int64_t* coef /* [degree + 1] */, int32_t degree, int32_t baby /* 0 = the planner's */, const uint64_t* in_dev, int32_t nlimbs,
+                           int64_t count, uint64_t* out_dev);
+
 /* ---- multi-GPU: independent ciphertexts are data-parallel, every GPU holds the context tables and a replica of
  * the key-switch matrices; RCCL collectives run on the context's stream.  librccl is loaded on first use (no RCCL needed on one GPU).
  * fhesi_comm_init_all: one process, one host thread per GPU -- ncclCommInitAll over `devices`, comms_out[r] is rank r's handle.
