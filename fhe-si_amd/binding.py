@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "fhesi_ct_rot_fold_dev", "fhesi_ct_linear_dev",
     "fhesi_linear_grid_plan", "fhesi_linear_grid_create", "fhesi_linear_grid_create_dev", "fhesi_linear_grid_free", "fhesi_linear_grid_info",
     "fhesi_linear_grid_diagonals", "fhesi_ct_linear_grid_dev",
+    "fhesi_conv2d_plan", "fhesi_conv2d_create", "fhesi_conv2d_create_dev", "fhesi_conv2d_free", "fhesi_conv2d_info", "fhesi_conv2d_masks", "fhesi_ct_conv2d_dev",
     "fhesi_ct_lin_comb_dev", "fhesi_poly_eval_plan", "fhesi_ct_poly_eval_dev",
 ]
 ROT_SUM_MAX_TERMS = 16   # FHESI_ROT_SUM_MAX_TERMS: the terms one launch of the rotated-sum kernel takes (more terms chain launches)
@@ -267,6 +268,13 @@ def _load():
         "fhesi_linear_grid_info": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
         "fhesi_linear_grid_diagonals": [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp],
         "fhesi_ct_linear_grid_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_conv2d_plan": [_i64] * 9 + [_i32, _vp, _vp, _vp, _vp, _vp],
+        "fhesi_conv2d_create": [_vp, _vp] + [_i64] * 8 + [_vp, _i32, _vp],
+        "fhesi_conv2d_create_dev": [_vp, _vp] + [_i64] * 8 + [_vp, _i32, _vp],
+        "fhesi_conv2d_free": [_vp],
+        "fhesi_conv2d_info": [_vp] * 15,
+        "fhesi_conv2d_masks": [_vp, _vp] + [_i64] * 8 + [_i32, _vp],
+        "fhesi_ct_conv2d_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
         "fhesi_ct_lin_comb_dev": [_vp, _i32, _u64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
         "fhesi_poly_eval_plan": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
         "fhesi_ct_poly_eval_dev": [_vp, _vp, _i32, _u64, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
@@ -696,6 +704,19 @@ def linear_grid_plan(cols: int, R: int, C: int, Rb: int, Cb: int, baby: int = 0)
             "key_switches": nJ.value * (B.value - 1) + nI.value * (G.value - 1) + nI.value * nfold.value}
 
 
+def conv2d_plan(cols: int, H: int, W: int, Cin: int, Cout: int, kh: int, kw: int, ah: int, aw: int, form: int = 0) -> dict:
+    """The plan of a kh x kw convolution anchored at (ah, aw) over H x W planes, Cin -> Cout channels, on rows of `cols` slots (fhesi_conv2d_plan):
+    form (given 0: the form of fewer key switches, flat on a tie; 1 flat, 2 split), nh and the amounts in the order Conv2d.apply takes their matrices --
+    flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; amount 0 exactly at the anchor --, the key switches per item and `terms`, the
+    longest plaintext sum.  Raises FhesiError naming the condition on a refused shape.  Touches no device."""
+    args = tuple(int(v) for v in (cols, H, W, Cin, Cout, kh, kw, ah, aw, form))
+    f, nh, ks, terms = _i32(0), _i32(0), _i64(0), _i64(0)
+    _ck(_load().fhesi_conv2d_plan(*args, _byref(f), _byref(nh), _byref(ks), _byref(terms), None))
+    amounts = np.zeros(nh.value, dtype=np.int64)
+    _ck(_load().fhesi_conv2d_plan(*args, None, None, None, None, _p(amounts)))
+    return {"form": f.value, "nh": nh.value, "key_switches": ks.value, "terms": terms.value, "amounts": [int(a) for a in amounts]}
+
+
 def plain_sum_bits(m: int, logQ: int, maxabs: int, terms: int) -> float:
     """Bits the chain product must exceed for a sum of `terms` ciphertext x plaintext products on the ring m: log2 of twice
     terms * growth * phi(m) * 2^(logQ-1) * maxabs, growth = 1 (m a power of two), 2 (m = q^k, 2 q^k) or phi(m).  Touches no device."""
@@ -788,6 +809,47 @@ class LinearGrid:
     def close(self):
         if getattr(self, "h", None):
             _load().fhesi_linear_grid_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Conv2d:
+    """A 2-D convolution K [Cout][Cin][kh][kw] over H x W planes on a slot space, one channel per ciphertext (fhesi_conv2d): its masked weight
+    plaintexts, its biases and its plan, resident in HBM; made by SlotSpace.conv2d.  .amounts lists the rotation amounts whose hoisted matrices apply()
+    takes -- flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; 0 (no matrix) exactly at the anchor; .key_switches is what apply()
+    runs per item."""
+
+    def __init__(self, space: "SlotSpace", h):
+        self.space, self.ctx, self.h = space, space.ctx, h
+        v = [_i64(0) for _ in range(8)]
+        form, nh, ks, terms, bias = _i32(0), _i32(0), _i64(0), _i64(0), _i32(0)
+        _ck(_load().fhesi_conv2d_info(self.h, *(_byref(x) for x in v), _byref(form), _byref(nh), _byref(ks), _byref(terms), _byref(bias), None))
+        self.Cout, self.Cin, self.kh, self.kw, self.H, self.W, self.ah, self.aw = (x.value for x in v)
+        self.shape, self.image, self.anchor = (self.Cout, self.Cin, self.kh, self.kw), (self.H, self.W), (self.ah, self.aw)
+        self.form, self.nh, self.key_switches, self.terms, self.has_bias = form.value, nh.value, ks.value, terms.value, bool(bias.value)
+        a = np.zeros(self.nh, dtype=np.int64)
+        _ck(_load().fhesi_conv2d_info(self.h, *([None] * 13), _p(a)))
+        self.amounts = [int(x) for x in a]
+
+    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[I][i] = output channel I of item i (fhesi_ct_conv2d_dev): src [Cin][count] holds the input channels (SlotSpace.pack_images encrypted),
+        out [Cout][count] the convolution with zero padding plus b[I].  hoisted_by_amount: a mapping amount -> hoisted matrix of
+        SlotSpace.rotation_k(amount) covering the non-zero .amounts, or the list of matrices in the order of .amounts with None at the anchor."""
+        if hasattr(hoisted_by_amount, "keys"):
+            hs = [hoisted_by_amount[a] if a else None for a in self.amounts]
+        else:
+            hs = list(hoisted_by_amount)
+        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
+        _ck(_load().fhesi_ct_conv2d_dev(self.ctx.h, self.h, arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+
+    def close(self):
+        if getattr(self, "h", None):
+            _load().fhesi_conv2d_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -1078,6 +1140,74 @@ class SlotSpace:
         _ck(_load().fhesi_linear_grid_diagonals(self.h, _p(M), M.shape[0], M.shape[1], Rb, Cb, int(baby), _p(vals)))
         return vals
 
+    # ---- convolution layers: image planes in the slots, one channel per ciphertext (fhesi_conv2d_*)
+    @staticmethod
+    def _conv_anchor(kh: int, kw: int, anchor):
+        return ((kh - 1) // 2, (kw - 1) // 2) if anchor is None else (int(anchor[0]), int(anchor[1]))
+
+    def conv2d(self, K, bias=None, image=None, anchor=None, form: int = 0, device: bool = False) -> Conv2d:
+        """The convolution of K [Cout][Cin][kh][kw], bias [Cout] or None, any int64 (reduced modulo p on the device), over planes image = (H, W), H W
+        dividing the row; stride 1, zero padding, anchor (default ((kh - 1) // 2, (kw - 1) // 2)) the kernel entry that meets the output pixel.
+        form: 0 the planner's, 1 flat, 2 split (conv2d_plan).  device=True: K and bias are int64 tensors in HBM (torch tensors), read where they are."""
+        if image is None:
+            raise ValueError("conv2d: image = (H, W)")
+        H, W = int(image[0]), int(image[1])
+        h = _vp()
+        if device:
+            kp, shape = self._device_words(K, "the kernel")
+            bp = None
+            if bias is not None:
+                bp, bshape = self._device_words(bias, "the bias")
+                if len(shape) == 4 and bshape != (shape[0],):
+                    raise ValueError(f"conv2d: a bias of shape {bshape} for {shape[0]} output channels")
+            fn = _load().fhesi_conv2d_create_dev
+        else:
+            K = np.ascontiguousarray(K, dtype=np.int64)
+            shape, kp, bp = K.shape, _p(K), None
+            if bias is not None:
+                b = np.ascontiguousarray(bias, dtype=np.int64)
+                if K.ndim == 4 and b.shape != (shape[0],):
+                    raise ValueError(f"conv2d: a bias of shape {b.shape} for {shape[0]} output channels")
+                bp = _p(b)
+            fn = _load().fhesi_conv2d_create
+        if len(shape) != 4:
+            raise ValueError("conv2d: the kernel is [Cout][Cin][kh][kw]")
+        ah, aw = self._conv_anchor(shape[2], shape[3], anchor)
+        _ck(fn(self.h, kp, shape[0], shape[1], shape[2], shape[3], H, W, ah, aw, bp, int(form), _byref(h)))
+        return Conv2d(self, h)
+
+    def conv2d_masks(self, K, image, anchor=None, form: int = 0) -> np.ndarray:
+        """The masked weight plaintexts of the convolution as slot values: [Cout][Cin][kh kw][total], entry t = dy kw + dx the weight under its mask,
+        moved back by its giant amount in the split form (fhesi_conv2d_masks) -- what SlotSpace.conv2d embeds, downloaded."""
+        K = np.ascontiguousarray(K, dtype=np.int64)
+        if K.ndim != 4:
+            raise ValueError("conv2d_masks: the kernel is [Cout][Cin][kh][kw]")
+        Cout, Cin, kh, kw = K.shape
+        ah, aw = self._conv_anchor(kh, kw, anchor)
+        conv2d_plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, form)      # the shape, before the output is sized
+        vals = np.zeros((Cout, Cin, kh * kw, self.total), dtype=np.int64)
+        _ck(_load().fhesi_conv2d_masks(self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw, int(form), _p(vals)))
+        return vals
+
+    def pack_images(self, x) -> np.ndarray:
+        """x [..][rows][cols / P][H][W] (the rows axis dropped on a one-row space) -> slot values [..][total]: image (r, b) in the P-block b of row r,
+        pixel (y, x) at y W + x.  Host only."""
+        x = np.asarray(x)
+        rows, cols = max(self.rows, 1), self.total // max(self.rows, 1)
+        H, W = x.shape[-2:]
+        lead = x.shape[:-4] if rows == 2 else x.shape[:-3]
+        if H * W < 1 or cols % (H * W) or x.shape[len(lead):] != ((rows,) if rows == 2 else ()) + (cols // (H * W), H, W):
+            raise ValueError(f"pack_images: images of shape {x.shape}, a plaintext takes [{rows}][cols / (H W)][H][W] on rows of {cols} slots")
+        return np.ascontiguousarray(x.reshape(lead + (self.total,)))
+
+    def unpack_images(self, vals, H: int, W: int) -> np.ndarray:
+        """The inverse: slot values [..][total] -> [..][rows][cols / P][H][W] (the rows axis dropped on a one-row space).  Host only."""
+        vals = np.asarray(vals)
+        rows, cols = max(self.rows, 1), self.total // max(self.rows, 1)
+        if H < 1 or W < 1 or cols % (H * W) or vals.shape[-1] != self.total:
+            raise ValueError(f"unpack_images: {vals.shape[-1] if vals.ndim else 0} values as {H} x {W} planes on rows of {cols} slots")
+        return vals.reshape(vals.shape[:-1] + ((rows,) if rows == 2 else ()) + (cols // (H * W), H, W))
+
     def replicate_blocks(self, x, Cb: int) -> np.ndarray:
         """x [count][rows][C] (or [count][C] on a one-row space), C = nJ Cb -> slot values [nJ][count][total]: plaintext (J, i) holds x_i[J Cb ..
         (J + 1) Cb) with period Cb in every row, the input layout of LinearGrid.apply.  Host only."""
@@ -1305,6 +1435,23 @@ class SlotBasis:
         words = 2 * self.ctx.phim * nlimbs * 8
         for c in range(self.k):
             layers[c].apply(hoisted_by_amount, logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
+
+    def conv2d(self, K, bias=None, image=None, anchor=None, form: int = 0) -> list:
+        """SlotSpace.conv2d per channel: the k handles of the convolution K [Cout][Cin][kh][kw], bias [Cout] (integers of any size), channel c holding
+        them modulo primes[c]."""
+        K = np.asarray(K)
+        out = []
+        for c in range(self.k):
+            Kc = self._residues(K.reshape(1, -1), c).reshape(K.shape)
+            out.append(self.channel(c).conv2d(Kc, None if bias is None else self._residues(bias, c)[0], image, anchor, form))
+        return out
+
+    def conv2d_apply(self, layers, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """Conv2d.apply per channel (one key set serves every channel): src [k][Cin][count], out [k][Cout][count] logical ciphertexts, layers from
+        SlotBasis.conv2d."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        for c in range(self.k):
+            layers[c].apply(hoisted_by_amount, logQ, _View(src, c * layers[c].Cin * count * words), nlimbs, count, _View(out, c * layers[c].Cout * count * words), decomp_bytes)
 
     def poly_eval(self, ksk: "KeySwitchMatrix", coef, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, baby: int = 0, decomp_bytes: int = 3):
         """SlotSpace.poly_eval per channel (one key set serves every channel): src, out [k][count] logical ciphertexts; coef Python integers of any

@@ -2,6 +2,7 @@
 #include "capi_common.h"
 #include "wave_plan.h"
 #include "poly_plan.h"
+#include "conv_plan.h"
 
 // ---- coefficient-domain ciphertext algebra on device batches (kernels_ct.hip)
 extern "C" int fhesi_ct_add_dev(fhesi_ctx* c, int32_t logQ, uint64_t* dst, const uint64_t* src, int32_t nparts, int32_t nlimbs, int64_t count) {
@@ -619,6 +620,53 @@ extern "C" int fhesi_ct_add_slots_dev(fhesi_ctx* c, fhesi_slots* s, int32_t logQ
 // its own arguments and plans the layer; nothing here synchronises.
 // A layer is the grid of one block (Rb = R, Cb = C): everything below is written for the grid.  The blocks are staged in chunks of whole blocks, so the
 // values slot holds a chunk and never the grid.
+//
+// What the stages of a dense grid and of a convolution share.  A layer is `nunits` units (blocks, channel pairs) of unit_vals slot values each, written by a
+// kernel from a tensor where it lies: chunks of whole units in the values slot (workspace 9) -- at most cap_bytes of them, a single unit may take more --,
+// a host tensor of src_words uploaded into the same slot, behind them.  The workspace holds a chunk and never the layer; nothing here synchronises.
+struct ValueStage {
+  i64 per = 0;                 // units per chunk
+  i64* d_vals = nullptr;       // [per][unit_vals] in workspace slot 9, a host tensor behind them
+  const i64* d_src = nullptr;  // the tensor in HBM
+};
+static int value_stage_open(fhesi_ctx* c, i64 nunits, size_t unit_vals, size_t cap_bytes, const int64_t* src, bool on_dev, size_t src_words, ValueStage* st) {
+  st->per = std::max<i64>(1, std::min<i64>(nunits, (i64)(cap_bytes / (unit_vals * 8))));
+  const size_t nvals = (size_t)st->per * unit_vals;
+  FHESI_TRY(ws_i64(c, 9, (nvals + (on_dev ? 0 : src_words)) * 8, &st->d_vals));
+  st->d_src = src;
+  if (!on_dev) {
+    HIP_TRY(hipMemcpyAsync(st->d_vals + nvals, src, src_words * 8, hipMemcpyHostToDevice, c->stream));
+    st->d_src = st->d_vals + nvals;
+  }
+  return 0;
+}
+// the prepared plaintext of the layer, T rows per unit: write(first, nb) fills d_vals with the slot vectors of the units [first, first + nb), nb <= per, which
+// are embedded and transformed into their rows chunk by chunk.  Synchronises (plain_rows_close): a host tensor is the caller's again on return.
+template <class F> static int value_stage_plain(fhesi_slots* s, i64 nunits, i64 T, i64 per, const i64* d_vals, F write, fhesi_plain** made) {
+  fhesi_ctx* c = s->ctx;
+  i64* d_msg = nullptr;
+  fhesi_plain* w = nullptr;
+  int rc = msg_staging(c, per * T, &d_msg);
+  if (!rc) rc = plain_alloc(c, nunits * T, s->S.p - 1, s->S.p, &w);      // the embedding leaves coefficients in [0, p)
+  if (rc) { hipStreamSynchronize(c->stream); return rc; }
+  for (i64 first = 0; first < nunits && !rc; first += per) {
+    const i64 nb = std::min(per, nunits - first);
+    rc = write(first, nb);
+    if (!rc) rc = slots_embed_rows(s, d_vals, s->S.phim, false, nb * T, d_msg);
+    if (!rc) rc = plain_rows_fill(c, w, first * T, d_msg, nb * T);
+  }
+  return plain_rows_close(c, w, rc, made);
+}
+// the same chunks downloaded instead: vals_host [nunits][unit_vals]
+template <class F> static int value_stage_download(fhesi_ctx* c, i64 nunits, size_t unit_vals, i64 per, const i64* d_vals, F write, int64_t* vals_host) {
+  for (i64 first = 0; first < nunits; first += per) {
+    const i64 nb = std::min(per, nunits - first);
+    FHESI_TRY(write(first, nb));
+    HIP_TRY(hipMemcpyAsync(vals_host + (size_t)first * unit_vals, d_vals, (size_t)nb * unit_vals * 8, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
 struct LinearPlan { int32_t nI = 0, nJ = 0, T = 0, B = 0, G = 0, nfold = 0; std::vector<int64_t> amounts; };
 struct LinearStage {
   LinearPlan plan;
@@ -638,15 +686,9 @@ static int linear_stage_open(fhesi_slots* s, const int64_t* M, bool on_dev, i64 
   FHESI_TRY(fhesi_linear_grid_plan(cols, R, C, Rb, Cb, baby, &plan.nI, &plan.nJ, &plan.T, &plan.B, &plan.G, &plan.nfold, nullptr));
   plan.amounts.resize((size_t)(plan.B - 1 + plan.G - 1 + plan.nfold));
   FHESI_TRY(fhesi_linear_grid_plan(cols, R, C, Rb, Cb, baby, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plan.amounts.data()));
-  const size_t block_vals = (size_t)plan.T * total;
-  st->per = std::max<i64>(1, std::min<i64>((i64)plan.nI * plan.nJ, (i64)(kLinearChunkBytes / (block_vals * 8))));
-  const size_t nvals = (size_t)st->per * block_vals;
-  FHESI_TRY(ws_i64(c, 9, (nvals + (on_dev ? 0 : (size_t)R * C)) * 8, &st->d_vals));
-  st->d_M = M; st->ld = C;
-  if (!on_dev) {
-    HIP_TRY(hipMemcpyAsync(st->d_vals + nvals, M, (size_t)R * C * 8, hipMemcpyHostToDevice, c->stream));
-    st->d_M = st->d_vals + nvals;
-  }
+  ValueStage vs;
+  FHESI_TRY(value_stage_open(c, (i64)plan.nI * plan.nJ, (size_t)plan.T * total, kLinearChunkBytes, M, on_dev, (size_t)R * C, &vs));
+  st->per = vs.per; st->d_vals = vs.d_vals; st->d_M = vs.d_src; st->ld = C;
   return 0;
 }
 // the slot vectors of the blocks [first, first + nb), nb <= per, into d_vals
@@ -680,21 +722,11 @@ static int linear_create(fhesi_slots* s, const int64_t* M, const int64_t* bias, 
     if (const int rc = linear_bias_vals(s, bias, on_dev, Rb, nI, d_bias)) { hipFree(d_bias); return rc; }
   }
   LinearStage st;
-  i64* d_msg = nullptr;
-  fhesi_plain *w = nullptr, *made = nullptr;
+  fhesi_plain* made = nullptr;
   int rc = linear_stage_open(s, M, on_dev, R, C, Rb, Cb, baby, what, &st);
   const LinearPlan& plan = st.plan;
-  const i64 nblocks = (i64)plan.nI * plan.nJ;
-  if (!rc) rc = msg_staging(c, st.per * plan.T, &d_msg);
-  if (!rc) rc = plain_alloc(c, nblocks * plan.T, s->S.p - 1, s->S.p, &w);      // the embedding leaves coefficients in [0, p)
-  if (rc) { hipStreamSynchronize(c->stream); hipFree(d_bias); return rc; }
-  for (i64 first = 0; first < nblocks && !rc; first += st.per) {
-    const i64 nb = std::min(st.per, nblocks - first);
-    rc = linear_stage_blocks(s, st, Rb, Cb, first, nb);
-    if (!rc) rc = slots_embed_rows(s, st.d_vals, s->S.phim, false, nb * plan.T, d_msg);
-    if (!rc) rc = plain_rows_fill(c, w, first * plan.T, d_msg, nb * plan.T);
-  }
-  rc = plain_rows_close(c, w, rc, &made);      // synchronises: a host matrix and bias are the caller's again
+  if (rc) hipStreamSynchronize(c->stream);
+  else rc = value_stage_plain(s, (i64)plan.nI * plan.nJ, plan.T, st.per, st.d_vals, [&](i64 first, i64 nb) { return linear_stage_blocks(s, st, Rb, Cb, first, nb); }, &made);
   if (rc) { hipFree(d_bias); return rc; }
   lin->ctx = c; lin->slots = s; lin->R = R; lin->C = C; lin->Rb = Rb; lin->Cb = Cb;
   lin->nI = plan.nI; lin->nJ = plan.nJ; lin->T = plan.T; lin->B = plan.B; lin->G = plan.G; lin->nfold = plan.nfold;
@@ -721,16 +753,8 @@ static int linear_diagonals(fhesi_slots* s, const int64_t* M_host, i64 R, i64 C,
   if (!vals_host) FHESI_FAIL("%s: null output", what);
   LinearStage st;
   FHESI_TRY(linear_stage_open(s, M_host, false, R, C, Rb, Cb, baby, what, &st));
-  fhesi_ctx* c = s->ctx;
-  const i64 nblocks = (i64)st.plan.nI * st.plan.nJ;
-  const size_t block_vals = (size_t)st.plan.T * s->S.phim;
-  for (i64 first = 0; first < nblocks; first += st.per) {
-    const i64 nb = std::min(st.per, nblocks - first);
-    FHESI_TRY(linear_stage_blocks(s, st, Rb, Cb, first, nb));
-    HIP_TRY(hipMemcpyAsync(vals_host + (size_t)first * block_vals, st.d_vals, (size_t)nb * block_vals * 8, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return value_stage_download(s->ctx, (i64)st.plan.nI * st.plan.nJ, (size_t)st.plan.T * s->S.phim, st.per, st.d_vals,
+                              [&](i64 first, i64 nb) { return linear_stage_blocks(s, st, Rb, Cb, first, nb); }, vals_host);
 }
 extern "C" int fhesi_linear_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, const int64_t* bias_host, int32_t baby, fhesi_linear** out) {
   return linear_create_handle(s, M_host, bias_host, false, R, C, R, C, baby, "linear_create", out);
@@ -792,6 +816,123 @@ extern "C" int fhesi_linear_grid_info(const fhesi_linear_grid* lin, int64_t* R, 
 }
 extern "C" int fhesi_linear_grid_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int64_t* vals_host) {
   return linear_diagonals(s, M_host, R, C, Rb, Cb, baby, "linear_grid_diagonals", vals_host);
+}
+
+// --------------------------------------------------------------------------------------------- convolution layers
+// fhesi_conv2d (include/fhesi_hip.h; the plan and its refusals: conv_plan.h).  The stage next to linear_stage_open: the kh kw masked weight plaintexts of a
+// channel pair [kh kw][phi(m)] in the values slot, written by conv_mask_kernel from the weight tensor where it is, in chunks of whole channel pairs
+// (option "stage_chunk_bytes" lowers the cap, for tests).
+struct ConvStage {
+  ConvShape sh;
+  ConvPlan plan;
+  ValueStage vs;
+};
+static int conv_shape_plan(const char* what, const ConvShape& sh, int32_t form, ConvPlan* plan) {
+  char why[256];
+  if (conv_refused(sh, form, why, sizeof why)) FHESI_FAIL("%s: %s", what, why);
+  *plan = conv_plan(sh, form);
+  return 0;
+}
+extern "C" int fhesi_conv2d_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw, int32_t form, int32_t* form_out,
+                                 int32_t* nh, int64_t* key_switches, int64_t* terms, int64_t* amounts) {
+  ConvPlan plan;
+  FHESI_TRY(conv_shape_plan("conv2d_plan", ConvShape{cols, H, W, Cin, Cout, kh, kw, ah, aw}, form, &plan));
+  if (form_out) *form_out = plan.form;
+  if (nh) *nh = plan.nh;
+  if (key_switches) *key_switches = plan.key_switches;
+  if (terms) *terms = plan.terms;
+  if (amounts) std::copy(plan.amounts.begin(), plan.amounts.end(), amounts);
+  return 0;
+}
+static int conv_stage_open(fhesi_slots* s, const int64_t* K, bool on_dev, i64 Cout, i64 Cin, i64 kh, i64 kw, i64 H, i64 W, i64 ah, i64 aw, int32_t form, const char* what,
+                           ConvStage* st) {
+  if (!s) FHESI_FAIL("%s: null plaintext space", what);
+  fhesi_ctx* c = s->ctx;
+  CHECK_CTX(c);
+  if (!K) FHESI_FAIL("%s: null kernel", what);
+  st->sh = ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw};
+  FHESI_TRY(conv_shape_plan(what, st->sh, form, &st->plan));
+  const size_t cap = c->opt.stage_chunk_bytes > 0 ? (size_t)c->opt.stage_chunk_bytes : kLinearChunkBytes;
+  return value_stage_open(c, Cout * Cin, (size_t)(kh * kw) * s->S.phim, cap, K, on_dev, (size_t)(Cout * Cin * kh * kw), &st->vs);
+}
+// the plaintexts of the channel pairs [first, first + nb), nb <= per, into d_vals
+static int conv_stage_pairs(fhesi_slots* s, const ConvStage& st, i64 first, i64 nb) {
+  const ConvShape& sh = st.sh;
+  return launch_conv_mask(s->ctx, s->S, st.vs.d_src, (int)first, (int)nb, (int)sh.kh, (int)sh.kw, (int)sh.ah, (int)sh.aw, sh.H, sh.W, st.plan.form == 2, st.vs.d_vals);
+}
+static int conv_create(fhesi_slots* s, const int64_t* K, const int64_t* bias, bool on_dev, i64 Cout, i64 Cin, i64 kh, i64 kw, i64 H, i64 W, i64 ah, i64 aw, int32_t form,
+                       fhesi_conv2d** out) {
+  const char* what = "conv2d_create";
+  if (!out) FHESI_FAIL("%s: null output pointer", what);
+  *out = nullptr;
+  if (!s) FHESI_FAIL("%s: null plaintext space", what);
+  fhesi_ctx* c = s->ctx;
+  CHECK_CTX(c);
+  if (!K) FHESI_FAIL("%s: null kernel", what);
+  ConvPlan shape_only;
+  FHESI_TRY(conv_shape_plan(what, ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, form, &shape_only));      // the shape, before anything is launched
+  const size_t n = (size_t)s->S.phim;
+  i64* d_bias = nullptr;
+  if (bias) {      // b[I] in every slot: the diagonal of a 1 x 1 block per output channel
+    if (hipMalloc(&d_bias, (size_t)Cout * n * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("%s: hipMalloc of %zu bytes failed", what, (size_t)Cout * n * 8); }
+    if (const int rc = linear_bias_vals(s, bias, on_dev, 1, (int)Cout, d_bias)) { hipFree(d_bias); return rc; }
+  }
+  ConvStage st;
+  fhesi_plain* made = nullptr;
+  int rc = conv_stage_open(s, K, on_dev, Cout, Cin, kh, kw, H, W, ah, aw, form, what, &st);
+  if (rc) hipStreamSynchronize(c->stream);
+  else rc = value_stage_plain(s, Cout * Cin, kh * kw, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); }, &made);
+  if (rc) { hipFree(d_bias); return rc; }
+  fhesi_conv2d* cv = new fhesi_conv2d();
+  cv->ctx = c; cv->slots = s; cv->Cout = Cout; cv->Cin = Cin; cv->kh = kh; cv->kw = kw; cv->H = H; cv->W = W; cv->ah = ah; cv->aw = aw;
+  cv->form = st.plan.form; cv->nh = st.plan.nh; cv->key_switches = st.plan.key_switches; cv->terms = st.plan.terms;
+  cv->amounts.assign(st.plan.amounts.begin(), st.plan.amounts.end());
+  cv->w = made; cv->d_bias = d_bias;
+  *out = cv;
+  return 0;
+}
+extern "C" int fhesi_conv2d_create(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                   const int64_t* bias_host, int32_t form, fhesi_conv2d** out) {
+  return conv_create(s, K_host, bias_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, out);
+}
+extern "C" int fhesi_conv2d_create_dev(fhesi_slots* s, const int64_t* K_dev, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                       const int64_t* bias_dev, int32_t form, fhesi_conv2d** out) {
+  return conv_create(s, K_dev, bias_dev, true, Cout, Cin, kh, kw, H, W, ah, aw, form, out);
+}
+extern "C" int fhesi_conv2d_free(fhesi_conv2d* cv) {
+  if (!cv) return 0;
+  fhesi_plain_free(cv->w);      // (synchronises; the one live handle the layer counts as)
+  hipFree(cv->d_bias);
+  delete cv;
+  return 0;
+}
+extern "C" int fhesi_conv2d_info(const fhesi_conv2d* cv, int64_t* Cout, int64_t* Cin, int64_t* kh, int64_t* kw, int64_t* H, int64_t* W, int64_t* ah, int64_t* aw, int32_t* form,
+                                 int32_t* nh, int64_t* key_switches, int64_t* terms, int32_t* has_bias, int64_t* amounts) {
+  if (!cv) FHESI_FAIL("null convolution layer");
+  if (Cout) *Cout = cv->Cout;
+  if (Cin) *Cin = cv->Cin;
+  if (kh) *kh = cv->kh;
+  if (kw) *kw = cv->kw;
+  if (H) *H = cv->H;
+  if (W) *W = cv->W;
+  if (ah) *ah = cv->ah;
+  if (aw) *aw = cv->aw;
+  if (form) *form = cv->form;
+  if (nh) *nh = cv->nh;
+  if (key_switches) *key_switches = cv->key_switches;
+  if (terms) *terms = cv->terms;
+  if (has_bias) *has_bias = cv->d_bias ? 1 : 0;
+  if (amounts) std::copy(cv->amounts.begin(), cv->amounts.end(), amounts);
+  return 0;
+}
+// the same stage without a handle: vals_host [Cout][Cin][kh kw][phi(m)], chunk by chunk
+extern "C" int fhesi_conv2d_masks(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                  int32_t form, int64_t* vals_host) {
+  if (!vals_host) FHESI_FAIL("conv2d_masks: null output");
+  ConvStage st;
+  FHESI_TRY(conv_stage_open(s, K_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, "conv2d_masks", &st));
+  return value_stage_download(s->ctx, Cout * Cin, (size_t)(kh * kw) * s->S.phim, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); },
+                              vals_host);
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

@@ -95,6 +95,7 @@ static const OptDesc kOptions[] = {
   {"stagger", "FHESI_STAGGER", offsetof(CtxOptions, stagger), false},
   {"batch_chunk", "FHESI_BATCH_CHUNK", offsetof(CtxOptions, batch_chunk), true},
   {"wave_operands", "FHESI_WAVE_OPERANDS", offsetof(CtxOptions, wave_operands), true},
+  {"stage_chunk_bytes", "FHESI_STAGE_CHUNK_BYTES", offsetof(CtxOptions, stage_chunk_bytes), true},
   {"wave_single", "FHESI_WAVE_SINGLE", offsetof(CtxOptions, wave_single), false},
   {"tensor32", "FHESI_TENSOR32", offsetof(CtxOptions, tensor32), false},
   {"tensor_bits", "FHESI_TENSOR_BITS", offsetof(CtxOptions, tensor_bits), false},

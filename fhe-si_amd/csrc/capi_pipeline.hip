@@ -3,6 +3,7 @@
 #include "copy_pool.h"
 #include "wave_plan.h"
 #include "poly_plan.h"
+#include "conv_plan.h"
 
 // --------------------------------------------------------------------------------------------- key-switch matrix
 extern "C" int fhesi_ksk_create(fhesi_ctx* c, int32_t ncomp, int32_t ndigits, fhesi_ksk** out) {
@@ -557,7 +558,8 @@ static int matvec_args(fhesi_ctx* c, const char* who, const fhesi_plain* w, int 
 }
 // out[i] = Reduce( sum_g rot_kg[g]( sum_j rot_kb[j](in[i]) (*) w[g B + j] ) )  (include/fhesi_hip.h): per chunk of ciphertexts the baby rotations from one digit
 // set into the pool (slot 12), ONE plaintext sum with G groups per ciphertext (slot 13), one key switch per giant into its slice of slot 14, one rotated sum.
-// flat (G = 1, no giant): the plaintext sums ARE the result and go straight to out -- fhesi_ct_matvec_dev; no slot 13 or 14, no rotated sum.
+// flat (G = 1, no giant): the plaintext sums ARE the result and go straight to out -- fhesi_ct_matvec_dev; no slot 13 or 14, no rotated sum.  With several
+// output blocks and a chunk below count (fhesi_ct_conv2d_dev in its flat form) a chunk's sums [nI][cnt] go to slot 13 and are copied block by block.
 // g_mode: the giants' forms, their tables built by the caller.  Every argument checked by the caller.
 // The grid of nI x nJ blocks (fhesi_ct_linear_grid_dev) runs the same schedule with two of its three factors shared: in [nJ][count], out [nI][count], w row
 // (I nJ + J) nk + t.  The babies of input block J, from one digit set, serve every output block -- pool [nJ][nb][cnt]; the ONE plaintext sum has the
@@ -570,31 +572,27 @@ static int matvec_run(fhesi_ctx* c, const fhesi_ksk* const* baby_hoisted, const 
   const size_t ct_words = (size_t)2 * c->phim * nlimbs;
   const i64 nterms = (i64)nI * nJ * nk;      // terms of one ciphertext's sums
   // ciphertexts per pass: about 4 GiB of rotated ciphertexts, of inner sums and of key-switched sums each; and index lists that 32 bits hold
-  const i64 chunk = std::max<i64>(1, std::min<i64>(std::min<i64>(count, ((i64)1 << 31) / (nterms + 1) - 1),
-                                                  (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(nJ * nb, nI * G) * ct_words * 8))));
+  i64 chunk = std::max<i64>(1, std::min<i64>(std::min<i64>(count, ((i64)1 << 31) / (nterms + 1) - 1),
+                                            (i64)(4.0 * 1024 * 1024 * 1024 / ((double)std::max(nJ * nb, nI * G) * ct_words * 8))));
+  if (c->opt.wave_operands > 0) chunk = std::max<i64>(1, std::min<i64>(chunk, c->opt.wave_operands / std::max(nJ * nb, nI * G)));      // (for tests: chunks below count)
+  // flat with several output blocks: a chunk's sums come out as [nI][cnt], out is [nI][count] -- the same place only where one chunk covers count
+  const bool gather = flat && nI > 1 && chunk < count;
   std::vector<int32_t> a_idx((size_t)chunk * nterms), b_idx((size_t)chunk * nterms), seg((size_t)chunk * nI * G + 1);
   for (i64 done = 0; done < count; done += chunk) {
     const i64 cnt = std::min(chunk, count - done);
     void *d_pool, *d_inner = out + (size_t)done * ct_words, *d_pre = nullptr;
     FHESI_TRY(ws_reserve(c, 12, (size_t)nJ * nb * cnt * ct_words * 8, &d_pool));
-    if (!flat) {
-      FHESI_TRY(ws_reserve(c, 13, (size_t)nI * G * cnt * ct_words * 8, &d_inner));
-      FHESI_TRY(ws_reserve(c, 14, (size_t)G * cnt * ct_words * 8, &d_pre));
-    }
+    if (!flat || gather) FHESI_TRY(ws_reserve(c, 13, (size_t)nI * G * cnt * ct_words * 8, &d_inner));
+    if (!flat) FHESI_TRY(ws_reserve(c, 14, (size_t)G * cnt * ct_words * 8, &d_pre));
     for (int J = 0; J < nJ; ++J)
       FHESI_TRY(rotations_run(c, baby_hoisted, kb, nb, logQ, decomp_bytes, in + ((size_t)J * count + done) * ct_words, nlimbs, cnt,
                               (uint64_t*)d_pool + (size_t)J * nb * cnt * ct_words, nlimbs));
-    // group (I G + g) cnt + i = sum_J sum_j pool[J][j][i] (*) w[(I nJ + J) nk + g B + j]
-    i64 at = 0;
-    for (int I = 0; I < nI; ++I)
-      for (int g = 0; g < G; ++g)
-        for (i64 i = 0; i < cnt; ++i) {
-          seg[((size_t)I * G + g) * cnt + i] = (int32_t)at;
-          for (int J = 0; J < nJ; ++J)
-            for (int j = 0; j < B && g * B + j < nk; ++j, ++at) { a_idx[at] = (int32_t)(((i64)J * nb + j) * cnt + i); b_idx[at] = (I * nJ + J) * nk + g * B + j; }
-        }
-    seg[(size_t)nI * G * cnt] = (int32_t)at;
+    // group (I G + g) cnt + i = sum_J sum_j pool[J][j][i] (*) w[(I nJ + J) nk + g B + j]  (conv_plan.h)
+    grid_sum_lists(nI, nJ, nk, B, G, cnt, a_idx.data(), b_idx.data(), seg.data());
     FHESI_TRY(fhesi_ct_plain_sum_dev(c, w, logQ, (const uint64_t*)d_pool, (int64_t)nJ * nb * cnt, nlimbs, a_idx.data(), b_idx.data(), seg.data(), cnt * nI * G, (uint64_t*)d_inner));
+    if (gather)
+      for (int I = 0; I < nI; ++I)
+        HIP_TRY(hipMemcpyAsync(out + ((size_t)I * count + done) * ct_words, (const u64*)d_inner + (size_t)I * cnt * ct_words, (size_t)cnt * ct_words * 8, hipMemcpyDeviceToDevice, c->stream));
     if (flat) continue;
     for (int I = 0; I < nI; ++I) {
       for (int g = 0; g < G; ++g) {
@@ -787,6 +785,50 @@ extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const 
 extern "C" int fhesi_ct_linear_grid_dev(fhesi_ctx* c, const fhesi_linear_grid* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
                                         const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
   return linear_run(c, "ct_linear_grid", "linear grid", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
+}
+
+// --------------------------------------------------------------------------------------------- convolution layers
+// out[I][i] = sum_J K[I][J] * in[J][i] + b[I] on the planes in the slots (include/fhesi_hip.h; conv_plan.h): matvec_run with the channels as its blocks --
+// nI = Cout, nJ = Cin, nk = kh kw plaintexts per pair, the plan's amounts as its babies and giants, the identity at the anchor --, then the biases as
+// linear_run adds them.  flat: B = kh kw, the plaintext sums are the result.  split: B = kw babies (horizontal), G = kh giants (vertical).
+extern "C" int fhesi_ct_conv2d_dev(fhesi_ctx* c, const fhesi_conv2d* cv, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
+                                   int32_t nlimbs, int64_t count, uint64_t* out) {
+  const char* who = "ct_conv2d";
+  CHECK_CTX(c);
+  if (!cv) FHESI_FAIL("%s: null convolution layer", who);
+  if (cv->ctx != c) FHESI_FAIL("%s: the convolution layer belongs to another context", who);
+  const int nI = (int)cv->Cout, nJ = (int)cv->Cin, nk = (int)(cv->kh * cv->kw);
+  const bool flat = cv->form == 1;
+  const int B = flat ? nk : (int)cv->kw, G = flat ? 1 : (int)cv->kh;
+  if (nh != cv->nh) FHESI_FAIL("%s: %d matrices, the layer takes %d (one per amount of its plan, NULL at the anchor)", who, nh, cv->nh);
+  if (!hoisted) FHESI_FAIL("%s: null argument", who);
+  if ((double)std::max(nI, nJ) * (double)count > 2147483647.0) FHESI_FAIL("%s: %lld ciphertexts per channel exceed what %d -> %d channels can index", who, (long long)count, nJ, nI);
+  std::vector<int64_t> ks((size_t)nh, 1);
+  for (int t = 0; t < nh; ++t) {
+    const i64 a = cv->amounts[(size_t)t];
+    if (!a && hoisted[t]) FHESI_FAIL("%s: a matrix at entry %d, whose amount is 0 (the anchor takes none)", who, t);
+    if (a && !hoisted[t]) FHESI_FAIL("%s: entry %d has no matrix and its amount is %lld (only the anchor goes without one)", who, t, (long long)a);
+    ks[(size_t)t] = (int64_t)hm::powmod(cv->slots->S.g, (u64)a, (u64)c->m);
+  }
+  const fhesi_ksk* const* hb = hoisted, * const* hg = flat ? nullptr : hoisted + B;
+  const int64_t *kb = ks.data(), *kg = flat ? nullptr : kb + B;
+  FHESI_TRY(rotations_args(c, hb, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  if (!flat) FHESI_TRY(rotations_args(c, hg, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  FHESI_TRY(matvec_args(c, who, cv->w, nI, nJ, nk, (int)cv->terms, logQ, in, nlimbs, count, out));
+  if (!count) return 0;
+  std::vector<int> g_mode;      // the giants' tables before any digit row exists, as rotations_run builds its matrices'
+  if (!flat) FHESI_TRY(key_switch_forms(c, hg, G, logQ, decomp_bytes, &g_mode));
+  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, flat ? nullptr : g_mode.data(), G, flat, nI, nJ, nk, cv->w, logQ, decomp_bytes, in, nlimbs, count, out));
+  if (!cv->d_bias) return 0;
+  const size_t n = (size_t)c->phim;
+  void* d_msg;
+  FHESI_TRY(ws_reserve(c, 5, (size_t)nI * n * 8, &d_msg));
+  FHESI_TRY(slots_embed_rows(cv->slots, cv->d_bias, c->phim, false, nI, (i64*)d_msg));
+  for (int I = 0; I < nI; ++I)
+    FHESI_TRY(grid_chunks(count, [&](i64 done, i64 cnt) {
+      return launch_ct_add_const(c, (u64*)out + ((size_t)I * count + done) * 2 * n * nlimbs, (const i64*)d_msg + (size_t)I * n, 1, 2, nlimbs, logQ, cv->slots->S.p, cnt);
+    }));
+  return 0;
 }
 
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).

@@ -110,6 +110,7 @@ struct CtxOptions {
   int stagger = 0;          // lanes = 2: start the second lane after the first lane's digit transform
   long long batch_chunk = 0;      // ciphertexts per pipeline chunk (0 = derived from the ring)
   long long wave_operands = 0;    // distinct operands per pass of fhesi_ct_mul_sum_relin_dev (0 = about 4 GiB of rows)
+  long long stage_chunk_bytes = 0;  // slot values of one chunk of channel pairs while a convolution's plaintexts are staged (0 = 256 MiB; a test hook)
   int wave_single = 1;      // 1: a wave whose groups are single products takes the batch pipeline of fhesi_ct_mul_relin_batch_dev on gathered operands (0: the sum kernels, the checker)
   int automorph_rows = 0;   // 1: Ciphertext >>= through DoubleCRT::automorph on evaluation rows (the reference's structure) even where the coefficient gather applies
   int tensor32 = 1;         // 1: the fused pipeline's tensor half runs over 30-bit primes where that path applies (fhesi_ct_mul_relin_batch_dev)
@@ -458,6 +459,24 @@ struct fhesi_linear : fhesi_linear_grid {};
 // One layer: ld = C, nJ = 1, first = 0, nblocks = 1.
 int launch_linear_diag(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_M, i64 ld, int nJ, int first, int nblocks, i64 R, i64 C, int T, int B,
                        i64* d_out /* [nblocks][T][phim] */);
+
+// --------------------------------------------------------------------------------- convolution layers (capi_ct.hip, capi_pipeline.hip, kernels_slots.hip)
+// A 2-D convolution K [Cout][Cin][kh][kw] over H x W planes, one channel per ciphertext (include/fhesi_hip.h; the plan: conv_plan.h): the Cout Cin kh kw
+// masked weight plaintexts in ONE prepared plaintext, the biases as slot values, the plan
+struct fhesi_conv2d {
+  fhesi_ctx* ctx = nullptr;
+  fhesi_slots* slots = nullptr;        // the space the layer was made on, borrowed: embeds the bias in front of its addition
+  i64 Cout = 0, Cin = 0, kh = 0, kw = 0, H = 0, W = 0, ah = 0, aw = 0;
+  int form = 0, nh = 0;                // 1 flat, 2 split; the matrices the run call takes
+  i64 key_switches = 0, terms = 0;
+  std::vector<i64> amounts;            // flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; 0 exactly at the anchor
+  fhesi_plain* w = nullptr;            // row (I Cin + J) kh kw + t: w_t (flat), w'_t (split) of the channel pair (I, J)
+  i64* d_bias = nullptr;               // [Cout][phim] slot values b[I] in [0, p) in every slot; null without a bias
+};
+// d_out[(pair - first) kh kw + t][s] = the masked weight plaintext t of channel pair `pair` = I Cin + J at slot s, reduced into [0, p), for the pairs
+// first .. first + npairs - 1 of d_K [Cout Cin][kh kw] (conv_mask_kernel, kernels_slots.hip); split: every plaintext moved back by its giant amount
+int launch_conv_mask(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_K, int first, int npairs, int kh, int kw, int ah, int aw, i64 H, i64 W, bool split,
+                     i64* d_out /* [npairs][kh kw][phim] */);
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

@@ -72,7 +72,8 @@ int fhesi_ctx_sync(fhesi_ctx* ctx);
 void* fhesi_ctx_stream(fhesi_ctx* ctx);                     /* the hipStream_t all work of this context runs on */
 /* Behaviour switches of one context (A/B measurements, test hooks).  Names: "ks_direct" (1 = per-chain-prime key-switch dot product, the
  * reference's own structure FHE-SI.cpp:251-254), "ks_residues", "ks_aux60", "crt_exact", "crt_skip_cleanup" (test hook), "lanes" (2 = two
- * concurrent half-batches), "stagger", "batch_chunk", "wave_operands", "tensor32" (0 = the fused pipeline keeps the tensor product on the
+ * concurrent half-batches), "stagger", "batch_chunk", "wave_operands", "stage_chunk_bytes" (test hook: the chunk of channel pairs
+ * while fhesi_conv2d_create stages its plaintexts), "tensor32" (0 = the fused pipeline keeps the tensor product on the
  * chain primes), "tensor_bits" (30 / 29: the size of the tensor half's primes -- below 2^29 the row transforms skip half of their range steps
  * for one or two primes more; the integers formed are the same); layout switches that never change a result (round 5): "dot32_k4" (0 = the digit-tile dot product dot32_kernel2 where the
  * key-in-LDS form dot32_kernel4 would run), "parts_words" (0 = 64-bit limb rows between the tensor half and the digit loader),
@@ -638,6 +639,58 @@ int fhesi_linear_grid_diagonals(fhesi_slots* s, const int64_t* M_host /* [R][C] 
 int fhesi_ct_linear_grid_dev(fhesi_ctx* ctx, const fhesi_linear_grid* grid, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
                              const uint64_t* in_dev /* [nJ][count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count,
                              uint64_t* out_dev /* [nI][count][2][phi(m)][nlimbs] */);
+
+/* ---- convolution layers on packed slots: a 2-D convolution over image planes, one channel per ciphertext (capi_ct.hip, capi_pipeline.hip, conv_plan.h,
+ * conv_mask_kernel in kernels_slots.hip; tests/conv_model.py is the normative statement).  The space has rows of `cols` slots; rot_a moves
+ * every row a slots to the left.
+ *   plane      H x W, P = H W | cols: slot (r, i) holds pixel (y, x) = ((i mod P) div W, (i mod P) mod W) of image (r, i div P) -- cols / P images per row
+ *   channels   an item is Cin ciphertexts in[J][i], the result Cout ciphertexts out[I][i], the [block][count] order of fhesi_ct_linear_grid_dev
+ *   kernel     K [Cout][Cin][kh][kw] any int64 (reduced into [0, p) on the device), anchor (ah, aw), stride 1, zero padding ("same", cross-correlation):
+ *              out[I](y, x) = b[I] + sum_J sum_dy sum_dx K[I][J][dy][dx] in[J](y + dy - ah, x + dx - aw),  pixels outside the plane = 0
+ *   offsets    t = dy kw + dx, u = dy - ah, v = dx - aw, mask mu_{u,v}[i] = [0 <= y + u < H and 0 <= x + v < W]; where the mask is 1, i + u W + v stays
+ *              in the P-block of i, so the cyclic rotation of the whole row is harmless
+ *   flat       out[I] = sum_J sum_t w^{IJ}_t (*) rot_{a_t}(in[J]) + b[I],  a_t = (u W + v) mod cols,  w^{IJ}_t[i] = K[I][J][dy][dx] mu_{u,v}[i]
+ *   split      out[I] = sum_dy rot_{(u W) mod cols}( sum_J sum_dx w'^{IJ}_t (*) rot_{v mod cols}(in[J]) ) + b[I],  w'^{IJ}_t[i] = w^{IJ}_t[(i - u W) mod cols]
+ * Key switches per item: flat Cin (kh kw - 1) over up to kh kw - 1 distinct matrices; split Cin (kw - 1) + Cout (kh - 1) over kh + kw - 2 matrices -- one
+ * digit set of an input channel serves every output channel.  Two offsets may share an amount modulo cols; it is listed and run once per use.
+ *
+ * fhesi_conv2d_plan (host only): form 0 = the planner's (the form of fewer key switches, flat on a tie: one key-switch level less), 1 flat, 2 split.
+ *   amounts in the order the run call takes its matrices -- flat: nh = kh kw, entry t; split: nh = kw + kh, the kw baby amounts v mod cols, then the kh
+ *   giant amounts (u W) mod cols.  Amount 0 appears exactly at the anchor, and the matrix there is NULL.  terms = the longest plaintext sum: Cin kh kw
+ *   (flat), Cin kw (split).  Any output may be NULL.  REFUSED with the condition named: a size below 1; P not dividing cols; an anchor outside the kernel;
+ *   an offset whose mask is empty (|u| >= H or |v| >= W), naming the offset; more than 65535 plaintexts Cout Cin kh kw per handle; form outside 0 .. 2.
+ * fhesi_conv2d_create / _create_dev: K and bias [Cout] (or NULL) contiguous int64, on the host or in HBM where they stay, as for fhesi_linear_create.  The
+ *   handle owns ONE prepared plaintext of Cout Cin kh kw rows, row (I Cin + J) kh kw + t -- equal to fhesi_plain_create_slots of the w (flat) or w' (split)
+ *   above with only_usable = 0 --, the biases as slot values [Cout][phi(m)] (b[I] in every slot) and the plan; the plaintexts are written, embedded and
+ *   transformed in chunks of whole channel pairs, so the workspace holds a chunk and never the layer.  It counts as a live handle of the context and
+ *   borrows s.  fhesi_conv2d_info: shapes, plan, whether it has a bias, the amounts (any pointer may be NULL).
+ * fhesi_conv2d_masks: the same stage without a handle -- vals_host [Cout][Cin][kh kw][phi(m)] receives the slot vectors.
+ * fhesi_ct_conv2d_dev: in_dev [Cin][count], out_dev [Cout][count] two-part ciphertexts; hoisted [nh]: entry t the hoisted matrix of g^amounts[t] mod m.
+ *   DEFINED as, and word for word equal to -- flat: fhesi_ct_rotations_dev per input channel over the nh amounts into one pool [Cin][kh kw][count]; ONE
+ *   fhesi_ct_plain_sum_dev with the groups (I, i) and the terms (J, t); fhesi_ct_add_slots_dev with b[I] per output channel.  split: the rotations per
+ *   input channel over the kw baby amounts into a pool [Cin][kw][count]; ONE plaintext sum with the groups (I, dy, i) and the terms (J, dx); per output
+ *   channel fhesi_ct_rotations_dev (nk = 1) of each inner sum by its giant, the first into out, the others added with fhesi_ct_add_dev; then the bias.
+ *   The capacity rule of fhesi_ct_plain_sum_dev is checked with `terms` before anything is launched.  REFUSED with the condition named: nh other than
+ *   the plan's; a matrix missing where the amount is not 0, present where it is 0, not hoisted, hoisted for another k or of another context; a layer of
+ *   another context; out overlapping in; whatever the calls it is composed of refuse.
+ * NOT HERE: stride and dilation; "valid" output; several channels inside one ciphertext; depthwise / grouped kernels; a form that keeps the weights as
+ *   scalars against kh kw shared masks; pruning zero weights; a form of the C++ mirror; mixing the two rows of a two-row space. */
+typedef struct fhesi_conv2d fhesi_conv2d; /* a convolution layer on a slot space: its masked weight plaintexts, its biases and its plan */
+int fhesi_conv2d_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw,
+                      int32_t form /* 0 planner, 1 flat, 2 split */, int32_t* form_out, int32_t* nh, int64_t* key_switches, int64_t* terms,
+                      int64_t* amounts /* [nh] or NULL */);
+int fhesi_conv2d_create(fhesi_slots* s, const int64_t* K_host /* [Cout][Cin][kh][kw] */, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W,
+                        int64_t ah, int64_t aw, const int64_t* bias_host /* [Cout] or NULL */, int32_t form, fhesi_conv2d** out);
+int fhesi_conv2d_create_dev(fhesi_slots* s, const int64_t* K_dev /* [Cout][Cin][kh][kw] */, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W,
+                            int64_t ah, int64_t aw, const int64_t* bias_dev /* [Cout] or NULL */, int32_t form, fhesi_conv2d** out);
+int fhesi_conv2d_free(fhesi_conv2d* conv);
+int fhesi_conv2d_info(const fhesi_conv2d* conv, int64_t* Cout, int64_t* Cin, int64_t* kh, int64_t* kw, int64_t* H, int64_t* W, int64_t* ah, int64_t* aw,
+                      int32_t* form, int32_t* nh, int64_t* key_switches, int64_t* terms, int32_t* has_bias, int64_t* amounts /* [nh] or NULL */);
+int fhesi_conv2d_masks(fhesi_slots* s, const int64_t* K_host /* [Cout][Cin][kh][kw] */, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W,
+                       int64_t ah, int64_t aw, int32_t form, int64_t* vals_host /* [Cout][Cin][kh kw][phi(m)] */);
+int fhesi_ct_conv2d_dev(fhesi_ctx* ctx, const fhesi_conv2d* conv, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
+                        const uint64_t* in_dev /* [Cin][count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count,
+                        uint64_t* out_dev /* [Cout][count][2][phi(m)][nlimbs] */);
 
 /* ---- polynomial activations on packed slots: y = f(x) = sum_{k <= d} c_k x^k slot by slot, the non-linear step between two linear layers (DESIGN.md 9a;
  * tests/poly_model.py is the normative statement of the plan and of the schedule).
