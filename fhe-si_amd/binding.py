@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "fhesi_linear_grid_plan", "fhesi_linear_grid_create", "fhesi_linear_grid_create_dev", "fhesi_linear_grid_free", "fhesi_linear_grid_info",
     "fhesi_linear_grid_diagonals", "fhesi_ct_linear_grid_dev",
     "fhesi_conv2d_plan", "fhesi_conv2d_create", "fhesi_conv2d_create_dev", "fhesi_conv2d_free", "fhesi_conv2d_info", "fhesi_conv2d_masks", "fhesi_ct_conv2d_dev",
+    "fhesi_conv2d_lattice_plan", "fhesi_conv2d_lattice_create", "fhesi_conv2d_lattice_create_dev", "fhesi_conv2d_lattice_masks", "fhesi_conv2d_lattice_info",
+    "fhesi_pool2d_plan", "fhesi_ct_pool2d_dev", "fhesi_slots_lattice_columns", "fhesi_slots_lattice_columns_dev",
     "fhesi_ct_lin_comb_dev", "fhesi_poly_eval_plan", "fhesi_ct_poly_eval_dev",
 ]
 ROT_SUM_MAX_TERMS = 16   # FHESI_ROT_SUM_MAX_TERMS: the terms one launch of the rotated-sum kernel takes (more terms chain launches)
@@ -275,6 +277,15 @@ def _load():
         "fhesi_conv2d_info": [_vp] * 15,
         "fhesi_conv2d_masks": [_vp, _vp] + [_i64] * 8 + [_i32, _vp],
         "fhesi_ct_conv2d_dev": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_conv2d_lattice_plan": [_i64] * 15 + [_i32] + [_vp] * 7,
+        "fhesi_conv2d_lattice_create": [_vp, _vp] + [_i64] * 14 + [_vp, _i32, _vp],
+        "fhesi_conv2d_lattice_create_dev": [_vp, _vp] + [_i64] * 14 + [_vp, _i32, _vp],
+        "fhesi_conv2d_lattice_masks": [_vp, _vp] + [_i64] * 14 + [_i32, _vp],
+        "fhesi_conv2d_lattice_info": [_vp] * 9,
+        "fhesi_pool2d_plan": [_i64] * 7 + [_i32] + [_vp] * 8,
+        "fhesi_ct_pool2d_dev": [_vp] + [_i64] * 6 + [_i32, _vp, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
+        "fhesi_slots_lattice_columns": [_vp, _vp] + [_i64] * 6 + [_vp],
+        "fhesi_slots_lattice_columns_dev": [_vp, _vp] + [_i64] * 6 + [_vp],
         "fhesi_ct_lin_comb_dev": [_vp, _i32, _u64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
         "fhesi_poly_eval_plan": [_i32, _i32, _vp, _vp, _vp, _vp, _vp],
         "fhesi_ct_poly_eval_dev": [_vp, _vp, _i32, _u64, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _vp],
@@ -717,6 +728,43 @@ def conv2d_plan(cols: int, H: int, W: int, Cin: int, Cout: int, kh: int, kw: int
     return {"form": f.value, "nh": nh.value, "key_switches": ks.value, "terms": terms.value, "amounts": [int(a) for a in amounts]}
 
 
+def _geometry(step, stride, dilation):
+    """(sy, sx, ty, tx, ey, ex) of step, stride, dilation, each a pair of integers"""
+    out = []
+    for name, v in (("step", step), ("stride", stride), ("dilation", dilation)):
+        if len(tuple(v)) != 2:
+            raise ValueError(f"{name} = (vertical, horizontal)")
+        out += [int(v[0]), int(v[1])]
+    return tuple(out)
+
+
+def conv2d_lattice_plan(cols: int, H: int, W: int, Cin: int, Cout: int, kh: int, kw: int, ah: int, aw: int, step=(1, 1), stride=(1, 1), dilation=(1, 1),
+                        form: int = 0) -> dict:
+    """conv2d_plan on a plane that carries a lattice step (fhesi_conv2d_lattice_plan): logical pixel (a, b) at physical pixel (a sy, b sx), the kernel
+    read with stride (ty, tx) and dilation (ey, ex) on the logical plane.  The amounts are those of the offsets stretched to physical pixels; "out_step"
+    = (sy ty, sx tx) is the step the next layer takes.  With the defaults: conv2d_plan.  Raises FhesiError naming the condition.  Touches no device."""
+    args = tuple(int(v) for v in (cols, H, W, Cin, Cout, kh, kw, ah, aw)) + _geometry(step, stride, dilation) + (int(form),)
+    f, nh, ks, terms, oy, ox = _i32(0), _i32(0), _i64(0), _i64(0), _i64(0), _i64(0)
+    _ck(_load().fhesi_conv2d_lattice_plan(*args, _byref(f), _byref(nh), _byref(ks), _byref(terms), _byref(oy), _byref(ox), None))
+    amounts = np.zeros(nh.value, dtype=np.int64)
+    _ck(_load().fhesi_conv2d_lattice_plan(*args, None, None, None, None, None, None, _p(amounts)))
+    return {"form": f.value, "nh": nh.value, "key_switches": ks.value, "terms": terms.value, "amounts": [int(a) for a in amounts], "out_step": (oy.value, ox.value)}
+
+
+def pool2d_plan(cols: int, H: int, W: int, kh: int, kw: int, sy: int = 1, sx: int = 1, form: int = 0) -> dict:
+    """The plan of a sum pooling over non-overlapping windows of kh x kw logical pixels on H x W planes of step (sy, sx) (fhesi_pool2d_plan): form (given 0:
+    the form of fewer key switches, form 1 on a tie; 1 hoisted sums, 2 doubling), the amounts in the order SlotSpace.pool2d takes their matrices -- "nhor"
+    horizontal ones, then the vertical ones --, the key switches per ciphertext, the key-switch levels and "out_step" = (sy kh, sx kw).  Raises FhesiError
+    naming the condition on a refused shape.  Touches no device."""
+    args = tuple(int(v) for v in (cols, H, W, kh, kw, sy, sx, form))
+    f, nh, nhor, ks, lv, oy, ox = _i32(0), _i32(0), _i32(0), _i64(0), _i32(0), _i64(0), _i64(0)
+    _ck(_load().fhesi_pool2d_plan(*args, _byref(f), _byref(nh), _byref(nhor), _byref(ks), _byref(lv), _byref(oy), _byref(ox), None))
+    amounts = np.zeros(nh.value, dtype=np.int64)
+    _ck(_load().fhesi_pool2d_plan(*args, None, None, None, None, None, None, None, _p(amounts) if nh.value else None))
+    return {"form": f.value, "nh": nh.value, "nhor": nhor.value, "key_switches": ks.value, "levels": lv.value, "amounts": [int(a) for a in amounts],
+            "out_step": (oy.value, ox.value)}
+
+
 def plain_sum_bits(m: int, logQ: int, maxabs: int, terms: int) -> float:
     """Bits the chain product must exceed for a sum of `terms` ciphertext x plaintext products on the ring m: log2 of twice
     terms * growth * phi(m) * 2^(logQ-1) * maxabs, growth = 1 (m a power of two), 2 (m = q^k, 2 q^k) or phi(m).  Touches no device."""
@@ -822,7 +870,8 @@ class Conv2d:
     """A 2-D convolution K [Cout][Cin][kh][kw] over H x W planes on a slot space, one channel per ciphertext (fhesi_conv2d): its masked weight
     plaintexts, its biases and its plan, resident in HBM; made by SlotSpace.conv2d.  .amounts lists the rotation amounts whose hoisted matrices apply()
     takes -- flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; 0 (no matrix) exactly at the anchor; .key_switches is what apply()
-    runs per item."""
+    runs per item.  .step, .stride, .dilation: the lattice it was made for (all (1, 1) without one); .out_step = step * stride is the step of its output
+    planes, which the next layer takes as its own."""
 
     def __init__(self, space: "SlotSpace", h):
         self.space, self.ctx, self.h = space, space.ctx, h
@@ -835,6 +884,10 @@ class Conv2d:
         a = np.zeros(self.nh, dtype=np.int64)
         _ck(_load().fhesi_conv2d_info(self.h, *([None] * 13), _p(a)))
         self.amounts = [int(x) for x in a]
+        g = [_i64(0) for _ in range(8)]
+        _ck(_load().fhesi_conv2d_lattice_info(self.h, *(_byref(x) for x in g)))
+        g = [x.value for x in g]
+        self.step, self.stride, self.dilation, self.out_step = (g[0], g[1]), (g[2], g[3]), (g[4], g[5]), (g[6], g[7])
 
     def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
         """out[I][i] = output channel I of item i (fhesi_ct_conv2d_dev): src [Cin][count] holds the input channels (SlotSpace.pack_images encrypted),
@@ -1145,10 +1198,12 @@ class SlotSpace:
     def _conv_anchor(kh: int, kw: int, anchor):
         return ((kh - 1) // 2, (kw - 1) // 2) if anchor is None else (int(anchor[0]), int(anchor[1]))
 
-    def conv2d(self, K, bias=None, image=None, anchor=None, form: int = 0, device: bool = False) -> Conv2d:
+    def conv2d(self, K, bias=None, image=None, anchor=None, form: int = 0, device: bool = False, step=(1, 1), stride=(1, 1), dilation=(1, 1)) -> Conv2d:
         """The convolution of K [Cout][Cin][kh][kw], bias [Cout] or None, any int64 (reduced modulo p on the device), over planes image = (H, W), H W
-        dividing the row; stride 1, zero padding, anchor (default ((kh - 1) // 2, (kw - 1) // 2)) the kernel entry that meets the output pixel.
-        form: 0 the planner's, 1 flat, 2 split (conv2d_plan).  device=True: K and bias are int64 tensors in HBM (torch tensors), read where they are."""
+        dividing the row; zero padding, anchor (default ((kh - 1) // 2, (kw - 1) // 2)) the kernel entry that meets the output pixel.
+        form: 0 the planner's, 1 flat, 2 split (conv2d_plan).  device=True: K and bias are int64 tensors in HBM (torch tensors), read where they are.
+        step, stride, dilation: the lattice (conv2d_lattice_plan) -- the input's live pixels on every step-th row and column, the output's on every
+        (step * stride)-th, every other output slot 0; all (1, 1), the default, takes the stride-1 path (fhesi_conv2d_create)."""
         if image is None:
             raise ValueError("conv2d: image = (H, W)")
         H, W = int(image[0]), int(image[1])
@@ -1160,7 +1215,7 @@ class SlotSpace:
                 bp, bshape = self._device_words(bias, "the bias")
                 if len(shape) == 4 and bshape != (shape[0],):
                     raise ValueError(f"conv2d: a bias of shape {bshape} for {shape[0]} output channels")
-            fn = _load().fhesi_conv2d_create_dev
+            fn = "fhesi_conv2d_create_dev"
         else:
             K = np.ascontiguousarray(K, dtype=np.int64)
             shape, kp, bp = K.shape, _p(K), None
@@ -1169,30 +1224,94 @@ class SlotSpace:
                 if K.ndim == 4 and b.shape != (shape[0],):
                     raise ValueError(f"conv2d: a bias of shape {b.shape} for {shape[0]} output channels")
                 bp = _p(b)
-            fn = _load().fhesi_conv2d_create
+            fn = "fhesi_conv2d_create"
         if len(shape) != 4:
             raise ValueError("conv2d: the kernel is [Cout][Cin][kh][kw]")
         ah, aw = self._conv_anchor(shape[2], shape[3], anchor)
-        _ck(fn(self.h, kp, shape[0], shape[1], shape[2], shape[3], H, W, ah, aw, bp, int(form), _byref(h)))
+        geom = _geometry(step, stride, dilation)
+        if geom == (1,) * 6:
+            _ck(getattr(_load(), fn)(self.h, kp, shape[0], shape[1], shape[2], shape[3], H, W, ah, aw, bp, int(form), _byref(h)))
+        else:
+            _ck(getattr(_load(), fn.replace("conv2d_", "conv2d_lattice_"))(self.h, kp, shape[0], shape[1], shape[2], shape[3], H, W, ah, aw, *geom, bp, int(form), _byref(h)))
         return Conv2d(self, h)
 
-    def conv2d_masks(self, K, image, anchor=None, form: int = 0) -> np.ndarray:
+    def conv2d_masks(self, K, image, anchor=None, form: int = 0, step=(1, 1), stride=(1, 1), dilation=(1, 1)) -> np.ndarray:
         """The masked weight plaintexts of the convolution as slot values: [Cout][Cin][kh kw][total], entry t = dy kw + dx the weight under its mask,
-        moved back by its giant amount in the split form (fhesi_conv2d_masks) -- what SlotSpace.conv2d embeds, downloaded."""
+        moved back by its giant amount in the split form (fhesi_conv2d_masks; with a step, stride or dilation other than (1, 1)
+        fhesi_conv2d_lattice_masks) -- what SlotSpace.conv2d embeds, downloaded."""
         K = np.ascontiguousarray(K, dtype=np.int64)
         if K.ndim != 4:
             raise ValueError("conv2d_masks: the kernel is [Cout][Cin][kh][kw]")
         Cout, Cin, kh, kw = K.shape
         ah, aw = self._conv_anchor(kh, kw, anchor)
-        conv2d_plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, form)      # the shape, before the output is sized
+        geom = _geometry(step, stride, dilation)
+        if geom == (1,) * 6:
+            conv2d_plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, form)      # the shape, before the output is sized
+            vals = np.zeros((Cout, Cin, kh * kw, self.total), dtype=np.int64)
+            _ck(_load().fhesi_conv2d_masks(self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw, int(form), _p(vals)))
+            return vals
+        return self.conv2d_lattice_masks(K, image, anchor, form, step, stride, dilation)
+
+    def conv2d_lattice_masks(self, K, image, anchor=None, form: int = 0, step=(1, 1), stride=(1, 1), dilation=(1, 1)) -> np.ndarray:
+        """conv2d_masks through fhesi_conv2d_lattice_masks whatever the geometry: with all (1, 1) the words of conv2d_masks, from the lattice kernel."""
+        K = np.ascontiguousarray(K, dtype=np.int64)
+        if K.ndim != 4:
+            raise ValueError("conv2d_lattice_masks: the kernel is [Cout][Cin][kh][kw]")
+        Cout, Cin, kh, kw = K.shape
+        ah, aw = self._conv_anchor(kh, kw, anchor)
+        conv2d_lattice_plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, step, stride, dilation, form)
         vals = np.zeros((Cout, Cin, kh * kw, self.total), dtype=np.int64)
-        _ck(_load().fhesi_conv2d_masks(self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw, int(form), _p(vals)))
+        _ck(_load().fhesi_conv2d_lattice_masks(self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw, *_geometry(step, stride, dilation), int(form), _p(vals)))
         return vals
 
-    def pack_images(self, x) -> np.ndarray:
+    # ---- sum pooling and the bridge to a dense layer on a lattice of the plane (fhesi_ct_pool2d_dev, fhesi_slots_lattice_columns)
+    def pool2d(self, hoisted_by_amount, image, window, step, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, form: int = 0, decomp_bytes: int = 3) -> dict:
+        """out[i] = the sums of src[i] over non-overlapping windows = (kh, kw) of logical pixels on planes image = (H, W) of step = (sy, sx), each at its
+        window's top left pixel (fhesi_ct_pool2d_dev): rotations and sums only, no plaintext product.  A SUM -- fold 1 / (kh kw) into the next layer.
+        count: channels and items alike.  hoisted_by_amount: a mapping amount -> hoisted matrix of rotation_k(amount) covering pool2d_plan's amounts, or
+        the list of matrices in their order.  out may be src.  Returns the plan; its "out_step" is the step of the result."""
+        H, W, kh, kw, sy, sx = (int(v) for v in (image[0], image[1], window[0], window[1], step[0], step[1]))
+        pl = pool2d_plan(self.total // max(self.rows, 1), H, W, kh, kw, sy, sx, form)
+        hs = [hoisted_by_amount[a] for a in pl["amounts"]] if hasattr(hoisted_by_amount, "keys") else list(hoisted_by_amount)
+        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
+        _ck(_load().fhesi_ct_pool2d_dev(self.h, H, W, kh, kw, sy, sx, int(form), arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+        return pl
+
+    def lattice_columns(self, M, nch: int, image, step, device: bool = False, out=None):
+        """M [R][nch Hl Wl] over the logical pixels of nch planes image = (H, W) of step = (sy, sx) -> M' [R][nch H W] over their slots, zero columns off
+        the lattice (fhesi_slots_lattice_columns): what linear_grid(M', block=(Rb, H W)) takes as it is.  device=True: M and `out` are contiguous int64
+        tensors in HBM (torch tensors); out is filled and returned."""
+        H, W, sy, sx = (int(v) for v in (image[0], image[1], step[0], step[1]))
+        if device:
+            mp, shape = self._device_words(M, "the matrix")
+            if out is None:
+                raise ValueError("lattice_columns: device=True fills `out`, an int64 tensor [R][nch H W] in HBM")
+            op, oshape = self._device_words(out, "the output")
+            if len(shape) != 2 or oshape != (shape[0], int(nch) * H * W):
+                raise ValueError(f"lattice_columns: a matrix of shape {shape} into an output of shape {oshape}")
+            if sy < 1 or sx < 1 or H % sy or W % sx or shape[1] != int(nch) * (H // sy) * (W // sx):
+                raise ValueError(f"lattice_columns: {shape[1]} columns are not {nch} logical planes of {H} x {W} at step ({sy}, {sx})")
+            _ck(_load().fhesi_slots_lattice_columns_dev(self.h, mp, shape[0], int(nch), H, W, sy, sx, op))
+            return out
+        M = np.ascontiguousarray(M, dtype=np.int64)
+        if M.ndim != 2 or sy < 1 or sx < 1 or H < 1 or W < 1 or H % sy or W % sx or M.shape[1] != int(nch) * (H // sy) * (W // sx):
+            raise ValueError(f"lattice_columns: a matrix of shape {M.shape} is not [R][{nch} logical planes of {H} x {W} at step ({sy}, {sx})]")
+        res = np.zeros((M.shape[0], int(nch) * H * W), dtype=np.int64)
+        _ck(_load().fhesi_slots_lattice_columns(self.h, _p(M), M.shape[0], int(nch), H, W, sy, sx, _p(res)))
+        return res
+
+    def pack_images(self, x, step=(1, 1)) -> np.ndarray:
         """x [..][rows][cols / P][H][W] (the rows axis dropped on a one-row space) -> slot values [..][total]: image (r, b) in the P-block b of row r,
-        pixel (y, x) at y W + x.  Host only."""
+        pixel (y, x) at y W + x.  step = (sy, sx): x holds the LOGICAL planes [Hl][Wl], pixel (a, b) goes to (a sy, b sx) of the H x W = Hl sy x Wl sx
+        plane and the slots off the lattice are 0.  Host only."""
         x = np.asarray(x)
+        if tuple(step) != (1, 1):
+            sy, sx = int(step[0]), int(step[1])
+            if sy < 1 or sx < 1 or x.ndim < 2:
+                raise ValueError(f"pack_images: step ({sy}, {sx})")
+            full = np.zeros(x.shape[:-2] + (x.shape[-2] * sy, x.shape[-1] * sx), dtype=x.dtype)
+            full[..., ::sy, ::sx] = x
+            x = full
         rows, cols = max(self.rows, 1), self.total // max(self.rows, 1)
         H, W = x.shape[-2:]
         lead = x.shape[:-4] if rows == 2 else x.shape[:-3]
@@ -1200,8 +1319,14 @@ class SlotSpace:
             raise ValueError(f"pack_images: images of shape {x.shape}, a plaintext takes [{rows}][cols / (H W)][H][W] on rows of {cols} slots")
         return np.ascontiguousarray(x.reshape(lead + (self.total,)))
 
-    def unpack_images(self, vals, H: int, W: int) -> np.ndarray:
-        """The inverse: slot values [..][total] -> [..][rows][cols / P][H][W] (the rows axis dropped on a one-row space).  Host only."""
+    def unpack_images(self, vals, H: int, W: int, step=(1, 1)) -> np.ndarray:
+        """The inverse: slot values [..][total] -> [..][rows][cols / P][H][W] (the rows axis dropped on a one-row space); step = (sy, sx): only the
+        lattice's pixels, [..][H / sy][W / sx].  Host only."""
+        if tuple(step) != (1, 1):
+            sy, sx = int(step[0]), int(step[1])
+            if sy < 1 or sx < 1 or H % sy or W % sx:
+                raise ValueError(f"unpack_images: the step ({sy}, {sx}) does not divide the {H} x {W} plane")
+            return self.unpack_images(vals, H, W)[..., ::sy, ::sx]
         vals = np.asarray(vals)
         rows, cols = max(self.rows, 1), self.total // max(self.rows, 1)
         if H < 1 or W < 1 or cols % (H * W) or vals.shape[-1] != self.total:
@@ -1436,15 +1561,24 @@ class SlotBasis:
         for c in range(self.k):
             layers[c].apply(hoisted_by_amount, logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), decomp_bytes)
 
-    def conv2d(self, K, bias=None, image=None, anchor=None, form: int = 0) -> list:
+    def conv2d(self, K, bias=None, image=None, anchor=None, form: int = 0, step=(1, 1), stride=(1, 1), dilation=(1, 1)) -> list:
         """SlotSpace.conv2d per channel: the k handles of the convolution K [Cout][Cin][kh][kw], bias [Cout] (integers of any size), channel c holding
-        them modulo primes[c]."""
+        them modulo primes[c]; step, stride, dilation as SlotSpace.conv2d takes them."""
         K = np.asarray(K)
         out = []
         for c in range(self.k):
             Kc = self._residues(K.reshape(1, -1), c).reshape(K.shape)
-            out.append(self.channel(c).conv2d(Kc, None if bias is None else self._residues(bias, c)[0], image, anchor, form))
+            out.append(self.channel(c).conv2d(Kc, None if bias is None else self._residues(bias, c)[0], image, anchor, form, step=step, stride=stride, dilation=dilation))
         return out
+
+    def pool2d(self, hoisted_by_amount, image, window, step, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, form: int = 0, decomp_bytes: int = 3) -> dict:
+        """SlotSpace.pool2d channel by channel (one key set serves every channel): src, out [k][count] logical ciphertexts.  Exact while the window sums
+        stay below half the product of the primes."""
+        words = 2 * self.ctx.phim * nlimbs * 8
+        pl = None
+        for c in range(self.k):
+            pl = self.channel(c).pool2d(hoisted_by_amount, image, window, step, logQ, _View(src, c * count * words), nlimbs, count, _View(out, c * count * words), form, decomp_bytes)
+        return pl
 
     def conv2d_apply(self, layers, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
         """Conv2d.apply per channel (one key set serves every channel): src [k][Cin][count], out [k][Cout][count] logical ciphertexts, layers from

@@ -3,6 +3,7 @@
 #include "wave_plan.h"
 #include "poly_plan.h"
 #include "conv_plan.h"
+#include "lattice_plan.h"
 
 // ---- coefficient-domain ciphertext algebra on device batches (kernels_ct.hip)
 extern "C" int fhesi_ct_add_dev(fhesi_ctx* c, int32_t logQ, uint64_t* dst, const uint64_t* src, int32_t nparts, int32_t nlimbs, int64_t count) {
@@ -822,10 +823,14 @@ extern "C" int fhesi_linear_grid_diagonals(fhesi_slots* s, const int64_t* M_host
 // fhesi_conv2d (include/fhesi_hip.h; the plan and its refusals: conv_plan.h).  The stage next to linear_stage_open: the kh kw masked weight plaintexts of a
 // channel pair [kh kw][phi(m)] in the values slot, written by conv_mask_kernel from the weight tensor where it is, in chunks of whole channel pairs
 // (option "stage_chunk_bytes" lowers the cap, for tests).
+// On a lattice of the plane (fhesi_conv2d_lattice_*; lattice_plan.h) the same stage with conv_lattice_mask_kernel: `geom` the step, stride and dilation, null
+// from the entries without one, which keep conv_mask_kernel.
 struct ConvStage {
   ConvShape sh;
   ConvPlan plan;
   ValueStage vs;
+  bool lattice = false;
+  LatticeGeom g;
 };
 static int conv_shape_plan(const char* what, const ConvShape& sh, int32_t form, ConvPlan* plan) {
   char why[256];
@@ -844,42 +849,70 @@ extern "C" int fhesi_conv2d_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin
   if (amounts) std::copy(plan.amounts.begin(), plan.amounts.end(), amounts);
   return 0;
 }
+static int lattice_shape_plan(const char* what, const LatticeShape& sh, int32_t form, LatticeConvPlan* plan) {
+  char why[256];
+  if (lattice_refused(sh, form, why, sizeof why)) FHESI_FAIL("%s: %s", what, why);
+  *plan = lattice_conv_plan(sh, form);
+  return 0;
+}
 static int conv_stage_open(fhesi_slots* s, const int64_t* K, bool on_dev, i64 Cout, i64 Cin, i64 kh, i64 kw, i64 H, i64 W, i64 ah, i64 aw, int32_t form, const char* what,
-                           ConvStage* st) {
+                           ConvStage* st, const LatticeGeom* geom = nullptr) {
   if (!s) FHESI_FAIL("%s: null plaintext space", what);
   fhesi_ctx* c = s->ctx;
   CHECK_CTX(c);
   if (!K) FHESI_FAIL("%s: null kernel", what);
   st->sh = ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw};
-  FHESI_TRY(conv_shape_plan(what, st->sh, form, &st->plan));
+  if (geom) {
+    LatticeConvPlan lp;
+    FHESI_TRY(lattice_shape_plan(what, LatticeShape{st->sh, *geom}, form, &lp));
+    st->plan = lp.p; st->lattice = true; st->g = *geom;
+  } else FHESI_TRY(conv_shape_plan(what, st->sh, form, &st->plan));
   const size_t cap = c->opt.stage_chunk_bytes > 0 ? (size_t)c->opt.stage_chunk_bytes : kLinearChunkBytes;
   return value_stage_open(c, Cout * Cin, (size_t)(kh * kw) * s->S.phim, cap, K, on_dev, (size_t)(Cout * Cin * kh * kw), &st->vs);
 }
 // the plaintexts of the channel pairs [first, first + nb), nb <= per, into d_vals
 static int conv_stage_pairs(fhesi_slots* s, const ConvStage& st, i64 first, i64 nb) {
   const ConvShape& sh = st.sh;
+  const LatticeGeom& g = st.g;
+  if (st.lattice)
+    return launch_conv_lattice_mask(s->ctx, s->S, st.vs.d_src, (int)first, (int)nb, (int)sh.kh, (int)sh.kw, (int)sh.ah, (int)sh.aw, sh.H, sh.W, g.ey * g.sy, g.ex * g.sx, g.sy * g.ty,
+                                    g.sx * g.tx, st.plan.form == 2, st.vs.d_vals);
   return launch_conv_mask(s->ctx, s->S, st.vs.d_src, (int)first, (int)nb, (int)sh.kh, (int)sh.kw, (int)sh.ah, (int)sh.aw, sh.H, sh.W, st.plan.form == 2, st.vs.d_vals);
 }
+// b[I] on the output lattice of step (oy, ox), 0 off it: the plaintexts of the 1 x 1 kernel [Cout][1] whose only weight is the bias.  Before conv_stage_open,
+// which takes the values slot over.
+static int lattice_bias_vals(fhesi_slots* s, const int64_t* bias, bool on_dev, i64 Cout, i64 H, i64 W, i64 oy, i64 ox, i64* d_bias) {
+  const i64* d_b = bias;
+  if (!on_dev) {
+    i64* up;
+    FHESI_TRY(upload_vals(s->ctx, bias, (size_t)Cout * 8, &up));
+    d_b = up;
+  }
+  return launch_conv_lattice_mask(s->ctx, s->S, d_b, 0, (int)Cout, 1, 1, 0, 0, H, W, 1, 1, oy, ox, false, d_bias);
+}
 static int conv_create(fhesi_slots* s, const int64_t* K, const int64_t* bias, bool on_dev, i64 Cout, i64 Cin, i64 kh, i64 kw, i64 H, i64 W, i64 ah, i64 aw, int32_t form,
-                       fhesi_conv2d** out) {
-  const char* what = "conv2d_create";
+                       fhesi_conv2d** out, const LatticeGeom* geom = nullptr) {
+  const char* what = geom ? "conv2d_lattice_create" : "conv2d_create";
   if (!out) FHESI_FAIL("%s: null output pointer", what);
   *out = nullptr;
   if (!s) FHESI_FAIL("%s: null plaintext space", what);
   fhesi_ctx* c = s->ctx;
   CHECK_CTX(c);
   if (!K) FHESI_FAIL("%s: null kernel", what);
-  ConvPlan shape_only;
-  FHESI_TRY(conv_shape_plan(what, ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, form, &shape_only));      // the shape, before anything is launched
+  ConvPlan shape_only;      // the shape, before anything is launched
+  LatticeConvPlan lattice_only;
+  if (geom) FHESI_TRY(lattice_shape_plan(what, LatticeShape{ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, *geom}, form, &lattice_only));
+  else FHESI_TRY(conv_shape_plan(what, ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, form, &shape_only));
   const size_t n = (size_t)s->S.phim;
   i64* d_bias = nullptr;
   if (bias) {      // b[I] in every slot: the diagonal of a 1 x 1 block per output channel
     if (hipMalloc(&d_bias, (size_t)Cout * n * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("%s: hipMalloc of %zu bytes failed", what, (size_t)Cout * n * 8); }
-    if (const int rc = linear_bias_vals(s, bias, on_dev, 1, (int)Cout, d_bias)) { hipFree(d_bias); return rc; }
+    const int rc = geom ? lattice_bias_vals(s, bias, on_dev, Cout, H, W, lattice_only.oy, lattice_only.ox, d_bias) : linear_bias_vals(s, bias, on_dev, 1, (int)Cout, d_bias);
+    if (rc) { hipFree(d_bias); return rc; }
   }
   ConvStage st;
   fhesi_plain* made = nullptr;
-  int rc = conv_stage_open(s, K, on_dev, Cout, Cin, kh, kw, H, W, ah, aw, form, what, &st);
+  int rc = conv_stage_open(s, K, on_dev, Cout, Cin, kh, kw, H, W, ah, aw, form, what, &st, geom);
   if (rc) hipStreamSynchronize(c->stream);
   else rc = value_stage_plain(s, Cout * Cin, kh * kw, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); }, &made);
   if (rc) { hipFree(d_bias); return rc; }
@@ -888,6 +921,7 @@ static int conv_create(fhesi_slots* s, const int64_t* K, const int64_t* bias, bo
   cv->form = st.plan.form; cv->nh = st.plan.nh; cv->key_switches = st.plan.key_switches; cv->terms = st.plan.terms;
   cv->amounts.assign(st.plan.amounts.begin(), st.plan.amounts.end());
   cv->w = made; cv->d_bias = d_bias;
+  if (geom) { cv->sy = geom->sy; cv->sx = geom->sx; cv->ty = geom->ty; cv->tx = geom->tx; cv->ey = geom->ey; cv->ex = geom->ex; }
   *out = cv;
   return 0;
 }
@@ -933,6 +967,91 @@ extern "C" int fhesi_conv2d_masks(fhesi_slots* s, const int64_t* K_host, int64_t
   FHESI_TRY(conv_stage_open(s, K_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, "conv2d_masks", &st));
   return value_stage_download(s->ctx, Cout * Cin, (size_t)(kh * kw) * s->S.phim, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); },
                               vals_host);
+}
+
+// --------------------------------------------------------------------------------------------- convolutions and the dense bridge on a lattice of the plane
+// fhesi_conv2d_lattice_* (include/fhesi_hip.h; lattice_plan.h): the stage above with the geometry -- step, stride, dilation -- in the mask and the bias; the
+// handle is a fhesi_conv2d that also records its geometry, and the run call is fhesi_ct_conv2d_dev as it is.
+extern "C" int fhesi_conv2d_lattice_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw, int64_t sy, int64_t sx,
+                                         int64_t ty, int64_t tx, int64_t ey, int64_t ex, int32_t form, int32_t* form_out, int32_t* nh, int64_t* key_switches, int64_t* terms,
+                                         int64_t* out_sy, int64_t* out_sx, int64_t* amounts) {
+  LatticeConvPlan plan;
+  FHESI_TRY(lattice_shape_plan("conv2d_lattice_plan", LatticeShape{ConvShape{cols, H, W, Cin, Cout, kh, kw, ah, aw}, LatticeGeom{sy, sx, ty, tx, ey, ex}}, form, &plan));
+  if (form_out) *form_out = plan.p.form;
+  if (nh) *nh = plan.p.nh;
+  if (key_switches) *key_switches = plan.p.key_switches;
+  if (terms) *terms = plan.p.terms;
+  if (out_sy) *out_sy = plan.oy;
+  if (out_sx) *out_sx = plan.ox;
+  if (amounts) std::copy(plan.p.amounts.begin(), plan.p.amounts.end(), amounts);
+  return 0;
+}
+extern "C" int fhesi_conv2d_lattice_create(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                           int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, const int64_t* bias_host, int32_t form, fhesi_conv2d** out) {
+  const LatticeGeom g{sy, sx, ty, tx, ey, ex};
+  return conv_create(s, K_host, bias_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, out, &g);
+}
+extern "C" int fhesi_conv2d_lattice_create_dev(fhesi_slots* s, const int64_t* K_dev, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                               int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, const int64_t* bias_dev, int32_t form, fhesi_conv2d** out) {
+  const LatticeGeom g{sy, sx, ty, tx, ey, ex};
+  return conv_create(s, K_dev, bias_dev, true, Cout, Cin, kh, kw, H, W, ah, aw, form, out, &g);
+}
+extern "C" int fhesi_conv2d_lattice_info(const fhesi_conv2d* cv, int64_t* sy, int64_t* sx, int64_t* ty, int64_t* tx, int64_t* ey, int64_t* ex, int64_t* out_sy, int64_t* out_sx) {
+  if (!cv) FHESI_FAIL("null convolution layer");
+  if (sy) *sy = cv->sy;
+  if (sx) *sx = cv->sx;
+  if (ty) *ty = cv->ty;
+  if (tx) *tx = cv->tx;
+  if (ey) *ey = cv->ey;
+  if (ex) *ex = cv->ex;
+  if (out_sy) *out_sy = cv->sy * cv->ty;
+  if (out_sx) *out_sx = cv->sx * cv->tx;
+  return 0;
+}
+// the same stage without a handle: vals_host [Cout][Cin][kh kw][phi(m)], chunk by chunk
+extern "C" int fhesi_conv2d_lattice_masks(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                          int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, int32_t form, int64_t* vals_host) {
+  if (!vals_host) FHESI_FAIL("conv2d_lattice_masks: null output");
+  const LatticeGeom g{sy, sx, ty, tx, ey, ex};
+  ConvStage st;
+  FHESI_TRY(conv_stage_open(s, K_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, "conv2d_lattice_masks", &st, &g));
+  return value_stage_download(s->ctx, Cout * Cin, (size_t)(kh * kw) * s->S.phim, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); },
+                              vals_host);
+}
+// M [R][nch Hl Wl] over logical pixels -> M' [R][nch H W] over the slots of the planes, zero columns off the lattice (lattice_columns_kernel): what
+// fhesi_linear_grid_create[_dev] with Cb = H W takes as it is
+static int lattice_columns_args(fhesi_slots* s, const char* what, const void* M, const void* out, i64 R, i64 nch, i64 H, i64 W, i64 sy, i64 sx) {
+  if (!s) FHESI_FAIL("%s: null plaintext space", what);
+  CHECK_CTX(s->ctx);
+  if (!M || !out) FHESI_FAIL("%s: null argument", what);
+  const long long cols = s->S.phim / s->S.rows;
+  if (R < 1 || nch < 1 || H < 1 || W < 1 || sy < 1 || sx < 1)
+    FHESI_FAIL("%s: %lld rows, %lld planes of %lld x %lld pixels, a step (%lld, %lld) (every size at least 1)", what, (long long)R, (long long)nch, (long long)H, (long long)W, (long long)sy, (long long)sx);
+  if (H > cols || W > cols || H * W > cols || cols % (H * W)) FHESI_FAIL("%s: the plane of %lld x %lld pixels does not divide the row of %lld slots", what, (long long)H, (long long)W, cols);
+  if (H % sy || W % sx) FHESI_FAIL("%s: the step (%lld, %lld) does not divide the %lld x %lld plane", what, (long long)sy, (long long)sx, (long long)H, (long long)W);
+  if (nch > 65535 || R > ((i64)1 << 31) / (nch * H * W)) FHESI_FAIL("%s: %lld rows of %lld planes, at most 2^31 entries and 65535 planes are taken", what, (long long)R, (long long)nch);
+  return 0;
+}
+extern "C" int fhesi_slots_lattice_columns_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t nch, int64_t H, int64_t W, int64_t sy, int64_t sx, int64_t* out_dev) {
+  const char* what = "lattice_columns";
+  FHESI_TRY(lattice_columns_args(s, what, M_dev, out_dev, R, nch, H, W, sy, sx));
+  const size_t in_bytes = (size_t)R * nch * (H / sy) * (W / sx) * 8, out_bytes = (size_t)R * nch * H * W * 8;
+  const uintptr_t a = (uintptr_t)M_dev, b = (uintptr_t)out_dev;
+  if (a < b + out_bytes && b < a + in_bytes) FHESI_FAIL("%s: out overlaps the matrix", what);
+  return launch_lattice_columns(s->ctx, M_dev, R, nch, H, W, sy, sx, out_dev);
+}
+extern "C" int fhesi_slots_lattice_columns(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t nch, int64_t H, int64_t W, int64_t sy, int64_t sx, int64_t* out_host) {
+  const char* what = "lattice_columns";
+  FHESI_TRY(lattice_columns_args(s, what, M_host, out_host, R, nch, H, W, sy, sx));
+  fhesi_ctx* c = s->ctx;
+  const size_t in_words = (size_t)R * nch * (H / sy) * (W / sx), out_words = (size_t)R * nch * H * W;
+  i64* d_buf;      // the result, the uploaded matrix behind it (the values slot)
+  FHESI_TRY(ws_i64(c, 9, (out_words + in_words) * 8, &d_buf));
+  HIP_TRY(hipMemcpyAsync(d_buf + out_words, M_host, in_words * 8, hipMemcpyHostToDevice, c->stream));
+  FHESI_TRY(launch_lattice_columns(c, d_buf + out_words, R, nch, H, W, sy, sx, d_buf));
+  HIP_TRY(hipMemcpyAsync(out_host, d_buf, out_words * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // KeySwitchSI::Init (FHE-SI.cpp:153-209) for all columns of a matrix at once; the randomness is the caller's, in the reference's draw order

@@ -4,6 +4,7 @@
 #include "wave_plan.h"
 #include "poly_plan.h"
 #include "conv_plan.h"
+#include "lattice_plan.h"
 
 // --------------------------------------------------------------------------------------------- key-switch matrix
 extern "C" int fhesi_ksk_create(fhesi_ctx* c, int32_t ncomp, int32_t ndigits, fhesi_ksk** out) {
@@ -829,6 +830,85 @@ extern "C" int fhesi_ct_conv2d_dev(fhesi_ctx* c, const fhesi_conv2d* cv, const f
       return launch_ct_add_const(c, (u64*)out + ((size_t)I * count + done) * 2 * n * nlimbs, (const i64*)d_msg + (size_t)I * n, 1, 2, nlimbs, logQ, cv->slots->S.p, cnt);
     }));
   return 0;
+}
+
+// --------------------------------------------------------------------------------------------- sum pooling on a lattice of the plane
+// fhesi_pool2d_plan, fhesi_ct_pool2d_dev (include/fhesi_hip.h; lattice_plan.h): non-overlapping windows that tile the plane never cross its border, so
+// there is no mask and NO plaintext product -- rotations and sums only.
+extern "C" int fhesi_pool2d_plan(int64_t cols, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sy, int64_t sx, int32_t form, int32_t* form_out, int32_t* nh, int32_t* nhor,
+                                 int64_t* key_switches, int32_t* levels, int64_t* out_sy, int64_t* out_sx, int64_t* amounts) {
+  char why[256];
+  const PoolShape sh{cols, H, W, kh, kw, sy, sx};
+  if (pool_refused(sh, form, why, sizeof why)) FHESI_FAIL("pool2d_plan: %s", why);
+  const PoolPlan pl = pool_plan(sh, form);
+  if (form_out) *form_out = pl.form;
+  if (nh) *nh = pl.nh;
+  if (nhor) *nhor = pl.nhor;
+  if (key_switches) *key_switches = pl.key_switches;
+  if (levels) *levels = pl.levels;
+  if (out_sy) *out_sy = pl.oy;
+  if (out_sx) *out_sx = pl.ox;
+  if (amounts) std::copy(pl.amounts.begin(), pl.amounts.end(), amounts);
+  return 0;
+}
+// y[i] <- Reduce(y[i] + sum_t rot_ks[t](y[i])), t < nk, in place: the step rot_fold_run takes with nk terms in place of 1.  Per chunk of ciphertexts the
+// digit rows of y ONCE, one key switch per term from them into consecutive slices of workspace slot 14, in front of their sigma_k, then ONE rotated sum
+// with base = out = y -- every term read once, the result written once.  Every matrix present and of one form `ks_mode`, its table built by the caller in
+// front of any digit row.  Every argument checked by the caller.
+static int rot_hoisted_sum_run(fhesi_ctx* c, const fhesi_ksk* const* hoisted, const int64_t* ks, int32_t nk, int ks_mode, int32_t logQ, int32_t decomp_bytes, u64* y,
+                               int32_t nlimbs, int64_t count) {
+  if (!nk) return 0;
+  const size_t ct_words = (size_t)2 * c->phim * nlimbs;
+  const int nd = hoisted[0]->ndigits;
+  // ciphertexts per chunk: what the digit rows of the batch pipeline admit, and about 4 GiB of key-switched terms
+  i64 chunk = std::min<i64>(std::min<i64>(16384, batch_chunk(c, 2 * nd, ks_mode == KS_MODE_LIMB32, count)), (i64)(4.0 * 1024 * 1024 * 1024 / ((double)nk * ct_words * 8)));
+  if (c->opt.wave_operands > 0) chunk = std::min<i64>(chunk, c->opt.wave_operands / nk);      // (for tests: chunks below count)
+  chunk = std::max<i64>(1, std::min<i64>(chunk, count));
+  for (i64 done = 0; done < count; done += chunk) {
+    const i64 cnt = std::min(chunk, count - done);
+    u64* o = y + (size_t)done * ct_words;
+    void *d_dig, *d_pre;
+    FHESI_TRY(ws_reserve(c, 14, (size_t)nk * cnt * ct_words * 8, &d_pre));
+    FHESI_TRY(unscaled_digits(c, ks_mode, nd, logQ, decomp_bytes, o, nlimbs, cnt, &d_dig));
+    for (int t = 0; t < nk; ++t)
+      FHESI_TRY(key_switch_finish(c, hoisted[t], ks_mode, logQ, decomp_bytes, d_dig, cnt, (uint64_t*)d_pre + (size_t)t * cnt * ct_words, nlimbs));
+    FHESI_TRY(rot_sum_run(c, ks, nk, logQ, o, (const u64*)d_pre, (i64)cnt * (i64)ct_words, cnt, nlimbs, o));
+  }
+  return 0;
+}
+// out[i] = the window sums of in[i] (include/fhesi_hip.h).  Form 1: rot_hoisted_sum_run over the horizontal amounts, then over the vertical ones.  Form 2:
+// rot_fold_run over the plan's amounts.  Both on y_0 = Reduce(in), as fhesi_ct_rot_fold_dev starts.
+extern "C" int fhesi_ct_pool2d_dev(fhesi_slots* s, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sy, int64_t sx, int32_t form, const fhesi_ksk* const* hoisted, int32_t nh,
+                                   int32_t logQ, int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
+  const char* who = "ct_pool2d";
+  if (!s) FHESI_FAIL("%s: null plaintext space", who);
+  fhesi_ctx* c = s->ctx;
+  CHECK_CTX(c);
+  char why[256];
+  const PoolShape sh{s->S.phim / s->S.rows, H, W, kh, kw, sy, sx};
+  if (pool_refused(sh, form, why, sizeof why)) FHESI_FAIL("%s: %s", who, why);
+  const PoolPlan pl = pool_plan(sh, form);
+  if (nh != pl.nh) FHESI_FAIL("%s: %d matrices, the pooling takes %d (%d horizontal, %d vertical, one per amount of its plan)", who, nh, pl.nh, pl.nhor, pl.nh - pl.nhor);
+  if (nh && !hoisted) FHESI_FAIL("%s: null argument", who);
+  std::vector<int64_t> ks((size_t)nh, 1);
+  for (int t = 0; t < nh; ++t) {
+    if (!hoisted[t]) FHESI_FAIL("%s: entry %d has no matrix and its amount is %lld (every amount of a pooling takes one)", who, t, (long long)pl.amounts[(size_t)t]);
+    ks[(size_t)t] = (int64_t)hm::powmod(s->S.g, (u64)pl.amounts[(size_t)t], (u64)c->m);
+  }
+  FHESI_TRY(rotations_args(c, hoisted, ks.data(), nh, logQ, decomp_bytes, nlimbs, count, nlimbs));
+  if (!count) return 0;
+  if (!in || !out) FHESI_FAIL("%s: null argument", who);
+  const size_t bytes = (size_t)count * 2 * c->phim * nlimbs * 8;
+  if (in != out && ranges_overlap(in, bytes, out, bytes)) FHESI_FAIL("%s: out overlaps in without being in", who);
+  std::vector<int> mode;      // every table before any digit row exists, as rotations_run builds its matrices'
+  FHESI_TRY(key_switch_forms(c, hoisted, nh, logQ, decomp_bytes, &mode));
+  for (int t = 1; t < nh; ++t) if (mode[(size_t)t] != mode[0]) FHESI_FAIL("%s: matrices of one call run different forms (internal)", who);
+  // y_0 = Reduce(in): the copy, times one
+  if (in != out) HIP_TRY(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
+  FHESI_TRY(launch_ct_mul_long(c, (u64*)out, count * 2 * c->phim, nlimbs, logQ, 1));
+  if (pl.form == 2) return rot_fold_run(c, hoisted, ks.data(), nh, mode.data(), logQ, decomp_bytes, (u64*)out, nlimbs, count);
+  FHESI_TRY(rot_hoisted_sum_run(c, hoisted, ks.data(), pl.nhor, nh ? mode[0] : -1, logQ, decomp_bytes, (u64*)out, nlimbs, count));
+  return rot_hoisted_sum_run(c, hoisted + pl.nhor, ks.data() + pl.nhor, nh - pl.nhor, nh ? mode[0] : -1, logQ, decomp_bytes, (u64*)out, nlimbs, count);
 }
 
 // One wave of Matrix<Ciphertext> arithmetic followed by the key switch (see include/fhesi_hip.h).

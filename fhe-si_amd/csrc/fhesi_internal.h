@@ -471,12 +471,19 @@ struct fhesi_conv2d {
   i64 key_switches = 0, terms = 0;
   std::vector<i64> amounts;            // flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; 0 exactly at the anchor
   fhesi_plain* w = nullptr;            // row (I Cin + J) kh kw + t: w_t (flat), w'_t (split) of the channel pair (I, J)
-  i64* d_bias = nullptr;               // [Cout][phim] slot values b[I] in [0, p) in every slot; null without a bias
+  i64* d_bias = nullptr;               // [Cout][phim] slot values b[I] in [0, p) in every slot of the output lattice, 0 off it; null without a bias
+  i64 sy = 1, sx = 1, ty = 1, tx = 1, ey = 1, ex = 1;      // the lattice (lattice_plan.h): input step, stride, dilation; all 1 from fhesi_conv2d_create
 };
 // d_out[(pair - first) kh kw + t][s] = the masked weight plaintext t of channel pair `pair` = I Cin + J at slot s, reduced into [0, p), for the pairs
 // first .. first + npairs - 1 of d_K [Cout Cin][kh kw] (conv_mask_kernel, kernels_slots.hip); split: every plaintext moved back by its giant amount
 int launch_conv_mask(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_K, int first, int npairs, int kh, int kw, int ah, int aw, i64 H, i64 W, bool split,
                      i64* d_out /* [npairs][kh kw][phim] */);
+// the same on a lattice of the plane (conv_lattice_mask_kernel; lattice_plan.h): (fy, fx) = dilation times input step, the physical pixels of one kernel
+// step; (oy, ox) the output step, whose lattice every plaintext is masked to.  All 1: the words of launch_conv_mask
+int launch_conv_lattice_mask(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_K, int first, int npairs, int kh, int kw, int ah, int aw, i64 H, i64 W, i64 fy, i64 fx,
+                             i64 oy, i64 ox, bool split, i64* d_out /* [npairs][kh kw][phim] */);
+// d_out [R][nch H W] = the columns of d_M [R][nch (H / sy) (W / sx)] spread onto the lattice of step (sy, sx), zero columns off it (lattice_columns_kernel)
+int launch_lattice_columns(fhesi_ctx* ctx, const i64* d_M, i64 R, i64 nch, i64 H, i64 W, i64 sy, i64 sx, i64* d_out);
 
 // --------------------------------------------------------------------------------- kernel launchers
 // kernels_ntt.hip : negacyclic NTT for power-of-two m.  rows: [count][nprimes_in_layout][n]; the prime of layout

@@ -673,7 +673,7 @@ int fhesi_ct_linear_grid_dev(fhesi_ctx* ctx, const fhesi_linear_grid* grid, cons
  *   The capacity rule of fhesi_ct_plain_sum_dev is checked with `terms` before anything is launched.  REFUSED with the condition named: nh other than
  *   the plan's; a matrix missing where the amount is not 0, present where it is 0, not hoisted, hoisted for another k or of another context; a layer of
  *   another context; out overlapping in; whatever the calls it is composed of refuse.
- * NOT HERE: stride and dilation; "valid" output; several channels inside one ciphertext; depthwise / grouped kernels; a form that keeps the weights as
+ * NOT HERE: stride and dilation (fhesi_conv2d_lattice_*, below); "valid" output; several channels inside one ciphertext; depthwise / grouped kernels; a form that keeps the weights as
  *   scalars against kh kw shared masks; pruning zero weights; a form of the C++ mirror; mixing the two rows of a two-row space. */
 typedef struct fhesi_conv2d fhesi_conv2d; /* a convolution layer on a slot space: its masked weight plaintexts, its biases and its plan */
 int fhesi_conv2d_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw,
@@ -691,6 +691,68 @@ int fhesi_conv2d_masks(fhesi_slots* s, const int64_t* K_host /* [Cout][Cin][kh][
 int fhesi_ct_conv2d_dev(fhesi_ctx* ctx, const fhesi_conv2d* conv, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
                         const uint64_t* in_dev /* [Cin][count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count,
                         uint64_t* out_dev /* [Cout][count][2][phi(m)][nlimbs] */);
+
+/* ---- strided and dilated convolutions and sum pooling: the plane carries a lattice step and is never compacted (capi_ct.hip, capi_pipeline.hip,
+ * lattice_plan.h, conv_lattice_mask_kernel and lattice_columns_kernel in kernels_slots.hip; tests/lattice_model.py is the normative statement).
+ *   lattice    input step (sy, sx), sy | H, sx | W: logical pixel (a, b) of the Hl x Wl = H/sy x W/sx logical plane at physical pixel (a sy, b sx); slots
+ *              off the lattice are don't care on input.  A strided convolution and a pooling multiply the step; the next layer takes it as its input step
+ *   geometry   six integers sy, sx, ty, tx, ey, ex: step, stride (ty | Hl, tx | Wl), dilation (at least 1); the output step is (sy ty, sx tx)
+ *   definition out[I](a', b') = b[I] + sum_J sum_dy sum_dx K[I][J][dy][dx] in[J](a' ty + (dy - ah) ey, b' tx + (dx - aw) ex),  logical pixels outside
+ *              Hl x Wl = 0;  EVERY output slot off the output lattice is exactly 0, bias included
+ *   offsets    t = dy kw + dx in physical pixels u = (dy - ah) ey sy, v = (dx - aw) ex sx, amount a_t = (u W + v) mod cols,
+ *              mu_t[i] = [sy ty | y and sx tx | x and 0 <= y + u < H and 0 <= x + v < W];  flat and split as above, the split form's plaintexts moved
+ *              back by (u W) mod cols, lattice factor included.  Key switches and the planner's rule do not change.
+ * fhesi_conv2d_lattice_plan (host only): fhesi_conv2d_plan's outputs and the output step.  REFUSED with the condition named, in this order: cols; a size
+ *   below 1; P not dividing cols; a factor of the geometry below 1; a step not dividing the plane; a stride not dividing the logical plane; the anchor; an
+ *   offset whose mask is empty after step and dilation (|u| >= H or |v| >= W), naming it in physical pixels; the plaintexts of one handle; the form.  With
+ *   step, stride and dilation all (1, 1): the refusals, the plan and every word of the plaintexts of fhesi_conv2d_*.
+ * fhesi_conv2d_lattice_create / _create_dev / _masks: as fhesi_conv2d_create / _create_dev / _masks; the bias rows are b[I] on the output lattice and 0 off
+ *   it.  The handle is a fhesi_conv2d that also records its geometry (fhesi_conv2d_lattice_info: the six integers and the output step; all 1 for a handle of
+ *   fhesi_conv2d_create); fhesi_conv2d_info, fhesi_conv2d_free and the run call fhesi_ct_conv2d_dev take it as it is.
+ * fhesi_pool2d_plan (host only), fhesi_ct_pool2d_dev: SUM pooling over non-overlapping windows of kh x kw logical pixels on a plane of step (sy, sx).  The
+ *   windows must tile the plane (kh sy | H, kw sx | W); they then never cross a plane border, so there is no mask and NO plaintext product:
+ *     out = sum_{dy < kh} rot_{(dy sy W) mod cols}( sum_{dx < kw} rot_{(dx sx) mod cols}(in) ),
+ *   the window's sum at its top left pixel, output step (sy kh, sx kw); slots off the output lattice hold the cyclic sums this formula gives.  It is a
+ *   sum: the caller folds 1 / (kh kw) into the next layer's weights.  Global pooling is kh = Hl, kw = Wl.  Channels and items are one `count`.
+ *   form 1     per direction the k - 1 rotations hoisted from ONE digit set, summed with the running value as base in one rotated sum: (kw - 1) + (kh - 1)
+ *              key switches over two key-switch levels.  amounts: dx sx for dx = 1 .. kw - 1, then dy sy W for dy = 1 .. kh - 1
+ *   form 2     kw and kh powers of two: doubling folds y <- y + rot(y) by sx 2^j, then by sy W 2^j: log2 kw + log2 kh key switches and as many levels
+ *   form 0     the form of fewer key switches, form 1 on a tie (fewer levels)
+ *   hoisted [nh]: entry t the hoisted matrix of g^amounts[t] mod m, horizontal amounts first (nhor of them), none NULL.  out_dev may be in_dev.
+ *   DEFINED as, and word for word equal to -- form 1: y = Reduce(in); per direction fhesi_ct_rotations_dev of y over the direction's amounts and
+ *   fhesi_ct_add_dev of every term onto y, horizontal then vertical (sums are exact modulo 2^logQ with the centred store, so the order of terms is free);
+ *   form 2: fhesi_ct_rot_fold_dev over the amounts.  REFUSED with the condition named before any launch: a size below 1; P not dividing cols; a step not
+ *   dividing the plane; windows that do not tile the logical plane; a form outside 0 .. 2, form 2 on a window that is no power of two; nh other than the
+ *   plan's; a matrix missing, not hoisted, hoisted for another k or of another context; out overlapping in without being in.
+ *   Overlapping or padded pooling is no tiling: it stays a convolution with a constant kernel, run with Cin = Cout = 1 over `count`.
+ * fhesi_slots_lattice_columns / _dev: the bridge to a dense layer.  M [R][nch Hl Wl] over logical pixels (host / HBM) -> M' [R][nch H W] over the slots of
+ *   nch planes, column c P + (a sy) W + b sx = column c Hl Wl + a Wl + b, zero columns off the lattice, the words as they are;
+ *   fhesi_linear_grid_create[_dev] with Cb = H W takes M' as it is.  out must not overlap M.
+ * NOT HERE: compaction of a stepped plane; several channels inside one ciphertext; depthwise / grouped kernels; "valid" output; max pooling; a form of the
+ *   C++ mirror. */
+int fhesi_conv2d_lattice_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw, int64_t sy, int64_t sx,
+                              int64_t ty, int64_t tx, int64_t ey, int64_t ex, int32_t form /* 0 planner, 1 flat, 2 split */, int32_t* form_out, int32_t* nh,
+                              int64_t* key_switches, int64_t* terms, int64_t* out_sy, int64_t* out_sx, int64_t* amounts /* [nh] or NULL */);
+int fhesi_conv2d_lattice_create(fhesi_slots* s, const int64_t* K_host /* [Cout][Cin][kh][kw] */, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W,
+                                int64_t ah, int64_t aw, int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex,
+                                const int64_t* bias_host /* [Cout] or NULL */, int32_t form, fhesi_conv2d** out);
+int fhesi_conv2d_lattice_create_dev(fhesi_slots* s, const int64_t* K_dev /* [Cout][Cin][kh][kw] */, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W,
+                                    int64_t ah, int64_t aw, int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex,
+                                    const int64_t* bias_dev /* [Cout] or NULL */, int32_t form, fhesi_conv2d** out);
+int fhesi_conv2d_lattice_masks(fhesi_slots* s, const int64_t* K_host /* [Cout][Cin][kh][kw] */, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W,
+                               int64_t ah, int64_t aw, int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, int32_t form,
+                               int64_t* vals_host /* [Cout][Cin][kh kw][phi(m)] */);
+int fhesi_conv2d_lattice_info(const fhesi_conv2d* conv, int64_t* sy, int64_t* sx, int64_t* ty, int64_t* tx, int64_t* ey, int64_t* ex, int64_t* out_sy, int64_t* out_sx);
+int fhesi_pool2d_plan(int64_t cols, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sy, int64_t sx, int32_t form /* 0 planner, 1 hoisted sums, 2 doubling */,
+                      int32_t* form_out, int32_t* nh, int32_t* nhor, int64_t* key_switches, int32_t* levels, int64_t* out_sy, int64_t* out_sx,
+                      int64_t* amounts /* [nh] or NULL */);
+int fhesi_ct_pool2d_dev(fhesi_slots* s, int64_t H, int64_t W, int64_t kh, int64_t kw, int64_t sy, int64_t sx, int32_t form, const fhesi_ksk* const* hoisted, int32_t nh,
+                        int32_t logQ, int32_t decomp_bytes, const uint64_t* in_dev /* [count][2][phi(m)][nlimbs] */, int32_t nlimbs, int64_t count,
+                        uint64_t* out_dev /* [count][2][phi(m)][nlimbs]; may be in_dev */);
+int fhesi_slots_lattice_columns(fhesi_slots* s, const int64_t* M_host /* [R][nch (H/sy) (W/sx)] */, int64_t R, int64_t nch, int64_t H, int64_t W, int64_t sy, int64_t sx,
+                                int64_t* out_host /* [R][nch H W] */);
+int fhesi_slots_lattice_columns_dev(fhesi_slots* s, const int64_t* M_dev /* [R][nch (H/sy) (W/sx)] */, int64_t R, int64_t nch, int64_t H, int64_t W, int64_t sy, int64_t sx,
+                                    int64_t* out_dev /* [R][nch H W] */);
 
 /* ---- polynomial activations on packed slots: y = f(x) = sum_{k <= d} c_k x^k slot by slot, the non-linear step between two linear layers (DESIGN.md 9a;
  * tests/poly_model.py is the normative statement of the plan and of the schedule).
