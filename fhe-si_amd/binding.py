@@ -795,30 +795,32 @@ class Plain:
             pass
 
 
-class Linear:
-    """One R x C layer y = M x + b on a slot space (fhesi_linear): its T = min(R, C) prepared diagonals, its replicated bias and its plan, resident in
-    HBM; made by SlotSpace.linear.  .amounts lists the rotation amounts whose hoisted matrices apply() takes: babies, giants, folds."""
+def _hoisted_by_amount(hoisted_by_amount, amounts, anchored: bool = False):
+    """a mapping amount -> hoisted matrix covering `amounts` (anchored: the non-zero ones, None at 0), or the list of matrices in their order ->
+    (the pointer array of a run call, its length)"""
+    if hasattr(hoisted_by_amount, "keys"):
+        hs = [hoisted_by_amount[a] if a or not anchored else None for a in amounts]
+    else:
+        hs = list(hoisted_by_amount)
+    return (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs]), len(hs)
+
+
+class _Layer:
+    """What Linear, LinearGrid and Conv2d share: the handle on its space, the run call (_apply) through _run, close through _free (names of the C symbols) and
+    _anchored -- whether .amounts holds a 0, which takes no matrix."""
+    _run = _free = None
+    _anchored = False
 
     def __init__(self, space: "SlotSpace", h):
         self.space, self.ctx, self.h = space, space.ctx, h
-        R, Cc, T, B, G, nfold, bias = _i64(0), _i64(0), _i32(0), _i32(0), _i32(0), _i32(0), _i32(0)
-        _ck(_load().fhesi_linear_info(self.h, _byref(R), _byref(Cc), _byref(T), _byref(B), _byref(G), _byref(nfold), _byref(bias), None))
-        self.R, self.C, self.T, self.B, self.G, self.nfold, self.has_bias = R.value, Cc.value, T.value, B.value, G.value, nfold.value, bool(bias.value)
-        a = np.zeros(self.B - 1 + self.G - 1 + self.nfold, dtype=np.int64)
-        _ck(_load().fhesi_linear_info(self.h, None, None, None, None, None, None, None, _p(a) if len(a) else None))
-        self.amounts = [int(x) for x in a]
 
-    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
-        """out[i] = the layer of src[i] (fhesi_ct_linear_dev): src holds x replicated with period C in every row (SlotSpace.replicate), out holds
-        M x + b with period R.  hoisted_by_amount: a mapping amount -> hoisted matrix of SlotSpace.rotation_k(amount) covering .amounts, or the
-        list of matrices in the order of .amounts.  The words of SlotSpace.matvec_bsgs, SlotSpace.fold and SlotSpace.ct_add_slots_dev in that order."""
-        hs = [hoisted_by_amount[a] for a in self.amounts] if hasattr(hoisted_by_amount, "keys") else list(hoisted_by_amount)
-        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
-        _ck(_load().fhesi_ct_linear_dev(self.ctx.h, self.h, arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+    def _apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int):
+        arr, nh = _hoisted_by_amount(hoisted_by_amount, self.amounts, self._anchored)
+        _ck(getattr(_load(), self._run)(self.ctx.h, self.h, arr, nh, logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
 
     def close(self):
         if getattr(self, "h", None):
-            _load().fhesi_linear_free(self.h)
+            getattr(_load(), self._free)(self.h)
             self.h = None
 
     def __del__(self):
@@ -828,13 +830,41 @@ class Linear:
             pass
 
 
-class LinearGrid:
+class Linear(_Layer):
+    """One R x C layer y = M x + b on a slot space (fhesi_linear): its T = min(R, C) prepared diagonals, its replicated bias and its plan, resident in
+    HBM; made by SlotSpace.linear.  .amounts lists the rotation amounts whose hoisted matrices apply() takes: babies, giants, folds."""
+    _run, _free = "fhesi_ct_linear_dev", "fhesi_linear_free"
+
+    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[i] = the layer of src[i] (fhesi_ct_linear_dev): src holds x replicated with period C in every row (SlotSpace.replicate), out holds
+        M x + b with period R.  hoisted_by_amount: a mapping amount -> hoisted matrix of SlotSpace.rotation_k(amount) covering .amounts, or the
+        list of matrices in the order of .amounts.  The words of SlotSpace.matvec_bsgs, SlotSpace.fold and SlotSpace.ct_add_slots_dev in that order."""
+        self._apply(hoisted_by_amount, logQ, src, nlimbs, count, out, decomp_bytes)
+
+    def __init__(self, space: "SlotSpace", h):
+        super().__init__(space, h)
+        R, Cc, T, B, G, nfold, bias = _i64(0), _i64(0), _i32(0), _i32(0), _i32(0), _i32(0), _i32(0)
+        _ck(_load().fhesi_linear_info(self.h, _byref(R), _byref(Cc), _byref(T), _byref(B), _byref(G), _byref(nfold), _byref(bias), None))
+        self.R, self.C, self.T, self.B, self.G, self.nfold, self.has_bias = R.value, Cc.value, T.value, B.value, G.value, nfold.value, bool(bias.value)
+        a = np.zeros(self.B - 1 + self.G - 1 + self.nfold, dtype=np.int64)
+        _ck(_load().fhesi_linear_info(self.h, None, None, None, None, None, None, None, _p(a) if len(a) else None))
+        self.amounts = [int(x) for x in a]
+
+
+class LinearGrid(_Layer):
     """An R x C matrix larger than a row of slots as a grid of nI x nJ blocks of Rb x Cb (fhesi_linear_grid): the prepared diagonals of every block,
     the replicated biases and the plan, resident in HBM; made by SlotSpace.linear_grid.  .amounts lists the rotation amounts whose hoisted matrices
     apply() takes -- babies, giants, the block's folds; .key_switches is what apply() runs per item."""
+    _run, _free = "fhesi_ct_linear_grid_dev", "fhesi_linear_grid_free"
+
+    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[I][i] = block row I of the product for item i (fhesi_ct_linear_grid_dev): src [nJ][count] holds SlotSpace.replicate_blocks(x, Cb)
+        encrypted, out [nI][count] holds (M x + b)[I Rb ..] with period Rb.  hoisted_by_amount as Linear.apply takes it.  The babies of an input
+        block serve every output block; the giants and folds of an output block run once, behind the sum over the input blocks."""
+        self._apply(hoisted_by_amount, logQ, src, nlimbs, count, out, decomp_bytes)
 
     def __init__(self, space: "SlotSpace", h):
-        self.space, self.ctx, self.h = space, space.ctx, h
+        super().__init__(space, h)
         R, Cc, Rb, Cb = _i64(0), _i64(0), _i64(0), _i64(0)
         nI, nJ, T, B, G, nfold, bias = (_i32(0) for _ in range(7))
         _ck(_load().fhesi_linear_grid_info(self.h, _byref(R), _byref(Cc), _byref(Rb), _byref(Cb), _byref(nI), _byref(nJ), _byref(T), _byref(B), _byref(G),
@@ -846,35 +876,23 @@ class LinearGrid:
         self.amounts = [int(x) for x in a]
         self.key_switches = self.nJ * (self.B - 1) + self.nI * (self.G - 1) + self.nI * self.nfold
 
-    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
-        """out[I][i] = block row I of the product for item i (fhesi_ct_linear_grid_dev): src [nJ][count] holds SlotSpace.replicate_blocks(x, Cb)
-        encrypted, out [nI][count] holds (M x + b)[I Rb ..] with period Rb.  hoisted_by_amount as Linear.apply takes it.  The babies of an input
-        block serve every output block; the giants and folds of an output block run once, behind the sum over the input blocks."""
-        hs = [hoisted_by_amount[a] for a in self.amounts] if hasattr(hoisted_by_amount, "keys") else list(hoisted_by_amount)
-        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
-        _ck(_load().fhesi_ct_linear_grid_dev(self.ctx.h, self.h, arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
 
-    def close(self):
-        if getattr(self, "h", None):
-            _load().fhesi_linear_grid_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Conv2d:
+class Conv2d(_Layer):
     """A 2-D convolution K [Cout][Cin][kh][kw] over H x W planes on a slot space, one channel per ciphertext (fhesi_conv2d): its masked weight
     plaintexts, its biases and its plan, resident in HBM; made by SlotSpace.conv2d.  .amounts lists the rotation amounts whose hoisted matrices apply()
     takes -- flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; 0 (no matrix) exactly at the anchor; .key_switches is what apply()
     runs per item.  .step, .stride, .dilation: the lattice it was made for (all (1, 1) without one); .out_step = step * stride is the step of its output
     planes, which the next layer takes as its own."""
+    _run, _free, _anchored = "fhesi_ct_conv2d_dev", "fhesi_conv2d_free", True
+
+    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
+        """out[I][i] = output channel I of item i (fhesi_ct_conv2d_dev): src [Cin][count] holds the input channels (SlotSpace.pack_images encrypted),
+        out [Cout][count] the convolution with zero padding plus b[I].  hoisted_by_amount: a mapping amount -> hoisted matrix of
+        SlotSpace.rotation_k(amount) covering the non-zero .amounts, or the list of matrices in the order of .amounts with None at the anchor."""
+        self._apply(hoisted_by_amount, logQ, src, nlimbs, count, out, decomp_bytes)
 
     def __init__(self, space: "SlotSpace", h):
-        self.space, self.ctx, self.h = space, space.ctx, h
+        super().__init__(space, h)
         v = [_i64(0) for _ in range(8)]
         form, nh, ks, terms, bias = _i32(0), _i32(0), _i64(0), _i64(0), _i32(0)
         _ck(_load().fhesi_conv2d_info(self.h, *(_byref(x) for x in v), _byref(form), _byref(nh), _byref(ks), _byref(terms), _byref(bias), None))
@@ -888,28 +906,6 @@ class Conv2d:
         _ck(_load().fhesi_conv2d_lattice_info(self.h, *(_byref(x) for x in g)))
         g = [x.value for x in g]
         self.step, self.stride, self.dilation, self.out_step = (g[0], g[1]), (g[2], g[3]), (g[4], g[5]), (g[6], g[7])
-
-    def apply(self, hoisted_by_amount, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, decomp_bytes: int = 3):
-        """out[I][i] = output channel I of item i (fhesi_ct_conv2d_dev): src [Cin][count] holds the input channels (SlotSpace.pack_images encrypted),
-        out [Cout][count] the convolution with zero padding plus b[I].  hoisted_by_amount: a mapping amount -> hoisted matrix of
-        SlotSpace.rotation_k(amount) covering the non-zero .amounts, or the list of matrices in the order of .amounts with None at the anchor."""
-        if hasattr(hoisted_by_amount, "keys"):
-            hs = [hoisted_by_amount[a] if a else None for a in self.amounts]
-        else:
-            hs = list(hoisted_by_amount)
-        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
-        _ck(_load().fhesi_ct_conv2d_dev(self.ctx.h, self.h, arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
-
-    def close(self):
-        if getattr(self, "h", None):
-            _load().fhesi_conv2d_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def slots_plan(m: int, p: int, generator: int) -> dict:
@@ -1111,31 +1107,38 @@ class SlotSpace:
             raise ValueError(f"linear: device=True takes {what} as a contiguous int64 tensor in HBM")
         return _vp(a.data_ptr()), tuple(a.shape)
 
+    def _tensor_args(self, who: str, T, bias, device: bool, name: str, dims, per: str):
+        """a layer's tensor `name` with the dimensions named in `dims`, on the host or (device) in HBM, and its bias, one word per `per`, or None ->
+        (pointer, bias pointer or None, shape, what the pointers keep alive)"""
+        if device:
+            tp, shape = self._device_words(T, f"the {name}")
+        else:
+            T = np.ascontiguousarray(T, dtype=np.int64)
+            tp, shape = _p(T), T.shape
+        if len(shape) != len(dims):
+            raise ValueError(f"{who}: the {name} is " + "".join(f"[{d}]" for d in dims))
+        bp = None
+        if bias is not None:
+            if device:
+                bp, bshape = self._device_words(bias, "the bias")
+            else:
+                bias = np.ascontiguousarray(bias, dtype=np.int64)
+                bp, bshape = _p(bias), bias.shape
+            if bshape != (shape[0],):
+                raise ValueError(f"{who}: a bias of shape {bshape} for {shape[0]} {per}")
+        return tp, bp, shape, (T, bias)
+
+    def _linear(self, who: str, create, layer, M, bias, block, baby: int, device: bool):
+        """SlotSpace.linear (block None) and SlotSpace.linear_grid through `create`, the C constructor the method names"""
+        tp, bp, (R, Cc), keep = self._tensor_args(who, M, bias, device, "matrix", ("R", "C"), "rows")
+        h = _vp()
+        _ck(create(self.h, tp, R, Cc, *(block(R, Cc) if block else ()), bp, int(baby), _byref(h)))
+        return layer(self, h)
+
     def linear(self, M, bias=None, baby: int = 0, device: bool = False) -> Linear:
         """The layer y = M x + b for M [R][C], bias [R] or None, any int64 (reduced modulo p on the device).  device=True: M and bias are int64 tensors
         in HBM (torch tensors), read where they are.  baby: the baby step, 0 for the planner's.  Admitted shapes: linear_plan."""
-        h = _vp()
-        if device:
-            mp, shape = self._device_words(M, "the matrix")
-            if len(shape) != 2:
-                raise ValueError("linear: the matrix is [R][C]")
-            bp = None
-            if bias is not None:
-                bp, bshape = self._device_words(bias, "the bias")
-                if bshape != (shape[0],):
-                    raise ValueError(f"linear: a bias of shape {bshape} for {shape[0]} rows")
-            _ck(_load().fhesi_linear_create_dev(self.h, mp, shape[0], shape[1], bp, int(baby), _byref(h)))
-            return Linear(self, h)
-        M = np.ascontiguousarray(M, dtype=np.int64)
-        if M.ndim != 2:
-            raise ValueError("linear: the matrix is [R][C]")
-        b = None
-        if bias is not None:
-            b = np.ascontiguousarray(bias, dtype=np.int64)
-            if b.shape != (M.shape[0],):
-                raise ValueError(f"linear: a bias of shape {b.shape} for {M.shape[0]} rows")
-        _ck(_load().fhesi_linear_create(self.h, _p(M), M.shape[0], M.shape[1], _p(b) if b is not None else None, int(baby), _byref(h)))
-        return Linear(self, h)
+        return self._linear("linear", _load().fhesi_linear_create_dev if device else _load().fhesi_linear_create, Linear, M, bias, None, baby, device)
 
     def linear_diagonals(self, M, baby: int = 0) -> np.ndarray:
         """The prepared slot vectors of the layer M [R][C]: [T][total], row g B + j the diagonal g B + j rotated back by g B (fhesi_linear_diagonals) --
@@ -1156,30 +1159,8 @@ class SlotSpace:
     def linear_grid(self, M, bias=None, block=None, baby: int = 0, device: bool = False) -> LinearGrid:
         """The product y = M x + b for M [R][C] as a grid of blocks [Rb][Cb] = block (default (min(R, cols), min(C, cols))): R a multiple of Rb, C of
         Cb -- pad with zeros --, the block a shape linear_plan admits.  M, bias, device and baby as SlotSpace.linear takes them."""
-        h = _vp()
-        if device:
-            mp, shape = self._device_words(M, "the matrix")
-            if len(shape) != 2:
-                raise ValueError("linear_grid: the matrix is [R][C]")
-            bp = None
-            if bias is not None:
-                bp, bshape = self._device_words(bias, "the bias")
-                if bshape != (shape[0],):
-                    raise ValueError(f"linear_grid: a bias of shape {bshape} for {shape[0]} rows")
-            Rb, Cb = self._grid_block(shape[0], shape[1], block)
-            _ck(_load().fhesi_linear_grid_create_dev(self.h, mp, shape[0], shape[1], Rb, Cb, bp, int(baby), _byref(h)))
-            return LinearGrid(self, h)
-        M = np.ascontiguousarray(M, dtype=np.int64)
-        if M.ndim != 2:
-            raise ValueError("linear_grid: the matrix is [R][C]")
-        b = None
-        if bias is not None:
-            b = np.ascontiguousarray(bias, dtype=np.int64)
-            if b.shape != (M.shape[0],):
-                raise ValueError(f"linear_grid: a bias of shape {b.shape} for {M.shape[0]} rows")
-        Rb, Cb = self._grid_block(M.shape[0], M.shape[1], block)
-        _ck(_load().fhesi_linear_grid_create(self.h, _p(M), M.shape[0], M.shape[1], Rb, Cb, _p(b) if b is not None else None, int(baby), _byref(h)))
-        return LinearGrid(self, h)
+        create = _load().fhesi_linear_grid_create_dev if device else _load().fhesi_linear_grid_create
+        return self._linear("linear_grid", create, LinearGrid, M, bias, lambda R, Cc: self._grid_block(R, Cc, block), baby, device)
 
     def linear_grid_diagonals(self, M, block=None, baby: int = 0) -> np.ndarray:
         """The prepared slot vectors of the grid: [nI][nJ][T][total], entry (I, J) what linear_diagonals gives for the block M[I Rb .., J Cb ..] with
@@ -1203,66 +1184,49 @@ class SlotSpace:
         dividing the row; zero padding, anchor (default ((kh - 1) // 2, (kw - 1) // 2)) the kernel entry that meets the output pixel.
         form: 0 the planner's, 1 flat, 2 split (conv2d_plan).  device=True: K and bias are int64 tensors in HBM (torch tensors), read where they are.
         step, stride, dilation: the lattice (conv2d_lattice_plan) -- the input's live pixels on every step-th row and column, the output's on every
-        (step * stride)-th, every other output slot 0; all (1, 1), the default, takes the stride-1 path (fhesi_conv2d_create)."""
+        (step * stride)-th, every other output slot 0; all (1, 1), the default, goes through fhesi_conv2d_create."""
         if image is None:
             raise ValueError("conv2d: image = (H, W)")
         H, W = int(image[0]), int(image[1])
-        h = _vp()
-        if device:
-            kp, shape = self._device_words(K, "the kernel")
-            bp = None
-            if bias is not None:
-                bp, bshape = self._device_words(bias, "the bias")
-                if len(shape) == 4 and bshape != (shape[0],):
-                    raise ValueError(f"conv2d: a bias of shape {bshape} for {shape[0]} output channels")
-            fn = "fhesi_conv2d_create_dev"
-        else:
-            K = np.ascontiguousarray(K, dtype=np.int64)
-            shape, kp, bp = K.shape, _p(K), None
-            if bias is not None:
-                b = np.ascontiguousarray(bias, dtype=np.int64)
-                if K.ndim == 4 and b.shape != (shape[0],):
-                    raise ValueError(f"conv2d: a bias of shape {b.shape} for {shape[0]} output channels")
-                bp = _p(b)
-            fn = "fhesi_conv2d_create"
-        if len(shape) != 4:
-            raise ValueError("conv2d: the kernel is [Cout][Cin][kh][kw]")
+        kp, bp, shape, keep = self._tensor_args("conv2d", K, bias, device, "kernel", ("Cout", "Cin", "kh", "kw"), "output channels")
         ah, aw = self._conv_anchor(shape[2], shape[3], anchor)
         geom = _geometry(step, stride, dilation)
+        h = _vp()
         if geom == (1,) * 6:
-            _ck(getattr(_load(), fn)(self.h, kp, shape[0], shape[1], shape[2], shape[3], H, W, ah, aw, bp, int(form), _byref(h)))
+            create = _load().fhesi_conv2d_create_dev if device else _load().fhesi_conv2d_create
+            _ck(create(self.h, kp, *shape, H, W, ah, aw, bp, int(form), _byref(h)))
         else:
-            _ck(getattr(_load(), fn.replace("conv2d_", "conv2d_lattice_"))(self.h, kp, shape[0], shape[1], shape[2], shape[3], H, W, ah, aw, *geom, bp, int(form), _byref(h)))
+            create = _load().fhesi_conv2d_lattice_create_dev if device else _load().fhesi_conv2d_lattice_create
+            _ck(create(self.h, kp, *shape, H, W, ah, aw, *geom, bp, int(form), _byref(h)))
         return Conv2d(self, h)
+
+    def _conv_masks(self, who: str, K, image, anchor, form: int, geom, lattice: bool):
+        """conv2d_masks (a unit geometry: the entries without one) and conv2d_lattice_masks"""
+        K = np.ascontiguousarray(K, dtype=np.int64)
+        if K.ndim != 4:
+            raise ValueError(f"{who}: the kernel is [Cout][Cin][kh][kw]")
+        Cout, Cin, kh, kw = K.shape
+        ah, aw = self._conv_anchor(kh, kw, anchor)
+        lattice = lattice or _geometry(*geom) != (1,) * 6
+        plan = conv2d_lattice_plan if lattice else conv2d_plan      # the shape, before the output is sized
+        plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, *(geom if lattice else ()), form)
+        vals = np.zeros((Cout, Cin, kh * kw, self.total), dtype=np.int64)
+        args = (self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw)
+        if lattice:
+            _ck(_load().fhesi_conv2d_lattice_masks(*args, *_geometry(*geom), int(form), _p(vals)))
+        else:
+            _ck(_load().fhesi_conv2d_masks(*args, int(form), _p(vals)))
+        return vals
 
     def conv2d_masks(self, K, image, anchor=None, form: int = 0, step=(1, 1), stride=(1, 1), dilation=(1, 1)) -> np.ndarray:
         """The masked weight plaintexts of the convolution as slot values: [Cout][Cin][kh kw][total], entry t = dy kw + dx the weight under its mask,
         moved back by its giant amount in the split form (fhesi_conv2d_masks; with a step, stride or dilation other than (1, 1)
         fhesi_conv2d_lattice_masks) -- what SlotSpace.conv2d embeds, downloaded."""
-        K = np.ascontiguousarray(K, dtype=np.int64)
-        if K.ndim != 4:
-            raise ValueError("conv2d_masks: the kernel is [Cout][Cin][kh][kw]")
-        Cout, Cin, kh, kw = K.shape
-        ah, aw = self._conv_anchor(kh, kw, anchor)
-        geom = _geometry(step, stride, dilation)
-        if geom == (1,) * 6:
-            conv2d_plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, form)      # the shape, before the output is sized
-            vals = np.zeros((Cout, Cin, kh * kw, self.total), dtype=np.int64)
-            _ck(_load().fhesi_conv2d_masks(self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw, int(form), _p(vals)))
-            return vals
-        return self.conv2d_lattice_masks(K, image, anchor, form, step, stride, dilation)
+        return self._conv_masks("conv2d_masks", K, image, anchor, form, (step, stride, dilation), False)
 
     def conv2d_lattice_masks(self, K, image, anchor=None, form: int = 0, step=(1, 1), stride=(1, 1), dilation=(1, 1)) -> np.ndarray:
-        """conv2d_masks through fhesi_conv2d_lattice_masks whatever the geometry: with all (1, 1) the words of conv2d_masks, from the lattice kernel."""
-        K = np.ascontiguousarray(K, dtype=np.int64)
-        if K.ndim != 4:
-            raise ValueError("conv2d_lattice_masks: the kernel is [Cout][Cin][kh][kw]")
-        Cout, Cin, kh, kw = K.shape
-        ah, aw = self._conv_anchor(kh, kw, anchor)
-        conv2d_lattice_plan(self.total // max(self.rows, 1), image[0], image[1], Cin, Cout, kh, kw, ah, aw, step, stride, dilation, form)
-        vals = np.zeros((Cout, Cin, kh * kw, self.total), dtype=np.int64)
-        _ck(_load().fhesi_conv2d_lattice_masks(self.h, _p(K), Cout, Cin, kh, kw, int(image[0]), int(image[1]), ah, aw, *_geometry(step, stride, dilation), int(form), _p(vals)))
-        return vals
+        """conv2d_masks through fhesi_conv2d_lattice_masks whatever the geometry: with all (1, 1) the words of conv2d_masks, through the other entry."""
+        return self._conv_masks("conv2d_lattice_masks", K, image, anchor, form, (step, stride, dilation), True)
 
     # ---- sum pooling and the bridge to a dense layer on a lattice of the plane (fhesi_ct_pool2d_dev, fhesi_slots_lattice_columns)
     def pool2d(self, hoisted_by_amount, image, window, step, logQ: int, src: DevBuf, nlimbs: int, count: int, out: DevBuf, form: int = 0, decomp_bytes: int = 3) -> dict:
@@ -1272,9 +1236,8 @@ class SlotSpace:
         the list of matrices in their order.  out may be src.  Returns the plan; its "out_step" is the step of the result."""
         H, W, kh, kw, sy, sx = (int(v) for v in (image[0], image[1], window[0], window[1], step[0], step[1]))
         pl = pool2d_plan(self.total // max(self.rows, 1), H, W, kh, kw, sy, sx, form)
-        hs = [hoisted_by_amount[a] for a in pl["amounts"]] if hasattr(hoisted_by_amount, "keys") else list(hoisted_by_amount)
-        arr = (_vp * max(len(hs), 1))(*[h.h if h is not None else None for h in hs])
-        _ck(_load().fhesi_ct_pool2d_dev(self.h, H, W, kh, kw, sy, sx, int(form), arr, len(hs), logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
+        arr, nh = _hoisted_by_amount(hoisted_by_amount, pl["amounts"])
+        _ck(_load().fhesi_ct_pool2d_dev(self.h, H, W, kh, kw, sy, sx, int(form), arr, nh, logQ, decomp_bytes, src.ptr, nlimbs, count, out.ptr))
         return pl
 
     def lattice_columns(self, M, nch: int, image, step, device: bool = False, out=None):

@@ -3,7 +3,6 @@
 #include "wave_plan.h"
 #include "poly_plan.h"
 #include "conv_plan.h"
-#include "lattice_plan.h"
 
 // ---- coefficient-domain ciphertext algebra on device batches (kernels_ct.hip)
 extern "C" int fhesi_ct_add_dev(fhesi_ctx* c, int32_t logQ, uint64_t* dst, const uint64_t* src, int32_t nparts, int32_t nlimbs, int64_t count) {
@@ -615,16 +614,11 @@ extern "C" int fhesi_ct_add_slots_dev(fhesi_ctx* c, fhesi_slots* s, int32_t logQ
   return 0;
 }
 
-// --------------------------------------------------------------------------------------------- dense linear layers
-// fhesi_linear (include/fhesi_hip.h).  The stage next to stage_msg_slots: the T prepared slot vectors w_t of an R x C layer [T][phi(m)] in the values
-// slot (workspace 9), written by linear_diag_kernel from the matrix where it is -- a host matrix is uploaded into the same slot, behind them.  Checks
-// its own arguments and plans the layer; nothing here synchronises.
-// A layer is the grid of one block (Rb = R, Cb = C): everything below is written for the grid.  The blocks are staged in chunks of whole blocks, so the
-// values slot holds a chunk and never the grid.
-//
-// What the stages of a dense grid and of a convolution share.  A layer is `nunits` units (blocks, channel pairs) of unit_vals slot values each, written by a
-// kernel from a tensor where it lies: chunks of whole units in the values slot (workspace 9) -- at most cap_bytes of them, a single unit may take more --,
-// a host tensor of src_words uploaded into the same slot, behind them.  The workspace holds a chunk and never the layer; nothing here synchronises.
+// --------------------------------------------------------------------------------------------- layers on packed slots: the stage and the constructor
+// fhesi_linear, fhesi_linear_grid, fhesi_conv2d (include/fhesi_hip.h; GridLayer, fhesi_internal.h).  The stage next to stage_msg_slots.  A layer is nI nJ
+// units (blocks, channel pairs) of nk slot vectors each, written by a kernel from a tensor where it lies: chunks of whole units in the values slot
+// (workspace 9) -- at most cap_bytes of them, a single unit may take more --, a host tensor of src_words uploaded into the same slot, behind them.  The
+// workspace holds a chunk and never the layer; opening the stage synchronises nothing.
 struct ValueStage {
   i64 per = 0;                 // units per chunk
   i64* d_vals = nullptr;       // [per][unit_vals] in workspace slot 9, a host tensor behind them
@@ -668,356 +662,243 @@ template <class F> static int value_stage_download(fhesi_ctx* c, i64 nunits, siz
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
-struct LinearPlan { int32_t nI = 0, nJ = 0, T = 0, B = 0, G = 0, nfold = 0; std::vector<int64_t> amounts; };
-struct LinearStage {
-  LinearPlan plan;
-  i64 per = 0;                 // blocks per chunk
-  i64* d_vals = nullptr;       // [per][T][phi(m)] in workspace slot 9, a host matrix behind them
-  const i64* d_M = nullptr;    // the matrix in HBM
-  i64 ld = 0;
-};
-constexpr size_t kLinearChunkBytes = (size_t)256 << 20;      // slot values of one chunk of blocks (a single block may take more)
-static int linear_stage_open(fhesi_slots* s, const int64_t* M, bool on_dev, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what, LinearStage* st) {
-  if (!s) FHESI_FAIL("%s: null plaintext space", what);
-  fhesi_ctx* c = s->ctx;
-  CHECK_CTX(c);
-  if (!M) FHESI_FAIL("%s: null matrix", what);
-  LinearPlan& plan = st->plan;
-  const i64 total = s->S.phim, cols = total / s->S.rows;
-  FHESI_TRY(fhesi_linear_grid_plan(cols, R, C, Rb, Cb, baby, &plan.nI, &plan.nJ, &plan.T, &plan.B, &plan.G, &plan.nfold, nullptr));
-  plan.amounts.resize((size_t)(plan.B - 1 + plan.G - 1 + plan.nfold));
-  FHESI_TRY(fhesi_linear_grid_plan(cols, R, C, Rb, Cb, baby, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, plan.amounts.data()));
-  ValueStage vs;
-  FHESI_TRY(value_stage_open(c, (i64)plan.nI * plan.nJ, (size_t)plan.T * total, kLinearChunkBytes, M, on_dev, (size_t)R * C, &vs));
-  st->per = vs.per; st->d_vals = vs.d_vals; st->d_M = vs.d_src; st->ld = C;
+constexpr size_t kLayerChunkBytes = (size_t)256 << 20;      // slot values of one chunk of units (a single unit may take more)
+
+// A layer's entry E (LinearEntry, ConvEntry below) holds the space `s`, the shape, `what` -- the entry point, for its refusals -- and says
+//   tensor, src_words(), bias_words(), cap_bytes()     what the tensor is called, its words and the bias's, the cap of a chunk
+//   plan(h)                                             refuses the shape, or fills h's plan (GridLayer and the layer's own fields); launches nothing
+//   bias_vals(h, d_b, d_bias)                           the nI bias rows from the bias in HBM
+//   write(h, st, first, nb)                             the slot vectors of the units [first, first + nb) into st.d_vals
+// The checks every entry starts with, once, and the ONE planner call: the shape, before anything is launched
+template <class E> static int layer_plan(const E& e, const int64_t* src, typename E::Handle* h) {
+  if (!e.s) FHESI_FAIL("%s: null plaintext space", e.what);
+  CHECK_CTX(e.s->ctx);
+  if (!src) FHESI_FAIL("%s: null %s", e.what, E::tensor);
+  FHESI_TRY(e.plan(h));
+  h->ctx = e.s->ctx; h->slots = e.s;
   return 0;
 }
-// the slot vectors of the blocks [first, first + nb), nb <= per, into d_vals
-static int linear_stage_blocks(fhesi_slots* s, const LinearStage& st, i64 Rb, i64 Cb, i64 first, i64 nb) {
-  return launch_linear_diag(s->ctx, s->S, st.d_M, st.ld, st.plan.nJ, (int)first, (int)nb, Rb, Cb, st.plan.T, st.plan.B, st.d_vals);
+template <class E> static int layer_stage_open(const E& e, const typename E::Handle& h, const int64_t* src, bool on_dev, ValueStage* st) {
+  return value_stage_open(h.ctx, (i64)h.nI * h.nJ, (size_t)h.nk * e.s->S.phim, e.cap_bytes(), src, on_dev, e.src_words(), st);
 }
-// b[I Rb + i mod Rb] in every row, I < nI: per output block the diagonal of the Rb x 1 block whose only column is its part of the bias -- a grid of nI x 1
-// such blocks with leading dimension 1.  Before linear_stage_open, which takes the values slot over.
-static int linear_bias_vals(fhesi_slots* s, const int64_t* bias, bool on_dev, i64 Rb, int nI, i64* d_bias) {
-  fhesi_ctx* c = s->ctx;
-  const i64* d_b = bias;
-  if (!on_dev) {
-    i64* up;
-    FHESI_TRY(upload_vals(c, bias, (size_t)nI * Rb * 8, &up));
-    d_b = up;
-  }
-  return launch_linear_diag(c, s->S, d_b, 1, 1, 0, nI, Rb, 1, 1, 1, d_bias);
-}
-static int linear_create(fhesi_slots* s, const int64_t* M, const int64_t* bias, bool on_dev, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what,
-                         fhesi_linear_grid* lin) {
-  if (!s) FHESI_FAIL("%s: null plaintext space", what);
-  fhesi_ctx* c = s->ctx;
-  CHECK_CTX(c);
-  if (!M) FHESI_FAIL("%s: null matrix", what);
-  int32_t nI = 0;
-  FHESI_TRY(fhesi_linear_grid_plan(s->S.phim / s->S.rows, R, C, Rb, Cb, baby, &nI, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));      // the shape, before anything is launched
-  const size_t n = (size_t)s->S.phim;
-  i64* d_bias = nullptr;
-  if (bias) {
-    if (hipMalloc(&d_bias, (size_t)nI * n * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("%s: hipMalloc of %zu bytes failed", what, (size_t)nI * n * 8); }
-    if (const int rc = linear_bias_vals(s, bias, on_dev, Rb, nI, d_bias)) { hipFree(d_bias); return rc; }
-  }
-  LinearStage st;
-  fhesi_plain* made = nullptr;
-  int rc = linear_stage_open(s, M, on_dev, R, C, Rb, Cb, baby, what, &st);
-  const LinearPlan& plan = st.plan;
-  if (rc) hipStreamSynchronize(c->stream);
-  else rc = value_stage_plain(s, (i64)plan.nI * plan.nJ, plan.T, st.per, st.d_vals, [&](i64 first, i64 nb) { return linear_stage_blocks(s, st, Rb, Cb, first, nb); }, &made);
-  if (rc) { hipFree(d_bias); return rc; }
-  lin->ctx = c; lin->slots = s; lin->R = R; lin->C = C; lin->Rb = Rb; lin->Cb = Cb;
-  lin->nI = plan.nI; lin->nJ = plan.nJ; lin->T = plan.T; lin->B = plan.B; lin->G = plan.G; lin->nfold = plan.nfold;
-  lin->amounts.assign(plan.amounts.begin(), plan.amounts.end());
-  lin->w = made; lin->d_bias = d_bias;
-  return 0;
-}
-template <class H>
-static int linear_create_handle(fhesi_slots* s, const int64_t* M, const int64_t* bias, bool on_dev, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what, H** out) {
-  if (!out) FHESI_FAIL("%s: null output pointer", what);
+// The ONE constructor.  In order: the checks and the plan; the bias, allocated and written first -- a host bias goes through the values slot, which the stage
+// takes over behind it --; the stage; the prepared plaintext (synchronises); the handle.  A failure behind the first launch synchronises before it returns
+// and frees the bias.
+template <class E, class H> static int layer_create(const E& e, const int64_t* src, const int64_t* bias, bool on_dev, H** out) {
+  if (!out) FHESI_FAIL("%s: null output pointer", e.what);
   *out = nullptr;
-  H* lin = new H();
-  if (const int rc = linear_create(s, M, bias, on_dev, R, C, Rb, Cb, baby, what, lin)) { delete lin; return rc; }
-  *out = lin;
+  H h;
+  FHESI_TRY(layer_plan(e, src, &h));
+  fhesi_ctx* c = h.ctx;
+  if (bias) {
+    const size_t bytes = (size_t)h.nI * e.s->S.phim * 8;
+    if (hipMalloc(&h.d_bias, bytes) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("%s: hipMalloc of %zu bytes failed", e.what, bytes); }
+    i64* d_b = const_cast<i64*>(bias);
+    int rc = on_dev ? 0 : upload_vals(c, bias, e.bias_words() * 8, &d_b);
+    if (!rc) rc = e.bias_vals(h, d_b, h.d_bias);
+    if (rc) { hipStreamSynchronize(c->stream); hipFree(h.d_bias); return rc; }
+  }
+  ValueStage st;
+  int rc = layer_stage_open(e, h, src, on_dev, &st);
+  if (rc) hipStreamSynchronize(c->stream);
+  else rc = value_stage_plain(e.s, (i64)h.nI * h.nJ, h.nk, st.per, st.d_vals, [&](i64 first, i64 nb) { return e.write(h, st, first, nb); }, &h.w);
+  if (rc) { hipFree(h.d_bias); return rc; }
+  *out = new H(h);
   return 0;
 }
-static int linear_free(fhesi_linear_grid* lin) {
-  fhesi_plain_free(lin->w);      // (synchronises; the one live handle the grid counts as)
-  hipFree(lin->d_bias);
+// the same stage without a handle: vals_host [nI][nJ][nk][phi(m)], chunk by chunk
+template <class E> static int layer_download(const E& e, const int64_t* src_host, int64_t* vals_host) {
+  if (!vals_host) FHESI_FAIL("%s: null output", e.what);
+  typename E::Handle h;
+  ValueStage st;
+  FHESI_TRY(layer_plan(e, src_host, &h));
+  FHESI_TRY(layer_stage_open(e, h, src_host, false, &st));
+  return value_stage_download(h.ctx, (i64)h.nI * h.nJ, (size_t)h.nk * e.s->S.phim, st.per, st.d_vals, [&](i64 first, i64 nb) { return e.write(h, st, first, nb); }, vals_host);
+}
+template <class H> static int layer_free(H* h) {
+  if (!h) return 0;
+  fhesi_plain_free(h->w);      // (synchronises; the one live handle the layer counts as)
+  hipFree(h->d_bias);
+  delete h;
   return 0;
 }
-// the same stage without a handle: vals_host [nI][nJ][T][phi(m)], chunk by chunk
-static int linear_diagonals(fhesi_slots* s, const int64_t* M_host, i64 R, i64 C, i64 Rb, i64 Cb, int32_t baby, const char* what, int64_t* vals_host) {
-  if (!vals_host) FHESI_FAIL("%s: null output", what);
-  LinearStage st;
-  FHESI_TRY(linear_stage_open(s, M_host, false, R, C, Rb, Cb, baby, what, &st));
-  return value_stage_download(s->ctx, (i64)st.plan.nI * st.plan.nJ, (size_t)st.plan.T * s->S.phim, st.per, st.d_vals,
-                              [&](i64 first, i64 nb) { return linear_stage_blocks(s, st, Rb, Cb, first, nb); }, vals_host);
+// what the info entries share
+template <class T, class V> static void put(T* out, V v) { if (out) *out = (T)v; }
+static int layer_info(const GridLayer& L, int32_t* has_bias, int64_t* amounts) {
+  put(has_bias, L.d_bias ? 1 : 0);
+  if (amounts) std::copy(L.amounts.begin(), L.amounts.end(), amounts);
+  return 0;
 }
+
+// --------------------------------------------------------------------------------------------- dense linear layers
+// The units are the nI nJ blocks, T prepared slot vectors w_t [T][phi(m)] each, written by linear_diag_kernel from the matrix where it is.  A layer is the
+// grid of one block (Rb = R, Cb = C): everything here is written for the grid.
+namespace {
+struct LinearEntry {
+  typedef fhesi_linear_grid Handle;
+  static constexpr const char* tensor = "matrix";
+  fhesi_slots* s;
+  i64 R, C, Rb, Cb;
+  int32_t baby;
+  const char* what;
+  size_t src_words() const { return (size_t)R * C; }
+  size_t bias_words() const { return (size_t)R; }
+  size_t cap_bytes() const { return kLayerChunkBytes; }
+  int plan(Handle* lin) const {
+    const i64 cols = s->S.phim / s->S.rows;
+    int32_t nI = 0, nJ = 0, T = 0, B = 0, G = 0, nfold = 0;
+    FHESI_TRY(linear_grid_plan(cols, R, C, Rb, Cb, baby, &nI, &nJ, &T, &B, &G, &nfold, &lin->amounts));
+    lin->R = R; lin->C = C; lin->Rb = Rb; lin->Cb = Cb;
+    lin->nI = nI; lin->nJ = nJ; lin->nk = T; lin->B = B; lin->G = G; lin->nfold = nfold;
+    lin->terms = (i64)nJ * std::min(B, T);
+    for (int t = 0; t < (int)lin->amounts.size(); ++t) lin->place.push_back(t + (t < B - 1 ? 1 : 2));      // the identity in front of the babies and of the giants
+    return 0;
+  }
+  // b[I Rb + i mod Rb] in every row, I < nI: per output block the diagonal of the Rb x 1 block whose only column is its part of the bias -- a grid of nI x 1
+  // such blocks with leading dimension 1
+  int bias_vals(const Handle& lin, const i64* d_b, i64* d_bias) const { return launch_linear_diag(lin.ctx, s->S, d_b, 1, 1, 0, lin.nI, Rb, 1, 1, 1, d_bias); }
+  int write(const Handle& lin, const ValueStage& st, i64 first, i64 nb) const {
+    return launch_linear_diag(lin.ctx, s->S, st.d_src, C, lin.nJ, (int)first, (int)nb, Rb, Cb, lin.nk, lin.B, st.d_vals);
+  }
+};
+}  // namespace
 extern "C" int fhesi_linear_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, const int64_t* bias_host, int32_t baby, fhesi_linear** out) {
-  return linear_create_handle(s, M_host, bias_host, false, R, C, R, C, baby, "linear_create", out);
+  return layer_create(LinearEntry{s, R, C, R, C, baby, "linear_create"}, M_host, bias_host, false, out);
 }
 extern "C" int fhesi_linear_create_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t C, const int64_t* bias_dev, int32_t baby, fhesi_linear** out) {
-  return linear_create_handle(s, M_dev, bias_dev, true, R, C, R, C, baby, "linear_create", out);
+  return layer_create(LinearEntry{s, R, C, R, C, baby, "linear_create"}, M_dev, bias_dev, true, out);
 }
-extern "C" int fhesi_linear_free(fhesi_linear* lin) {
-  if (!lin) return 0;
-  linear_free(lin);
-  delete lin;
-  return 0;
-}
-extern "C" int fhesi_linear_info(const fhesi_linear* lin, int64_t* R, int64_t* C, int32_t* T, int32_t* B, int32_t* G, int32_t* nfold, int32_t* has_bias, int64_t* amounts) {
-  if (!lin) FHESI_FAIL("null linear layer");
-  if (R) *R = lin->R;
-  if (C) *C = lin->C;
-  if (T) *T = lin->T;
-  if (B) *B = lin->B;
-  if (G) *G = lin->G;
-  if (nfold) *nfold = lin->nfold;
-  if (has_bias) *has_bias = lin->d_bias ? 1 : 0;
-  if (amounts) std::copy(lin->amounts.begin(), lin->amounts.end(), amounts);
-  return 0;
-}
-extern "C" int fhesi_linear_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int32_t baby, int64_t* vals_host) {
-  return linear_diagonals(s, M_host, R, C, R, C, baby, "linear_diagonals", vals_host);
-}
-extern "C" int fhesi_linear_grid_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int64_t Rb, int64_t Cb, const int64_t* bias_host, int32_t baby,
-                                        fhesi_linear_grid** out) {
-  return linear_create_handle(s, M_host, bias_host, false, R, C, Rb, Cb, baby, "linear_grid_create", out);
-}
-extern "C" int fhesi_linear_grid_create_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t C, int64_t Rb, int64_t Cb, const int64_t* bias_dev, int32_t baby,
-                                            fhesi_linear_grid** out) {
-  return linear_create_handle(s, M_dev, bias_dev, true, R, C, Rb, Cb, baby, "linear_grid_create", out);
-}
-extern "C" int fhesi_linear_grid_free(fhesi_linear_grid* lin) {
-  if (!lin) return 0;
-  linear_free(lin);
-  delete lin;
-  return 0;
-}
+extern "C" int fhesi_linear_free(fhesi_linear* lin) { return layer_free(lin); }
 extern "C" int fhesi_linear_grid_info(const fhesi_linear_grid* lin, int64_t* R, int64_t* C, int64_t* Rb, int64_t* Cb, int32_t* nI, int32_t* nJ, int32_t* T, int32_t* B, int32_t* G,
                                       int32_t* nfold, int32_t* has_bias, int64_t* amounts) {
   if (!lin) FHESI_FAIL("null linear grid");
-  if (R) *R = lin->R;
-  if (C) *C = lin->C;
-  if (Rb) *Rb = lin->Rb;
-  if (Cb) *Cb = lin->Cb;
-  if (nI) *nI = lin->nI;
-  if (nJ) *nJ = lin->nJ;
-  if (T) *T = lin->T;
-  if (B) *B = lin->B;
-  if (G) *G = lin->G;
-  if (nfold) *nfold = lin->nfold;
-  if (has_bias) *has_bias = lin->d_bias ? 1 : 0;
-  if (amounts) std::copy(lin->amounts.begin(), lin->amounts.end(), amounts);
-  return 0;
+  put(R, lin->R); put(C, lin->C); put(Rb, lin->Rb); put(Cb, lin->Cb); put(nI, lin->nI); put(nJ, lin->nJ);
+  put(T, lin->nk); put(B, lin->B); put(G, lin->G); put(nfold, lin->nfold);
+  return layer_info(*lin, has_bias, amounts);
 }
+extern "C" int fhesi_linear_info(const fhesi_linear* lin, int64_t* R, int64_t* C, int32_t* T, int32_t* B, int32_t* G, int32_t* nfold, int32_t* has_bias, int64_t* amounts) {
+  if (!lin) FHESI_FAIL("null linear layer");
+  return fhesi_linear_grid_info(lin, R, C, nullptr, nullptr, nullptr, nullptr, T, B, G, nfold, has_bias, amounts);
+}
+extern "C" int fhesi_linear_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int32_t baby, int64_t* vals_host) {
+  return layer_download(LinearEntry{s, R, C, R, C, baby, "linear_diagonals"}, M_host, vals_host);
+}
+extern "C" int fhesi_linear_grid_create(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int64_t Rb, int64_t Cb, const int64_t* bias_host, int32_t baby,
+                                        fhesi_linear_grid** out) {
+  return layer_create(LinearEntry{s, R, C, Rb, Cb, baby, "linear_grid_create"}, M_host, bias_host, false, out);
+}
+extern "C" int fhesi_linear_grid_create_dev(fhesi_slots* s, const int64_t* M_dev, int64_t R, int64_t C, int64_t Rb, int64_t Cb, const int64_t* bias_dev, int32_t baby,
+                                            fhesi_linear_grid** out) {
+  return layer_create(LinearEntry{s, R, C, Rb, Cb, baby, "linear_grid_create"}, M_dev, bias_dev, true, out);
+}
+extern "C" int fhesi_linear_grid_free(fhesi_linear_grid* lin) { return layer_free(lin); }
 extern "C" int fhesi_linear_grid_diagonals(fhesi_slots* s, const int64_t* M_host, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int64_t* vals_host) {
-  return linear_diagonals(s, M_host, R, C, Rb, Cb, baby, "linear_grid_diagonals", vals_host);
+  return layer_download(LinearEntry{s, R, C, Rb, Cb, baby, "linear_grid_diagonals"}, M_host, vals_host);
 }
 
 // --------------------------------------------------------------------------------------------- convolution layers
-// fhesi_conv2d (include/fhesi_hip.h; the plan and its refusals: conv_plan.h).  The stage next to linear_stage_open: the kh kw masked weight plaintexts of a
-// channel pair [kh kw][phi(m)] in the values slot, written by conv_mask_kernel from the weight tensor where it is, in chunks of whole channel pairs
-// (option "stage_chunk_bytes" lowers the cap, for tests).
-// On a lattice of the plane (fhesi_conv2d_lattice_*; lattice_plan.h) the same stage with conv_lattice_mask_kernel: `geom` the step, stride and dilation, null
-// from the entries without one, which keep conv_mask_kernel.
-struct ConvStage {
-  ConvShape sh;
-  ConvPlan plan;
-  ValueStage vs;
-  bool lattice = false;
+// The plan and its refusals: conv_plan.h.  The units are the Cout Cin channel pairs, kh kw masked weight plaintexts [kh kw][phi(m)] each, written by
+// conv_lattice_mask_kernel from the weight tensor where it is (option "stage_chunk_bytes" lowers the cap of a chunk, for tests).  The geometry -- step,
+// stride, dilation -- is in the mask and in the bias; fhesi_conv2d_plan, _create[_dev] and _masks are the entries of the unit geometry, fhesi_conv2d_lattice_*
+// take one, the handle records it, and the run call is fhesi_ct_conv2d_dev whatever it is.
+static int conv_geom_plan(const char* what, const ConvShape& sh, const LatticeGeom& g, int32_t form, LatticeConvPlan* plan) {
+  char why[256];
+  if (lattice_refused(LatticeShape{sh, g}, form, why, sizeof why)) FHESI_FAIL("%s: %s", what, why);
+  *plan = lattice_conv_plan(LatticeShape{sh, g}, form);
+  return 0;
+}
+namespace {
+struct ConvEntry {
+  typedef fhesi_conv2d Handle;
+  static constexpr const char* tensor = "kernel";
+  fhesi_slots* s;
+  i64 Cout, Cin, kh, kw, H, W, ah, aw;
   LatticeGeom g;
-};
-static int conv_shape_plan(const char* what, const ConvShape& sh, int32_t form, ConvPlan* plan) {
-  char why[256];
-  if (conv_refused(sh, form, why, sizeof why)) FHESI_FAIL("%s: %s", what, why);
-  *plan = conv_plan(sh, form);
-  return 0;
-}
-extern "C" int fhesi_conv2d_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw, int32_t form, int32_t* form_out,
-                                 int32_t* nh, int64_t* key_switches, int64_t* terms, int64_t* amounts) {
-  ConvPlan plan;
-  FHESI_TRY(conv_shape_plan("conv2d_plan", ConvShape{cols, H, W, Cin, Cout, kh, kw, ah, aw}, form, &plan));
-  if (form_out) *form_out = plan.form;
-  if (nh) *nh = plan.nh;
-  if (key_switches) *key_switches = plan.key_switches;
-  if (terms) *terms = plan.terms;
-  if (amounts) std::copy(plan.amounts.begin(), plan.amounts.end(), amounts);
-  return 0;
-}
-static int lattice_shape_plan(const char* what, const LatticeShape& sh, int32_t form, LatticeConvPlan* plan) {
-  char why[256];
-  if (lattice_refused(sh, form, why, sizeof why)) FHESI_FAIL("%s: %s", what, why);
-  *plan = lattice_conv_plan(sh, form);
-  return 0;
-}
-static int conv_stage_open(fhesi_slots* s, const int64_t* K, bool on_dev, i64 Cout, i64 Cin, i64 kh, i64 kw, i64 H, i64 W, i64 ah, i64 aw, int32_t form, const char* what,
-                           ConvStage* st, const LatticeGeom* geom = nullptr) {
-  if (!s) FHESI_FAIL("%s: null plaintext space", what);
-  fhesi_ctx* c = s->ctx;
-  CHECK_CTX(c);
-  if (!K) FHESI_FAIL("%s: null kernel", what);
-  st->sh = ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw};
-  if (geom) {
+  int32_t form;
+  const char* what;
+  size_t src_words() const { return (size_t)(Cout * Cin * kh * kw); }
+  size_t bias_words() const { return (size_t)Cout; }
+  size_t cap_bytes() const { return s->ctx->opt.stage_chunk_bytes > 0 ? (size_t)s->ctx->opt.stage_chunk_bytes : kLayerChunkBytes; }
+  int plan(Handle* cv) const {
     LatticeConvPlan lp;
-    FHESI_TRY(lattice_shape_plan(what, LatticeShape{st->sh, *geom}, form, &lp));
-    st->plan = lp.p; st->lattice = true; st->g = *geom;
-  } else FHESI_TRY(conv_shape_plan(what, st->sh, form, &st->plan));
-  const size_t cap = c->opt.stage_chunk_bytes > 0 ? (size_t)c->opt.stage_chunk_bytes : kLinearChunkBytes;
-  return value_stage_open(c, Cout * Cin, (size_t)(kh * kw) * s->S.phim, cap, K, on_dev, (size_t)(Cout * Cin * kh * kw), &st->vs);
-}
-// the plaintexts of the channel pairs [first, first + nb), nb <= per, into d_vals
-static int conv_stage_pairs(fhesi_slots* s, const ConvStage& st, i64 first, i64 nb) {
-  const ConvShape& sh = st.sh;
-  const LatticeGeom& g = st.g;
-  if (st.lattice)
-    return launch_conv_lattice_mask(s->ctx, s->S, st.vs.d_src, (int)first, (int)nb, (int)sh.kh, (int)sh.kw, (int)sh.ah, (int)sh.aw, sh.H, sh.W, g.ey * g.sy, g.ex * g.sx, g.sy * g.ty,
-                                    g.sx * g.tx, st.plan.form == 2, st.vs.d_vals);
-  return launch_conv_mask(s->ctx, s->S, st.vs.d_src, (int)first, (int)nb, (int)sh.kh, (int)sh.kw, (int)sh.ah, (int)sh.aw, sh.H, sh.W, st.plan.form == 2, st.vs.d_vals);
-}
-// b[I] on the output lattice of step (oy, ox), 0 off it: the plaintexts of the 1 x 1 kernel [Cout][1] whose only weight is the bias.  Before conv_stage_open,
-// which takes the values slot over.
-static int lattice_bias_vals(fhesi_slots* s, const int64_t* bias, bool on_dev, i64 Cout, i64 H, i64 W, i64 oy, i64 ox, i64* d_bias) {
-  const i64* d_b = bias;
-  if (!on_dev) {
-    i64* up;
-    FHESI_TRY(upload_vals(s->ctx, bias, (size_t)Cout * 8, &up));
-    d_b = up;
+    FHESI_TRY(conv_geom_plan(what, ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, g, form, &lp));
+    cv->Cout = Cout; cv->Cin = Cin; cv->kh = kh; cv->kw = kw; cv->H = H; cv->W = W; cv->ah = ah; cv->aw = aw;
+    cv->sy = g.sy; cv->sx = g.sx; cv->ty = g.ty; cv->tx = g.tx; cv->ey = g.ey; cv->ex = g.ex;
+    cv->form = lp.p.form; cv->nh = lp.p.nh; cv->key_switches = lp.p.key_switches; cv->terms = lp.p.terms;
+    cv->nI = (int)Cout; cv->nJ = (int)Cin; cv->nk = (int)(kh * kw);
+    cv->flat = cv->form == 1; cv->anchored = true;
+    cv->B = cv->flat ? cv->nk : (int)kw; cv->G = cv->flat ? 1 : (int)kh;
+    cv->amounts.assign(lp.p.amounts.begin(), lp.p.amounts.end());
+    for (int t = 0; t < cv->nh; ++t) cv->place.push_back(t);      // the babies, then the giants, the anchor among them
+    return 0;
   }
-  return launch_conv_lattice_mask(s->ctx, s->S, d_b, 0, (int)Cout, 1, 1, 0, 0, H, W, 1, 1, oy, ox, false, d_bias);
-}
-static int conv_create(fhesi_slots* s, const int64_t* K, const int64_t* bias, bool on_dev, i64 Cout, i64 Cin, i64 kh, i64 kw, i64 H, i64 W, i64 ah, i64 aw, int32_t form,
-                       fhesi_conv2d** out, const LatticeGeom* geom = nullptr) {
-  const char* what = geom ? "conv2d_lattice_create" : "conv2d_create";
-  if (!out) FHESI_FAIL("%s: null output pointer", what);
-  *out = nullptr;
-  if (!s) FHESI_FAIL("%s: null plaintext space", what);
-  fhesi_ctx* c = s->ctx;
-  CHECK_CTX(c);
-  if (!K) FHESI_FAIL("%s: null kernel", what);
-  ConvPlan shape_only;      // the shape, before anything is launched
-  LatticeConvPlan lattice_only;
-  if (geom) FHESI_TRY(lattice_shape_plan(what, LatticeShape{ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, *geom}, form, &lattice_only));
-  else FHESI_TRY(conv_shape_plan(what, ConvShape{s->S.phim / s->S.rows, H, W, Cin, Cout, kh, kw, ah, aw}, form, &shape_only));
-  const size_t n = (size_t)s->S.phim;
-  i64* d_bias = nullptr;
-  if (bias) {      // b[I] in every slot: the diagonal of a 1 x 1 block per output channel
-    if (hipMalloc(&d_bias, (size_t)Cout * n * 8) != hipSuccess) { (void)hipGetLastError(); FHESI_FAIL("%s: hipMalloc of %zu bytes failed", what, (size_t)Cout * n * 8); }
-    const int rc = geom ? lattice_bias_vals(s, bias, on_dev, Cout, H, W, lattice_only.oy, lattice_only.ox, d_bias) : linear_bias_vals(s, bias, on_dev, 1, (int)Cout, d_bias);
-    if (rc) { hipFree(d_bias); return rc; }
+  // b[I] on the output lattice, 0 off it: the plaintexts of the 1 x 1 kernel [Cout][1] whose only weight is the bias
+  int bias_vals(const Handle& cv, const i64* d_b, i64* d_bias) const {
+    return launch_conv_lattice_mask(cv.ctx, s->S, d_b, 0, (int)Cout, 1, 1, 0, 0, H, W, 1, 1, g.sy * g.ty, g.sx * g.tx, false, d_bias);
   }
-  ConvStage st;
-  fhesi_plain* made = nullptr;
-  int rc = conv_stage_open(s, K, on_dev, Cout, Cin, kh, kw, H, W, ah, aw, form, what, &st, geom);
-  if (rc) hipStreamSynchronize(c->stream);
-  else rc = value_stage_plain(s, Cout * Cin, kh * kw, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); }, &made);
-  if (rc) { hipFree(d_bias); return rc; }
-  fhesi_conv2d* cv = new fhesi_conv2d();
-  cv->ctx = c; cv->slots = s; cv->Cout = Cout; cv->Cin = Cin; cv->kh = kh; cv->kw = kw; cv->H = H; cv->W = W; cv->ah = ah; cv->aw = aw;
-  cv->form = st.plan.form; cv->nh = st.plan.nh; cv->key_switches = st.plan.key_switches; cv->terms = st.plan.terms;
-  cv->amounts.assign(st.plan.amounts.begin(), st.plan.amounts.end());
-  cv->w = made; cv->d_bias = d_bias;
-  if (geom) { cv->sy = geom->sy; cv->sx = geom->sx; cv->ty = geom->ty; cv->tx = geom->tx; cv->ey = geom->ey; cv->ex = geom->ex; }
-  *out = cv;
-  return 0;
-}
-extern "C" int fhesi_conv2d_create(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
-                                   const int64_t* bias_host, int32_t form, fhesi_conv2d** out) {
-  return conv_create(s, K_host, bias_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, out);
-}
-extern "C" int fhesi_conv2d_create_dev(fhesi_slots* s, const int64_t* K_dev, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
-                                       const int64_t* bias_dev, int32_t form, fhesi_conv2d** out) {
-  return conv_create(s, K_dev, bias_dev, true, Cout, Cin, kh, kw, H, W, ah, aw, form, out);
-}
-extern "C" int fhesi_conv2d_free(fhesi_conv2d* cv) {
-  if (!cv) return 0;
-  fhesi_plain_free(cv->w);      // (synchronises; the one live handle the layer counts as)
-  hipFree(cv->d_bias);
-  delete cv;
-  return 0;
-}
-extern "C" int fhesi_conv2d_info(const fhesi_conv2d* cv, int64_t* Cout, int64_t* Cin, int64_t* kh, int64_t* kw, int64_t* H, int64_t* W, int64_t* ah, int64_t* aw, int32_t* form,
-                                 int32_t* nh, int64_t* key_switches, int64_t* terms, int32_t* has_bias, int64_t* amounts) {
-  if (!cv) FHESI_FAIL("null convolution layer");
-  if (Cout) *Cout = cv->Cout;
-  if (Cin) *Cin = cv->Cin;
-  if (kh) *kh = cv->kh;
-  if (kw) *kw = cv->kw;
-  if (H) *H = cv->H;
-  if (W) *W = cv->W;
-  if (ah) *ah = cv->ah;
-  if (aw) *aw = cv->aw;
-  if (form) *form = cv->form;
-  if (nh) *nh = cv->nh;
-  if (key_switches) *key_switches = cv->key_switches;
-  if (terms) *terms = cv->terms;
-  if (has_bias) *has_bias = cv->d_bias ? 1 : 0;
-  if (amounts) std::copy(cv->amounts.begin(), cv->amounts.end(), amounts);
-  return 0;
-}
-// the same stage without a handle: vals_host [Cout][Cin][kh kw][phi(m)], chunk by chunk
-extern "C" int fhesi_conv2d_masks(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
-                                  int32_t form, int64_t* vals_host) {
-  if (!vals_host) FHESI_FAIL("conv2d_masks: null output");
-  ConvStage st;
-  FHESI_TRY(conv_stage_open(s, K_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, "conv2d_masks", &st));
-  return value_stage_download(s->ctx, Cout * Cin, (size_t)(kh * kw) * s->S.phim, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); },
-                              vals_host);
-}
-
-// --------------------------------------------------------------------------------------------- convolutions and the dense bridge on a lattice of the plane
-// fhesi_conv2d_lattice_* (include/fhesi_hip.h; lattice_plan.h): the stage above with the geometry -- step, stride, dilation -- in the mask and the bias; the
-// handle is a fhesi_conv2d that also records its geometry, and the run call is fhesi_ct_conv2d_dev as it is.
+  int write(const Handle& cv, const ValueStage& st, i64 first, i64 nb) const {
+    return launch_conv_lattice_mask(cv.ctx, s->S, st.d_src, (int)first, (int)nb, (int)kh, (int)kw, (int)ah, (int)aw, H, W, g.ey * g.sy, g.ex * g.sx, g.sy * g.ty, g.sx * g.tx,
+                                    cv.form == 2, st.d_vals);
+  }
+};
+}  // namespace
 extern "C" int fhesi_conv2d_lattice_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw, int64_t sy, int64_t sx,
                                          int64_t ty, int64_t tx, int64_t ey, int64_t ex, int32_t form, int32_t* form_out, int32_t* nh, int64_t* key_switches, int64_t* terms,
                                          int64_t* out_sy, int64_t* out_sx, int64_t* amounts) {
   LatticeConvPlan plan;
-  FHESI_TRY(lattice_shape_plan("conv2d_lattice_plan", LatticeShape{ConvShape{cols, H, W, Cin, Cout, kh, kw, ah, aw}, LatticeGeom{sy, sx, ty, tx, ey, ex}}, form, &plan));
-  if (form_out) *form_out = plan.p.form;
-  if (nh) *nh = plan.p.nh;
-  if (key_switches) *key_switches = plan.p.key_switches;
-  if (terms) *terms = plan.p.terms;
-  if (out_sy) *out_sy = plan.oy;
-  if (out_sx) *out_sx = plan.ox;
+  FHESI_TRY(conv_geom_plan("conv2d_lattice_plan", ConvShape{cols, H, W, Cin, Cout, kh, kw, ah, aw}, LatticeGeom{sy, sx, ty, tx, ey, ex}, form, &plan));
+  put(form_out, plan.p.form); put(nh, plan.p.nh); put(key_switches, plan.p.key_switches); put(terms, plan.p.terms); put(out_sy, plan.oy); put(out_sx, plan.ox);
   if (amounts) std::copy(plan.p.amounts.begin(), plan.p.amounts.end(), amounts);
   return 0;
 }
+extern "C" int fhesi_conv2d_plan(int64_t cols, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t kh, int64_t kw, int64_t ah, int64_t aw, int32_t form, int32_t* form_out,
+                                 int32_t* nh, int64_t* key_switches, int64_t* terms, int64_t* amounts) {
+  LatticeConvPlan plan;
+  FHESI_TRY(conv_geom_plan("conv2d_plan", ConvShape{cols, H, W, Cin, Cout, kh, kw, ah, aw}, LatticeGeom{}, form, &plan));
+  put(form_out, plan.p.form); put(nh, plan.p.nh); put(key_switches, plan.p.key_switches); put(terms, plan.p.terms);
+  if (amounts) std::copy(plan.p.amounts.begin(), plan.p.amounts.end(), amounts);
+  return 0;
+}
+extern "C" int fhesi_conv2d_create(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                   const int64_t* bias_host, int32_t form, fhesi_conv2d** out) {
+  return layer_create(ConvEntry{s, Cout, Cin, kh, kw, H, W, ah, aw, LatticeGeom{}, form, "conv2d_create"}, K_host, bias_host, false, out);
+}
+extern "C" int fhesi_conv2d_create_dev(fhesi_slots* s, const int64_t* K_dev, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                       const int64_t* bias_dev, int32_t form, fhesi_conv2d** out) {
+  return layer_create(ConvEntry{s, Cout, Cin, kh, kw, H, W, ah, aw, LatticeGeom{}, form, "conv2d_create"}, K_dev, bias_dev, true, out);
+}
 extern "C" int fhesi_conv2d_lattice_create(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
                                            int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, const int64_t* bias_host, int32_t form, fhesi_conv2d** out) {
-  const LatticeGeom g{sy, sx, ty, tx, ey, ex};
-  return conv_create(s, K_host, bias_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, out, &g);
+  return layer_create(ConvEntry{s, Cout, Cin, kh, kw, H, W, ah, aw, LatticeGeom{sy, sx, ty, tx, ey, ex}, form, "conv2d_lattice_create"}, K_host, bias_host, false, out);
 }
 extern "C" int fhesi_conv2d_lattice_create_dev(fhesi_slots* s, const int64_t* K_dev, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
                                                int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, const int64_t* bias_dev, int32_t form, fhesi_conv2d** out) {
-  const LatticeGeom g{sy, sx, ty, tx, ey, ex};
-  return conv_create(s, K_dev, bias_dev, true, Cout, Cin, kh, kw, H, W, ah, aw, form, out, &g);
+  return layer_create(ConvEntry{s, Cout, Cin, kh, kw, H, W, ah, aw, LatticeGeom{sy, sx, ty, tx, ey, ex}, form, "conv2d_lattice_create"}, K_dev, bias_dev, true, out);
+}
+extern "C" int fhesi_conv2d_free(fhesi_conv2d* cv) { return layer_free(cv); }
+extern "C" int fhesi_conv2d_info(const fhesi_conv2d* cv, int64_t* Cout, int64_t* Cin, int64_t* kh, int64_t* kw, int64_t* H, int64_t* W, int64_t* ah, int64_t* aw, int32_t* form,
+                                 int32_t* nh, int64_t* key_switches, int64_t* terms, int32_t* has_bias, int64_t* amounts) {
+  if (!cv) FHESI_FAIL("null convolution layer");
+  put(Cout, cv->Cout); put(Cin, cv->Cin); put(kh, cv->kh); put(kw, cv->kw); put(H, cv->H); put(W, cv->W); put(ah, cv->ah); put(aw, cv->aw);
+  put(form, cv->form); put(nh, cv->nh); put(key_switches, cv->key_switches); put(terms, cv->terms);
+  return layer_info(*cv, has_bias, amounts);
 }
 extern "C" int fhesi_conv2d_lattice_info(const fhesi_conv2d* cv, int64_t* sy, int64_t* sx, int64_t* ty, int64_t* tx, int64_t* ey, int64_t* ex, int64_t* out_sy, int64_t* out_sx) {
   if (!cv) FHESI_FAIL("null convolution layer");
-  if (sy) *sy = cv->sy;
-  if (sx) *sx = cv->sx;
-  if (ty) *ty = cv->ty;
-  if (tx) *tx = cv->tx;
-  if (ey) *ey = cv->ey;
-  if (ex) *ex = cv->ex;
-  if (out_sy) *out_sy = cv->sy * cv->ty;
-  if (out_sx) *out_sx = cv->sx * cv->tx;
+  put(sy, cv->sy); put(sx, cv->sx); put(ty, cv->ty); put(tx, cv->tx); put(ey, cv->ey); put(ex, cv->ex); put(out_sy, cv->sy * cv->ty); put(out_sx, cv->sx * cv->tx);
   return 0;
 }
-// the same stage without a handle: vals_host [Cout][Cin][kh kw][phi(m)], chunk by chunk
+// vals_host [Cout][Cin][kh kw][phi(m)]
+extern "C" int fhesi_conv2d_masks(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
+                                  int32_t form, int64_t* vals_host) {
+  return layer_download(ConvEntry{s, Cout, Cin, kh, kw, H, W, ah, aw, LatticeGeom{}, form, "conv2d_masks"}, K_host, vals_host);
+}
 extern "C" int fhesi_conv2d_lattice_masks(fhesi_slots* s, const int64_t* K_host, int64_t Cout, int64_t Cin, int64_t kh, int64_t kw, int64_t H, int64_t W, int64_t ah, int64_t aw,
                                           int64_t sy, int64_t sx, int64_t ty, int64_t tx, int64_t ey, int64_t ex, int32_t form, int64_t* vals_host) {
-  if (!vals_host) FHESI_FAIL("conv2d_lattice_masks: null output");
-  const LatticeGeom g{sy, sx, ty, tx, ey, ex};
-  ConvStage st;
-  FHESI_TRY(conv_stage_open(s, K_host, false, Cout, Cin, kh, kw, H, W, ah, aw, form, "conv2d_lattice_masks", &st, &g));
-  return value_stage_download(s->ctx, Cout * Cin, (size_t)(kh * kw) * s->S.phim, st.vs.per, st.vs.d_vals, [&](i64 first, i64 nb) { return conv_stage_pairs(s, st, first, nb); },
-                              vals_host);
+  return layer_download(ConvEntry{s, Cout, Cin, kh, kw, H, W, ah, aw, LatticeGeom{sy, sx, ty, tx, ey, ex}, form, "conv2d_lattice_masks"}, K_host, vals_host);
 }
+
+// --------------------------------------------------------------------------------------------- the dense bridge on a lattice of the plane
 // M [R][nch Hl Wl] over logical pixels -> M' [R][nch H W] over the slots of the planes, zero columns off the lattice (lattice_columns_kernel): what
 // fhesi_linear_grid_create[_dev] with Cb = H W takes as it is
 static int lattice_columns_args(fhesi_slots* s, const char* what, const void* M, const void* out, i64 R, i64 nch, i64 H, i64 W, i64 sy, i64 sx) {

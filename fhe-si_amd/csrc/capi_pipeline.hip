@@ -708,8 +708,8 @@ extern "C" int fhesi_linear_plan(int64_t cols, int64_t R, int64_t C, int32_t bab
 
 // host only.  The grid of nI x nJ blocks of Rb x Cb: the block's plan with the B that suits the shared schedule -- the babies run once per input block, the
 // giants once per output block, so B minimises nJ (B - 1) + nI (G - 1); of equal costs the larger B.  One block: what fhesi_linear_plan picks.
-extern "C" int fhesi_linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int32_t* nI_out, int32_t* nJ_out, int32_t* T_out, int32_t* B_out,
-                                      int32_t* G_out, int32_t* nfold_out, int64_t* amounts) {
+int linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int32_t* nI_out, int32_t* nJ_out, int32_t* T_out, int32_t* B_out, int32_t* G_out,
+                     int32_t* nfold_out, std::vector<int64_t>* amounts) {
   int32_t T = 0, B = 0, G = 0, nfold = 0;
   FHESI_TRY(fhesi_linear_plan(cols, Rb, Cb, baby, &T, &B, &G, &nfold, nullptr));      // the block's shape, in the planner's own words
   if (R < 1 || C < 1) FHESI_FAIL("linear_grid_plan: a %lld x %lld matrix (both sizes at least 1)", (long long)R, (long long)C);
@@ -731,105 +731,96 @@ extern "C" int fhesi_linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_
   if (B_out) *B_out = B;
   if (G_out) *G_out = G;
   if (nfold_out) *nfold_out = nfold;
-  if (amounts) FHESI_TRY(fhesi_linear_plan(cols, Rb, Cb, B, nullptr, nullptr, nullptr, nullptr, amounts));      // (baby = B > 0: min(B, T) = B)
+  if (amounts) {
+    amounts->resize((size_t)(B - 1 + G - 1 + nfold));
+    FHESI_TRY(fhesi_linear_plan(cols, Rb, Cb, B, nullptr, nullptr, nullptr, nullptr, amounts->data()));      // (baby = B > 0: min(B, T) = B)
+  }
+  return 0;
+}
+extern "C" int fhesi_linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int32_t* nI_out, int32_t* nJ_out, int32_t* T_out, int32_t* B_out,
+                                      int32_t* G_out, int32_t* nfold_out, int64_t* amounts) {
+  std::vector<int64_t> a;
+  FHESI_TRY(linear_grid_plan(cols, R, C, Rb, Cb, baby, nI_out, nJ_out, T_out, B_out, G_out, nfold_out, amounts ? &a : nullptr));
+  std::copy(a.begin(), a.end(), amounts);
   return 0;
 }
 
-// out[I][i] = sum_J M_IJ in[J][i] + b_I on the slots (include/fhesi_hip.h): matvec_run over the grid's diagonals, the folds in place on out -- nI count
-// ciphertexts in a row --, the biases -- embedded into the message staging slot once the sums' index lists in it are dead -- through launch_ct_add_const.
-// One block: the words of fhesi_ct_matvec_bsgs_dev, fhesi_ct_rot_fold_dev and fhesi_ct_add_slots_dev in that order.  who: the entry point, for its refusals.
-static int linear_run(fhesi_ctx* c, const char* who, const char* what, const fhesi_linear_grid* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ,
-                      int32_t decomp_bytes, const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
+// k = g^amount mod m for each rotation amount of a plan on the space's rows
+static std::vector<int64_t> rotation_ks(const fhesi_slots* s, const std::vector<int64_t>& amounts) {
+  std::vector<int64_t> ks(amounts.size());
+  for (size_t t = 0; t < amounts.size(); ++t) ks[t] = (int64_t)hm::powmod(s->S.g, (u64)amounts[t], (u64)s->ctx->m);
+  return ks;
+}
+// out[I][i] += b_I: the biases embedded into the message staging slot -- the sums' index lists in it are dead -- and added through launch_ct_add_const
+static int layer_add_bias(fhesi_ctx* c, const GridLayer& L, int32_t logQ, int32_t nlimbs, int64_t count, uint64_t* out) {
+  if (!L.d_bias) return 0;
+  const size_t n = (size_t)c->phim;
+  void* d_msg;
+  FHESI_TRY(ws_reserve(c, 5, (size_t)L.nI * n * 8, &d_msg));
+  FHESI_TRY(slots_embed_rows(L.slots, L.d_bias, c->phim, false, L.nI, (i64*)d_msg));
+  for (int I = 0; I < L.nI; ++I)
+    FHESI_TRY(grid_chunks(count, [&](i64 done, i64 cnt) {
+      return launch_ct_add_const(c, (u64*)out + ((size_t)I * count + done) * 2 * n * nlimbs, (const i64*)d_msg + (size_t)I * n, 1, 2, nlimbs, logQ, L.slots->S.p, cnt);
+    }));
+  return 0;
+}
+// The ONE run path of a layer (GridLayer, fhesi_internal.h): out[I][i] = sum_J (block or channel pair (I, J))(in[J][i]) + b_I on the slots -- matvec_run over
+// the layer's plaintexts with the blocks or channels as its grid, the folds in place on out -- nI count ciphertexts in a row --, the biases.  The caller's
+// matrices go to their places among the babies, giants and folds; every other place is the identity.  A dense block: the words of fhesi_ct_matvec_bsgs_dev,
+// fhesi_ct_rot_fold_dev and fhesi_ct_add_slots_dev in that order.  A convolution: flat, B = kh kw and the plaintext sums are the result; split, B = kw
+// babies (horizontal) and G = kh giants (vertical).  who: the entry point, what: its layer, for the refusals.
+static int layer_run(fhesi_ctx* c, const char* who, const char* what, const GridLayer* L, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
+                     const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
   CHECK_CTX(c);
-  if (!lin) FHESI_FAIL("%s: null %s", who, what);
-  if (lin->ctx != c) FHESI_FAIL("%s: the %s belongs to another context", who, what);
-  const int B = lin->B, G = lin->G, nf = lin->nfold, nI = lin->nI, nJ = lin->nJ;
-  if (nh != B - 1 + G - 1 + nf) FHESI_FAIL("%s: %d matrices, the layer takes %d (%d baby, %d giant and %d fold rotations)", who, nh, B - 1 + G - 1 + nf, B - 1, G - 1, nf);
+  if (!L) FHESI_FAIL("%s: null %s", who, what);
+  if (L->ctx != c) FHESI_FAIL("%s: the %s belongs to another context", who, what);
+  const int B = L->B, G = L->G, nf = L->nfold, nI = L->nI, nJ = L->nJ, want = (int)L->amounts.size();
+  if (nh != want) {
+    if (L->anchored) FHESI_FAIL("%s: %d matrices, the layer takes %d (one per amount of its plan, NULL at the anchor)", who, nh, want);
+    FHESI_FAIL("%s: %d matrices, the layer takes %d (%d baby, %d giant and %d fold rotations)", who, nh, want, B - 1, G - 1, nf);
+  }
   if (nh && !hoisted) FHESI_FAIL("%s: null argument", who);
-  if ((double)std::max(nI, nJ) * (double)count > 2147483647.0) FHESI_FAIL("%s: %lld ciphertexts per block exceed what the grid of %d x %d blocks can index", who, (long long)count, nI, nJ);
-  // the identity in front of the babies and of the giants; k = g^amount mod m
-  std::vector<const fhesi_ksk*> hs((size_t)nh + 2, nullptr);
-  std::vector<int64_t> ks((size_t)nh + 2, 1);
+  if ((double)std::max(nI, nJ) * (double)count > 2147483647.0) {
+    if (L->anchored) FHESI_FAIL("%s: %lld ciphertexts per channel exceed what %d -> %d channels can index", who, (long long)count, nJ, nI);
+    FHESI_FAIL("%s: %lld ciphertexts per block exceed what the grid of %d x %d blocks can index", who, (long long)count, nI, nJ);
+  }
+  // the row [B babies][G giants][nf folds], the identity wherever no entry goes; k = g^amount mod m
+  std::vector<const fhesi_ksk*> hs((size_t)(B + G + nf), nullptr);
+  std::vector<int64_t> ks((size_t)(B + G + nf), 1);
+  const std::vector<int64_t> k_entry = rotation_ks(L->slots, L->amounts);
   for (int t = 0; t < nh; ++t) {
-    const size_t at = (size_t)t + (t < B - 1 ? 1 : 2);
-    hs[at] = hoisted[t];
-    ks[at] = (int64_t)hm::powmod(lin->slots->S.g, (u64)lin->amounts[(size_t)t], (u64)c->m);
+    const i64 a = L->amounts[(size_t)t];
+    if (L->anchored && !a && hoisted[t]) FHESI_FAIL("%s: a matrix at entry %d, whose amount is 0 (the anchor takes none)", who, t);
+    if (L->anchored && a && !hoisted[t]) FHESI_FAIL("%s: entry %d has no matrix and its amount is %lld (only the anchor goes without one)", who, t, (long long)a);
+    hs[(size_t)L->place[(size_t)t]] = hoisted[t];
+    ks[(size_t)L->place[(size_t)t]] = k_entry[(size_t)t];
   }
   const fhesi_ksk* const* hb = hs.data(), * const* hg = hb + B, * const* hf = hg + G;
   const int64_t *kb = ks.data(), *kg = kb + B, *kf = kg + G;
   FHESI_TRY(rotations_args(c, hb, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
   FHESI_TRY(rotations_args(c, hg, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
   FHESI_TRY(rotations_args(c, hf, kf, nf, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  FHESI_TRY(matvec_args(c, who, lin->w, nI, nJ, lin->T, nJ * std::min(B, lin->T), logQ, in, nlimbs, count, out));
+  FHESI_TRY(matvec_args(c, who, L->w, nI, nJ, L->nk, (int)L->terms, logQ, in, nlimbs, count, out));
   if (!count) return 0;
   // every table before any digit row exists, as rotations_run builds its matrices'
   std::vector<int> g_mode, f_mode;
   FHESI_TRY(key_switch_forms(c, hg, G, logQ, decomp_bytes, &g_mode));
   FHESI_TRY(key_switch_forms(c, hf, nf, logQ, decomp_bytes, &f_mode));
-  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, g_mode.data(), G, false, nI, nJ, lin->T, lin->w, logQ, decomp_bytes, in, nlimbs, count, out));
+  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, g_mode.data(), G, L->flat, nI, nJ, L->nk, L->w, logQ, decomp_bytes, in, nlimbs, count, out));
   FHESI_TRY(rot_fold_run(c, hf, kf, nf, f_mode.data(), logQ, decomp_bytes, (u64*)out, nlimbs, (i64)nI * count));
-  if (!lin->d_bias) return 0;
-  const size_t n = (size_t)c->phim;
-  void* d_msg;
-  FHESI_TRY(ws_reserve(c, 5, (size_t)nI * n * 8, &d_msg));
-  FHESI_TRY(slots_embed_rows(lin->slots, lin->d_bias, c->phim, false, nI, (i64*)d_msg));
-  for (int I = 0; I < nI; ++I)
-    FHESI_TRY(grid_chunks(count, [&](i64 done, i64 cnt) {
-      return launch_ct_add_const(c, (u64*)out + ((size_t)I * count + done) * 2 * n * nlimbs, (const i64*)d_msg + (size_t)I * n, 1, 2, nlimbs, logQ, lin->slots->S.p, cnt);
-    }));
-  return 0;
+  return layer_add_bias(c, *L, logQ, nlimbs, count, out);
 }
 extern "C" int fhesi_ct_linear_dev(fhesi_ctx* c, const fhesi_linear* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
                                    int32_t nlimbs, int64_t count, uint64_t* out) {
-  return linear_run(c, "ct_linear", "linear layer", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
+  return layer_run(c, "ct_linear", "linear layer", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
 }
 extern "C" int fhesi_ct_linear_grid_dev(fhesi_ctx* c, const fhesi_linear_grid* lin, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes,
                                         const uint64_t* in, int32_t nlimbs, int64_t count, uint64_t* out) {
-  return linear_run(c, "ct_linear_grid", "linear grid", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
+  return layer_run(c, "ct_linear_grid", "linear grid", lin, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
 }
-
-// --------------------------------------------------------------------------------------------- convolution layers
-// out[I][i] = sum_J K[I][J] * in[J][i] + b[I] on the planes in the slots (include/fhesi_hip.h; conv_plan.h): matvec_run with the channels as its blocks --
-// nI = Cout, nJ = Cin, nk = kh kw plaintexts per pair, the plan's amounts as its babies and giants, the identity at the anchor --, then the biases as
-// linear_run adds them.  flat: B = kh kw, the plaintext sums are the result.  split: B = kw babies (horizontal), G = kh giants (vertical).
 extern "C" int fhesi_ct_conv2d_dev(fhesi_ctx* c, const fhesi_conv2d* cv, const fhesi_ksk* const* hoisted, int32_t nh, int32_t logQ, int32_t decomp_bytes, const uint64_t* in,
                                    int32_t nlimbs, int64_t count, uint64_t* out) {
-  const char* who = "ct_conv2d";
-  CHECK_CTX(c);
-  if (!cv) FHESI_FAIL("%s: null convolution layer", who);
-  if (cv->ctx != c) FHESI_FAIL("%s: the convolution layer belongs to another context", who);
-  const int nI = (int)cv->Cout, nJ = (int)cv->Cin, nk = (int)(cv->kh * cv->kw);
-  const bool flat = cv->form == 1;
-  const int B = flat ? nk : (int)cv->kw, G = flat ? 1 : (int)cv->kh;
-  if (nh != cv->nh) FHESI_FAIL("%s: %d matrices, the layer takes %d (one per amount of its plan, NULL at the anchor)", who, nh, cv->nh);
-  if (!hoisted) FHESI_FAIL("%s: null argument", who);
-  if ((double)std::max(nI, nJ) * (double)count > 2147483647.0) FHESI_FAIL("%s: %lld ciphertexts per channel exceed what %d -> %d channels can index", who, (long long)count, nJ, nI);
-  std::vector<int64_t> ks((size_t)nh, 1);
-  for (int t = 0; t < nh; ++t) {
-    const i64 a = cv->amounts[(size_t)t];
-    if (!a && hoisted[t]) FHESI_FAIL("%s: a matrix at entry %d, whose amount is 0 (the anchor takes none)", who, t);
-    if (a && !hoisted[t]) FHESI_FAIL("%s: entry %d has no matrix and its amount is %lld (only the anchor goes without one)", who, t, (long long)a);
-    ks[(size_t)t] = (int64_t)hm::powmod(cv->slots->S.g, (u64)a, (u64)c->m);
-  }
-  const fhesi_ksk* const* hb = hoisted, * const* hg = flat ? nullptr : hoisted + B;
-  const int64_t *kb = ks.data(), *kg = flat ? nullptr : kb + B;
-  FHESI_TRY(rotations_args(c, hb, kb, B, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  if (!flat) FHESI_TRY(rotations_args(c, hg, kg, G, logQ, decomp_bytes, nlimbs, count, nlimbs));
-  FHESI_TRY(matvec_args(c, who, cv->w, nI, nJ, nk, (int)cv->terms, logQ, in, nlimbs, count, out));
-  if (!count) return 0;
-  std::vector<int> g_mode;      // the giants' tables before any digit row exists, as rotations_run builds its matrices'
-  if (!flat) FHESI_TRY(key_switch_forms(c, hg, G, logQ, decomp_bytes, &g_mode));
-  FHESI_TRY(matvec_run(c, hb, kb, B, hg, kg, flat ? nullptr : g_mode.data(), G, flat, nI, nJ, nk, cv->w, logQ, decomp_bytes, in, nlimbs, count, out));
-  if (!cv->d_bias) return 0;
-  const size_t n = (size_t)c->phim;
-  void* d_msg;
-  FHESI_TRY(ws_reserve(c, 5, (size_t)nI * n * 8, &d_msg));
-  FHESI_TRY(slots_embed_rows(cv->slots, cv->d_bias, c->phim, false, nI, (i64*)d_msg));
-  for (int I = 0; I < nI; ++I)
-    FHESI_TRY(grid_chunks(count, [&](i64 done, i64 cnt) {
-      return launch_ct_add_const(c, (u64*)out + ((size_t)I * count + done) * 2 * n * nlimbs, (const i64*)d_msg + (size_t)I * n, 1, 2, nlimbs, logQ, cv->slots->S.p, cnt);
-    }));
-  return 0;
+  return layer_run(c, "ct_conv2d", "convolution layer", cv, hoisted, nh, logQ, decomp_bytes, in, nlimbs, count, out);
 }
 
 // --------------------------------------------------------------------------------------------- sum pooling on a lattice of the plane
@@ -890,11 +881,9 @@ extern "C" int fhesi_ct_pool2d_dev(fhesi_slots* s, int64_t H, int64_t W, int64_t
   const PoolPlan pl = pool_plan(sh, form);
   if (nh != pl.nh) FHESI_FAIL("%s: %d matrices, the pooling takes %d (%d horizontal, %d vertical, one per amount of its plan)", who, nh, pl.nh, pl.nhor, pl.nh - pl.nhor);
   if (nh && !hoisted) FHESI_FAIL("%s: null argument", who);
-  std::vector<int64_t> ks((size_t)nh, 1);
-  for (int t = 0; t < nh; ++t) {
+  for (int t = 0; t < nh; ++t)
     if (!hoisted[t]) FHESI_FAIL("%s: entry %d has no matrix and its amount is %lld (every amount of a pooling takes one)", who, t, (long long)pl.amounts[(size_t)t]);
-    ks[(size_t)t] = (int64_t)hm::powmod(s->S.g, (u64)pl.amounts[(size_t)t], (u64)c->m);
-  }
+  const std::vector<int64_t> ks = rotation_ks(s, pl.amounts);
   FHESI_TRY(rotations_args(c, hoisted, ks.data(), nh, logQ, decomp_bytes, nlimbs, count, nlimbs));
   if (!count) return 0;
   if (!in || !out) FHESI_FAIL("%s: null argument", who);

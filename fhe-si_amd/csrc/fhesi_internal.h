@@ -440,46 +440,54 @@ constexpr int kPlainSumFold = 64;      // terms an accumulator of plain_sum_kern
 int launch_plain_sum(fhesi_ctx* ctx, const u64* d_ca /* [nu][2][L][n] */, const u64* d_w /* [nw][L][n] */, const int* d_slot_a, const int* d_slot_w, const int* d_seg,
                      i64 ngroups, bool accumulate, u64* d_out /* [ngroups][2][L][n] */, double nterms);
 
-// --------------------------------------------------------------------------------- dense linear layers (capi_ct.hip, capi_pipeline.hip, kernels_slots.hip)
-// An R x C matrix, R = nI Rb, C = nJ Cb, as a grid of Rb x Cb blocks on a slot space (include/fhesi_hip.h): the nI nJ T prepared diagonals of the blocks,
-// T = min(Rb, Cb), in ONE prepared plaintext, the replicated biases of the nI output blocks, the plan every block shares
-struct fhesi_linear_grid {
+// --------------------------------------------------------------------------------- layers on packed slots (capi_ct.hip, capi_pipeline.hip, kernels_slots.hip)
+// What a dense grid and a convolution share, and all that layer_create (capi_ct.hip) fills and layer_run (capi_pipeline.hip) reads: nI output and nJ input
+// blocks (channels), nk prepared plaintexts per block pair in G groups of B -- the schedule of matvec_run --, nfold folds behind it, all in ONE prepared
+// plaintext; the biases of the nI output blocks as slot values.  The run call's matrices, one per entry of `amounts`, go to place[t] of the row
+// [B babies][G giants][nfold folds]; a place no entry names is the identity.
+struct GridLayer {
   fhesi_ctx* ctx = nullptr;
-  fhesi_slots* slots = nullptr;        // the space the grid was made on, borrowed: embeds the bias in front of its addition
+  fhesi_slots* slots = nullptr;        // the space the layer was made on, borrowed: its generator, and it embeds the bias in front of its addition
+  int nI = 0, nJ = 0, nk = 0, B = 0, G = 0, nfold = 0;
+  bool flat = false;                   // the plaintext sums are the result: G = 1, and the one giant is the identity, which matvec_run does not read
+  bool anchored = false;               // the entries include the identity, at the amount 0, which takes no matrix (a convolution's anchor)
+  i64 terms = 0;                       // the longest plaintext sum: nJ min(B, nk)
+  std::vector<i64> amounts;            // the order of the run call's matrices
+  std::vector<int> place;
+  fhesi_plain* w = nullptr;            // row (I nJ + J) nk + t
+  i64* d_bias = nullptr;               // [nI][phim] slot values in [0, p); null without a bias
+};
+// An R x C matrix, R = nI Rb, C = nJ Cb, as a grid of Rb x Cb blocks on a slot space (include/fhesi_hip.h): nk = T = min(Rb, Cb) prepared diagonals per block,
+// row (I nJ + J) T + t: w_t = rot_{-gB}(e_t) of block (I, J), t = g B + j; the bias rows b[I Rb + i mod Rb], every row alike.  amounts: babies 1 .. B - 1,
+// giants B .. (G - 1) B, folds Cb/2 .. Rb -- the identity in front of the babies and of the giants is no entry
+struct fhesi_linear_grid : GridLayer {
   i64 R = 0, C = 0, Rb = 0, Cb = 0;
-  int nI = 0, nJ = 0, T = 0, B = 0, G = 0, nfold = 0;
-  std::vector<i64> amounts;            // babies 1 .. B - 1, giants B .. (G - 1) B, folds Cb/2 .. Rb: the order of the apply call's matrices
-  fhesi_plain* w = nullptr;            // row (I nJ + J) T + t: w_t = rot_{-gB}(e_t) of block (I, J), t = g B + j
-  i64* d_bias = nullptr;               // [nI][phim] slot values b[I Rb + i mod Rb] in [0, p), every row alike; null without a bias
 };
 // One R x C layer (include/fhesi_hip.h): the grid of one block, Rb = R, Cb = C
 struct fhesi_linear : fhesi_linear_grid {};
+// fhesi_linear_grid_plan with the amounts in a vector it sizes: the counts and the amounts of a grid from ONE call (capi_pipeline.hip)
+int linear_grid_plan(int64_t cols, int64_t R, int64_t C, int64_t Rb, int64_t Cb, int32_t baby, int32_t* nI_out, int32_t* nJ_out, int32_t* T_out, int32_t* B_out, int32_t* G_out,
+                     int32_t* nfold_out, std::vector<int64_t>* amounts);
 // d_out[(b - first) T + t][s] = w_t of block b = I nJ + J at slot s = (row, i), reduced into [0, p): the blocks first .. first + nblocks - 1 of the row-major
 // matrix d_M of leading dimension ld, block (I, J) at d_M + I R ld + J C; t < T slot vectors of S.phim values each (linear_diag_kernel, kernels_slots.hip).
 // One layer: ld = C, nJ = 1, first = 0, nblocks = 1.
 int launch_linear_diag(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_M, i64 ld, int nJ, int first, int nblocks, i64 R, i64 C, int T, int B,
                        i64* d_out /* [nblocks][T][phim] */);
 
-// --------------------------------------------------------------------------------- convolution layers (capi_ct.hip, capi_pipeline.hip, kernels_slots.hip)
-// A 2-D convolution K [Cout][Cin][kh][kw] over H x W planes, one channel per ciphertext (include/fhesi_hip.h; the plan: conv_plan.h): the Cout Cin kh kw
-// masked weight plaintexts in ONE prepared plaintext, the biases as slot values, the plan
-struct fhesi_conv2d {
-  fhesi_ctx* ctx = nullptr;
-  fhesi_slots* slots = nullptr;        // the space the layer was made on, borrowed: embeds the bias in front of its addition
+// A 2-D convolution K [Cout][Cin][kh][kw] over H x W planes, one channel per ciphertext (include/fhesi_hip.h; the plan: conv_plan.h): nI = Cout, nJ = Cin, the
+// nk = kh kw masked weight plaintexts of a channel pair, row (I Cin + J) kh kw + t: w_t (flat, B = kh kw), w'_t (split, B = kw babies and G = kh giants); the
+// bias rows b[I] in every slot of the output lattice, 0 off it.  amounts: flat entry t = dy kw + dx; split the kw babies, then the kh giants; 0 exactly at
+// the anchor
+struct fhesi_conv2d : GridLayer {
   i64 Cout = 0, Cin = 0, kh = 0, kw = 0, H = 0, W = 0, ah = 0, aw = 0;
   int form = 0, nh = 0;                // 1 flat, 2 split; the matrices the run call takes
-  i64 key_switches = 0, terms = 0;
-  std::vector<i64> amounts;            // flat: entry t = dy kw + dx; split: the kw babies, then the kh giants; 0 exactly at the anchor
-  fhesi_plain* w = nullptr;            // row (I Cin + J) kh kw + t: w_t (flat), w'_t (split) of the channel pair (I, J)
-  i64* d_bias = nullptr;               // [Cout][phim] slot values b[I] in [0, p) in every slot of the output lattice, 0 off it; null without a bias
-  i64 sy = 1, sx = 1, ty = 1, tx = 1, ey = 1, ex = 1;      // the lattice (lattice_plan.h): input step, stride, dilation; all 1 from fhesi_conv2d_create
+  i64 key_switches = 0;
+  i64 sy = 1, sx = 1, ty = 1, tx = 1, ey = 1, ex = 1;      // the lattice (conv_plan.h): input step, stride, dilation; all 1 from fhesi_conv2d_create
 };
 // d_out[(pair - first) kh kw + t][s] = the masked weight plaintext t of channel pair `pair` = I Cin + J at slot s, reduced into [0, p), for the pairs
-// first .. first + npairs - 1 of d_K [Cout Cin][kh kw] (conv_mask_kernel, kernels_slots.hip); split: every plaintext moved back by its giant amount
-int launch_conv_mask(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_K, int first, int npairs, int kh, int kw, int ah, int aw, i64 H, i64 W, bool split,
-                     i64* d_out /* [npairs][kh kw][phim] */);
-// the same on a lattice of the plane (conv_lattice_mask_kernel; lattice_plan.h): (fy, fx) = dilation times input step, the physical pixels of one kernel
-// step; (oy, ox) the output step, whose lattice every plaintext is masked to.  All 1: the words of launch_conv_mask
+// first .. first + npairs - 1 of d_K [Cout Cin][kh kw] (conv_lattice_mask_kernel, kernels_slots.hip); split: every plaintext moved back by its giant amount.
+// (fy, fx) = dilation times input step, the physical pixels of one kernel step; (oy, ox) the output step, whose lattice every plaintext is masked to; all 1:
+// the convolution of stride 1
 int launch_conv_lattice_mask(fhesi_ctx* ctx, const hm::SlotSpace& S, const i64* d_K, int first, int npairs, int kh, int kw, int ah, int aw, i64 H, i64 W, i64 fy, i64 fx,
                              i64 oy, i64 ox, bool split, i64* d_out /* [npairs][kh kw][phim] */);
 // d_out [R][nch H W] = the columns of d_M [R][nch (H / sy) (W / sx)] spread onto the lattice of step (sy, sx), zero columns off it (lattice_columns_kernel)

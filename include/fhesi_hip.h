@@ -641,7 +641,7 @@ int fhesi_ct_linear_grid_dev(fhesi_ctx* ctx, const fhesi_linear_grid* grid, cons
                              uint64_t* out_dev /* [nI][count][2][phi(m)][nlimbs] */);
 
 /* ---- convolution layers on packed slots: a 2-D convolution over image planes, one channel per ciphertext (capi_ct.hip, capi_pipeline.hip, conv_plan.h,
- * conv_mask_kernel in kernels_slots.hip; tests/conv_model.py is the normative statement).  The space has rows of `cols` slots; rot_a moves
+ * conv_lattice_mask_kernel in kernels_slots.hip; tests/conv_model.py is the normative statement).  The space has rows of `cols` slots; rot_a moves
  * every row a slots to the left.
  *   plane      H x W, P = H W | cols: slot (r, i) holds pixel (y, x) = ((i mod P) div W, (i mod P) mod W) of image (r, i div P) -- cols / P images per row
  *   channels   an item is Cin ciphertexts in[J][i], the result Cout ciphertexts out[I][i], the [block][count] order of fhesi_ct_linear_grid_dev
@@ -693,7 +693,7 @@ int fhesi_ct_conv2d_dev(fhesi_ctx* ctx, const fhesi_conv2d* conv, const fhesi_ks
                         uint64_t* out_dev /* [Cout][count][2][phi(m)][nlimbs] */);
 
 /* ---- strided and dilated convolutions and sum pooling: the plane carries a lattice step and is never compacted (capi_ct.hip, capi_pipeline.hip,
- * lattice_plan.h, conv_lattice_mask_kernel and lattice_columns_kernel in kernels_slots.hip; tests/lattice_model.py is the normative statement).
+ * conv_plan.h, lattice_plan.h, conv_lattice_mask_kernel and lattice_columns_kernel in kernels_slots.hip; tests/lattice_model.py is the normative statement).
  *   lattice    input step (sy, sx), sy | H, sx | W: logical pixel (a, b) of the Hl x Wl = H/sy x W/sx logical plane at physical pixel (a sy, b sx); slots
  *              off the lattice are don't care on input.  A strided convolution and a pooling multiply the step; the next layer takes it as its input step
  *   geometry   six integers sy, sx, ty, tx, ey, ex: step, stride (ty | Hl, tx | Wl), dilation (at least 1); the output step is (sy ty, sx tx)

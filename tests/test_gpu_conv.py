@@ -1,5 +1,5 @@
-"""GPU: convolution layers on packed slots (fhesi_conv2d_*, fhesi_ct_conv2d_dev) through the C ABI -- the masked weight plaintexts conv_mask_kernel writes
-against the model of tests/conv_model.py without any key, the call word for word against the composition of existing entry points it is defined as,
+"""GPU: convolution layers on packed slots (fhesi_conv2d_*, fhesi_ct_conv2d_dev) through the C ABI -- the masked weight plaintexts conv_lattice_mask_kernel
+writes with the unit geometry against the model of tests/conv_model.py without any key, the call word for word against the composition of existing entry points it is defined as,
 through the scheme, inside a small network, over a slot basis, and the refusals.  Exact throughout."""
 import ctypes
 import functools
@@ -255,6 +255,50 @@ def test_conv_through_the_scheme():
     print("noise budget of the same map through linear_grid on its Toeplitz matrix (%d key switches):" % lin.key_switches,
           I(S.noise_budget(sk1, LOGQ, og, NL, Cout * count)))
     lin.close()
+
+
+def test_the_edges_of_the_places_the_matrices_go_to_in_chunks_of_one_ciphertext():
+    """(4096, 65537, logQ 128), the 4 x 8 plane, two ciphertexts per channel, "wave_operands" set so that a chunk is ONE of them.  The layer's run call puts
+    the caller's matrices at their places among babies and giants: a 1 x 1 kernel, 2 -> 2 channels with a bias, has the anchor as its ONLY entry and takes no
+    matrix -- on every pixel, and at step (2, 2), stride (2, 2), where every slot off the output lattice (4, 4) decrypts to 0, the bias included; a split
+    3 x 3 kernel anchored at (2, 2) has its null entries LAST among the babies and last among the giants; the flat 3 x 3 of 2 -> 3 channels leaves a chunk's
+    sums where the result does not go.  Each: the words of the composition, and every decrypted slot the model's."""
+    import lattice_model as LM
+    from test_gpu_lattice import lattice_composition, ring as lattice_ring      # (that module imports this one; its ring holds the amounts c - 2 and c - 16)
+    ctx, S, (sk1, pk0, pk1), mats = lattice_ring(4096)
+    p, n, count, c = S.p, S.total, 2, S.cols
+    H, W = 4, 8
+    ctb = 2 * n * NL * 8
+    rng = np.random.default_rng(41)
+    xs = rng.integers(1, p, size=(2, count, n))                     # every slot live or garbage, never 0
+    cx = ctx.alloc(2 * count * ctb)
+    S.encrypt_batch_seeded(pk0, pk1, LOGQ, 7400, 0, xs.reshape(2 * count, n), cx, NL, only_usable=False)
+    unit = ((1, 1), (1, 1), (1, 1))
+    # (kernel, Cout, anchor, form, geometry, the rotated ciphertexts or key-switched sums of one item, the amounts)
+    cases = [((1, 1), 2, (0, 0), 1, unit, 2, [0]),
+             ((1, 1), 2, (0, 0), 1, ((2, 2), (2, 2), (1, 1)), 2, [0]),
+             ((3, 3), 2, (2, 2), 2, unit, 6, [c - 2, c - 1, 0, c - 16, c - 8, 0]),
+             ((3, 3), 3, (1, 1), 1, unit, 18, [c - 9, c - 8, c - 7, c - 1, 0, 1, 7, 8, 9])]
+    for (kh, kw), Cout, anchor, form, geom, per_item, amounts in cases:
+        K, b = rng.integers(0, p, size=(Cout, 2, kh, kw)), rng.integers(1, p, size=Cout)
+        cv = S.conv2d(K, b, (H, W), anchor, form, step=geom[0], stride=geom[1], dilation=geom[2])
+        assert (cv.form, cv.amounts, cv.nh, cv.has_bias) == (form, amounts, len(amounts), True)
+        want = lattice_composition(ctx, S, mats, K, b, (H, W), anchor, geom, form, cx, count)
+        out = ctx.alloc(Cout * count * ctb)
+        ctx.set_option("wave_operands", per_item)
+        try:
+            cv.apply(mats, LOGQ, cx, NL, count, out)
+        finally:
+            ctx.set_option("wave_operands", 0)
+        assert np.array_equal(out.download((Cout, count, 2, n, NL)), want), ((kh, kw), anchor, form, geom)
+        got = S.decrypt_batch(sk1, LOGQ, out, NL, Cout * count, only_usable=False).reshape(Cout, count, n)
+        for i in range(count):
+            model = LM.direct(K, b, xs[:, i], H, W, anchor, *geom, p, S.rows)
+            for Ic in range(Cout):
+                assert I(got[Ic][i]) == I(model[Ic]), ((kh, kw), anchor, form, geom, Ic, i)
+        off = LM.lattice(H, W, cv.out_step, S.rows, S.cols) == 0
+        assert off.sum() == (0 if geom == unit else 15 * n // 16) and not got[:, :, off].any()
+        cv.close()
 
 
 # ------------------------------------------------------------------------------------------------ a network

@@ -227,6 +227,31 @@ def test_layer_and_total_sum_through_the_scheme():
     assert (budget > 0).all()
 
 
+def test_a_layer_of_folds_only_in_chunks_of_one_ciphertext():
+    """(4096, 65537, logQ 128), R = 1, C = 8 with a bias: B = G = 1 -- no baby, no giant, and every matrix of the run call goes to a fold; two ciphertexts
+    in chunks of one ("wave_operands" 1).  The words of the three-call composition, and every decrypted slot the model's."""
+    ctx, S, (sk1, pk0, pk1), mats = ring(4096)
+    p, n, count = S.p, S.total, 2
+    rng = np.random.default_rng(18)
+    M, b = rng.integers(0, p, size=(1, 8)), rng.integers(1, p, size=1)
+    x = rng.integers(0, p, size=(count, S.rows, 8))
+    cx, out = ctx.alloc(count * 2 * n * NL * 8), ctx.alloc(count * 2 * n * NL * 8)
+    S.encrypt_batch_seeded(pk0, pk1, LOGQ, 4200, 0, S.replicate(x, 8), cx, NL, only_usable=False)
+    lin = S.linear(M, b)
+    assert (lin.T, lin.B, lin.G, lin.nfold, lin.amounts, lin.has_bias) == (1, 1, 1, 3, [4, 2, 1], True)
+    want = composition(ctx, S, mats, M, b, 0, cx, count)
+    ctx.set_option("wave_operands", 1)
+    try:
+        lin.apply(mats, LOGQ, cx, NL, count, out)
+    finally:
+        ctx.set_option("wave_operands", 0)
+    assert np.array_equal(out.download((count, 2, n, NL)), want)
+    got = S.decrypt_batch(sk1, LOGQ, out, NL, count, only_usable=False)
+    for i in range(count):
+        assert I(got[i]) == LM.expected_slots(M, b, x[i], p, S.rows, S.cols), i
+    lin.close()
+
+
 def test_layer_over_a_slot_basis():
     """two primes below 2^20 on m = 4096: a (4,16) layer of 12-bit weights and data -- the exact sums exceed either prime and stay inside (-P/2, P/2)"""
     m, g = 4096, 3
